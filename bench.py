@@ -82,7 +82,15 @@ def parse(argv=None):
     ap.add_argument("--no-drop-in", action="store_true",
                     help="skip the legs that launch the matcher's kernels on lists of other sizes (the single-pair latency leg, "
                          "the 200-scan loop, configs[3] on one GPU): they would blur a kernel's average in a rocprofv3 --stats summary")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the records of the last timed step (original pair order) as DIR/*.npy: "
+                         "best_pose_index (n, 3) float64, score (n,) float32, pair_index (n,) float64; a fixed, seeded sample "
+                         "of the pairs when the whole table would exceed 64 MB (see dump_outputs)")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.config4_loop > 0:
+        ap.error("--dump-outputs applies to the matcher's bench, not to --config4-loop")
     if a.mode is None:
         a.mode = "weak" if a.gpus <= 1 else "config4"
     return a
@@ -673,6 +681,29 @@ def emit(out, name="bench_details.json"):
     return line
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, table, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """--dump-outputs: the (n_pairs, 4) int32 table of nhip_match_t records the timed step returned (original pair order)
+    as path/best_pose_index.npy ((n, 3) float64: itheta, ix, iy), path/score.npy ((n,) float32) and path/pair_index.npy
+    ((n,) float64: which pairs the rows are).  Above max_bytes in all, a fixed sample (seeded, sorted) of the pairs."""
+    from nautilus_amd.csm import MATCH_DTYPE
+    rec = np.ascontiguousarray(table, dtype=np.int32).reshape(-1).view(MATCH_DTYPE)
+    n = len(rec)
+    row_bytes, header_bytes = 3 * 8 + 4 + 8, 3 * 1024  # (the three files' .npy headers take well under 1 KB each)
+    idx = np.arange(n)
+    if n * row_bytes + header_bytes > max_bytes:
+        idx = np.sort(np.random.default_rng(seed).choice(n, (max_bytes - header_bytes) // row_bytes, replace=False))
+        rec = rec[idx]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "best_pose_index.npy"),
+            np.stack([rec["itheta"], rec["ix"], rec["iy"]], axis=1).astype(np.float64))
+    np.save(os.path.join(path, "score.npy"), np.ascontiguousarray(rec["score"], dtype=np.float32))
+    np.save(os.path.join(path, "pair_index.npy"), idx.astype(np.float64))
+    sys.stderr.write("bench.py: wrote %d of %d pairs' records to %s\n" % (len(rec), n, path))
+
+
 # ------------------------------------------------------------------------------------------ worker
 def worker(a):
     rank = int(os.environ.get("RANK", "0"))
@@ -735,6 +766,7 @@ def worker(a):
 
     elapsed, full = run_sharded(plan, rank, world, dev, m, a.steps, a.warmup, dist if use_dist else None, start_timers)
     lib.nhip_timing_enable(0)
+    last_step = full.cpu().numpy() if a.dump_outputs and rank == 0 else None  # (outside the timed region)
     k_ms, k_n = _timer(lib, _lib, _lib.NHIP_TIMER_CSM)
     g_ms, g_n = _timer(lib, _lib, _lib.NHIP_TIMER_GRID)
     c_ms, _ = _timer(lib, _lib, _lib.NHIP_TIMER_GRID_CLEAR)
@@ -757,6 +789,8 @@ def worker(a):
     if rank != 0:
         dist.destroy_process_group()
         return 0
+    if last_step is not None:
+        dump_outputs(a.dump_outputs, last_step)
 
     got = m.records()[0].cpu().numpy().view(csm.MATCH_DTYPE).reshape(-1)
     got_sums = m.records()[1].cpu().numpy()
