@@ -521,9 +521,10 @@ int nhip_csm_cache_stats(int64_t *entries, int64_t *bytes, int64_t *hits, int64_
 int nhip_csm_get_transformation(const nhip_csm_params_t *params, const float *pc_a, int32_t n_a, const float *pc_b,
                                 int32_t n_b, double rot_a, double rot_b, double rot_restriction, double *score,
                                 float *tx, float *ty, float *theta);
-/* What the calling thread's last cached-target nhip_csm_get_transformation did: {the coarse optimum's score, the fine level's
- * form (0: the branch-and-bound matcher, 1: every add by the strip kernels, 2: every add by the kernel whose lanes are poses --
- * the default), 1 if the two levels were chained on the device, the coarse optimum's rotation index}.  (Measurement / tests.) */
+/* What the calling thread's last nhip_csm_get_transformation did: {the coarse optimum's score, the form the fine level ran in
+ * (0: the branch-and-bound matcher, 1: every add by the strip kernels -- a fine plane too large for the tiles of rows, 2: every
+ * add by the kernel whose lanes are poses -- the default), 1 if the two levels were chained on the device (a cached target),
+ * the coarse optimum's rotation index}.  (Measurement / tests.) */
 int nhip_csm_get_transformation_info(double out[4]);
 
 /* Residual batch: all LIDAR residual blocks of one ceres::Problem build (immutable after

@@ -688,10 +688,8 @@ int nhip_csm_match_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_sc
   rc = make_layout(spec, &L);
   if (rc) return rc;
   const IdBounds ids = {n_scans, n_grids, dev_status()};
-  nhip_search_t pub = *search;
-  pub.flags &= ~(SEARCH_I_KEYS_ZERO | SEARCH_I_NO_FINALIZE);  // (the library's own bits: never a caller's)
   return launch_csm_match(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs,
-                          d_delta_cs, d_pair_origin, n_pairs, &pub, d_keys, d_out, d_sums,
+                          d_delta_cs, d_pair_origin, n_pairs, search, csm_plan(L, search, n_pairs), d_keys, d_out, d_sums,
                           static_cast<hipStream_t>(stream), d_workspace, workspace_bytes);
 }
 
@@ -1115,18 +1113,13 @@ int nhip_grids_download_pool4(const nhip_grids_t *grids, int32_t slot, uint8_t *
   return NHIP_OK;
 }
 
-// 16-bit grids are built without skip maps unless their spec asks (the branch-and-bound matcher never reads them).
-// The first search on a handle that takes the kernel that performs every add builds them, once.
-static int ensure_skip_maps(const nhip_grids_t *grids, const nhip_search_t *search, int32_t n_pairs = 0x7fffffff) {
+// 16-bit grids are built without skip maps unless their spec asks (only the 16-bit strip kernels read them).
+// The first search on a handle whose plan takes those kernels builds them, once.
+static int ensure_skip_maps(const nhip_grids_t *grids, const MatchPlan &plan) {
   // (writes to the handle -- the maps, then the flag -- under the handle's mutex, which is taken before the flag is looked
   //  at: concurrent nhip_csm_match calls on one handle are ordered, the loser finds the maps built.  L and n never change.)
   nhip_grids *g = const_cast<nhip_grids *>(grids);
-  if (g->L.cb != 2 || g->n == 0 || !g->L.has_image) return NHIP_OK;
-  NHIP_REQUIRE(search->n_theta >= 1 && search->nx >= 1 && search->ny >= 1, "search: empty lattice");
-  if (!csm_takes_exhaustive(g->L, search)) return NHIP_OK;
-  // (the kernel whose lanes are poses reads no skip map)
-  if (csm_small_plane_fits(search) || ((search->flags & NHIP_SEARCH_LATENCY) && csm_small_tiled_fits(search, n_pairs, nullptr, nullptr)))
-    return NHIP_OK;
+  if (plan.form != MATCH_STRIPS16 || g->n == 0 || !g->L.has_image) return NHIP_OK;
   std::lock_guard<std::mutex> lock(g->mu);
   if (g->spec.flags & NHIP_GRID_SKIP_MAP) return NHIP_OK;
   g->dirty = true;  // (maps the build's tile list does not know of)
@@ -1164,15 +1157,8 @@ int nhip_csm_match(const nhip_scans_t *scans, const nhip_grids_t *grids, const i
     NHIP_REQUIRE(n_i <= max_pts, "csm_match: pair %d: scan %d has %lld points; with %d-bit cells at most %lld fit the "
                  "int32 sums", i, pair_src[i], (long long)n_i, 8 * grids->L.cb, (long long)max_pts);
   }
-  if ((rc = ensure_skip_maps(grids, search))) return rc;
-  nhip_grid_spec_t spec_now;  // (the flags may be written by a concurrent call's ensure_skip_maps: read them under the same lock)
-  {
-    std::lock_guard<std::mutex> lock(const_cast<nhip_grids *>(grids)->mu);
-    spec_now = grids->spec;
-  }
   // the host knows the scan lengths: when every source fits the by-rotation form the general kernel is not launched
   nhip_search_t search_now = *search;
-  search_now.flags &= ~(SEARCH_I_KEYS_ZERO | SEARCH_I_NO_FINALIZE);  // (the library's own bits: never a caller's)
   {
     bool all_short = true;
     for (int32_t i = 0; i < n_pairs && all_short; i++)
@@ -1180,6 +1166,13 @@ int nhip_csm_match(const nhip_scans_t *scans, const nhip_grids_t *grids, const i
     if (all_short) search_now.flags |= NHIP_SEARCH_SHORT_SCANS;
   }
   search = &search_now;
+  const MatchPlan plan = csm_plan(grids->L, search, n_pairs);
+  if ((rc = ensure_skip_maps(grids, plan))) return rc;
+  nhip_grid_spec_t spec_now;  // (the flags may be written by a concurrent call's ensure_skip_maps: read them under the same lock)
+  {
+    std::lock_guard<std::mutex> lock(const_cast<nhip_grids *>(grids)->mu);
+    spec_now = grids->spec;
+  }
   std::vector<double> rot0(2 * (size_t)n_pairs), delta(2 * (size_t)search->n_theta);
   if ((rc = nhip_csm_rot0(theta0, nullptr, n_pairs, rot0.data()))) return rc;
   if ((rc = nhip_csm_delta_table(search, delta.data()))) return rc;
@@ -1216,7 +1209,8 @@ int nhip_csm_match(const nhip_scans_t *scans, const nhip_grids_t *grids, const i
                         static_cast<const uint8_t *>(grids->grids.p), &spec_now, grids->L,
                         static_cast<const int32_t *>(d_src.p), static_cast<const int32_t *>(d_slot.p),
                         static_cast<const double *>(d_rot0.p), static_cast<const double *>(d_delta.p),
-                        pair_origin ? static_cast<const int32_t *>(d_org.p) : nullptr, n_pairs, search, static_cast<uint64_t *>(d_keys.p), static_cast<nhip_match_t *>(d_out.p),
+                        pair_origin ? static_cast<const int32_t *>(d_org.p) : nullptr, n_pairs, search, plan,
+                        static_cast<uint64_t *>(d_keys.p), static_cast<nhip_match_t *>(d_out.p),
                         static_cast<int32_t *>(d_sums.p), nullptr, d_ws.p, ws_bytes);
   if (rc) return rc;
   {
@@ -1240,9 +1234,11 @@ int nhip_csm_scores(const nhip_scans_t *scans, const nhip_grids_t *grids, int32_
   NHIP_REQUIRE(scans && grids && search && out_sums, "csm_scores: bad arguments");
   NHIP_REQUIRE(src >= 0 && src < scans->n_scans && slot >= 0 && slot < grids->n, "csm_scores: index out of range");
   {
+    // (the volume comes from the strip kernels, which read skip maps where they exist: built for the lattices an exhaustive
+    //  search of a list takes the strip kernels for)
     nhip_search_t ex = *search;
-    ex.flags |= NHIP_SEARCH_EXHAUSTIVE;  // (the volume always comes from the kernel that performs every add)
-    if ((rc = ensure_skip_maps(grids, &ex))) return rc;
+    ex.flags = (ex.flags | NHIP_SEARCH_EXHAUSTIVE) & ~NHIP_SEARCH_LATENCY;
+    if ((rc = ensure_skip_maps(grids, csm_plan(grids->L, &ex, 1)))) return rc;
   }
   double rot0[2];
   std::vector<double> delta(2 * (size_t)search->n_theta);
@@ -1415,6 +1411,21 @@ bool same_params(const nhip_csm_params_t &a, const nhip_csm_params_t &b) {
          (a.cell_bits == 0 ? 16 : a.cell_bits) == (b.cell_bits == 0 ? 16 : b.cell_bits);
 }
 
+// the entry of this target cloud (n points, hash h) under these parameters on this device
+bool same_target(const CachedTarget &c, uint64_t h, int device, const nhip_csm_params_t &p, const float *cloud, int32_t n) {
+  return c.hash == h && c.device == device && c.cloud.size() == 2 * (size_t)n && same_params(c.params, p) &&
+         memcmp(c.cloud.data(), cloud, sizeof(float) * 2 * (size_t)n) == 0;
+}
+
+// the least recently used entries beyond the cap move to `drop` (under g_cache_mu; the caller frees them outside the lock)
+void trim_cache(std::vector<std::shared_ptr<CachedTarget>> &drop) {
+  int64_t tot = 0;
+  size_t keep = 0;
+  for (; keep < g_cache.size() && tot + g_cache[keep]->bytes <= g_cache_cap; keep++) tot += g_cache[keep]->bytes;
+  drop.assign(g_cache.begin() + (long)keep, g_cache.end());
+  g_cache.resize(keep);
+}
+
 // The calling thread's scratch for one pair (device buffers that live as long as the thread's library use: a call is
 // two launches and four small copies, no allocation).
 constexpr int DROPIN_PARTS_MAX = 8;  // "pairs" (workgroups) one search's rotations may be dealt over
@@ -1509,12 +1520,7 @@ int scratch_for(int device, int32_t n_a, const nhip_search_t &s1, const nhip_sea
   return NHIP_OK;
 }
 
-// One pair (scan 0 of the scratch against slot 0 of `g`) on the null stream; the record comes back to the host.
-// The branch-and-bound matcher computes a pair's bounds in the pair's ONE workgroup, eight rotations at a time: a search
-// of 21 rotations is three rounds on one CU while 255 idle.  So the rotations are dealt over `parts` workgroups -- to the
-// kernels they are `parts` pairs of the same scan and table whose rotation 0 is entry kbase of the rotation table
-// (BnbParams::pair_kbase) -- and the host takes the best of their records: the larger sum, on a tie the smaller index
-// ((k * nx + ix) * ny + iy with the part's rotations counted from the search's first), which is the one-workgroup result.
+// The per-call blocks of one level: scan 0 of the scratch against slot 0 of its grids, on the null stream.
 struct DropInPar {  // the per-call parameter block as the kernels read it (device copy: DropInScratch::par / par2)
   int32_t off[4];   // scan offsets {0, n_a}
   double cs[2 * DROPIN_PARTS_MAX];   // (cos, sin) theta0 per part
@@ -1528,52 +1534,59 @@ struct DropInRes {
 };
 static_assert(sizeof(DropInRes) == 160 && offsetof(DropInRes, sums) == 128, "DropInRes layout");
 
-// parts: the fewest (2 .. 8) that give every workgroup an odd number (the lattice's rule) of at most 8 rotations
-void dropin_parts(const nhip_grids_t *g, const nhip_search_t *search, int *parts, int *per) {
-  *parts = 1;
-  *per = search->n_theta;
-  const char *one = tunable("NHIP_DROPIN_PARTS");  // (measurement: "1" keeps the search in one workgroup)
-  const int q0 = one && atoi(one) >= 2 ? atoi(one) : 2;  // (measurement: at least that many parts)
-  if (!csm_takes_exhaustive(g->L, search) && search->n_theta > 8 && !(one && one[0] == '1'))
-    for (int q = q0; q <= DROPIN_PARTS_MAX; q++) {
-      const int r = (search->n_theta + q - 1) / q;
-      if ((r & 1) && r <= 8) {
-        *parts = q;
-        *per = r;
-        break;
+// One level of a call: its search on grids `g` and the plan for it.  The branch-and-bound matcher computes a pair's bounds
+// in the pair's ONE workgroup, eight rotations at a time: a search of 21 rotations is three rounds on one CU while 255 idle.
+// So its rotations are dealt over `parts` workgroups of `per` -- the fewest parts (2 .. 8) that give every workgroup an odd
+// number (the lattice's rule) of at most 8.  To the kernels they are `parts` pairs of the same scan and table whose rotation
+// 0 is entry kbase of the rotation table (BnbParams::pair_kbase), and the host takes the best of their records: the larger
+// sum, on a tie the smaller index ((k * nx + ix) * ny + iy with the part's rotations counted from the search's first), which
+// is the one-workgroup result.  Every other form takes the search as one pair.
+struct DropInLevel {
+  nhip_grids_t *g = nullptr;
+  nhip_search_t s = {};
+  MatchPlan plan;
+  int parts = 1, per = 0;
+  DropInLevel() = default;
+  DropInLevel(nhip_grids_t *g_, const nhip_search_t &s_) : g(g_), s(s_), plan(csm_plan(g_->L, &s_, 1)), per(s_.n_theta) {
+    if (plan.form == MATCH_BNB && s.n_theta > 8)
+      for (int q = 2; q <= DROPIN_PARTS_MAX; q++) {
+        const int r = (s.n_theta + q - 1) / q;
+        if ((r & 1) && r <= 8) {
+          parts = q;
+          per = r;
+          break;
+        }
       }
-    }
-}
+  }
+};
 
-// enqueue one level: scan 0 of the scratch against slot 0 of `g`, parameters in the device block `d_par` (DropInPar),
-// records into the device block `d_res` (DropInRes)
-int dropin_enqueue(DropInScratch &S, int32_t n_a, nhip_grids_t *g, const nhip_grid_spec_t &spec_now, const nhip_search_t *search,
-                   const void *d_delta, const void *d_par, bool with_origin, int parts, int per, void *d_keys, void *d_ws,
-                   size_t ws_bytes, void *d_res) {
+// enqueue one level: parameters in the device block `d_par` (DropInPar), records into the device block `d_res` (DropInRes)
+int dropin_enqueue(DropInScratch &S, int32_t n_a, const DropInLevel &v, const nhip_grid_spec_t &spec_now, const void *d_delta,
+                   const void *d_par, bool with_origin, void *d_keys, void *d_ws, size_t ws_bytes, void *d_res) {
   const uint8_t *dp = static_cast<const uint8_t *>(d_par);
   uint8_t *dr = static_cast<uint8_t *>(d_res);
-  nhip_search_t part = *search;
-  part.n_theta = per;
+  nhip_search_t part = v.s;
+  part.n_theta = v.per;
   // (the host holds the cloud: a source that fits the matcher's by-rotation form saves the launch of the other instantiation)
   if (n_a <= NHIP_SHORT_SCAN_POINTS) part.flags |= NHIP_SEARCH_SHORT_SCANS;
-  const IdBounds idb = {1, g->n, dev_status()};  // (the scratch holds one scan; every part reads scan 0, slot 0)
+  const IdBounds idb = {1, v.g->n, dev_status()};  // (the scratch holds one scan; every part reads scan 0, slot 0)
   return launch_csm_match(static_cast<const float *>(S.xy.p), reinterpret_cast<const int32_t *>(dp), idb,
-                          static_cast<const uint8_t *>(g->grids.p), &spec_now, g->L, static_cast<const int32_t *>(S.idx.p),
+                          static_cast<const uint8_t *>(v.g->grids.p), &spec_now, v.g->L, static_cast<const int32_t *>(S.idx.p),
                           static_cast<const int32_t *>(S.idx.p) + DROPIN_PARTS_MAX, reinterpret_cast<const double *>(dp + 16),
                           static_cast<const double *>(d_delta), with_origin ? reinterpret_cast<const int32_t *>(dp + 144) : nullptr,
-                          parts, &part, static_cast<uint64_t *>(d_keys), reinterpret_cast<nhip_match_t *>(dr),
+                          v.parts, &part, v.plan, static_cast<uint64_t *>(d_keys), reinterpret_cast<nhip_match_t *>(dr),
                           reinterpret_cast<int32_t *>(dr + 128), nullptr, d_ws, (int64_t)ws_bytes,
-                          parts > 1 ? reinterpret_cast<const int32_t *>(dp + 208) : nullptr);
+                          v.parts > 1 ? reinterpret_cast<const int32_t *>(dp + 208) : nullptr);
 }
 
 // the best of the parts' records
-void dropin_pick(DropInRes &res, int parts, int per, const nhip_search_t *search, nhip_match_t *m) {
+void dropin_pick(DropInRes &res, const DropInLevel &v, nhip_match_t *m) {
   int best = -1;
   int64_t best_lin = 0;
-  for (int q = 0; q < parts; q++) {
+  for (int q = 0; q < v.parts; q++) {
     // (a copy of the last rotation past the table's end IS the last rotation)
-    res.rec[q].itheta = std::min(res.rec[q].itheta + q * per, search->n_theta - 1);
-    const int64_t lin = ((int64_t)res.rec[q].itheta * search->nx + res.rec[q].ix) * search->ny + res.rec[q].iy;
+    res.rec[q].itheta = std::min(res.rec[q].itheta + q * v.per, v.s.n_theta - 1);
+    const int64_t lin = ((int64_t)res.rec[q].itheta * v.s.nx + res.rec[q].ix) * v.s.ny + res.rec[q].iy;
     if (best < 0 || res.sums[q] > res.sums[best] || (res.sums[q] == res.sums[best] && lin < best_lin)) {
       best = q;
       best_lin = lin;
@@ -1588,31 +1601,30 @@ int spec_under_lock(nhip_grids_t *g, nhip_grid_spec_t *out) {
   return NHIP_OK;
 }
 
-int match_one(DropInScratch &S, int32_t n_a, nhip_grids_t *g, const nhip_search_t *search, const void *d_delta, double theta0,
-              const int32_t *origin, nhip_match_t *m) {
-  int parts, per;
-  dropin_parts(g, search, &parts, &per);
-  int rc = ensure_skip_maps(g, search, parts);
+// One level with the host after it: the record comes back to the host.
+int match_one(DropInScratch &S, int32_t n_a, const DropInLevel &v, const void *d_delta, double theta0, const int32_t *origin,
+              nhip_match_t *m) {
+  int rc = ensure_skip_maps(v.g, v.plan);
   if (rc) return rc;
   nhip_grid_spec_t spec_now;
-  spec_under_lock(g, &spec_now);
+  spec_under_lock(v.g, &spec_now);
   DropInPar par;
   memset(&par, 0, sizeof(par));
   par.off[1] = n_a;
   if ((rc = nhip_csm_rot0(&theta0, nullptr, 1, par.cs))) return rc;
-  for (int q = 0; q < parts; q++) {
+  for (int q = 0; q < v.parts; q++) {
     par.cs[2 * q] = par.cs[0];
     par.cs[2 * q + 1] = par.cs[1];
     par.org[2 * q] = origin ? origin[0] : 0;
     par.org[2 * q + 1] = origin ? origin[1] : 0;
-    par.kb[q] = q * per;
+    par.kb[q] = q * v.per;
   }
   NHIP_TRY_HIP(hipMemcpyAsync(S.par.p, &par, sizeof(par), hipMemcpyHostToDevice, nullptr));
-  if ((rc = dropin_enqueue(S, n_a, g, spec_now, search, d_delta, S.par.p, origin != nullptr, parts, per, S.keys.p, S.ws.p, S.ws.bytes, S.res.p)))
+  if ((rc = dropin_enqueue(S, n_a, v, spec_now, d_delta, S.par.p, origin != nullptr, S.keys.p, S.ws.p, S.ws.bytes, S.res.p)))
     return rc;
   DropInRes res;
   NHIP_TRY_HIP(hipMemcpy(&res, S.res.p, sizeof(res), hipMemcpyDeviceToHost));
-  dropin_pick(res, parts, per, search, m);
+  dropin_pick(res, v, m);
   return NHIP_OK;
 }
 
@@ -1629,8 +1641,8 @@ __global__ void dropin_bridge_kernel(const nhip_match_t *rec1, const double *rot
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   nhip_match_t m;
   if (keys1) {
-    // the coarse search left its keys undecoded (SEARCH_I_NO_FINALIZE): csm_finalize_kernel's decoding, here, and the fine
-    // search's keys zeroed for it (SEARCH_I_KEYS_ZERO) -- two small launches and a memset fewer per call
+    // the coarse search left its keys undecoded (MatchPlan::keys_undecoded): csm_finalize_kernel's decoding, here, and the
+    // fine search's keys zeroed for it (keys_zeroed) -- two small launches and a memset fewer per call
     const unsigned long long key = keys1[0];
     const uint32_t sum = (uint32_t)(key >> 32), lin = 0xffffffffu - (uint32_t)key;
     m.iy = (int32_t)(lin % (uint32_t)ny1);
@@ -1666,21 +1678,18 @@ __global__ void dropin_bridge_kernel(const nhip_match_t *rec1, const double *rot
 
 // Both levels behind one another on the null stream, ONE synchronisation: upload (source cloud; coarse parameters + the
 // table of fine-centre rotations, one pinned block), coarse search, bridge, fine search (+ exact score), download of both
-// levels' records in one pinned block.  Same records as two match_one calls (tests/test_csm_gpu.py, test_adapters_gpu.py
-// compare the call with the oracle's two-level search float for float).  Returns NHIP_ERR_STATE when the form does not
-// apply (no pinned staging, more coarse rotations than the table holds): the caller takes the two-synchronisation form.
-int match_chained(DropInScratch &S, const float *pc_a, int32_t n_a, CachedTarget &T, const nhip_search_t &s1, const nhip_search_t &s2,
-                  const nhip_grid_spec_t &spec1, double theta0, nhip_match_t *m1, nhip_match_t *m2) {
-  if (!S.pin || s1.n_theta > DROPIN_CHAIN_ROT_MAX) return NHIP_ERR_STATE;
+// levels' records and of the centre the fine search ran at in one pinned block.  Same records as two match_one calls
+// (tests/test_csm_gpu.py, test_adapters_gpu.py compare the call with the oracle's two-level search float for float).  The
+// caller has checked that the form applies: pinned staging, a coarse search in one part of at most DROPIN_CHAIN_ROT_MAX
+// rotations.
+int match_chained(DropInScratch &S, const float *pc_a, int32_t n_a, const DropInLevel &c1, const DropInLevel &c2, double low_res,
+                  double high_res, double theta0, nhip_match_t *m1, nhip_match_t *m2, int32_t dev_origin[2]) {
   int rc;
-  int parts1, per1, parts2, per2;
-  dropin_parts(T.g1, &s1, &parts1, &per1);
-  dropin_parts(T.g2, &s2, &parts2, &per2);
-  if ((rc = ensure_skip_maps(T.g1, &s1, parts1)) || (rc = ensure_skip_maps(T.g2, &s2, parts2))) return rc;
+  if ((rc = ensure_skip_maps(c1.g, c1.plan)) || (rc = ensure_skip_maps(c2.g, c2.plan))) return rc;
   nhip_grid_spec_t spec1_now, spec2_now;
-  spec_under_lock(T.g1, &spec1_now);
-  spec_under_lock(T.g2, &spec2_now);
-  if (parts1 != 1) return NHIP_ERR_STATE;  // (the bridge reads ONE coarse record; the coarse lattice is the every-add kernels')
+  spec_under_lock(c1.g, &spec1_now);
+  spec_under_lock(c2.g, &spec2_now);
+  const nhip_search_t &s1 = c1.s;
   uint8_t *up = static_cast<uint8_t *>(S.pin), *down = up + DROPIN_UP_BYTES;
   DropInPar *par1 = reinterpret_cast<DropInPar *>(up);
   memset(par1, 0, sizeof(*par1));
@@ -1699,32 +1708,28 @@ int match_chained(DropInScratch &S, const float *pc_a, int32_t n_a, CachedTarget
   uint8_t *dres = static_cast<uint8_t *>(S.res.p);
   // both levels through the kernel whose lanes are poses (the default): the bridge decodes the coarse keys and zeroes the fine
   // ones, the exact-score pass decodes the fine keys -- no finalize launches, no second memset
-  const bool fused = csm_takes_exhaustive(T.g1->L, &s1) && csm_small_plane_fits(&s1) && csm_takes_exhaustive(T.g2->L, &s2) &&
-                     (csm_small_plane_fits(&s2) || ((s2.flags & NHIP_SEARCH_LATENCY) && csm_small_tiled_fits(&s2, parts2, nullptr, nullptr))) &&
-                     (s2.flags & NHIP_SEARCH_EXACT_SCORE) && parts2 == 1 && !tunable("NHIP_CSM_SMALL") && !tunable("NHIP_DROPIN_UNFUSED");
-  nhip_search_t s1c = s1, s2c = s2;
-  if (fused) {
-    s1c.flags |= SEARCH_I_NO_FINALIZE;
-    s2c.flags |= SEARCH_I_KEYS_ZERO | SEARCH_I_NO_FINALIZE;
-  }
-  if ((rc = dropin_enqueue(S, n_a, T.g1, spec1_now, &s1c, S.delta1.p, S.rot1.p, false, 1, per1, S.keys.p, S.ws.p, S.ws.bytes, dres))) return rc;
+  const bool fused = c1.plan.form == MATCH_POSES && c2.plan.form == MATCH_POSES && (c2.s.flags & NHIP_SEARCH_EXACT_SCORE);
+  DropInLevel v1 = c1, v2 = c2;
+  v1.plan.keys_undecoded = v2.plan.keys_zeroed = v2.plan.keys_undecoded = fused;
+  if ((rc = dropin_enqueue(S, n_a, v1, spec1_now, S.delta1.p, S.rot1.p, false, S.keys.p, S.ws.p, S.ws.bytes, dres))) return rc;
   hipLaunchKernelGGL(dropin_bridge_kernel, dim3(1), dim3(64), 0, nullptr, reinterpret_cast<const nhip_match_t *>(dres),
                      reinterpret_cast<const double *>(static_cast<uint8_t *>(S.rot1.p) + 256), (s1.nx - 1) / 2, (s1.ny - 1) / 2,
-                     spec1.res, T.spec2.res, n_a, parts2, per2, static_cast<DropInPar *>(S.par2.p),
+                     low_res, high_res, n_a, c2.parts, c2.per, static_cast<DropInPar *>(S.par2.p),
                      reinterpret_cast<int32_t *>(dres + 480),
-                     fused ? static_cast<const unsigned long long *>(S.keys.p) : nullptr, s1.nx, s1.ny, T.g1->L.Lf, T.g1->L.step,
+                     fused ? static_cast<const unsigned long long *>(S.keys.p) : nullptr, s1.nx, s1.ny, c1.g->L.Lf, c1.g->L.step,
                      reinterpret_cast<nhip_match_t *>(dres), reinterpret_cast<int32_t *>(dres + 128),
                      static_cast<unsigned long long *>(S.keys2.p));
   NHIP_TRY_HIP(hipGetLastError());
-  if ((rc = dropin_enqueue(S, n_a, T.g2, spec2_now, &s2c, S.delta2.p, S.par2.p, true, parts2, per2, S.keys2.p, S.ws2.p, S.ws2.bytes, dres + 256)))
+  if ((rc = dropin_enqueue(S, n_a, v2, spec2_now, S.delta2.p, S.par2.p, true, S.keys2.p, S.ws2.p, S.ws2.bytes, dres + 256)))
     return rc;
   NHIP_TRY_HIP(hipMemcpyAsync(down, dres, DROPIN_DOWN_BYTES, hipMemcpyDeviceToHost, nullptr));
   NHIP_TRY_HIP(hipStreamSynchronize(nullptr));
   DropInRes r1, r2;
   memcpy(&r1, down, sizeof(r1));
   memcpy(&r2, down + 256, sizeof(r2));
-  dropin_pick(r1, 1, per1, &s1, m1);
-  dropin_pick(r2, parts2, per2, &s2, m2);
+  memcpy(dev_origin, down + 480, 2 * sizeof(int32_t));
+  dropin_pick(r1, c1, m1);
+  dropin_pick(r2, c2, m2);
   return NHIP_OK;
 }
 
@@ -1735,14 +1740,7 @@ int nhip_csm_cache_configure(int64_t max_bytes) {
   std::vector<std::shared_ptr<CachedTarget>> drop;  // (freed outside the lock)
   std::lock_guard<std::mutex> lock(g_cache_mu);
   g_cache_cap = max_bytes;
-  int64_t tot = 0;
-  size_t keep = 0;
-  for (; keep < g_cache.size(); keep++) {
-    if (tot + g_cache[keep]->bytes > g_cache_cap) break;
-    tot += g_cache[keep]->bytes;
-  }
-  drop.assign(g_cache.begin() + (long)keep, g_cache.end());
-  g_cache.resize(keep);
+  trim_cache(drop);
   return NHIP_OK;
 }
 
@@ -1794,10 +1792,8 @@ int nhip_csm_get_transformation(const nhip_csm_params_t *p, const float *pc_a, i
   // (The coarse lattice is many rotations of few translations -- 181 x 13 x 13 at the reference's constants: the kernel that
   //  performs every add spreads its rotations over the whole chip, where the branch-and-bound matcher would compute the
   //  bounds of all of them in the pair's ONE workgroup, 23 rounds of its eight waves.  Same records either way.)
-  const char *l1 = tunable("NHIP_DROPIN_COARSE");  // (measurement: "bnb" keeps the branch-and-bound matcher)
-  const bool coarse_every_add = !(l1 && l1[0] == 'b') && (2 * h1 + 1) <= 21;
   const nhip_search_t s1 = {2 * (int32_t)floor(rot_restriction / coarse_step) + 1, 2 * h1 + 1, 2 * h1 + 1,
-                            coarse_every_add ? NHIP_SEARCH_EXHAUSTIVE : 0, coarse_step};
+                            (2 * h1 + 1) <= 21 ? NHIP_SEARCH_EXHAUSTIVE : 0, coarse_step};
   // level 2: high_res grid, +-low_res around the coarse optimum, +-1 coarse step in 0.1 steps.  Its tables are built for
   // the largest search centre a coarse optimum can produce (+ the fine half-width), so that they serve every source.
   const int32_t ratio = (int32_t)lround(p->low_res / p->high_res);
@@ -1805,128 +1801,103 @@ int nhip_csm_get_transformation(const nhip_csm_params_t *p, const float *pc_a, i
   // (the score the call returns is the fine optimum's on the UNQUANTISED table -- NHIP_SEARCH_EXACT_SCORE: the reference's
   //  table holds doubles, cimg_debug.h:19; both searches run on the quantised tables)
   // The fine level performs EVERY add, in the kernel whose lanes are poses (NHIP_SEARCH_LATENCY: 21 x 16 tiles of four rows of
-  // the 61 x 61 plane, ~45 us whatever the clouds).  Round 6 measured the alternatives (profiles/r06_dropin_fine_level.txt):
-  // the branch-and-bound matcher takes 110 us where the clouds match and 0.8-10 ms where they do not -- a flat landscape
-  // leaves it thousands of candidate blocks on a table whose pooled level does not fit LDS; the strip kernels 0.16-0.48 ms.
-  // NHIP_DROPIN_FINE=bnb / strips (under NHIP_TUNABLES=1) select those.  Same records in every form.
-  const char *l2 = tunable("NHIP_DROPIN_FINE");
-  const int32_t fine_flags = (l2 && l2[0] == 'b') ? 0 : ((l2 && l2[0] == 's') ? NHIP_SEARCH_EXHAUSTIVE : (NHIP_SEARCH_EXHAUSTIVE | NHIP_SEARCH_LATENCY));
-  const nhip_search_t s2 = {21, 2 * ratio + 1, 2 * ratio + 1, NHIP_SEARCH_EXACT_SCORE | fine_flags, coarse_step / 10.0};
+  // the 61 x 61 plane, ~45 us whatever the clouds; where the tiles do not fit -- a low_res / high_res ratio of ~64 and more --
+  // the strip kernels).  Round 6 measured the alternatives (profiles/r06_dropin_fine_level.txt): the branch-and-bound matcher
+  // takes 110 us where the clouds match and 0.8-10 ms where they do not -- a flat landscape leaves it thousands of candidate
+  // blocks on a table whose pooled level does not fit LDS; the strip kernels 0.16-0.48 ms.  Same records in every form.
+  const nhip_search_t s2 = {21, 2 * ratio + 1, 2 * ratio + 1, NHIP_SEARCH_EXACT_SCORE | NHIP_SEARCH_EXHAUSTIVE | NHIP_SEARCH_LATENCY,
+                            coarse_step / 10.0};
+  // (a target whose fine tables would exceed the common reach, or an empty one, is not cached: its fine table is built for
+  //  this call's coarse optimum alone, below)
   const bool cacheable = reach_max <= 4096 && n_b > 0;
 
   // ---- the target's tables: from the cache, or built now
   std::shared_ptr<CachedTarget> T;
-  const size_t b_bytes = sizeof(float) * 2 * (size_t)n_b;
-  const uint64_t h = cacheable ? hash_bytes(pc_b, b_bytes) ^ (uint64_t)n_b : 0;
+  const uint64_t h = cacheable ? hash_bytes(pc_b, sizeof(float) * 2 * (size_t)n_b) ^ (uint64_t)n_b : 0;
   if (cacheable) {
     std::lock_guard<std::mutex> lock(g_cache_mu);
-    for (size_t i = 0; i < g_cache.size(); i++) {
-      CachedTarget &c = *g_cache[i];
-      if (c.hash == h && c.device == device && c.cloud.size() == 2 * (size_t)n_b && same_params(c.params, *p) &&
-          memcmp(c.cloud.data(), pc_b, b_bytes) == 0) {
+    for (size_t i = 0; i < g_cache.size(); i++)
+      if (same_target(*g_cache[i], h, device, *p, pc_b, n_b)) {
         T = g_cache[i];
         g_cache.erase(g_cache.begin() + (long)i);
         g_cache.insert(g_cache.begin(), T);
         g_cache_hits++;
         break;
       }
-    }
     if (!T) g_cache_misses++;
   }
-  nhip_match_t m1;
-  float tx1, ty1, th1;
+  const int32_t target = 0;
+  std::unique_ptr<nhip_scans_t, int (*)(nhip_scans_t *)> bs(nullptr, nhip_scans_free);  // (the target's scans, while needed)
   if (!T) {
     T = std::make_shared<CachedTarget>();
     T->hash = h;
     T->params = *p;
     T->device = device;
     if (n_b) T->cloud.assign(pc_b, pc_b + 2 * (size_t)n_b);
-    const int32_t off[2] = {0, n_b}, target = 0;
-    nhip_scans_t *bs = nullptr;
-    if ((rc = nhip_scans_upload(pc_b, off, 1, &bs))) return rc;
+    const int32_t off[2] = {0, n_b};
+    nhip_scans_t *up = nullptr;
+    if ((rc = nhip_scans_upload(pc_b, off, 1, &up))) return rc;
+    bs.reset(up);
     T->spec1 = spec1;
-    rc = nhip_grids_build(bs, &target, 1, &spec1, &T->g1);
-    if (rc == NHIP_OK && cacheable) {
+    if ((rc = nhip_grids_build(bs.get(), &target, 1, &spec1, &T->g1))) return rc;
+    if (cacheable) {
       T->spec2 = {p->scanner_range, p->high_res, p->sigma, p->floor_p, reach_max, bits, 0, 0};
-      rc = nhip_grids_build(bs, &target, 1, &T->spec2, &T->g2);
-    }
-    if (rc) {
-      nhip_scans_free(bs);
-      return rc;
-    }
-    if (!cacheable) {
-      // (no common reach, or an empty target: the fine grid is sized by this call's coarse optimum, below; nothing is kept.
-      //  The target's scan table must outlive the coarse match: matched here.)
-      DropInScratch *S0 = nullptr;
-      if ((rc = scratch_for(device, n_a, s1, s2, &S0))) { nhip_scans_free(bs); return rc; }
-      hipError_t e = hipSuccess;
-      if (n_a) e = hipMemcpy(S0->xy.p, pc_a, sizeof(float) * 2 * (size_t)n_a, hipMemcpyHostToDevice);
-      if (e != hipSuccess) { nhip_scans_free(bs); return hip_fail(e, "csm_get_transformation upload", __FILE__, __LINE__); }
-      rc = match_one(*S0, n_a, T->g1, &s1, S0->delta1.p, theta0, nullptr, &m1);
-      if (rc == NHIP_OK) rc = nhip_match_to_transform(&m1, &spec1, &s1, theta0, 0, 0, &tx1, &ty1, &th1);
-      if (rc) { nhip_scans_free(bs); return rc; }
-      const int32_t origin[2] = {(int32_t)lround((double)tx1 / p->high_res), (int32_t)lround((double)ty1 / p->high_res)};
-      const int32_t reach = std::max(abs(origin[0]), abs(origin[1])) + ratio;
-      T->spec2 = {p->scanner_range, p->high_res, p->sigma, p->floor_p, reach, bits, 0, 0};
-      rc = nhip_grids_build(bs, &target, 1, &T->spec2, &T->g2);
-      nhip_scans_free(bs);
-      if (rc) return rc;
-      nhip_match_t m2;
-      const double theta1 = th1;
-      if ((rc = match_one(*S0, n_a, T->g2, &s2, S0->delta2.p, theta1, origin, &m2))) return rc;
-      if ((rc = nhip_match_to_transform(&m2, &T->spec2, &s2, theta1, origin[0], origin[1], tx, ty, theta))) return rc;
-      *score = (double)m2.score;
-      return NHIP_OK;
-    }
-    nhip_scans_free(bs);
-    T->bytes = (int64_t)T->g1->grids.bytes + (int64_t)T->g2->grids.bytes;
-    std::vector<std::shared_ptr<CachedTarget>> drop;  // (evicted entries are freed outside the lock; a thread still matching
-    {                                                  //  against one keeps it alive through its own shared_ptr)
-      std::lock_guard<std::mutex> lock(g_cache_mu);
-      // (two threads that missed on the same target at once both built it: the second finds the first's entry and keeps
-      //  its own tables for this call only, so that no target counts twice against the cap)
-      bool have = false;
-      for (auto &c : g_cache)
-        have = have || (c->hash == h && c->device == device && c->cloud.size() == T->cloud.size() && same_params(c->params, *p) &&
-                        memcmp(c->cloud.data(), T->cloud.data(), b_bytes) == 0);
-      if (!have && T->bytes <= g_cache_cap) {
-        g_cache.insert(g_cache.begin(), T);
-        int64_t tot = 0;
-        size_t keep = 0;
-        for (; keep < g_cache.size(); keep++) {
-          if (tot + g_cache[keep]->bytes > g_cache_cap) break;
-          tot += g_cache[keep]->bytes;
+      if ((rc = nhip_grids_build(bs.get(), &target, 1, &T->spec2, &T->g2))) return rc;
+      bs.reset();
+      T->bytes = (int64_t)T->g1->grids.bytes + (int64_t)T->g2->grids.bytes;
+      std::vector<std::shared_ptr<CachedTarget>> drop;  // (evicted entries are freed outside the lock; a thread still matching
+      {                                                  //  against one keeps it alive through its own shared_ptr)
+        std::lock_guard<std::mutex> lock(g_cache_mu);
+        // (two threads that missed on the same target at once both built it: the second finds the first's entry and keeps
+        //  its own tables for this call only, so that no target counts twice against the cap)
+        bool have = false;
+        for (auto &c : g_cache) have = have || same_target(*c, h, device, *p, pc_b, n_b);
+        if (!have && T->bytes <= g_cache_cap) {
+          g_cache.insert(g_cache.begin(), T);
+          trim_cache(drop);
         }
-        drop.assign(g_cache.begin() + (long)keep, g_cache.end());
-        g_cache.resize(keep);
       }
     }
   }
-  // ---- the two searches of this source against the target's tables, chained on the device: upload, coarse search, bridge
+
+  // ---- the two searches of this source.  Chained on the device where the form applies -- upload, coarse search, bridge
   // kernel (the fine level's parameter block from the coarse record), fine search, exact score, ONE download, ONE
-  // synchronisation.  (No pinned staging, a coarse search of more rotations than the chain's table holds, or
-  // NHIP_DROPIN_CHAIN=0: one level after the other with the host in between.)
+  // synchronisation: the fine tables exist before the coarse search (a cached target), pinned staging, a coarse search in
+  // one part of at most DROPIN_CHAIN_ROT_MAX rotations.  Otherwise one level after the other with the host in between.
   DropInScratch *S = nullptr;
   if ((rc = scratch_for(device, n_a, s1, s2, &S))) return rc;
-  nhip_match_t m2;
-  const char *ch = tunable("NHIP_DROPIN_CHAIN");
-  rc = (ch && ch[0] == '0') ? NHIP_ERR_STATE : match_chained(*S, pc_a, n_a, *T, s1, s2, spec1, theta0, &m1, &m2);
-  const bool chained = rc == NHIP_OK;
-  if (rc != NHIP_OK && rc != NHIP_ERR_STATE) return rc;
-  if (!chained) {
+  const DropInLevel c1(T->g1, s1);
+  DropInLevel c2 = cacheable ? DropInLevel(T->g2, s2) : DropInLevel();
+  const bool chained = cacheable && S->pin && s1.n_theta <= DROPIN_CHAIN_ROT_MAX && c1.parts == 1;
+  nhip_match_t m1, m2;
+  int32_t dev_origin[2] = {0, 0};
+  if (chained) {
+    if ((rc = match_chained(*S, pc_a, n_a, c1, c2, p->low_res, p->high_res, theta0, &m1, &m2, dev_origin))) return rc;
+  } else {
     if (n_a) NHIP_TRY_HIP(hipMemcpyAsync(S->xy.p, pc_a, sizeof(float) * 2 * (size_t)n_a, hipMemcpyHostToDevice, nullptr));
-    if ((rc = match_one(*S, n_a, T->g1, &s1, S->delta1.p, theta0, nullptr, &m1))) return rc;
+    if ((rc = match_one(*S, n_a, c1, S->delta1.p, theta0, nullptr, &m1))) return rc;
   }
+  float tx1, ty1, th1;
   if ((rc = nhip_match_to_transform(&m1, &spec1, &s1, theta0, 0, 0, &tx1, &ty1, &th1))) return rc;
   const int32_t origin[2] = {(int32_t)lround((double)tx1 / p->high_res), (int32_t)lround((double)ty1 / p->high_res)};
-  NHIP_REQUIRE(std::max(abs(origin[0]), abs(origin[1])) + ratio <= reach_max, "csm_get_transformation: coarse optimum (%d, %d) beyond "
-               "the fine tables' reach %d", origin[0], origin[1], reach_max);
+  if (!cacheable) {
+    T->spec2 = {p->scanner_range, p->high_res, p->sigma, p->floor_p, std::max(abs(origin[0]), abs(origin[1])) + ratio, bits, 0, 0};
+    if ((rc = nhip_grids_build(bs.get(), &target, 1, &T->spec2, &T->g2))) return rc;
+    c2 = DropInLevel(T->g2, s2);
+  }
+  NHIP_REQUIRE(std::max(abs(origin[0]), abs(origin[1])) + ratio <= T->spec2.max_shift, "csm_get_transformation: coarse optimum "
+               "(%d, %d) beyond the fine tables' reach %d", origin[0], origin[1], T->spec2.max_shift);
+  // (the chained fine search ran at the centre dropin_bridge_kernel derived on the device from the same record: the
+  //  transform below is built around the host's, so the two must agree)
+  NHIP_REQUIRE(!chained || (dev_origin[0] == origin[0] && dev_origin[1] == origin[1]), "csm_get_transformation: the fine search "
+               "ran around (%d, %d) on the device, the coarse optimum is at (%d, %d) on the host", dev_origin[0], dev_origin[1],
+               origin[0], origin[1]);
   const double theta1 = th1;
+  if (!chained && (rc = match_one(*S, n_a, c2, S->delta2.p, theta1, origin, &m2))) return rc;
   t_dropin_info[0] = (double)m1.score;
-  t_dropin_info[1] = (s2.flags & NHIP_SEARCH_LATENCY) ? 2.0 : ((s2.flags & NHIP_SEARCH_EXHAUSTIVE) ? 1.0 : 0.0);
+  t_dropin_info[1] = c2.plan.form == MATCH_BNB ? 0.0 : (c2.plan.form == MATCH_POSES ? 2.0 : 1.0);
   t_dropin_info[2] = chained ? 1.0 : 0.0;
   t_dropin_info[3] = (double)m1.itheta;
-  if (!chained && (rc = match_one(*S, n_a, T->g2, &s2, S->delta2.p, theta1, origin, &m2))) return rc;
   if ((rc = nhip_match_to_transform(&m2, &T->spec2, &s2, theta1, origin[0], origin[1], tx, ty, theta))) return rc;
   *score = (double)m2.score;
   return NHIP_OK;

@@ -134,11 +134,10 @@ int launch_csm_bnb(const float *d_xy, const int32_t *d_offsets, const IdBounds &
                    const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
                    const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
                    const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search,
-                   uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s, int *handled,
+                   uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
                    void *d_workspace, int64_t workspace_bytes, const int32_t *d_pair_kbase) {
-  *handled = 0;
-  if (!bnb_fits(L, search)) return NHIP_OK;
-  *handled = 1;
+  NHIP_REQUIRE(bnb_fits(L, search), "csm_match: lattice %d x %d x %d beyond the branch-and-bound matcher's envelope",
+               search->n_theta, search->nx, search->ny);
   if (n_pairs == 0) return NHIP_OK;
   BnbParams P;
   memset(&P, 0, sizeof(P));

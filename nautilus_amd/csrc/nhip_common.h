@@ -181,19 +181,37 @@ int launch_grid_build(const float *d_xy, const int32_t *d_offsets, int32_t n_sca
                       int32_t n_targets, const nhip_grid_spec_t *spec, const GridLayout &L,
                       uint8_t *d_grids, void *d_ws, int64_t ws_bytes, hipStream_t s, bool incremental = false);
 
+// Which kernel matches a list: decided by csm_plan (nhip_csm.hip) and nowhere else; launch_csm_match dispatches on it.
+enum MatchForm : int32_t {
+  MATCH_BNB,       // the branch-and-bound matcher (nhip_bnb.hip)
+  MATCH_POSES,     // every add in the kernel whose lanes are poses (nhip_csm_small.hip): one plane, or tiles of rows
+  MATCH_STRIPS8,   // every add in the strip kernels, 8-bit cells (nhip_csm.hip)
+  MATCH_STRIPS16,  // every add in the strip kernels, 16-bit cells (nhip_csm16.hip): the one form that reads skip maps
+};
+struct MatchPlan {
+  MatchForm form = MATCH_BNB;
+  int32_t tile_rows = 0, n_tiles = 0;  // MATCH_POSES: rows of the plane per workgroup, workgroups per rotation
+  // Set only by the chained GetTransformation, for its levels through the kernel whose lanes are poses: the kernel before
+  // zeroed the keys (no memset), the kernel after decodes them (no finalize) -- dropin_bridge_kernel for the coarse level,
+  // csm_exact_score_kernel for the fine one.
+  bool keys_zeroed = false, keys_undecoded = false;
+};
+// the plan of a search of n_pairs pairs on these grids (the test hooks NHIP_CSM_EXHAUSTIVE / NHIP_CSM_SMALL are read here)
+MatchPlan csm_plan(const GridLayout &L, const nhip_search_t *search, int32_t n_pairs);
+
 int launch_csm_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
                      const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
                      const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                     const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search,
+                     const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, const MatchPlan &plan,
                      uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
                      void *d_workspace = nullptr, int64_t workspace_bytes = 0, const int32_t *d_pair_kbase = nullptr);
 
-// branch-and-bound matcher (nhip_bnb.hip); returns NHIP_ERR_STATE-free: `*handled` = 0 when the lattice does not fit it
+// branch-and-bound matcher (nhip_bnb.hip); the lattice is one bnb_fits takes (csm_plan chose it)
 int launch_csm_bnb(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
                    const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
                    const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
                    const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search,
-                   uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s, int *handled,
+                   uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
                    void *d_workspace = nullptr, int64_t workspace_bytes = 0, const int32_t *d_pair_kbase = nullptr);
 int64_t bnb_workspace_bytes(int32_t n_pairs);
 int64_t bnb_workspace_bytes_lists(int32_t n_pairs);
@@ -222,24 +240,16 @@ int launch_csm16_scores(const float *d_xy, const int32_t *d_offsets, const uint8
                         const nhip_grid_spec_t *spec, const GridLayout &L, int32_t src, int32_t slot,
                         const double *d_rot0_cs, const double *d_delta_cs, int32_t origin_x, int32_t origin_y,
                         const nhip_search_t *search, int32_t *d_sums, hipStream_t s);
-// every add for lattices of few translations (nx * ny <= 256), both cell widths (nhip_csm_small.hip)
-// Internal bits of nhip_search_t::flags (never part of the ABI: the extern "C" entry points mask them off).  The chained
-// GetTransformation sets them for the searches it sends through the small-plane kernel: the keys were zeroed by the
-// kernel before (no memset node), and the kernel after decodes the keys itself (no finalize node) -- dropin_bridge_kernel for
-// the coarse level, csm_exact_score_kernel for the fine one.
-constexpr int32_t SEARCH_I_KEYS_ZERO = 1 << 28;
-constexpr int32_t SEARCH_I_NO_FINALIZE = 1 << 29;
+// every add for lattices of few translations (nx * ny <= 256), both cell widths (nhip_csm_small.hip); tiling from the plan
 bool csm_small_plane_fits(const nhip_search_t *search);
 bool csm_small_tiled_fits(const nhip_search_t *search, int32_t n_pairs, int32_t *tile_rows, int32_t *n_tiles);
 int launch_csm_small_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
                            const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
                            const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                           const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search,
+                           const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, const MatchPlan &plan,
                            uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s);
 // skip maps of n finished 16-bit grids (the handle API's late build; occupancy unknown: every map tile is computed)
 int launch_skipmap_build(uint8_t *d_grids, int32_t n_grids, const GridLayout &L, hipStream_t s);
-// true when a search on these grids takes the kernel that performs every add
-bool csm_takes_exhaustive(const GridLayout &L, const nhip_search_t *search);
 
 int launch_resid_lidar(int kind, const float *d_corr, const int32_t *d_corr_block, int64_t n_corr,
                        const int32_t *d_block_src, const int32_t *d_block_tgt, int32_t n_blocks,

@@ -624,7 +624,7 @@ int launch_csm_exact_score(const float *d_xy, const int32_t *d_offsets, const Id
   return NHIP_OK;
 }
 
-int check_search(const nhip_grid_spec_t *spec, const GridLayout &L, const nhip_search_t *search, bool exhaustive) {
+int check_search(const nhip_grid_spec_t *spec, const GridLayout &L, const nhip_search_t *search) {
   NHIP_REQUIRE(search->n_theta >= 1 && (search->n_theta & 1), "search: n_theta must be odd >= 1");
   NHIP_REQUIRE(search->nx >= 1 && (search->nx & 1), "search: nx must be odd >= 1");
   NHIP_REQUIRE(search->ny >= 1 && (search->ny & 1), "search: ny must be odd >= 1");
@@ -636,7 +636,6 @@ int check_search(const nhip_grid_spec_t *spec, const GridLayout &L, const nhip_s
   NHIP_REQUIRE(L.S + 2 * L.pad < 65536, "search: stored grid side %d does not fit 16-bit cell packing",
                L.S + 2 * L.pad);
   NHIP_REQUIRE(L.pitch % 16 == 0, "search: grid pitch must be a multiple of 16");
-  (void)exhaustive;  // (both cell widths have a kernel that performs every add: this file and nhip_csm16.hip)
   return NHIP_OK;
 }
 
@@ -666,9 +665,27 @@ void fill_params(CsmParams &P, const nhip_grid_spec_t *spec, const GridLayout &L
 
 }  // namespace
 
-bool csm_takes_exhaustive(const GridLayout &L, const nhip_search_t *search) {
+MatchPlan csm_plan(const GridLayout &L, const nhip_search_t *search, int32_t n_pairs) {
+  MatchPlan plan;
+  // branch and bound unless every add is asked for (NHIP_CSM_EXHAUSTIVE=1: tests) or the lattice is beyond its envelope
   const char *ex = tunable("NHIP_CSM_EXHAUSTIVE");
-  return (search->flags & NHIP_SEARCH_EXHAUSTIVE) || (ex && ex[0] == '1') || !bnb_fits(L, search);
+  if (!(search->flags & NHIP_SEARCH_EXHAUSTIVE) && !(ex && ex[0] == '1') && bnb_fits(L, search)) return plan;
+  // every add: planes of few translations (the coarse level of GetTransformation: 13 x 13) in the kernel whose lanes are
+  // poses; so, for lists of a few pairs (NHIP_SEARCH_LATENCY), larger planes in tiles of whole rows (the fine level).
+  // NHIP_CSM_SMALL=0 (tests): the strip kernels for these lattices too.
+  const char *sm = tunable("NHIP_CSM_SMALL");
+  if (!(sm && sm[0] == '0')) {
+    plan.form = MATCH_POSES;
+    if (csm_small_plane_fits(search)) {
+      plan.tile_rows = search->ny;
+      plan.n_tiles = 1;
+      return plan;
+    }
+    if ((search->flags & NHIP_SEARCH_LATENCY) && csm_small_tiled_fits(search, n_pairs, &plan.tile_rows, &plan.n_tiles)) return plan;
+  }
+  plan.form = L.cb == 2 ? MATCH_STRIPS16 : MATCH_STRIPS8;
+  plan.tile_rows = plan.n_tiles = 0;
+  return plan;
 }
 
 void launch_csm_finalize(const uint64_t *d_keys, const int32_t *d_pair_src, const int32_t *d_offsets, int32_t n_scans, int32_t n_pairs,
@@ -678,64 +695,12 @@ void launch_csm_finalize(const uint64_t *d_keys, const int32_t *d_pair_src, cons
                      L.step, d_out, d_sums);
 }
 
-static int launch_csm_match_quantised(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
-                                      const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
-                                      const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                                      const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search,
-                                      uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
-                                      void *d_workspace, int64_t workspace_bytes, const int32_t *d_pair_kbase);
-
-int launch_csm_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
-                     const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
-                     const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                     const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search,
-                     uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
-                     void *d_workspace, int64_t workspace_bytes, const int32_t *d_pair_kbase) {
-  int rc = launch_csm_match_quantised(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
-                                      d_pair_origin, n_pairs, search, d_keys, d_out, d_sums, s, d_workspace, workspace_bytes,
-                                      d_pair_kbase);
-  if (rc || n_pairs == 0 || !(search->flags & NHIP_SEARCH_EXACT_SCORE)) return rc;
-  // (the records are final -- indices and integer sums; the pass replaces their score field)
-  // (SEARCH_I_NO_FINALIZE: the search left its keys undecoded -- the small-plane kernel of a chained call; this pass decodes them)
-  const bool decode = (search->flags & SEARCH_I_NO_FINALIZE) != 0;
-  return launch_csm_exact_score(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
-                                d_pair_origin, d_pair_kbase, n_pairs, search, d_out, s, decode ? d_keys : nullptr, decode ? d_sums : nullptr);
-}
-
-static int launch_csm_match_quantised(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
-                                      const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
-                                      const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                                      const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search,
-                                      uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
-                                      void *d_workspace, int64_t workspace_bytes, const int32_t *d_pair_kbase) {
-  const bool exhaustive = csm_takes_exhaustive(L, search);
-  // (per-pair offsets into the rotation table are the branch-and-bound matcher's: an internal caller that passes them has
-  //  made sure the lattice is one it takes)
-  NHIP_REQUIRE(!d_pair_kbase || !exhaustive, "csm_match: rotation offsets per pair with a lattice the matcher does not take");
-  int rc = check_search(spec, L, search, exhaustive);
-  if (rc) return rc;
-  NHIP_REQUIRE(L.has_image || !exhaustive, "csm_match: this search takes the kernel that performs every add (NHIP_SEARCH_EXHAUSTIVE, or "
-               "a lattice beyond the branch-and-bound matcher's envelope), which reads the row-major image the grids were built "
-               "without (NHIP_GRID_NO_IMAGE)");
-  if (n_pairs == 0) return NHIP_OK;
-  if (!exhaustive) {  // branch and bound: the same records, most adds never performed (nhip_bnb.hip)
-    int handled = 0;
-    rc = launch_csm_bnb(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
-                        d_pair_origin, n_pairs, search, d_keys, d_out, d_sums, s, &handled, d_workspace, workspace_bytes,
-                        d_pair_kbase);
-    if (rc || handled) return rc;
-  }
-  // planes of few translations (the coarse level of GetTransformation: 13 x 13): the kernel whose lanes are poses
-  // (NHIP_CSM_SMALL=0, measurement / tests: the strip kernels below for these lattices too)
-  const char *sm = tunable("NHIP_CSM_SMALL");
-  // ... and, for lists of a few pairs, larger planes in tiles of whole rows (the fine level of GetTransformation)
-  if ((csm_small_plane_fits(search) || ((search->flags & NHIP_SEARCH_LATENCY) && csm_small_tiled_fits(search, n_pairs, nullptr, nullptr))) &&
-      !(sm && sm[0] == '0'))
-    return launch_csm_small_match(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
-                                  d_pair_origin, n_pairs, search, d_keys, d_out, d_sums, s);
-  if (L.cb == 2)
-    return launch_csm16_match(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
-                              d_pair_origin, n_pairs, search, d_keys, d_out, d_sums, s);
+// the strip kernels, 8-bit cells (the 16-bit ones: nhip_csm16.hip)
+static int launch_csm8_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
+                             const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
+                             const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
+                             const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search,
+                             uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s) {
   CsmParams P;
   fill_params(P, spec, L, search);
   P.xy = reinterpret_cast<const float2 *>(d_xy);
@@ -766,12 +731,53 @@ static int launch_csm_match_quantised(const float *d_xy, const int32_t *d_offset
   return NHIP_OK;
 }
 
+int launch_csm_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
+                     const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
+                     const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
+                     const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, const MatchPlan &plan,
+                     uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
+                     void *d_workspace, int64_t workspace_bytes, const int32_t *d_pair_kbase) {
+  // (per-pair offsets into the rotation table are the branch-and-bound matcher's: an internal caller that passes them has
+  //  made sure the lattice is one it takes)
+  NHIP_REQUIRE(!d_pair_kbase || plan.form == MATCH_BNB, "csm_match: rotation offsets per pair with a lattice the matcher does not take");
+  int rc = check_search(spec, L, search);
+  if (rc) return rc;
+  NHIP_REQUIRE(L.has_image || plan.form == MATCH_BNB, "csm_match: this search takes the kernel that performs every add "
+               "(NHIP_SEARCH_EXHAUSTIVE, or a lattice beyond the branch-and-bound matcher's envelope), which reads the row-major "
+               "image the grids were built without (NHIP_GRID_NO_IMAGE)");
+  if (n_pairs == 0) return NHIP_OK;
+  switch (plan.form) {
+    case MATCH_BNB:  // the same records, most adds never performed (nhip_bnb.hip)
+      rc = launch_csm_bnb(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs, d_pair_origin,
+                          n_pairs, search, d_keys, d_out, d_sums, s, d_workspace, workspace_bytes, d_pair_kbase);
+      break;
+    case MATCH_POSES:
+      rc = launch_csm_small_match(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
+                                  d_pair_origin, n_pairs, search, plan, d_keys, d_out, d_sums, s);
+      break;
+    case MATCH_STRIPS16:
+      rc = launch_csm16_match(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
+                              d_pair_origin, n_pairs, search, d_keys, d_out, d_sums, s);
+      break;
+    case MATCH_STRIPS8:
+      rc = launch_csm8_match(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
+                             d_pair_origin, n_pairs, search, d_keys, d_out, d_sums, s);
+      break;
+  }
+  if (rc || !(search->flags & NHIP_SEARCH_EXACT_SCORE)) return rc;
+  // (the records are final -- indices and integer sums; the pass replaces their score field.  A search that left its keys
+  //  undecoded -- the fine level of a chained call -- has them decoded by this pass.)
+  return launch_csm_exact_score(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
+                                d_pair_origin, d_pair_kbase, n_pairs, search, d_out, s, plan.keys_undecoded ? d_keys : nullptr,
+                                plan.keys_undecoded ? d_sums : nullptr);
+}
+
 int launch_csm_scores(const float *d_xy, const int32_t *d_offsets, const uint8_t *d_grids,
                       const nhip_grid_spec_t *spec, const GridLayout &L, int32_t src, int32_t slot,
                       const double *d_rot0_cs, const double *d_delta_cs, int32_t origin_x,
                       int32_t origin_y, const nhip_search_t *search, int32_t *d_sums,
                       hipStream_t s) {
-  int rc = check_search(spec, L, search, true);
+  int rc = check_search(spec, L, search);
   if (rc) return rc;
   NHIP_REQUIRE(L.has_image, "csm_scores: the score volume comes from the kernel that performs every add, which reads the row-major "
                "image the grids were built without (NHIP_GRID_NO_IMAGE)");

@@ -176,7 +176,7 @@ bool csm_small_tiled_fits(const nhip_search_t *search, int32_t n_pairs, int32_t 
 int launch_csm_small_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
                            const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
                            const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                           const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search,
+                           const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, const MatchPlan &plan,
                            uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s) {
   CsmParams P;
   memset(&P, 0, sizeof(P));
@@ -205,16 +205,14 @@ int launch_csm_small_match(const float *d_xy, const int32_t *d_offsets, const Id
   P.slot_bytes = L.slot_bytes;
   P.res = spec->res;
   P.inv_res = 1.0 / spec->res;
-  if (csm_small_plane_fits(search)) {
-    P.tile_rows = P.ny;
-    P.n_tiles = 1;
-  } else {
-    NHIP_REQUIRE(csm_small_tiled_fits(search, n_pairs, &P.tile_rows, &P.n_tiles), "csm_match: lattice %d x %d x %d of %d pairs does not "
-                 "fit the small-plane kernel", search->n_theta, search->nx, search->ny, n_pairs);
-  }
+  P.tile_rows = plan.tile_rows;
+  P.n_tiles = plan.n_tiles;
+  NHIP_REQUIRE(P.tile_rows >= 1 && (int64_t)P.tile_rows * P.nx <= 64 * SMALL_PASSES && (int64_t)P.tile_rows * P.n_tiles >= P.ny,
+               "csm_match: a tiling of %d x %d rows does not cover the %d x %d plane in the small-plane kernel", P.n_tiles, P.tile_rows,
+               P.nx, P.ny);
   const int64_t blocks = (int64_t)n_pairs * (int64_t)P.n_theta * (int64_t)P.n_tiles;
   NHIP_REQUIRE(blocks < 0x7fffffffll, "csm_match: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-  if (!(search->flags & SEARCH_I_KEYS_ZERO)) NHIP_TRY_HIP(hipMemsetAsync(d_keys, 0, sizeof(uint64_t) * (size_t)n_pairs, s));
+  if (!plan.keys_zeroed) NHIP_TRY_HIP(hipMemsetAsync(d_keys, 0, sizeof(uint64_t) * (size_t)n_pairs, s));
   timer_begin(NHIP_TIMER_CSM, s);
   const int passes = (P.tile_rows * P.nx + 63) / 64;
 #define NHIP_SMALL_LAUNCH(CB_, PS_) hipLaunchKernelGGL((csm_small_plane_kernel<CB_, PS_>), dim3((uint32_t)blocks), dim3(SMALL_THREADS), 0, s, P)
@@ -227,7 +225,7 @@ int launch_csm_small_match(const float *d_xy, const int32_t *d_offsets, const Id
   }
 #undef NHIP_SMALL_LAUNCH
   timer_end(NHIP_TIMER_CSM, s);
-  if (!(search->flags & SEARCH_I_NO_FINALIZE))
+  if (!plan.keys_undecoded)
     launch_csm_finalize(d_keys, d_pair_src, d_offsets, ids.n_scans, n_pairs, P.nx, P.ny, L, d_out, d_sums, s);
   NHIP_TRY_HIP(hipGetLastError());
   return NHIP_OK;

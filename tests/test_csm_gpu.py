@@ -659,8 +659,10 @@ def test_drop_in_cache_serves_repeated_targets(gpu, small_bag):
 
 def test_drop_in_flat_landscape_first_pose_wins_across_the_parts(gpu, small_bag):
     """A source that scores nothing anywhere (every point beyond the table): every pose of both levels sums to 0 and the
-    FIRST pose of each lattice is the answer -- also across the three workgroups the fine level's rotations are dealt over
-    (their records tie; the host takes the smaller index), and through the small-plane kernel of the coarse level."""
+    FIRST pose of each lattice is the answer -- through the small-plane kernel of the default constructor's coarse level,
+    and across the six workgroups branch and bound deals the (30, 2, 0.15, 0.01) constructor's 27 x 27 coarse level over
+    at a 20 degree restriction (their records tie; the host takes the smaller index).  An empty source the same, and an
+    empty target (nothing to cache: its fine table is built for the call's own coarse optimum)."""
     far = (small_bag.scans[17][::3] + np.float32(500.0)).astype(np.float32)
     b = small_bag.scans[15][::3]
     m = csm.CorrelativeScanMatcher(30, 2, 0.3, 0.01)
@@ -668,9 +670,21 @@ def test_drop_in_flat_landscape_first_pose_wins_across_the_parts(gpu, small_bag)
     want = O.two_level_match(far, b, 0.3, 0.1, math.radians(90), 30.0, 2.0, 0.3, 0.01, cell_bits=16)
     assert _same_call(got, want)
     assert got[0] == pytest.approx(math.log(1e-10))          # the floor: nothing scored
+    m15 = csm.CorrelativeScanMatcher(30, 2, 0.15, 0.01)
+    got = m15.GetTransformation(far, b, 0.3, 0.1, math.radians(20))
+    assert not _dropin_info()["chained"]
+    want = O.two_level_match(far, b, 0.3, 0.1, math.radians(20), 30.0, 2.0, 0.15, 0.01, cell_bits=16)
+    assert _same_call(got, want)
+    assert got[0] == pytest.approx(math.log(1e-10))
     # an empty source: the same
     e = m.GetTransformation(np.zeros((0, 2), np.float32), b, 0.3, 0.1, math.radians(90))
     we = O.two_level_match(np.zeros((0, 2), np.float32), b, 0.3, 0.1, math.radians(90), 30.0, 2.0, 0.3, 0.01, cell_bits=16)
+    assert _same_call(e, we)
+    # an empty target
+    e = m.GetTransformation(small_bag.scans[17][::3], np.zeros((0, 2), np.float32), 0.3, 0.1, math.radians(90))
+    assert not _dropin_info()["chained"]
+    we = O.two_level_match(small_bag.scans[17][::3], np.zeros((0, 2), np.float32), 0.3, 0.1, math.radians(90), 30.0, 2.0, 0.3,
+                           0.01, cell_bits=16)
     assert _same_call(e, we)
 
 
@@ -680,41 +694,37 @@ def _dropin_info():
     return {"coarse_score": out[0], "fine_form": int(out[1]), "chained": out[2] == 1.0, "coarse_itheta": int(out[3])}
 
 
-def test_drop_in_fine_level_forms_return_the_same_floats(gpu, small_bag):
-    """Round 6: the fine level of GetTransformation performs every add in the kernel whose lanes are poses (NHIP_SEARCH_LATENCY:
-    tiles of four rows of the 61 x 61 plane; ~45 us whatever the clouds), both levels chained on the device.  The forms it
-    replaced stay selectable (NHIP_DROPIN_FINE=bnb: the branch-and-bound matcher, which a flat landscape costs milliseconds
-    on the 6000 x 6000 table; =strips: the strip kernels): on a matching pair and on a pair 6 m apart all three return the
-    SAME floats, which are the oracle's -- chained or with the host between the levels (NHIP_DROPIN_CHAIN=0)."""
+def test_drop_in_forms_reached_by_input_return_the_oracles_floats(gpu, small_bag):
+    """The default constructor chains both levels on the device, the fine level through the kernel whose lanes are poses in
+    tiles of rows (NHIP_SEARCH_LATENCY: 61 x 61 plane).  Other constructors reach the other flows by input:
+    (30, 2, 0.15, 0.01) at a 20 degree restriction has a 27 x 27 coarse lattice that branch and bound deals over six parts,
+    so the levels run one after the other with the host in between; (30, 2, 0.64, 0.01) has a 129 x 129 fine plane, too
+    wide for the tiles, which the strip kernels take.  On a matching pair and on a pair far apart each returns the oracle's
+    floats; the strip kernels on both levels of the default constructor (NHIP_CSM_SMALL=0) return the very same ones."""
     import os
     thin = lambda i: small_bag.scans[i][::3]
-    m = csm.CorrelativeScanMatcher(30, 2, 0.3, 0.01)
-    near = (thin(17), thin(15), small_bag.odom[17, 2], small_bag.odom[15, 2], math.radians(90))
     j = int(np.argmax(np.hypot(*(small_bag.truth[:, :2] - small_bag.truth[15, :2]).T)))          # the scan farthest from 15
-    far = (thin(j), thin(15), small_bag.odom[j, 2], small_bag.odom[15, 2], math.radians(90))
+    pairs = {"near": (thin(17), thin(15), small_bag.odom[17, 2], small_bag.odom[15, 2]),
+             "far": (thin(j), thin(15), small_bag.odom[j, 2], small_bag.odom[15, 2])}
     got = {}
+    for ctor, restriction, chained, form in (((30, 2, 0.3, 0.01), 90, True, 2), ((30, 2, 0.15, 0.01), 20, False, 2),
+                                             ((30, 2, 0.64, 0.01), 90, True, 1)):
+        m = csm.CorrelativeScanMatcher(*ctor)
+        for name, args in pairs.items():
+            got[(ctor, name)] = m.GetTransformation(*args, math.radians(restriction))
+            info = _dropin_info()
+            assert info["chained"] is chained and info["fine_form"] == form, (ctor, name, info)
+            want = O.two_level_match(*args, math.radians(restriction), *map(float, ctor), cell_bits=16)
+            assert _same_call(got[(ctor, name)], want), (ctor, name)
+    m = csm.CorrelativeScanMatcher(30, 2, 0.3, 0.01)
+    os.environ["NHIP_CSM_SMALL"] = "0"
     try:
-        for mode, form in (("bnb", 0), ("strips", 1), (None, 2)):
-            if mode is None:
-                os.environ.pop("NHIP_DROPIN_FINE", None)
-            else:
-                os.environ["NHIP_DROPIN_FINE"] = mode
-            for name, args in (("near", near), ("far", far)):
-                got[(mode, name)] = m.GetTransformation(*args)
-                info = _dropin_info()
-                assert info["chained"] and info["fine_form"] == form, (mode, info)
-        os.environ["NHIP_DROPIN_CHAIN"] = "0"
-        for name, args in (("near", near), ("far", far)):
-            got[("unchained", name)] = m.GetTransformation(*args)
-            assert not _dropin_info()["chained"]
+        for name, args in pairs.items():
+            assert m.GetTransformation(*args, math.radians(90)) == got[((30, 2, 0.3, 0.01), name)], name
+            info = _dropin_info()
+            assert info["chained"] and info["fine_form"] == 1, (name, info)
     finally:
-        os.environ.pop("NHIP_DROPIN_FINE", None)
-        os.environ.pop("NHIP_DROPIN_CHAIN", None)
-    for name in ("near", "far"):
-        assert got[("bnb", name)] == got[("strips", name)] == got[(None, name)] == got[("unchained", name)], name
-    for name, args in (("near", near), ("far", far)):
-        want = O.two_level_match(args[0], args[1], args[2], args[3], args[4], 30.0, 2.0, 0.3, 0.01, cell_bits=16)
-        assert _same_call(got[(None, name)], want), name
+        os.environ.pop("NHIP_CSM_SMALL", None)
 
 
 @pytest.mark.parametrize("cell_bits", [16, 8])
@@ -1624,3 +1634,28 @@ def test_handle_builds_rebuild_into_the_buffers_a_released_handle_left(gpu, smal
     c.close()
     st.close()
     _lib.check(lib.nhip_device_pool_configure(4 << 30))   # the library's default cap (per device)
+
+
+def test_latency_search_builds_no_skip_maps_on_a_handle(gpu, small_bag):
+    """A search of a few pairs with NHIP_SEARCH_EXHAUSTIVE | NHIP_SEARCH_LATENCY on 16-bit tables takes the kernel whose
+    lanes are poses in tiles of rows, which reads no skip map: the handle API builds none for it, so the handle's tables
+    stay what its build described and the next build of the same spec and count rebuilds into its buffers."""
+    lib = _lib.load()
+    spec = csm.grid_spec(30.0, 0.05, 2.0, 1e-10, 40, 16)
+    st = csm.ScanTable.from_list(small_bag.scans)
+    ids = np.array([2, 11, 20, 29, 38], dtype=np.int32)
+    _lib.check(lib.nhip_device_pool_release())
+    _lib.check(lib.nhip_device_pool_configure(32 << 30))
+    try:
+        a = csm.LikelihoodGrids(st, ids, spec)
+        src, slot, th0 = np.array([3, 12, 21], np.int32), np.array([0, 1, 2], np.int32), np.array([0.01, -0.02, 0.03])
+        got, sums = csm.match_pairs(st, a, src, slot, th0, csm.search_spec(5, 61, 61, DEG, exhaustive=True, latency=True))
+        bnb, bsums = csm.match_pairs(st, a, src, slot, th0, csm.search_spec(5, 61, 61, DEG))
+        assert got.tobytes() == bnb.tobytes() and np.array_equal(sums, bsums)
+        a.close()
+        b = csm.LikelihoodGrids(st, ids, spec)
+        assert b.was_rebuilt(), "a LATENCY search left the handle's tables as built"
+        b.close()
+    finally:
+        st.close()
+        _lib.check(lib.nhip_device_pool_configure(4 << 30))   # the library's default cap (per device)
