@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- loop-closure candidate pairs/s on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--mode weak|config4]
+  python bench.py --gpus N --steps K --warmup W [--mode weak|config4] [--full]
+
+A plain run does what its headline needs and nothing else: it sets up, warms up, times the K steps, writes
+--dump-outputs if given and prints the result line.  --full adds what takes runs of its own after the timed
+steps: on one GPU the CPU baseline and the secondary legs (other cell width, exhaustive kernels, residuals,
+configs[3] on one GPU, drop-in calls, configs[0], parity against the double table); with N > 1 the
+same workload on one GPU, the point `speedup_vs_one_gpu` is quoted against.
 
 N = 1 runs in this process.  N > 1 without RANK in the environment starts N fresh child ranks
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...`, one per GPU) BEFORE this process
@@ -61,8 +67,12 @@ def parse(argv=None):
                     help="likelihood-table cell width of the headline leg: 16-bit cells keep reported scores within 1e-5 "
                          "relative of an unquantised table (the north star's tolerance); 8-bit cells are the faster "
                          "path for callers that only gate on a threshold (secondary.csm_u8)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the cpu_baseline leg (0 = skip)")
-    ap.add_argument("--no-resid", action="store_true", help="skip the secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs that take runs of their own (see extra_legs): the CPU "
+                         "baseline and the secondary measurements on one GPU, the one-GPU point of the same workload with "
+                         "N > 1; off by default, so a plain run only sets up, warms up, times its steps and prints its line")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the cpu_baseline leg (0 = skip; with --full)")
+    ap.add_argument("--no-resid", action="store_true", help="skip the secondary measurements (with --full)")
     ap.add_argument("--no-cost-model", action="store_true",
                     help="shard by pair count (no per-pair cost estimate in the plan)")
     ap.add_argument("--launch-order", choices=["target", "weight"], default="target",
@@ -81,7 +91,8 @@ def parse(argv=None):
                          "2.3e-5 on 1,300 pairs)")
     ap.add_argument("--no-drop-in", action="store_true",
                     help="skip the legs that launch the matcher's kernels on lists of other sizes (the single-pair latency leg, "
-                         "the 200-scan loop, configs[3] on one GPU): they would blur a kernel's average in a rocprofv3 --stats summary")
+                         "the 200-scan loop, configs[3] on one GPU): they would blur a kernel's average in a rocprofv3 --stats "
+                         "summary (with --full)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the records of the last timed step (original pair order) as DIR/*.npy: "
                          "best_pose_index (n, 3) float64, score (n,) float32, pair_index (n,) float64; a fixed, seeded sample "
@@ -335,6 +346,16 @@ def scaling_fields(value, one, world, comm_world):
     return dict(one, speedup_vs_one_gpu=value / one["one_gpu_same_workload_pairs_per_s"], rccl_world_size=int(comm_world),
                 scaling_note="speedup_vs_one_gpu = value / one_gpu_same_workload_pairs_per_s: the whole list on rank 0's GPU, timed in "
                              "this run; the --gpus 1 bench line is BASELINE configs[1], another workload")
+
+
+def extra_legs(a, world):
+    """What a run measures after its timed steps besides the headline: nothing without --full.  With --full: the N > 1
+    run's one-GPU point of the same workload, and on one GPU in weak mode the CPU baseline (unless --cpu-seconds 0) and
+    the secondary legs (unless --no-resid)."""
+    one = a.full and world == 1 and a.mode == "weak"
+    return {"one_gpu_same_workload": a.full and world > 1,
+            "cpu_baseline": one and a.cpu_seconds > 0,
+            "secondary": one and not a.no_resid}
 
 
 # ------------------------------------------------------------------------------------------ helpers
@@ -606,12 +627,12 @@ def _pick(d, keys):
 
 
 def compact_line(out, details_path=None):
-    """The ONE stdout line: headline, config, roofline, cpu_baseline, kernel milliseconds, the parity summary and (N > 1)
-    the same-workload scaling fields -- scalars only, below COMPACT_LIMIT bytes.  Everything else (secondary legs, notes,
-    per-rank tables, per-run host phases) is in the details file the line names.  tests/test_bench_line.py builds a line
-    through this function and checks size, keys and strict JSON."""
+    """The ONE stdout line: headline, config, roofline, kernel milliseconds and, from a --full run, cpu_baseline, the
+    parity summary and (N > 1) the same-workload scaling fields -- scalars only, below COMPACT_LIMIT bytes.  Everything
+    else (secondary legs, notes, per-rank tables, per-run host phases) is in the details file the line names.
+    tests/test_bench_line.py builds a line through this function and checks size, keys and strict JSON."""
     c = _pick(out, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-                    "vs_baseline", "dtype", "data"))
+                    "vs_baseline", "dtype", "data", "full"))
     cfg = out.get("config") or {}
     c["config"] = _pick(cfg, ("workload", "mode", "pairs_total", "scans_total", "lattice", "grid", "cell_bytes",
                               "rccl_world_size", "collective_backend", "collective"))
@@ -781,8 +802,9 @@ def worker(a):
     # this rank's block of the gathered table must equal what this rank computed
     got_local = full.index_select(0, torch.from_numpy(shard[0].astype(np.int64)).to(dev))
     assert torch.equal(got_local, m.records()[0]), "all-gather returned a different block for this rank"
+    legs = extra_legs(a, world)
     one = None
-    if world > 1:
+    if legs["one_gpu_same_workload"]:
         # the same list on ONE GPU (rank 0's), timed in this run: the N = 1 point the speed-up is quoted against
         one = one_gpu_same_workload(wl.src, wl.tgt, wl.th0, weights, lambda sh: HipMatcher(wl, sh, dev, a.cell_bits, exact_score=exact), dev,
                                     rank, world, dist if use_dist else None, full)
@@ -854,6 +876,7 @@ def worker(a):
         "score": ("the winning pose's mean log-likelihood on the unquantised table, in double (NHIP_SEARCH_EXACT_SCORE; its kernel "
                   "is inside the timed step)" if exact else "Lf + step * sum / N on the quantised cells"),
         "data": "synthetic",
+        "full": bool(a.full),  # (False: a plain run, none of extra_legs ran)
         "config": config_block(wl.describe(world) + "; 61x81x81 lattice (1 deg / 5 cm over +-30 deg / +-2 m), "
                                "1200x1200 u%d log-likelihood grid at 0.05 m; grid build + match + all-gather" % a.cell_bits,
                                a.mode, wl.n_pairs, wl.n_scans, L.side, cell_bytes, dist.get_world_size() if use_dist else 1,
@@ -885,8 +908,7 @@ def worker(a):
     }
     if one is not None:
         out.update(scaling_fields(out["value"], one, world, dist.get_world_size() if use_dist else 1))
-    legs = world == 1 and a.mode == "weak"
-    if legs and a.cpu_seconds > 0:
+    if legs["cpu_baseline"]:
         try:
             cb, ok = cpu_baseline(wl, shard, got, got_sums, a.cpu_seconds, a.cell_bits)
             cb["gpu_matches_oracle_on_sample"] = ok
@@ -895,7 +917,7 @@ def worker(a):
                 print("PARITY FAILURE: GPU result differs from the oracle on the cpu_baseline sample", file=sys.stderr)
         except Exception as e:
             out["cpu_baseline_error"] = repr(e)
-    if legs and not a.no_resid:
+    if legs["secondary"]:
         sec = out["secondary"] = {}
         recs = {a.cell_bits: (got, got_sums)}  # the branch-and-bound records by cell width
 

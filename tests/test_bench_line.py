@@ -91,3 +91,20 @@ def test_emit_prints_the_line_last_and_writes_the_details(tmp_path, capsys, monk
     assert printed[-1] == line and json.loads(printed[-1])["details"] == "bench_details.json"
     full = json.load(open(tmp_path / "bench_details.json"))
     assert "secondary" in full and full["secondary"]["host_buffer_api"]
+
+
+def test_plain_run_runs_no_extra_legs_and_full_runs_them():
+    """Without --full a run stops after its timed steps (and --dump-outputs): no CPU baseline, no secondary legs, no
+    one-GPU point of an N > 1 run.  --full runs them as before, and the legs' own switches still turn them off."""
+    plain = bench.parse(["--steps", "5", "--warmup", "1"])
+    assert plain.full is False
+    for world in (1, 8):
+        assert not any(bench.extra_legs(plain, world).values())
+    full = bench.parse(["--full"])
+    assert bench.extra_legs(full, 1) == {"one_gpu_same_workload": False, "cpu_baseline": True, "secondary": True}
+    assert bench.extra_legs(full, 8) == {"one_gpu_same_workload": True, "cpu_baseline": False, "secondary": False}
+    assert not any(bench.extra_legs(bench.parse(["--full", "--cpu-seconds", "0", "--no-resid"]), 1).values())
+    assert not any(bench.extra_legs(bench.parse(["--full", "--mode", "config4"]), 1).values())
+    out = _fake()
+    out["full"] = False
+    assert json.loads(bench.compact_line(out))["full"] is False

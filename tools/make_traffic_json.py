@@ -40,7 +40,7 @@ def med(kernel, counter):
     return v[len(v) // 2] if v else None
 
 
-out = {"source": "tools/profile_round.sh: rocprofv3 --pmc passes of `bench.py --steps 3 --warmup 1 --cpu-seconds 0 --no-drop-in`; "
+out = {"source": "tools/profile_round.sh: rocprofv3 --pmc passes of `bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 --no-drop-in`; "
                  "bytes = (FETCH_SIZE*2 + WRITE_SIZE)*1024 per dispatch",
        "kernel_source_hash": kernel_source_hash(),
        "workload": {"mode": "weak", "pairs": 10000, "scans": 1000, "per_target": 10}}

@@ -7,6 +7,6 @@ bash tools/profile_round.sh r06 > $O/r06_profile_round.log 2>&1 || { tail -20 $O
 cp $O/prof_r06/traffic.json profiles/traffic.json
 timeout -k 10 300 python3 tools/ideal_matcher.py all > $O/r06_ideal.log 2>&1 || { tail -20 $O/r06_ideal.log; exit 1; }
 tail -4 $O/r06_ideal.log
-timeout -k 10 500 python3 bench.py --steps 20 --warmup 3 > $O/r06_bench.out 2> $O/r06_bench.err || { tail -20 $O/r06_bench.err; exit 1; }
+timeout -k 10 500 python3 bench.py --full --steps 20 --warmup 3 > $O/r06_bench.out 2> $O/r06_bench.err || { tail -20 $O/r06_bench.err; exit 1; }
 cp bench_details.json $O/r06_bench_details.json
 tail -c 3500 $O/r06_bench.out
