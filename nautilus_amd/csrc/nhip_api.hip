@@ -159,7 +159,6 @@ int make_layout(const nhip_grid_spec_t *spec, GridLayout *L) {
   L->hits_bytes = (((int64_t)L->hits_pitch * (L->S + 2 * HIT_PAD) + 8) + 15) & ~15ll;  // (+ 8: a row's last 64-bit window)
   L->slot_bytes = L->grid_bytes + L->skip_bytes + L->pool_bytes + L->pool4_bytes + L->hi_bytes + L->hits_bytes;
   L->hits_bytes += (128 - (L->slot_bytes & 127)) & 127;  // (every slot starts on a line boundary: see pool4_bytes above)
-  if (const char *sp = tunable("NHIP_GRID_SLOT_PAD")) L->hits_bytes += (int64_t)(atoi(sp) > 0 ? atoi(sp) : 0) * 128;  // (measurement: slot stride vs. channels)
   L->slot_bytes = L->grid_bytes + L->skip_bytes + L->pool_bytes + L->pool4_bytes + L->hi_bytes + L->hits_bytes;
   L->Lf = log(spec->floor_p);
   L->step = -L->Lf / (double)L->levels;

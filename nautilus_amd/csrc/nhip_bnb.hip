@@ -56,6 +56,7 @@
 #if NHIP_BNB_INSTR
 #define csm_bnb_kernel csm_bnb_kernel_instr          // (their own names in profiles)
 #define csm_bnb_rot_kernel csm_bnb_rot_kernel_instr
+#define launchers_product launchers_instr
 #define BNB_STATS(P) ((P).stats)
 #define BNB_TIMELINE(P) ((P).timeline)
 #else
@@ -1999,10 +2000,11 @@ namespace bnb {
 namespace {
 // hipFuncSetAttribute once per instantiation and LDS size reached (not per launch)
 template <int CB, bool PL, bool BR, bool SP = false>
-int launch_main(const BnbParams &P, size_t lds, int64_t blocks, hipStream_t s) {
+int launch_main(const BnbParams &P, const BnbPlan &plan, hipStream_t s) {
   // (the split form's first kernel: its own workgroup size, and the queue's space replaced by the lists' and the order's)
   constexpr int THREADS = SP ? 64 * SPLIT_WAVES : BNB_THREADS;
-  if (SP) lds = lds - (size_t)QCAP * 8 + (size_t)QSPACE_SPLIT * 8;
+  const size_t lds = SP ? (size_t)plan.lds - (size_t)QCAP * 8 + (size_t)QSPACE_SPLIT * 8 : (size_t)plan.lds;
+  const int64_t blocks = (int64_t)P.pairs_per_xcd * 8;
   // (the attribute belongs to the function object of the CURRENT device: one high-water mark per device, so that a host
   //  with one thread per device raises it on each of them)
   constexpr int MAX_DEV = 64;
@@ -2021,12 +2023,12 @@ int launch_main(const BnbParams &P, size_t lds, int64_t blocks, hipStream_t s) {
 // The split form's first part on one batch: bounds + seeds of the by-rotation pairs, the general kernel for the scans
 // that form does not take, the order of the candidates' launch ...
 template <int CB, bool PL>
-int launch_split_a(const BnbParams &P, size_t lds, int64_t blocks, hipStream_t s) {
-  int rc = launch_main<CB, PL, true, true>(P, lds, blocks, s);
+int launch_split_a(const BnbParams &P, const BnbPlan &plan, hipStream_t s) {
+  int rc = launch_main<CB, PL, true, true>(P, plan, s);
   if (rc) return rc;
   // (the general instantiation only has work when some scan does not fit the by-rotation form: a caller that knows its
   //  scan lengths says so -- NHIP_SEARCH_SHORT_SCANS -- and saves the launch of n_pairs workgroups that return at once)
-  if (!P.short_scans && (rc = launch_main<CB, PL, false>(P, lds, blocks, s))) return rc;
+  if (!P.short_scans && (rc = launch_main<CB, PL, false>(P, plan, s))) return rc;
   if (P.ps_ticket)
     hipLaunchKernelGGL(csm_bnb_order_spread_kernel, dim3((uint32_t)((P.n_pairs + ORDER_THREADS - 1) / ORDER_THREADS)), dim3(ORDER_THREADS), 0, s, P);
   else
@@ -2035,59 +2037,47 @@ int launch_split_a(const BnbParams &P, size_t lds, int64_t blocks, hipStream_t s
 }
 
 template <int CB, bool PL>
-int launch_both(const BnbParams &P, size_t lds, int64_t blocks, hipStream_t s) {
+int launch_both(const BnbParams &P, const BnbPlan &plan, hipStream_t s) {
   // both instantiations are launched; a workgroup whose pair belongs to the other one returns at once
   if (!P.general_all) {
-    int rc = launch_main<CB, PL, true>(P, lds, blocks, s);
+    int rc = launch_main<CB, PL, true>(P, plan, s);
     if (rc) return rc;
     if (P.short_scans) return NHIP_OK;
   }
-  return launch_main<CB, PL, false>(P, lds, blocks, s);
+  return launch_main<CB, PL, false>(P, plan, s);
 }
-}  // namespace
 
-#if NHIP_BNB_INSTR
-int launch_bnb_kernels_instr(const BnbParams &P, int cb, bool pool_lds, size_t lds, int64_t blocks, bool second_kernel,
-                             hipStream_t s) {
-#else
-int launch_bnb_kernels(const BnbParams &P, int cb, bool pool_lds, size_t lds, int64_t blocks, bool second_kernel,
-                       hipStream_t s) {
-#endif
+int launch_fused(const BnbParams &P, const BnbPlan &plan, hipStream_t s) {
   int rc;
-  if (cb == 1 && pool_lds) rc = launch_both<1, true>(P, lds, blocks, s);
-  else if (cb == 1) rc = launch_both<1, false>(P, lds, blocks, s);
-  else if (pool_lds) rc = launch_both<2, true>(P, lds, blocks, s);
-  else rc = launch_both<2, false>(P, lds, blocks, s);
+  if (plan.cb == 1 && plan.pool_lds) rc = launch_both<1, true>(P, plan, s);
+  else if (plan.cb == 1) rc = launch_both<1, false>(P, plan, s);
+  else if (plan.pool_lds) rc = launch_both<2, true>(P, plan, s);
+  else rc = launch_both<2, false>(P, plan, s);
   if (rc) return rc;
-  if (second_kernel) {
+  if (plan.second) {
     const uint32_t rot_blocks = 256 * 4;  // four workgroups of four waves per CU; the waves take entries off the lists
-    if (cb == 1) hipLaunchKernelGGL(csm_bnb_rot_kernel<1>, dim3(rot_blocks), dim3(256), 0, s, P);
+    if (plan.cb == 1) hipLaunchKernelGGL(csm_bnb_rot_kernel<1>, dim3(rot_blocks), dim3(256), 0, s, P);
     else hipLaunchKernelGGL(csm_bnb_rot_kernel<2>, dim3(rot_blocks), dim3(256), 0, s, P);
   }
   return NHIP_OK;
 }
 
-#if NHIP_BNB_INSTR
-int launch_bnb_split_a_instr(const BnbParams &P, int cb, bool pool_lds, size_t lds, int64_t blocks, hipStream_t s) {
-#else
-int launch_bnb_split_a(const BnbParams &P, int cb, bool pool_lds, size_t lds, int64_t blocks, hipStream_t s) {
-#endif
-  if (cb == 1 && pool_lds) return launch_split_a<1, true>(P, lds, blocks, s);
-  if (cb == 1) return launch_split_a<1, false>(P, lds, blocks, s);
-  if (pool_lds) return launch_split_a<2, true>(P, lds, blocks, s);
-  return launch_split_a<2, false>(P, lds, blocks, s);
+int launch_split_bounds(const BnbParams &P, const BnbPlan &plan, hipStream_t s) {
+  if (plan.cb == 1 && plan.pool_lds) return launch_split_a<1, true>(P, plan, s);
+  if (plan.cb == 1) return launch_split_a<1, false>(P, plan, s);
+  if (plan.pool_lds) return launch_split_a<2, true>(P, plan, s);
+  return launch_split_a<2, false>(P, plan, s);
 }
 
-// ... and its second: the candidates (on any stream ordered behind the first part of the same batch)
-#if NHIP_BNB_INSTR
-int launch_bnb_split_b_instr(const BnbParams &P, int cb, hipStream_t s) {
-#else
-int launch_bnb_split_b(const BnbParams &P, int cb, hipStream_t s) {
-#endif
-  if (cb == 1) hipLaunchKernelGGL(csm_bnb_cand_kernel<1>, dim3((uint32_t)(8 * P.ps_work_stride)), dim3(CAND_THREADS), 0, s, P);
+// the split form's candidates (on any stream ordered behind the first part of the same batch)
+int launch_split_cands(const BnbParams &P, const BnbPlan &plan, hipStream_t s) {
+  if (plan.cb == 1) hipLaunchKernelGGL(csm_bnb_cand_kernel<1>, dim3((uint32_t)(8 * P.ps_work_stride)), dim3(CAND_THREADS), 0, s, P);
   else hipLaunchKernelGGL(csm_bnb_cand_kernel<2>, dim3((uint32_t)(8 * P.ps_work_stride)), dim3(CAND_THREADS), 0, s, P);
   return NHIP_OK;
 }
+}  // namespace
+
+BnbLaunchers launchers_product() { return {launch_fused, launch_split_bounds, launch_split_cands}; }
 
 }  // namespace bnb
 

@@ -81,18 +81,13 @@ struct BnbParams {
   float inv_res_f;  // RN_f32(1 / res): the single-precision path of the window origins
 };
 
-// Launches the matcher's kernel(s) for one batch: the product build, or (nhip_bnb_instr.hip) the build that honours
-// P.stats / P.timeline / P.debug.  lds: dynamic LDS bytes of csm_bnb_kernel; blocks: its grid.
-int launch_bnb_kernels(const BnbParams &P, int cb, bool pool_lds, size_t lds, int64_t blocks, bool second_kernel,
-                       hipStream_t s);
-int launch_bnb_kernels_instr(const BnbParams &P, int cb, bool pool_lds, size_t lds, int64_t blocks, bool second_kernel,
-                             hipStream_t s);
-// The split form (P.ps_rows set) on one batch: bounds + seeds + the ordering of the pairs by candidates left (a),
-// then the candidates (b; on any stream ordered behind a).
-int launch_bnb_split_a(const BnbParams &P, int cb, bool pool_lds, size_t lds, int64_t blocks, hipStream_t s);
-int launch_bnb_split_a_instr(const BnbParams &P, int cb, bool pool_lds, size_t lds, int64_t blocks, hipStream_t s);
-int launch_bnb_split_b(const BnbParams &P, int cb, hipStream_t s);
-int launch_bnb_split_b_instr(const BnbParams &P, int cb, hipStream_t s);
+// The kernel launches of one batch in each build: launchers_product() (nhip_bnb.hip), launchers_instr()
+// (nhip_bnb_instr.hip: the build that honours P.stats / P.timeline).  split_a: the split form's bounds + seeds + the
+// ordering of the pairs by candidates left; split_b: its candidates (on any stream ordered behind split_a).
+using BnbLaunch = int (*)(const BnbParams &P, const BnbPlan &plan, hipStream_t s);
+struct BnbLaunchers { BnbLaunch fused, split_a, split_b; };
+BnbLaunchers launchers_product();
+BnbLaunchers launchers_instr();
 
 }  // namespace bnb
 }  // namespace nhip

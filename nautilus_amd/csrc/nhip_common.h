@@ -182,6 +182,7 @@ int launch_grid_build(const float *d_xy, const int32_t *d_offsets, int32_t n_sca
                       uint8_t *d_grids, void *d_ws, int64_t ws_bytes, hipStream_t s, bool incremental = false);
 
 // Which kernel matches a list: decided by csm_plan (nhip_csm.hip) and nowhere else; launch_csm_match dispatches on it.
+// For MATCH_BNB, the form of the branch-and-bound run is decided by bnb_plan (nhip_bnb_host.hip) and nowhere else.
 enum MatchForm : int32_t {
   MATCH_BNB,       // the branch-and-bound matcher (nhip_bnb.hip)
   MATCH_POSES,     // every add in the kernel whose lanes are poses (nhip_csm_small.hip): one plane, or tiles of rows
@@ -198,6 +199,21 @@ struct MatchPlan {
 };
 // the plan of a search of n_pairs pairs on these grids (the test hooks NHIP_CSM_EXHAUSTIVE / NHIP_CSM_SMALL are read here)
 MatchPlan csm_plan(const GridLayout &L, const nhip_search_t *search, int32_t n_pairs);
+
+// A branch-and-bound run's form and policies, decided by bnb_plan (nhip_bnb_host.hip; only it reads the NHIP_BNB_* hooks).
+// Forms (ids as nhip_csm_last_launch reports them): one kernel per pair (+ the hand-over kernel when `second`), the split
+// form in one round, in several rounds on the caller's stream, in rounds with the candidates on the helper stream.
+enum BnbForm : int32_t { BNB_FUSED, BNB_SPLIT_ONE, BNB_SPLIT_ROUNDS, BNB_SPLIT_OVERLAP };
+struct BnbPlan {
+  BnbForm form;
+  int32_t n_pairs, cb, levels;
+  bool second, general_all, short_scans, pool_lds, instrumented, stats, timeline;
+  bool sized_split;  // the size rule (bnb_workspace_bytes) gives this list room for the split form
+  uint32_t rot_cap, heavy_min, keep_ranks, split_min, split_max;  // split_max 0: by the round's length
+  int64_t batch, slots, slot_bytes, rounds;  // pairs per round (0: fused), rounds' state the workspace holds, bytes of one
+  int64_t lds, lds_first;
+};
+BnbPlan bnb_plan(const GridLayout &L, const nhip_search_t *search, int32_t n_pairs, int64_t workspace_bytes);
 
 int launch_csm_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
                      const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
