@@ -249,6 +249,12 @@ int nhip_match_to_transform(const nhip_match_t *m, const nhip_grid_spec_t *spec,
                             const nhip_search_t *search, double theta0, int32_t origin_x,
                             int32_t origin_y, float *tx, float *ty, float *theta);
 double nhip_score_from_sum(const nhip_grid_spec_t *spec, int64_t sum, int32_t n_points);
+/* Host helper: the FLOOR of the score gate (nhip_csm_match_gated) for a scan of n_points points,
+ *   floor = max(0, floor(n_points * ((min_score - Lf) / step - 1)))   (Lf = ln floor_p, step = -Lf / 255 or / 65535),
+ * one whole quantisation step per point below the sum min_score implies.  Every pose whose sum is below it scores below
+ * min_score, quantised or exact (NHIP_SEARCH_EXACT_SCORE): a gated search prunes against it from the start.  The kernels
+ * evaluate the same expression.  min_score NaN or n_points < 0: NHIP_ERR_ARG; -INFINITY: 0. */
+int nhip_csm_gate_floor(const nhip_grid_spec_t *spec, double min_score, int32_t n_points, int32_t *floor_sum);
 
 /* ------------------------------------------------------------------ device-pointer API */
 /* K1: build likelihood grids for n_targets scans (scan ids in d_target_ids) into
@@ -298,6 +304,23 @@ int nhip_csm_match_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_sc
                        const double *d_delta_cs, const int32_t *d_pair_origin, int32_t n_pairs,
                        const nhip_search_t *search, uint64_t *d_keys, nhip_match_t *d_out,
                        int32_t *d_sums, void *d_workspace, int64_t workspace_bytes, void *stream);
+/* The same match with a SCORE GATE: the caller's csm_score_threshold (default_config.lua:84-85, "above -5 => success").
+ * Let rec / sum be what nhip_csm_match_dev returns for the same arguments.  The gated call returns
+ *   - rec and sum unchanged when (double)rec.score >= min_score;
+ *   - otherwise the REJECTED record {itheta = ix = iy = -1, score = -INFINITY} and sum -1.
+ * This holds in every form the matcher runs in (branch and bound fused or split, with or without the hand-over kernel; the
+ * strip kernels; NHIP_SEARCH_LATENCY), with or without NHIP_SEARCH_EXACT_SCORE and d_pair_origin.  A pair whose ids are out
+ * of range still makes nhip_dev_status() report the error; its record (floor score) is gated like any other.
+ * min_score = -INFINITY: the gate is off -- records, sums and nhip_csm_last_launch byte-identical to nhip_csm_match_dev's,
+ * which is this call with -INFINITY.  min_score NaN: NHIP_ERR_ARG, nothing is written.  The gate never changes which form
+ * runs.  What it saves: branch and bound starts each pair's best at the floor (nhip_csm_gate_floor), so blocks whose bound
+ * is below it are pruned at once, and a pair whose highest bound is below it is settled right after its bounds. */
+int nhip_csm_match_gated_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const uint8_t *d_grids,
+                             int32_t n_grids, const nhip_grid_spec_t *spec, const int32_t *d_pair_src,
+                             const int32_t *d_pair_slot, const double *d_rot0_cs,
+                             const double *d_delta_cs, const int32_t *d_pair_origin, int32_t n_pairs,
+                             const nhip_search_t *search, uint64_t *d_keys, nhip_match_t *d_out,
+                             int32_t *d_sums, void *d_workspace, int64_t workspace_bytes, void *stream, double min_score);
 int64_t nhip_csm_workspace_bytes(int32_t n_pairs);
 /* The form the calling thread's last branch-and-bound match took (diagnostic; every form returns the same records):
  * out[0] = 0 one kernel per pair from start to end (+ the hand-over kernel when out[5]), 1 split form in one round,
@@ -315,7 +338,8 @@ int nhip_bnb_stats(uint64_t *evaluated, uint64_t *total);
  * sub-block bounds, 4 x 4 sub-blocks evaluated exactly}; out[4..10] = shader-clock sums of the matcher's kernel:
  * wave time in the candidate phase, of which window origins / sub-block bounds / exact sums, the slowest wave of
  * each pair, seed phase and bound phase (per workgroup); out[11..13] further clocks, out[14] = poses of 16-bit grids whose exact
- * sums were read from the 16-bit image (the rest was settled on the plane of high bytes); (synchronises; resets) */
+ * sums were read from the 16-bit image (the rest was settled on the plane of high bytes); out[15] = pairs a score gate
+ * settled right after their bounds (nhip_csm_match_gated); (synchronises; resets) */
 int nhip_bnb_stats_levels(uint64_t out[16]);
 /* ... and per pair of the last launch (4 x 4 sub-blocks evaluated exactly, a whole block counting four), before
  * nhip_bnb_stats resets the totals */
@@ -479,6 +503,12 @@ int nhip_csm_match(const nhip_scans_t *scans, const nhip_grids_t *grids, const i
                    const int32_t *pair_slot, const double *theta0, const int32_t *pair_origin,
                    int32_t n_pairs, const nhip_search_t *search, nhip_match_t *out,
                    int32_t *out_sums);
+/* ... with the score gate of nhip_csm_match_gated_dev (same contract): a record whose score is below min_score comes back
+ * as {-1, -1, -1, -INFINITY} with sum -1; -INFINITY is nhip_csm_match; NaN is NHIP_ERR_ARG and nothing is written. */
+int nhip_csm_match_gated(const nhip_scans_t *scans, const nhip_grids_t *grids, const int32_t *pair_src,
+                         const int32_t *pair_slot, const double *theta0, const int32_t *pair_origin,
+                         int32_t n_pairs, const nhip_search_t *search, nhip_match_t *out,
+                         int32_t *out_sums, double min_score);
 int nhip_csm_scores(const nhip_scans_t *scans, const nhip_grids_t *grids, int32_t src, int32_t slot,
                     double theta0, int32_t origin_x, int32_t origin_y, const nhip_search_t *search,
                     int32_t *out_sums);

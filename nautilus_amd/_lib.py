@@ -75,6 +75,7 @@ PROTOTYPES = {
     "nhip_match_to_transform": (C.c_int, [_P(Match), _P(GridSpec), _P(Search), _f64, _i32, _i32,
                                           _P(C.c_float), _P(C.c_float), _P(C.c_float)]),
     "nhip_score_from_sum": (_f64, [_P(GridSpec), _i64, _i32]),
+    "nhip_csm_gate_floor": (C.c_int, [_P(GridSpec), _f64, _i32, _P(_i32)]),
     "nhip_dev_status": (C.c_int, [_vp, _P(_i32)]),
     "nhip_host_phases": (C.c_int, [_P(_f64)]),
     "nhip_device_pool_configure": (C.c_int, [_i64]),
@@ -84,6 +85,8 @@ PROTOTYPES = {
     "nhip_grid_rebuild_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(GridSpec), _vp, _vp, _i64, _vp]),
     "nhip_csm_match_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(GridSpec), _vp, _vp, _vp, _vp, _vp, _i32,
                                      _P(Search), _vp, _vp, _vp, _vp, _i64, _vp]),
+    "nhip_csm_match_gated_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(GridSpec), _vp, _vp, _vp, _vp, _vp, _i32,
+                                           _P(Search), _vp, _vp, _vp, _vp, _i64, _vp, _f64]),
     "nhip_csm_workspace_bytes": (_i64, [_i32]),
     "nhip_csm_last_launch": (C.c_int, [_P(_i32)]),
     "nhip_csm_get_transformation_info": (C.c_int, [_vp]),
@@ -120,6 +123,7 @@ PROTOTYPES = {
     "nhip_grids_download_pool4": (C.c_int, [_vp, _i32, _vp]),
     "nhip_grids_download_hits": (C.c_int, [_vp, _i32, _vp]),
     "nhip_csm_match": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _P(Search), _vp, _vp]),
+    "nhip_csm_match_gated": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _P(Search), _vp, _vp, _f64]),
     "nhip_csm_scores": (C.c_int, [_vp, _vp, _i32, _i32, _f64, _i32, _i32, _P(Search), _vp]),
     "nhip_lc_scatter_scores_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
     "nhip_lc_pair_gate_dev": (C.c_int, [_vp, _i32, _vp, _i32, _f64, _i32, _vp, _vp]),

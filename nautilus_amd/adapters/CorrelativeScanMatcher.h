@@ -127,8 +127,11 @@ class CorrelativeScanMatcherBatch {
     float rotation;
   };
 
-  CorrelativeScanMatcherBatch(double scanner_range, double res, const nhip_search_t &search)
-      : search_(search) {
+  // min_score: the caller's csm_score_threshold (CONFIG_csm_score_threshold).  A pair whose score is below it comes back
+  // as {-inf, (0, 0), 0} and the matcher gives up on it early (nhip_csm_match_gated); the pairs it keeps are the ungated
+  // results, bit for bit.  -INFINITY (the default): every pair is matched to its optimum.
+  CorrelativeScanMatcherBatch(double scanner_range, double res, const nhip_search_t &search, double min_score = -INFINITY)
+      : search_(search), min_score_(min_score) {
     spec_ = {scanner_range, res, 2.0, 1e-10, std::max(search.nx, search.ny) / 2, NAUTILUS_HIP_CELL_BITS, 0, 0};
   }
 
@@ -152,10 +155,14 @@ class CorrelativeScanMatcherBatch {
     }
     GridsHandle grids(scans, targets, spec_);
     std::vector<nhip_match_t> m(pairs.size());
-    Check(nhip_csm_match(scans.h, grids.h, src.data(), slot.data(), theta0.data(), nullptr, (int32_t)pairs.size(),
-                         &search_, m.data(), nullptr), "nhip_csm_match");
+    Check(nhip_csm_match_gated(scans.h, grids.h, src.data(), slot.data(), theta0.data(), nullptr, (int32_t)pairs.size(),
+                               &search_, m.data(), nullptr, min_score_), "nhip_csm_match_gated");
     std::vector<Result> out(pairs.size());
     for (size_t i = 0; i < pairs.size(); i++) {
+      if (m[i].itheta < 0) {  // rejected by the gate: no pose to convert
+        out[i] = {-INFINITY, Vector2f(0.0f, 0.0f), 0.0f};
+        continue;
+      }
       float tx, ty, th;
       Check(nhip_match_to_transform(&m[i], &spec_, &search_, theta0[i], 0, 0, &tx, &ty, &th), "nhip_match_to_transform");
       out[i] = {(double)m[i].score, Vector2f(tx, ty), th};
@@ -166,6 +173,7 @@ class CorrelativeScanMatcherBatch {
  private:
   nhip_grid_spec_t spec_;
   nhip_search_t search_;
+  double min_score_;
 };
 
 #endif  // NAUTILUS_HIP_CORRELATIVE_SCAN_MATCHER_H_

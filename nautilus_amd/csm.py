@@ -183,8 +183,13 @@ class LikelihoodGrids:
     __del__ = close
 
 
-def match_pairs(scans, grids, pair_src, pair_slot, theta0, search, pair_origin=None):
-    """Batched GetTransformation.  Returns (matches MATCH_DTYPE[n], sums int32[n])."""
+def match_pairs(scans, grids, pair_src, pair_slot, theta0, search, pair_origin=None, min_score=None):
+    """Batched GetTransformation.  Returns (matches MATCH_DTYPE[n], sums int32[n]).
+
+    min_score: None matches every pair to its optimum (nhip_csm_match).  A number is the caller's csm_score_threshold
+    (nhip_csm_match_gated): a record whose score is below it comes back rejected -- indices -1, score -inf, sum -1 (see
+    rejected()) -- and the matcher prunes the poses it would reject from the start; the records it keeps are the ungated
+    ones, bit for bit."""
     pair_src = np.ascontiguousarray(pair_src, dtype=np.int32)
     pair_slot = np.ascontiguousarray(pair_slot, dtype=np.int32)
     theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
@@ -196,9 +201,25 @@ def match_pairs(scans, grids, pair_src, pair_slot, theta0, search, pair_origin=N
         org = np.ascontiguousarray(pair_origin, dtype=np.int32).reshape(n, 2)
     out = np.zeros(n, dtype=MATCH_DTYPE)
     sums = np.zeros(n, dtype=np.int32)
-    check(_lib.load().nhip_csm_match(scans._h, grids._h, ptr(pair_src), ptr(pair_slot), ptr(theta0),
-                                     ptr(org), n, C.byref(search), ptr(out), ptr(sums)))
+    if min_score is None:
+        check(_lib.load().nhip_csm_match(scans._h, grids._h, ptr(pair_src), ptr(pair_slot), ptr(theta0),
+                                         ptr(org), n, C.byref(search), ptr(out), ptr(sums)))
+    else:
+        check(_lib.load().nhip_csm_match_gated(scans._h, grids._h, ptr(pair_src), ptr(pair_slot), ptr(theta0),
+                                               ptr(org), n, C.byref(search), ptr(out), ptr(sums), float(min_score)))
     return out, sums
+
+
+def rejected(matches):
+    """Mask of the records a gated match_pairs rejected (itheta -1)."""
+    return np.asarray(matches)["itheta"] < 0
+
+
+def gate_floor(spec, min_score, n_points):
+    """The smallest sum a gated search keeps looking for on a scan of n_points points (nhip_csm_gate_floor)."""
+    out = C.c_int32(0)
+    check(_lib.load().nhip_csm_gate_floor(C.byref(spec), float(min_score), int(n_points), C.byref(out)))
+    return out.value
 
 
 def bnb_stats():
@@ -215,7 +236,8 @@ def bnb_stats_levels():
     return {"blocks_whole": v[0], "blocks_total": v[1], "candidates_refined": v[2], "sub_blocks": v[3],
             "clk_wave_phase3": v[4], "clk_origins": v[5], "clk_sub_bounds": v[6], "clk_exact": v[7],
             "clk_slowest_wave": v[8], "clk_seeds": v[9], "clk_bounds": v[10], "clk_wave_phase3_100MHz": v[11],
-            "pairs_handed_over": v[12], "clk_wave_second_kernel": v[13], "pose_evals16": v[14]}
+            "pairs_handed_over": v[12], "clk_wave_second_kernel": v[13], "pose_evals16": v[14],
+            "pairs_settled_by_gate": v[15]}
 
 
 def score_volume(scans, grids, src, slot, theta0, search, origin=(0, 0)):

@@ -12,6 +12,7 @@
 #include <mutex>
 
 #include "nhip_common.h"
+#include "nhip_csm_shared.h"  // (the score gate's floor)
 
 namespace nhip {
 
@@ -638,6 +639,17 @@ double nhip_score_from_sum(const nhip_grid_spec_t *spec, int64_t sum, int32_t n_
   return Lf + u;
 }
 
+int nhip_csm_gate_floor(const nhip_grid_spec_t *spec, double min_score, int32_t n_points, int32_t *floor_sum) {
+  NHIP_REQUIRE(spec && floor_sum, "csm_gate_floor: null argument");
+  NHIP_REQUIRE(!std::isnan(min_score), "csm_gate_floor: min_score is NaN");
+  NHIP_REQUIRE(n_points >= 0, "csm_gate_floor: n_points %d < 0", n_points);
+  GridLayout L;
+  const int rc = make_layout(spec, &L);
+  if (rc) return rc;
+  *floor_sum = gate_floor(ScoreGate{min_score, L.Lf, L.step}, n_points);
+  return NHIP_OK;
+}
+
 // ---------------------------------------------------------------- device-pointer API
 int nhip_grid_build_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const int32_t *d_target_ids,
                         int32_t n_targets, const nhip_grid_spec_t *spec, uint8_t *d_grids,
@@ -675,8 +687,20 @@ int nhip_csm_match_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_sc
                        const double *d_delta_cs, const int32_t *d_pair_origin, int32_t n_pairs,
                        const nhip_search_t *search, uint64_t *d_keys, nhip_match_t *d_out,
                        int32_t *d_sums, void *d_workspace, int64_t workspace_bytes, void *stream) {
+  return nhip_csm_match_gated_dev(d_xy, d_offsets, n_scans, d_grids, n_grids, spec, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
+                                  d_pair_origin, n_pairs, search, d_keys, d_out, d_sums, d_workspace, workspace_bytes, stream,
+                                  -INFINITY);
+}
+
+int nhip_csm_match_gated_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const uint8_t *d_grids,
+                             int32_t n_grids, const nhip_grid_spec_t *spec, const int32_t *d_pair_src,
+                             const int32_t *d_pair_slot, const double *d_rot0_cs,
+                             const double *d_delta_cs, const int32_t *d_pair_origin, int32_t n_pairs,
+                             const nhip_search_t *search, uint64_t *d_keys, nhip_match_t *d_out,
+                             int32_t *d_sums, void *d_workspace, int64_t workspace_bytes, void *stream, double min_score) {
   int rc = require_device();
   if (rc) return rc;
+  NHIP_REQUIRE(!std::isnan(min_score), "csm_match_dev: min_score is NaN");
   NHIP_REQUIRE(d_xy && d_offsets && d_grids && d_pair_src && d_pair_slot && d_rot0_cs && d_delta_cs &&
                    d_keys && d_out && search,
                "csm_match_dev: null pointer");
@@ -688,7 +712,7 @@ int nhip_csm_match_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_sc
   if (rc) return rc;
   const IdBounds ids = {n_scans, n_grids, dev_status()};
   return launch_csm_match(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs,
-                          d_delta_cs, d_pair_origin, n_pairs, search, csm_plan(L, search, n_pairs), d_keys, d_out, d_sums,
+                          d_delta_cs, d_pair_origin, n_pairs, search, csm_plan(L, search, n_pairs), min_score, d_keys, d_out, d_sums,
                           static_cast<hipStream_t>(stream), d_workspace, workspace_bytes);
 }
 
@@ -1133,8 +1157,16 @@ int nhip_csm_match(const nhip_scans_t *scans, const nhip_grids_t *grids, const i
                    const int32_t *pair_slot, const double *theta0, const int32_t *pair_origin,
                    int32_t n_pairs, const nhip_search_t *search, nhip_match_t *out,
                    int32_t *out_sums) {
+  return nhip_csm_match_gated(scans, grids, pair_src, pair_slot, theta0, pair_origin, n_pairs, search, out, out_sums, -INFINITY);
+}
+
+int nhip_csm_match_gated(const nhip_scans_t *scans, const nhip_grids_t *grids, const int32_t *pair_src,
+                         const int32_t *pair_slot, const double *theta0, const int32_t *pair_origin,
+                         int32_t n_pairs, const nhip_search_t *search, nhip_match_t *out,
+                         int32_t *out_sums, double min_score) {
   int rc = require_device();
   if (rc) return rc;
+  NHIP_REQUIRE(!std::isnan(min_score), "csm_match: min_score is NaN");
   NHIP_REQUIRE(scans && grids && search && n_pairs >= 0, "csm_match: bad arguments");
   NHIP_REQUIRE(n_pairs == 0 || (pair_src && pair_slot && theta0 && out), "csm_match: null array");
   phases_reset();
@@ -1208,7 +1240,7 @@ int nhip_csm_match(const nhip_scans_t *scans, const nhip_grids_t *grids, const i
                         static_cast<const uint8_t *>(grids->grids.p), &spec_now, grids->L,
                         static_cast<const int32_t *>(d_src.p), static_cast<const int32_t *>(d_slot.p),
                         static_cast<const double *>(d_rot0.p), static_cast<const double *>(d_delta.p),
-                        pair_origin ? static_cast<const int32_t *>(d_org.p) : nullptr, n_pairs, search, plan,
+                        pair_origin ? static_cast<const int32_t *>(d_org.p) : nullptr, n_pairs, search, plan, min_score,
                         static_cast<uint64_t *>(d_keys.p), static_cast<nhip_match_t *>(d_out.p),
                         static_cast<int32_t *>(d_sums.p), nullptr, d_ws.p, ws_bytes);
   if (rc) return rc;
@@ -1573,7 +1605,7 @@ int dropin_enqueue(DropInScratch &S, int32_t n_a, const DropInLevel &v, const nh
                           static_cast<const uint8_t *>(v.g->grids.p), &spec_now, v.g->L, static_cast<const int32_t *>(S.idx.p),
                           static_cast<const int32_t *>(S.idx.p) + DROPIN_PARTS_MAX, reinterpret_cast<const double *>(dp + 16),
                           static_cast<const double *>(d_delta), with_origin ? reinterpret_cast<const int32_t *>(dp + 144) : nullptr,
-                          v.parts, &part, v.plan, static_cast<uint64_t *>(d_keys), reinterpret_cast<nhip_match_t *>(dr),
+                          v.parts, &part, v.plan, -INFINITY, static_cast<uint64_t *>(d_keys), reinterpret_cast<nhip_match_t *>(dr),
                           reinterpret_cast<int32_t *>(dr + 128), nullptr, d_ws, (int64_t)ws_bytes,
                           v.parts > 1 ? reinterpret_cast<const int32_t *>(dp + 208) : nullptr);
 }

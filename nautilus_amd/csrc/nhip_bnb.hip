@@ -1428,6 +1428,7 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : BNB_THREADS, SPLIT ? SPL
   uint32_t *s_cnt = reinterpret_cast<uint32_t *>(s_best + 1);
   uint32_t *s_qn = s_cnt + 1, *s_qhead = s_cnt + 2;
   unsigned long long *s_slow = s_best + 4;  // (stats: the slowest wave's time in the candidate phase)
+  uint32_t *s_top = s_cnt + 8;              // (score gate: the workgroup's highest bound)
   // phase 1 only: per wave a ring of LIST_ENTRIES run-length entries, in the queue's space
   uint32_t *s_list = reinterpret_cast<uint32_t *>(s_queue);
   static_assert(BNB_WAVES * LIST_ENTRIES * 4 <= QCAP * 4, "the run lists fit the first half of the queue");
@@ -1456,8 +1457,11 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : BNB_THREADS, SPLIT ? SPL
   const bool centre_ok = (abs(cx) + P.hx <= P.max_shift) && (abs(cy) + P.hy <= P.max_shift);
   if (BY_ROT != (n_pts <= 64 * OCL && (uint32_t)P.rows < ORG_LIMIT && !P.general_all)) return;  // the other instantiation's pair
 
-  // pose 0 with sum 0 is a lower bound of the optimum (sums are >= 0; if all are 0, pose 0 is the answer)
-  const unsigned long long key0 = 0xffffffffull;
+  // pose 0 with sum 0 is a lower bound of the optimum (sums are >= 0; if all are 0, pose 0 is the answer): key0.  With a
+  // score gate the best starts at the pair's floor key instead -- every pose below the floor is one the caller rejects --
+  // and the kernels that take the pair over from keys[pair] prune against it alike (nhip_csm_shared.h; floor 0: key0)
+  const int32_t gfloor = gate_floor(P.gate, n_pts);
+  const unsigned long long fkey = gate_floor_key(gfloor);
   // (work counters: the instrumented build only.  Round 3 kept them in the general instantiation of the product build
   //  because it hung without them -- see wave_leader() for the cause, which was in the source, not in the counters.)
   unsigned long long *const stats_g = NHIP_BNB_INSTR ? P.stats : nullptr;
@@ -1465,13 +1469,14 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : BNB_THREADS, SPLIT ? SPL
   if (BNB_TIMELINE(P) && threadIdx.x == 0 && pair < BNB_STATS_PAIRS) BNB_TIMELINE(P)[4 * pair] = wall_clock64();
   if (threadIdx.x == 0) {
     *s_slow = 0ull;
-    *s_best = key0;
+    *s_best = fkey;
     s_cnt[0] = s_cnt[3] = s_cnt[4] = s_cnt[5] = 0u;
+    s_top[0] = 0u;
     *s_qn = 0u;
     *s_qhead = 0u;
   }
   if (!centre_ok || n_pts <= 0) {  // (a centre the stored border cannot cover scores nothing)
-    if (threadIdx.x == 0) P.keys[pair] = key0;
+    if (threadIdx.x == 0) P.keys[pair] = fkey;
     return;
   }
   if (POOL_LDS) {  // the target's pooled table -> LDS
@@ -1526,6 +1531,24 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : BNB_THREADS, SPLIT ? SPL
   for (int m = 32; m >= 1; m >>= 1) {
     const unsigned long long o = shfl_xor_u64b(wbest, m);
     wbest = o > wbest ? o : wbest;
+  }
+  if (gfloor > 0) {  // (score gate; uniform over the workgroup)
+    // no bound of the pair reaches the floor: no pose can be kept, the pair is settled -- no seeds, nothing handed over,
+    // no candidates left for the split form's second kernel (its counts stay the zeros the host wrote)
+    if (wave_leader(lane)) atomicMax(s_top, (uint32_t)(wbest >> 32));
+    __syncthreads();
+    if (*s_top < (uint32_t)gfloor) {
+      if (threadIdx.x == 0) {
+        P.keys[pair] = fkey;
+        if (stats_g) {
+          atomicAdd(&stats_g[1], (unsigned long long)(P.n_theta * P.nbx * P.nby));
+          atomicAdd(&stats_g[15], 1ull);  // pairs settled after their bounds
+        }
+      }
+      return;
+    }
+    // a wave's seed below the floor cannot raise the best: skipped
+    if ((uint32_t)(wbest >> 32) < (uint32_t)gfloor) wbest = 0ull;
   }
   // (2) seed: the wave's highest-bound block, evaluated exactly
   uint32_t n_work[4] = {0u, 0u, 0u, 0u};

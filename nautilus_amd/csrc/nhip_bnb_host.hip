@@ -353,7 +353,7 @@ static int run_rounds(const BnbParams &P, const BnbPlan &plan, const BnbLauncher
 int launch_csm_bnb(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
                    const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
                    const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                   const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search,
+                   const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, double min_score,
                    uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
                    void *d_workspace, int64_t workspace_bytes, const int32_t *d_pair_kbase) {
   NHIP_REQUIRE(bnb_fits(L, search), "csm_match: lattice %d x %d x %d beyond the branch-and-bound matcher's envelope",
@@ -376,6 +376,7 @@ int launch_csm_bnb(const float *d_xy, const int32_t *d_offsets, const IdBounds &
   P.pair_origin = d_pair_origin;
   P.pair_kbase = d_pair_kbase;
   P.keys = reinterpret_cast<unsigned long long *>(d_keys);
+  P.gate = {min_score, L.Lf, L.step};  // (a kernel parameter only: the plan does not read it)
   int rc = instr_buffers(plan, P, s);
   if (rc) return rc;
   if (plan.second) {  // (the hand-over lists in the workspace)
@@ -393,7 +394,7 @@ int launch_csm_bnb(const float *d_xy, const int32_t *d_offsets, const IdBounds &
   }
   if (rc) return rc;
   NHIP_TRY_HIP(hipGetLastError());
-  launch_csm_finalize(d_keys, d_pair_src, d_offsets, ids.n_scans, n_pairs, P.nx, P.ny, L, d_out, d_sums, s);
+  launch_csm_finalize(d_keys, d_pair_src, d_offsets, ids.n_scans, n_pairs, search, L, min_score, d_out, d_sums, s);
   NHIP_TRY_HIP(hipGetLastError());
   return NHIP_OK;
 }

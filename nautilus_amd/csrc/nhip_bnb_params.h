@@ -2,6 +2,7 @@
 // nhip_bnb.hip (the product kernels) and nhip_bnb_instr.hip (the same kernels with their instrumentation compiled in).
 #pragma once
 #include "nhip_common.h"
+#include "nhip_csm_shared.h"  // (ScoreGate)
 
 namespace nhip {
 namespace bnb {
@@ -79,6 +80,7 @@ struct BnbParams {
   int32_t t16_tpr;
   double res, inv_res;
   float inv_res_f;  // RN_f32(1 / res): the single-precision path of the window origins
+  ScoreGate gate;   // the caller's min_score (nhip_csm_match_gated): a pair's best starts at its floor key (nhip_csm_shared.h)
 };
 
 // The kernel launches of one batch in each build: launchers_product() (nhip_bnb.hip), launchers_instr()

@@ -219,14 +219,14 @@ int launch_csm_match(const float *d_xy, const int32_t *d_offsets, const IdBounds
                      const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
                      const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
                      const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, const MatchPlan &plan,
-                     uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
+                     double min_score, uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
                      void *d_workspace = nullptr, int64_t workspace_bytes = 0, const int32_t *d_pair_kbase = nullptr);
 
 // branch-and-bound matcher (nhip_bnb.hip); the lattice is one bnb_fits takes (csm_plan chose it)
 int launch_csm_bnb(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
                    const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
                    const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                   const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search,
+                   const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, double min_score,
                    uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
                    void *d_workspace = nullptr, int64_t workspace_bytes = 0, const int32_t *d_pair_kbase = nullptr);
 int64_t bnb_workspace_bytes(int32_t n_pairs);
@@ -237,8 +237,11 @@ int bnb_stats_read(unsigned long long out[16]);
 int bnb_timeline_read(unsigned long long *out, int32_t n);
 int bnb_timeline_cand_read(unsigned long long *out, int32_t n);
 int bnb_stats_per_pair(unsigned long long *out, int32_t n);
+// decodes the keys into records and sums and applies the score gate (min_score -INFINITY: off); with NHIP_SEARCH_EXACT_SCORE
+// in search->flags only the floor on the sums, the exact-score pass gates the scores
 void launch_csm_finalize(const uint64_t *d_keys, const int32_t *d_pair_src, const int32_t *d_offsets, int32_t n_scans, int32_t n_pairs,
-                         int32_t nx, int32_t ny, const GridLayout &L, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s);
+                         const nhip_search_t *search, const GridLayout &L, double min_score, nhip_match_t *d_out, int32_t *d_sums,
+                         hipStream_t s);
 
 int launch_csm_scores(const float *d_xy, const int32_t *d_offsets, const uint8_t *d_grids,
                       const nhip_grid_spec_t *spec, const GridLayout &L, int32_t src, int32_t slot,
@@ -250,7 +253,7 @@ int launch_csm_scores(const float *d_xy, const int32_t *d_offsets, const uint8_t
 int launch_csm16_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
                        const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
                        const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                       const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search,
+                       const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, double min_score,
                        uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s);
 int launch_csm16_scores(const float *d_xy, const int32_t *d_offsets, const uint8_t *d_grids,
                         const nhip_grid_spec_t *spec, const GridLayout &L, int32_t src, int32_t slot,
@@ -263,7 +266,7 @@ int launch_csm_small_match(const float *d_xy, const int32_t *d_offsets, const Id
                            const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
                            const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
                            const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, const MatchPlan &plan,
-                           uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s);
+                           double min_score, uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s);
 // skip maps of n finished 16-bit grids (the handle API's late build; occupancy unknown: every map tile is computed)
 int launch_skipmap_build(uint8_t *d_grids, int32_t n_grids, const GridLayout &L, hipStream_t s);
 

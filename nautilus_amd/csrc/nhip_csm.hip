@@ -391,7 +391,7 @@ __global__ __launch_bounds__(CSM_THREADS, NHIP_WAVES_PER_SIMD) void csm_correlat
 __global__ void csm_finalize_kernel(const unsigned long long *__restrict__ keys,
                                     const int32_t *__restrict__ pair_src,
                                     const int32_t *__restrict__ offsets, int32_t n_scans, int32_t n_pairs,
-                                    int32_t nx, int32_t ny, double Lf, double step,
+                                    int32_t nx, int32_t ny, ScoreGate gate, bool score_later,
                                     nhip_match_t *__restrict__ out, int32_t *__restrict__ sums) {
   const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_pairs) return;
@@ -404,11 +404,13 @@ __global__ void csm_finalize_kernel(const unsigned long long *__restrict__ keys,
   m.iy = (int32_t)(lin % (uint32_t)ny);
   m.ix = (int32_t)((lin / (uint32_t)ny) % (uint32_t)nx);
   m.itheta = (int32_t)(lin / ((uint32_t)ny * (uint32_t)nx));
-  double sc = Lf;
-  if (n > 0) sc = __dadd_rn(Lf, __ddiv_rn(__dmul_rn(step, (double)sum), (double)n));
+  double sc = gate.Lf;
+  if (n > 0) sc = __dadd_rn(gate.Lf, __ddiv_rn(__dmul_rn(gate.step, (double)sum), (double)n));
   m.score = __double2float_rn(sc);
-  out[i] = m;
-  if (sums) sums[i] = (int32_t)sum;
+  // (score_later: NHIP_SEARCH_EXACT_SCORE replaces the score and gates it; here only the floor on the sum)
+  const bool rejected = gate_rejects(gate, sum, n, score_later ? INFINITY : m.score);
+  out[i] = rejected ? gate_rejected_record() : m;
+  if (sums) sums[i] = rejected ? -1 : (int32_t)sum;
 }
 
 // ---- NHIP_SEARCH_EXACT_SCORE: the winning pose's score on the UNQUANTISED table -----------------------------------------
@@ -429,7 +431,8 @@ struct ExactParams {
   const int32_t *pair_kbase;  // optional: entry of delta_cs that is pair i's rotation 0 (nhip_bnb_params.h)
   nhip_match_t *out;
   const unsigned long long *keys;  // optional: the search's keys, decoded here (the record's indices, the sum) instead of by csm_finalize_kernel
-  int32_t *sums;                   // with keys: where the integer sums go (may be null)
+  int32_t *sums;                   // where the integer sums go (may be null): all of them with keys, else -1 of a rejected record
+  ScoreGate gate;                  // the caller's min_score: a pair that fails it gets the rejected record
   IdBounds ids;
   int32_t n_pairs, pairs_per_xcd, nx, ny, hx, hy, S, R, hits_pitch, max_shift;
   int64_t slot_bytes, hits_offset;
@@ -479,18 +482,26 @@ __global__ __launch_bounds__(EX_THREADS) void csm_exact_score_kernel(ExactParams
     m.ix = (int32_t)((lin / (uint32_t)P.ny) % (uint32_t)P.nx);
     m.itheta = (int32_t)(lin / ((uint32_t)P.ny * (uint32_t)P.nx));
     m.score = (float)P.Lf;
+    if (gate_rejects(P.gate, (uint32_t)(key >> 32), n_pts, INFINITY)) m = gate_rejected_record();  // (below the floor)
     if (threadIdx.x == 0) {
       P.out[pair] = m;
-      if (P.sums) P.sums[pair] = (int32_t)(uint32_t)(key >> 32);
+      if (P.sums) P.sums[pair] = m.itheta < 0 ? -1 : (int32_t)(uint32_t)(key >> 32);
     }
   } else {
     m = P.out[pair];
   }
+  if (m.itheta < 0) return;  // rejected by its sum already: no raster to read
   {
     // a search centre the stored border cannot cover "scores nothing" in every matcher kernel (sum 0, pose 0, score Lf):
     // the record keeps that score -- the real score at pose 0 would contradict the sum beside it
     const int32_t ox = P.pair_origin ? P.pair_origin[2 * pair] : 0, oy = P.pair_origin ? P.pair_origin[2 * pair + 1] : 0;
-    if (abs(ox) + P.hx > P.max_shift || abs(oy) + P.hy > P.max_shift) return;
+    if (abs(ox) + P.hx > P.max_shift || abs(oy) + P.hy > P.max_shift) {
+      if (threadIdx.x == 0 && gate_rejects(P.gate, 0u, 0, (float)P.Lf)) {
+        P.out[pair] = gate_rejected_record();
+        if (P.sums) P.sums[pair] = -1;
+      }
+      return;
+    }
   }
   const int32_t cx = (P.pair_origin ? P.pair_origin[2 * pair] : 0) + m.ix - P.hx;
   const int32_t cy = (P.pair_origin ? P.pair_origin[2 * pair + 1] : 0) + m.iy - P.hy;
@@ -568,7 +579,13 @@ __global__ __launch_bounds__(EX_THREADS) void csm_exact_score_kernel(ExactParams
     double tot = s_part[0];
 #pragma unroll
     for (int w = 1; w < EX_THREADS / 64; w++) tot += s_part[w];
-    P.out[pair].score = __double2float_rn(n_pts > 0 ? __ddiv_rn(tot, (double)n_pts) : P.Lf);
+    const float score = __double2float_rn(n_pts > 0 ? __ddiv_rn(tot, (double)n_pts) : P.Lf);
+    if (gate_rejects(P.gate, 0u, 0, score)) {  // (the sum passed the floor; the exact score decides)
+      P.out[pair] = gate_rejected_record();
+      if (P.sums) P.sums[pair] = -1;
+    } else {
+      P.out[pair].score = score;
+    }
   }
 }
 
@@ -576,8 +593,8 @@ int launch_csm_exact_score(const float *d_xy, const int32_t *d_offsets, const Id
                            const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
                            const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
                            const int32_t *d_pair_origin, const int32_t *d_pair_kbase, int32_t n_pairs,
-                           const nhip_search_t *search, nhip_match_t *d_out, hipStream_t s,
-                           const uint64_t *d_keys_to_decode = nullptr, int32_t *d_sums = nullptr) {
+                           const nhip_search_t *search, double min_score, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
+                           const uint64_t *d_keys_to_decode = nullptr) {
   NHIP_REQUIRE(L.R <= 15, "exact score: blur radius %d > 15", L.R);
   GridTables T;
   int rc = make_tables(spec, L, &T);
@@ -614,6 +631,7 @@ int launch_csm_exact_score(const float *d_xy, const int32_t *d_offsets, const Id
   P.K2 = (double)L.K * (double)L.K;
   P.floor_p = spec->floor_p;
   P.Lf = L.Lf;
+  P.gate = {min_score, L.Lf, L.step};
   for (int i = 0; i <= 2 * L.R; i++) P.taps[i] = T.taps[i];
   timer_begin(NHIP_TIMER_EXACT_SCORE, s);
   if (L.R == 6) hipLaunchKernelGGL(csm_exact_score_kernel<13>, dim3(8u * (uint32_t)P.pairs_per_xcd), dim3(EX_THREADS), 0, s, P);  // sigma = 2
@@ -689,17 +707,19 @@ MatchPlan csm_plan(const GridLayout &L, const nhip_search_t *search, int32_t n_p
 }
 
 void launch_csm_finalize(const uint64_t *d_keys, const int32_t *d_pair_src, const int32_t *d_offsets, int32_t n_scans, int32_t n_pairs,
-                         int32_t nx, int32_t ny, const GridLayout &L, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s) {
+                         const nhip_search_t *search, const GridLayout &L, double min_score, nhip_match_t *d_out, int32_t *d_sums,
+                         hipStream_t s) {
+  const ScoreGate gate = {min_score, L.Lf, L.step};
   hipLaunchKernelGGL(csm_finalize_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, s,
-                     reinterpret_cast<const unsigned long long *>(d_keys), d_pair_src, d_offsets, n_scans, n_pairs, nx, ny, L.Lf,
-                     L.step, d_out, d_sums);
+                     reinterpret_cast<const unsigned long long *>(d_keys), d_pair_src, d_offsets, n_scans, n_pairs, search->nx,
+                     search->ny, gate, (search->flags & NHIP_SEARCH_EXACT_SCORE) != 0, d_out, d_sums);
 }
 
 // the strip kernels, 8-bit cells (the 16-bit ones: nhip_csm16.hip)
 static int launch_csm8_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
                              const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
                              const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                             const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search,
+                             const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, double min_score,
                              uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s) {
   CsmParams P;
   fill_params(P, spec, L, search);
@@ -725,8 +745,7 @@ static int launch_csm8_match(const float *d_xy, const int32_t *d_offsets, const 
   else
     hipLaunchKernelGGL((csm_correlate_kernel<false, false>), dim3((uint32_t)blocks), dim3(CSM_THREADS), 0, s, P);
   timer_end(NHIP_TIMER_CSM, s);
-  hipLaunchKernelGGL(csm_finalize_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, s, P.keys,
-                     d_pair_src, d_offsets, ids.n_scans, n_pairs, P.nx, P.ny, L.Lf, L.step, d_out, d_sums);
+  launch_csm_finalize(d_keys, d_pair_src, d_offsets, ids.n_scans, n_pairs, search, L, min_score, d_out, d_sums, s);
   NHIP_TRY_HIP(hipGetLastError());
   return NHIP_OK;
 }
@@ -735,7 +754,7 @@ int launch_csm_match(const float *d_xy, const int32_t *d_offsets, const IdBounds
                      const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
                      const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
                      const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, const MatchPlan &plan,
-                     uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
+                     double min_score, uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
                      void *d_workspace, int64_t workspace_bytes, const int32_t *d_pair_kbase) {
   // (per-pair offsets into the rotation table are the branch-and-bound matcher's: an internal caller that passes them has
   //  made sure the lattice is one it takes)
@@ -749,27 +768,27 @@ int launch_csm_match(const float *d_xy, const int32_t *d_offsets, const IdBounds
   switch (plan.form) {
     case MATCH_BNB:  // the same records, most adds never performed (nhip_bnb.hip)
       rc = launch_csm_bnb(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs, d_pair_origin,
-                          n_pairs, search, d_keys, d_out, d_sums, s, d_workspace, workspace_bytes, d_pair_kbase);
+                          n_pairs, search, min_score, d_keys, d_out, d_sums, s, d_workspace, workspace_bytes, d_pair_kbase);
       break;
     case MATCH_POSES:
       rc = launch_csm_small_match(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
-                                  d_pair_origin, n_pairs, search, plan, d_keys, d_out, d_sums, s);
+                                  d_pair_origin, n_pairs, search, plan, min_score, d_keys, d_out, d_sums, s);
       break;
     case MATCH_STRIPS16:
       rc = launch_csm16_match(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
-                              d_pair_origin, n_pairs, search, d_keys, d_out, d_sums, s);
+                              d_pair_origin, n_pairs, search, min_score, d_keys, d_out, d_sums, s);
       break;
     case MATCH_STRIPS8:
       rc = launch_csm8_match(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
-                             d_pair_origin, n_pairs, search, d_keys, d_out, d_sums, s);
+                             d_pair_origin, n_pairs, search, min_score, d_keys, d_out, d_sums, s);
       break;
   }
   if (rc || !(search->flags & NHIP_SEARCH_EXACT_SCORE)) return rc;
   // (the records are final -- indices and integer sums; the pass replaces their score field.  A search that left its keys
   //  undecoded -- the fine level of a chained call -- has them decoded by this pass.)
   return launch_csm_exact_score(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
-                                d_pair_origin, d_pair_kbase, n_pairs, search, d_out, s, plan.keys_undecoded ? d_keys : nullptr,
-                                plan.keys_undecoded ? d_sums : nullptr);
+                                d_pair_origin, d_pair_kbase, n_pairs, search, min_score, d_out, d_sums, s,
+                                plan.keys_undecoded ? d_keys : nullptr);
 }
 
 int launch_csm_scores(const float *d_xy, const int32_t *d_offsets, const uint8_t *d_grids,

@@ -409,7 +409,7 @@ void fill_params16(CsmParams &P, const nhip_grid_spec_t *spec, const GridLayout 
 int launch_csm16_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
                        const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
                        const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                       const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search,
+                       const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, double min_score,
                        uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s) {
   CsmParams P;
   fill_params16(P, spec, L, search);
@@ -435,7 +435,7 @@ int launch_csm16_match(const float *d_xy, const int32_t *d_offsets, const IdBoun
   else
     hipLaunchKernelGGL((csm_correlate16_kernel<false, false>), dim3((uint32_t)blocks), dim3(THREADS), 0, s, P);
   timer_end(NHIP_TIMER_CSM, s);
-  launch_csm_finalize(d_keys, d_pair_src, d_offsets, ids.n_scans, n_pairs, P.nx, P.ny, L, d_out, d_sums, s);
+  launch_csm_finalize(d_keys, d_pair_src, d_offsets, ids.n_scans, n_pairs, search, L, min_score, d_out, d_sums, s);
   NHIP_TRY_HIP(hipGetLastError());
   return NHIP_OK;
 }

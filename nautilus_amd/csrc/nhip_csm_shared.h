@@ -4,6 +4,41 @@
 #include "nhip_common.h"
 
 namespace nhip {
+
+// ---- the score gate of nhip_csm_match_gated -------------------------------------------
+// A record is kept when (double)score >= min_score; otherwise it is the rejected record {-1, -1, -1, -inf}, sum -1.
+// For a scan of n points, every pose whose sum is below
+//     floor(n) = max(0, floor(n * ((min_score - Lf) / step - 1)))
+// scores below min_score: its quantised score is more than one step below it, and its exact score (NHIP_SEARCH_EXACT_SCORE)
+// at most half a step above the quantised one.  Branch and bound starts its best there and prunes every block whose
+// bound is below it; the host helper nhip_csm_gate_floor and the kernels evaluate this one expression.
+struct ScoreGate {
+  double min_score;  // -INFINITY: the gate is off (floor 0 for every scan, every record kept)
+  double Lf, step;   // the grids' floor score and quantisation step (GridLayout)
+};
+__host__ __device__ inline int32_t gate_floor(const ScoreGate &G, int32_t n_pts) {
+  if (n_pts <= 0) return 0;
+  const double f = floor((double)n_pts * ((G.min_score - G.Lf) / G.step - 1.0));
+  if (!(f > 0.0)) return 0;                                   // (min_score -INFINITY, or at most Lf + step)
+  return f >= 2147483647.0 ? 0x7fffffff : (int32_t)f;       // (above every sum an int32 holds: every pose is rejected)
+}
+// The best key a search starts from: below every pose of sum >= floor, above every pose of a smaller sum.  Floor 0 and 1
+// give key0 = pose 0 with sum 0, where an ungated search starts.
+__host__ __device__ inline unsigned long long gate_floor_key(int32_t floor_sum) {
+  return floor_sum <= 0 ? 0xffffffffull : ((unsigned long long)(uint32_t)(floor_sum - 1) << 32) | 0xffffffffull;
+}
+// The one decision "rejected": a sum below the floor (what branch and bound leaves behind for a pair it gave up on), or a
+// record score below min_score.  `score` = +INFINITY when the score is decided later (the exact-score pass).
+__host__ __device__ inline bool gate_rejects(const ScoreGate &G, uint32_t sum, int32_t n_pts, float score) {
+  return (int64_t)sum < (int64_t)gate_floor(G, n_pts) || (double)score < G.min_score;
+}
+__host__ __device__ inline nhip_match_t gate_rejected_record() {
+  nhip_match_t m;
+  m.itheta = m.ix = m.iy = -1;
+  m.score = -INFINITY;
+  return m;
+}
+
 namespace csm {
 
 struct CsmParams {

@@ -177,7 +177,7 @@ int launch_csm_small_match(const float *d_xy, const int32_t *d_offsets, const Id
                            const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
                            const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
                            const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, const MatchPlan &plan,
-                           uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s) {
+                           double min_score, uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s) {
   CsmParams P;
   memset(&P, 0, sizeof(P));
   P.xy = reinterpret_cast<const float2 *>(d_xy);
@@ -226,7 +226,7 @@ int launch_csm_small_match(const float *d_xy, const int32_t *d_offsets, const Id
 #undef NHIP_SMALL_LAUNCH
   timer_end(NHIP_TIMER_CSM, s);
   if (!plan.keys_undecoded)
-    launch_csm_finalize(d_keys, d_pair_src, d_offsets, ids.n_scans, n_pairs, P.nx, P.ny, L, d_out, d_sums, s);
+    launch_csm_finalize(d_keys, d_pair_src, d_offsets, ids.n_scans, n_pairs, search, L, min_score, d_out, d_sums, s);
   NHIP_TRY_HIP(hipGetLastError());
   return NHIP_OK;
 }
