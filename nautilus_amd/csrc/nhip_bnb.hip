@@ -301,7 +301,7 @@ __device__ __forceinline__ void coarse_rotation(const BnbParams &P, const uint8_
   const int32_t DP = P.pool_pitch;
   const uint32_t zero_a = (uint32_t)(((P.rows + BNB_B - 1) / BNB_B) * DP);  // NB + 1 rows of zeros below the pooled image
   tot[0] = tot[1] = 0u;
-  uint32_t E[NB][3], O[NB][3];  // per block row Y: 12 byte sums = dwords 0..2, even (b0 | b2) and odd (raw, see below)
+  uint32_t E[NB][3], O[NB][3];  // per block row Y: 12 byte sums = dwords 0..2, even (b0 | b2 << 16) and odd (b1 | b3 << 16)
 #pragma unroll
   for (int y = 0; y < NB; y++)
 #pragma unroll
@@ -310,9 +310,12 @@ __device__ __forceinline__ void coarse_rotation(const BnbParams &P, const uint8_
   bool pending = false;           // passes gathered since the last reduction
   uint32_t weight = 0u;           // this lane's run lengths gathered since the last reduction
 
-  // 64 list entries: every lane gathers the 11 x 12 bytes of its entry, weighted by the run length
+  // 64 list entries: every lane gathers the 11 x 12 bytes of its entry, weighted by the run length.  The bytes of dword d
+  // of the window (byte offset s = a & 3 into the aligned words) come out of the pair (w[d + 1], w[d]) by one v_perm_b32
+  // per field: selector bytes s, s + 2 give the even bytes b0 | b2 << 16, s + 1, s + 3 the odd ones b1 | b3 << 16, and
+  // 0x0c a zero byte.  Both fields come out clean: the reduction takes them as they are.
   auto gather = [&](uint32_t a, uint32_t cnt) {
-    const uint32_t sh = (a & 3u) * 8u;
+    const uint32_t se = __umul24(a & 3u, 0x10001u) + 0x0c020c00u, so = se + 0x00010001u;
     const uint32_t *q = reinterpret_cast<const uint32_t *>(pool + (a & ~3u));
 #pragma unroll
     for (int y = 0; y < NB; y++) {
@@ -324,12 +327,9 @@ __device__ __forceinline__ void coarse_rotation(const BnbParams &P, const uint8_
         const u32x4 r4 = __builtin_amdgcn_raw_buffer_load_b128(prs, (int)((a & ~3u) + (uint32_t)(y * DP)), 0, 0);
         w0 = r4.x; w1 = r4.y; w2 = r4.z; w3 = r4.w;
       }
-      const uint32_t n0 = __builtin_amdgcn_alignbit(w1, w0, sh), n1 = __builtin_amdgcn_alignbit(w2, w1, sh);
-      const uint32_t n2 = __builtin_amdgcn_alignbit(w3, w2, sh);
-      // even: b0 | b2 << 16; odd (raw): w >> 8 = b1 + 256 b2 + 65536 b3, repaired at the reduction
-      E[y][0] += __umul24(n0 & M8, cnt); O[y][0] += __umul24(n0 >> 8, cnt);
-      E[y][1] += __umul24(n1 & M8, cnt); O[y][1] += __umul24(n1 >> 8, cnt);
-      E[y][2] += __umul24(n2 & M8, cnt); O[y][2] += __umul24(n2 >> 8, cnt);
+      E[y][0] += __umul24(__builtin_amdgcn_perm(w1, w0, se), cnt); O[y][0] += __umul24(__builtin_amdgcn_perm(w1, w0, so), cnt);
+      E[y][1] += __umul24(__builtin_amdgcn_perm(w2, w1, se), cnt); O[y][1] += __umul24(__builtin_amdgcn_perm(w2, w1, so), cnt);
+      E[y][2] += __umul24(__builtin_amdgcn_perm(w3, w2, se), cnt); O[y][2] += __umul24(__builtin_amdgcn_perm(w3, w2, so), cnt);
     }
   };
   // the transposing reduction of the 128 packed sums (see the layout above); clears the accumulators
@@ -338,10 +338,6 @@ __device__ __forceinline__ void coarse_rotation(const BnbParams &P, const uint8_
     // the hi field of O[y][2] is X = 11 (unused): rows 0..2 carry X = 5, 7, 9 of block row 10 there.
     // R[60..62] = E[10][0..2], R[63] = O[10][0].
     uint32_t R[64];
-#pragma unroll
-    for (int y = 0; y < NB; y++)
-#pragma unroll
-      for (int d = 0; d < 3; d++) O[y][d] -= (E[y][d] >> 16) << 8;  // now b1 | b3 << 16
 #pragma unroll
     for (int y = 0; y < 10; y++)
 #pragma unroll
