@@ -144,7 +144,11 @@ int make_layout(const nhip_grid_spec_t *spec, GridLayout *L) {
   // multiple of 128: slots 1, 2, ... started 16, 32, ... bytes off a line, and the candidates kernel's L2 fetch went from 0.86
   // to 1.39 GB per 10,000 pairs -- profiles/r06_cand_traffic_bisect.txt.)  So the second table is padded to the next line
   // boundary of the slot here, and the raster -- the slot's last part -- below.
-  L->pool4_bytes += (128 - ((L->grid_bytes + L->skip_bytes + L->pool_bytes + L->pool4_bytes) & 127)) & 127;
+  L->skip_offset = L->grid_bytes;
+  L->pool_offset = L->skip_offset + L->skip_bytes;
+  L->pool4_offset = L->pool_offset + L->pool_bytes;
+  L->pool4_bytes += (128 - ((L->pool4_offset + L->pool4_bytes) & 127)) & 127;
+  L->hi_offset = L->pool4_offset + L->pool4_bytes;
   // 16-bit cells: the plane of their high bytes, one byte per cell at the 8-bit pitch.  The matcher sums exact 8 x 8
   // and 4 x 4 blocks on this plane at the cost of 8-bit cells (256 * sum(hi) + 255 * points bounds a pose's sum from
   // above) and reads 16-bit cells only for the poses that bound still admits (nhip_bnb.hip)
@@ -155,12 +159,13 @@ int make_layout(const nhip_grid_spec_t *spec, GridLayout *L) {
   L->t16_tpr = L->cb == 2 ? L->hi_pitch / 8 : 0;
   L->t16_bytes = (int64_t)((L->S + 2 * L->pad + 7) / 8) * L->t16_tpr * (int64_t)HI_TILE_BYTES;
   L->hi_bytes = 2 * L->hi_copy_bytes + L->t16_bytes;  // (the matcher's private planes, all three)
+  L->t16_offset = L->hi_offset + 2 * L->hi_copy_bytes;
+  L->hits_offset = L->hi_offset + L->hi_bytes;
   // the hit raster, one bit per cell + a zero border of HIT_PAD cells: bit rows of whole dwords
   L->hits_pitch = ((L->S + 2 * HIT_PAD + 31) / 32) * 4;
   L->hits_bytes = (((int64_t)L->hits_pitch * (L->S + 2 * HIT_PAD) + 8) + 15) & ~15ll;  // (+ 8: a row's last 64-bit window)
-  L->slot_bytes = L->grid_bytes + L->skip_bytes + L->pool_bytes + L->pool4_bytes + L->hi_bytes + L->hits_bytes;
-  L->hits_bytes += (128 - (L->slot_bytes & 127)) & 127;  // (every slot starts on a line boundary: see pool4_bytes above)
-  L->slot_bytes = L->grid_bytes + L->skip_bytes + L->pool_bytes + L->pool4_bytes + L->hi_bytes + L->hits_bytes;
+  L->hits_bytes += (128 - ((L->hits_offset + L->hits_bytes) & 127)) & 127;  // (every slot starts on a line boundary: see pool4_bytes above)
+  L->slot_bytes = L->hits_offset + L->hits_bytes;
   L->Lf = log(spec->floor_p);
   L->step = -L->Lf / (double)L->levels;
   // integer taps: round(16384 * g_i / sum g)
@@ -710,10 +715,28 @@ int nhip_csm_match_gated_dev(const float *d_xy, const int32_t *d_offsets, int32_
   GridLayout L;
   rc = make_layout(spec, &L);
   if (rc) return rc;
-  const IdBounds ids = {n_scans, n_grids, dev_status()};
-  return launch_csm_match(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs,
-                          d_delta_cs, d_pair_origin, n_pairs, search, csm_plan(L, search, n_pairs), min_score, d_keys, d_out, d_sums,
-                          static_cast<hipStream_t>(stream), d_workspace, workspace_bytes);
+  MatchJob job;
+  job.xy = d_xy;
+  job.offsets = d_offsets;
+  job.ids = {n_scans, n_grids, dev_status()};
+  job.grids = d_grids;
+  job.spec = spec;
+  job.L = &L;
+  job.pair_src = d_pair_src;
+  job.pair_slot = d_pair_slot;
+  job.rot0_cs = d_rot0_cs;
+  job.delta_cs = d_delta_cs;
+  job.pair_origin = d_pair_origin;
+  job.n_pairs = n_pairs;
+  job.search = search;
+  job.min_score = min_score;
+  job.keys = d_keys;
+  job.out = d_out;
+  job.sums = d_sums;
+  job.stream = static_cast<hipStream_t>(stream);
+  job.workspace = d_workspace;
+  job.workspace_bytes = workspace_bytes;
+  return launch_csm_match(job, csm_plan(L, search, n_pairs));
 }
 
 int64_t nhip_csm_workspace_bytes(int32_t n_pairs) { return bnb_workspace_bytes(n_pairs); }
@@ -808,8 +831,17 @@ int nhip_csm_scores_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_s
   GridLayout L;
   rc = make_layout(spec, &L);
   if (rc) return rc;
-  return launch_csm_scores(d_xy, d_offsets, d_grids, spec, L, src, slot, d_rot0_cs, d_delta_cs,
-                           origin_x, origin_y, search, d_sums, static_cast<hipStream_t>(stream));
+  MatchJob job;  // (a score volume is of one pair, passed by value below: no pair arrays, ids, keys or records)
+  job.xy = d_xy;
+  job.offsets = d_offsets;
+  job.grids = d_grids;
+  job.spec = spec;
+  job.L = &L;
+  job.rot0_cs = d_rot0_cs;
+  job.delta_cs = d_delta_cs;
+  job.search = search;
+  job.stream = static_cast<hipStream_t>(stream);
+  return launch_csm_scores(job, src, slot, origin_x, origin_y, d_sums);
 }
 
 int nhip_resid_lidar_dev(int kind, const float *d_corr, const int32_t *d_corr_block,
@@ -1071,8 +1103,7 @@ int nhip_grids_download_hi_plane_copy(const nhip_grids_t *grids, int32_t slot, i
   NHIP_REQUIRE(grids && out && slot >= 0 && slot < grids->n && (copy == 0 || copy == 1), "grids_download_hi_plane: bad arguments");
   const GridLayout &L = grids->L;
   std::vector<uint8_t> raw((size_t)L.hi_bytes);
-  NHIP_TRY_HIP(hipMemcpy(raw.data(), static_cast<const uint8_t *>(grids->grids.p) + (size_t)slot * L.slot_bytes + L.grid_bytes +
-                                         L.skip_bytes + L.pool_bytes + L.pool4_bytes,
+  NHIP_TRY_HIP(hipMemcpy(raw.data(), static_cast<const uint8_t *>(grids->grids.p) + (size_t)slot * L.slot_bytes + L.hi_offset,
                          (size_t)L.hi_bytes, hipMemcpyDeviceToHost));
   const int32_t rows = L.S + 2 * L.pad;
   for (int32_t r = 0; r < rows; r++)
@@ -1086,8 +1117,7 @@ int nhip_grids_download_tiled16(const nhip_grids_t *grids, int32_t slot, uint8_t
   const GridLayout &L = grids->L;
   NHIP_REQUIRE(L.t16_bytes > 0, "grids_download_tiled16: 8-bit grids have no tiled 16-bit copy");
   std::vector<uint8_t> raw((size_t)L.t16_bytes);
-  NHIP_TRY_HIP(hipMemcpy(raw.data(), static_cast<const uint8_t *>(grids->grids.p) + (size_t)slot * L.slot_bytes + L.grid_bytes +
-                                         L.skip_bytes + L.pool_bytes + L.pool4_bytes + 2 * L.hi_copy_bytes,
+  NHIP_TRY_HIP(hipMemcpy(raw.data(), static_cast<const uint8_t *>(grids->grids.p) + (size_t)slot * L.slot_bytes + L.t16_offset,
                          (size_t)L.t16_bytes, hipMemcpyDeviceToHost));
   const int32_t rows = L.S + 2 * L.pad;
   memset(out, 0, (size_t)L.plain_bytes);
@@ -1105,7 +1135,7 @@ int nhip_grids_download_skip_map(const nhip_grids_t *grids, int32_t slot, uint8_
   NHIP_REQUIRE(grids && out && slot >= 0 && slot < grids->n, "grids_download_skip_map: bad arguments");
   NHIP_REQUIRE(grids->L.has_image, "grids_download_skip_map: grids built with NHIP_GRID_NO_IMAGE carry no skip map");
   const GridLayout &L = grids->L;
-  NHIP_TRY_HIP(hipMemcpy(out, static_cast<const uint8_t *>(grids->grids.p) + (size_t)slot * L.slot_bytes + L.grid_bytes,
+  NHIP_TRY_HIP(hipMemcpy(out, static_cast<const uint8_t *>(grids->grids.p) + (size_t)slot * L.slot_bytes + L.skip_offset,
                          (size_t)L.skip_bytes, hipMemcpyDeviceToHost));
   return NHIP_OK;
 }
@@ -1113,7 +1143,7 @@ int nhip_grids_download_skip_map(const nhip_grids_t *grids, int32_t slot, uint8_
 int nhip_grids_download_pool(const nhip_grids_t *grids, int32_t slot, uint8_t *out) {
   NHIP_REQUIRE(grids && out && slot >= 0 && slot < grids->n, "grids_download_pool: bad arguments");
   const GridLayout &L = grids->L;
-  NHIP_TRY_HIP(hipMemcpy(out, static_cast<const uint8_t *>(grids->grids.p) + (size_t)slot * L.slot_bytes + L.grid_bytes + L.skip_bytes,
+  NHIP_TRY_HIP(hipMemcpy(out, static_cast<const uint8_t *>(grids->grids.p) + (size_t)slot * L.slot_bytes + L.pool_offset,
                          (size_t)L.pool_bytes, hipMemcpyDeviceToHost));
   return NHIP_OK;
 }
@@ -1121,8 +1151,7 @@ int nhip_grids_download_pool(const nhip_grids_t *grids, int32_t slot, uint8_t *o
 int nhip_grids_download_hits(const nhip_grids_t *grids, int32_t slot, uint8_t *out) {
   NHIP_REQUIRE(grids && out && slot >= 0 && slot < grids->n, "grids_download_hits: bad arguments");
   const GridLayout &L = grids->L;
-  NHIP_TRY_HIP(hipMemcpy(out, static_cast<const uint8_t *>(grids->grids.p) + (size_t)slot * L.slot_bytes + L.grid_bytes + L.skip_bytes +
-                                  L.pool_bytes + L.pool4_bytes + L.hi_bytes,
+  NHIP_TRY_HIP(hipMemcpy(out, static_cast<const uint8_t *>(grids->grids.p) + (size_t)slot * L.slot_bytes + L.hits_offset,
                          (size_t)L.hits_bytes, hipMemcpyDeviceToHost));
   return NHIP_OK;
 }
@@ -1131,7 +1160,7 @@ int nhip_grids_download_pool4(const nhip_grids_t *grids, int32_t slot, uint8_t *
   NHIP_REQUIRE(grids && out && slot >= 0 && slot < grids->n, "grids_download_pool4: bad arguments");
   const GridLayout &L = grids->L;
   // (rows x pitch: pool4_bytes may hold padding behind the table)
-  NHIP_TRY_HIP(hipMemcpy(out, static_cast<const uint8_t *>(grids->grids.p) + (size_t)slot * L.slot_bytes + L.grid_bytes + L.skip_bytes + L.pool_bytes,
+  NHIP_TRY_HIP(hipMemcpy(out, static_cast<const uint8_t *>(grids->grids.p) + (size_t)slot * L.slot_bytes + L.pool4_offset,
                          (size_t)L.pool4_rows * (size_t)L.pool4_pitch, hipMemcpyDeviceToHost));
   return NHIP_OK;
 }
@@ -1232,17 +1261,30 @@ int nhip_csm_match_gated(const nhip_scans_t *scans, const nhip_grids_t *grids, c
     NHIP_TRY_HIP(hipMemcpy(d_rot0.p, rot0.data(), sizeof(double) * rot0.size(), hipMemcpyHostToDevice));
     NHIP_TRY_HIP(hipMemcpy(d_delta.p, delta.data(), sizeof(double) * delta.size(), hipMemcpyHostToDevice));
   }
-  const IdBounds idb = {scans->n_scans, grids->n, dev_status()};  // (checked on the host above; the kernels check again)
+  MatchJob job;
+  job.xy = static_cast<const float *>(scans->xy.p);
+  job.offsets = static_cast<const int32_t *>(scans->offsets.p);
+  job.ids = {scans->n_scans, grids->n, dev_status()};  // (checked on the host above; the kernels check again)
+  job.grids = static_cast<const uint8_t *>(grids->grids.p);
+  job.spec = &spec_now;
+  job.L = &grids->L;
+  job.pair_src = static_cast<const int32_t *>(d_src.p);
+  job.pair_slot = static_cast<const int32_t *>(d_slot.p);
+  job.rot0_cs = static_cast<const double *>(d_rot0.p);
+  job.delta_cs = static_cast<const double *>(d_delta.p);
+  job.pair_origin = pair_origin ? static_cast<const int32_t *>(d_org.p) : nullptr;
+  job.n_pairs = n_pairs;
+  job.search = search;
+  job.min_score = min_score;
+  job.keys = static_cast<uint64_t *>(d_keys.p);
+  job.out = static_cast<nhip_match_t *>(d_out.p);
+  job.sums = static_cast<int32_t *>(d_sums.p);
+  job.workspace = d_ws.p;
+  job.workspace_bytes = ws_bytes;
   PhaseClock pc_enq(PH_ENQUEUE);  // (to the end of the call minus the phases inside it; nhip_host_phases subtracts nothing:
                                   //  read it as "enqueue + wait + download + frees")
   InFlight inflight;  // (a failure from here on: the DevBufs above wait for the device before they return to the pool)
-  rc = launch_csm_match(static_cast<const float *>(scans->xy.p), static_cast<const int32_t *>(scans->offsets.p), idb,
-                        static_cast<const uint8_t *>(grids->grids.p), &spec_now, grids->L,
-                        static_cast<const int32_t *>(d_src.p), static_cast<const int32_t *>(d_slot.p),
-                        static_cast<const double *>(d_rot0.p), static_cast<const double *>(d_delta.p),
-                        pair_origin ? static_cast<const int32_t *>(d_org.p) : nullptr, n_pairs, search, plan, min_score,
-                        static_cast<uint64_t *>(d_keys.p), static_cast<nhip_match_t *>(d_out.p),
-                        static_cast<int32_t *>(d_sums.p), nullptr, d_ws.p, ws_bytes);
+  rc = launch_csm_match(job, plan);
   if (rc) return rc;
   {
     PhaseClock pc(PH_WAIT);  // (the kernels; the downloads below find them done)
@@ -1282,11 +1324,17 @@ int nhip_csm_scores(const nhip_scans_t *scans, const nhip_grids_t *grids, int32_
     return rc;
   NHIP_TRY_HIP(hipMemcpy(d_rot0.p, rot0, sizeof(rot0), hipMemcpyHostToDevice));
   NHIP_TRY_HIP(hipMemcpy(d_delta.p, delta.data(), sizeof(double) * delta.size(), hipMemcpyHostToDevice));
+  MatchJob job;  // (one pair, passed by value below: no pair arrays, ids, keys or records)
+  job.xy = static_cast<const float *>(scans->xy.p);
+  job.offsets = static_cast<const int32_t *>(scans->offsets.p);
+  job.grids = static_cast<const uint8_t *>(grids->grids.p);
+  job.spec = &grids->spec;
+  job.L = &grids->L;
+  job.rot0_cs = static_cast<const double *>(d_rot0.p);
+  job.delta_cs = static_cast<const double *>(d_delta.p);
+  job.search = search;
   InFlight inflight;
-  rc = launch_csm_scores(static_cast<const float *>(scans->xy.p), static_cast<const int32_t *>(scans->offsets.p),
-                         static_cast<const uint8_t *>(grids->grids.p), &grids->spec, grids->L, src, slot,
-                         static_cast<const double *>(d_rot0.p), static_cast<const double *>(d_delta.p),
-                         origin_x, origin_y, search, static_cast<int32_t *>(d_vol.p), nullptr);
+  rc = launch_csm_scores(job, src, slot, origin_x, origin_y, static_cast<int32_t *>(d_vol.p));
   if (rc) return rc;
   NHIP_TRY_HIP(hipMemcpy(out_sums, d_vol.p, sizeof(int32_t) * vol, hipMemcpyDeviceToHost));  // (synchronises the null stream)
   InFlight::done();
@@ -1480,7 +1528,11 @@ struct DropInScratch {
 //  too -- run before the process's static destructors, i.e. while the HIP runtime is still there)
 static thread_local double t_dropin_info[4] = {0, 0, 0, 0};
 constexpr int DROPIN_CHAIN_ROT_MAX = 512;               // coarse rotations the chained form's table holds
-constexpr size_t DROPIN_UP_BYTES = 256 + 16 * (size_t)DROPIN_CHAIN_ROT_MAX, DROPIN_DOWN_BYTES = 512;
+// the upload block: the coarse level's DropInPar, at DROPIN_UP_TABLE the table; the download block (and DropInScratch::res
+// behind it): the coarse level's DropInRes, the fine level's, the centre the fine search ran at (int32[2])
+constexpr size_t DROPIN_PAR_BYTES = 256, DROPIN_UP_TABLE = DROPIN_PAR_BYTES;
+constexpr size_t DROPIN_UP_BYTES = DROPIN_UP_TABLE + 16 * (size_t)DROPIN_CHAIN_ROT_MAX, DROPIN_DOWN_BYTES = 512;
+constexpr size_t DROPIN_DOWN_RES2 = 256, DROPIN_DOWN_ORIGIN = 480;
 struct ScratchHolder {
   DropInScratch *p = nullptr;
   ~ScratchHolder() {
@@ -1505,8 +1557,8 @@ int scratch_for(int device, int32_t n_a, const nhip_search_t &s1, const nhip_sea
     reset();
     const int32_t zeros[2 * DROPIN_PARTS_MAX] = {0};
     constexpr size_t G = DROPIN_PARTS_MAX;
-    if ((rc = S.par.alloc(256)) || (rc = S.idx.alloc(8 * G)) || (rc = S.keys.alloc(8 * G)) || (rc = S.res.alloc(DROPIN_DOWN_BYTES)) ||
-        (rc = S.ws.alloc((size_t)bnb_workspace_bytes_lists((int32_t)G))) || (rc = S.par2.alloc(256)) ||
+    if ((rc = S.par.alloc(DROPIN_PAR_BYTES)) || (rc = S.idx.alloc(8 * G)) || (rc = S.keys.alloc(8 * G)) || (rc = S.res.alloc(DROPIN_DOWN_BYTES)) ||
+        (rc = S.ws.alloc((size_t)bnb_workspace_bytes_lists((int32_t)G))) || (rc = S.par2.alloc(DROPIN_PAR_BYTES)) ||
         (rc = S.rot1.alloc(DROPIN_UP_BYTES)) || (rc = S.keys2.alloc(8 * G)) ||
         (rc = S.ws2.alloc((size_t)bnb_workspace_bytes_lists((int32_t)G)))) {
       reset();
@@ -1558,12 +1610,14 @@ struct DropInPar {  // the per-call parameter block as the kernels read it (devi
   int32_t org[2 * DROPIN_PARTS_MAX], kb[DROPIN_PARTS_MAX];  // search centre per part, rotation base per part
 };
 static_assert(sizeof(DropInPar) == 240 && offsetof(DropInPar, cs) == 16 && offsetof(DropInPar, org) == 144 &&
-              offsetof(DropInPar, kb) == 208, "DropInPar layout");
+              offsetof(DropInPar, kb) == 208 && sizeof(DropInPar) <= DROPIN_PAR_BYTES, "DropInPar layout");
 struct DropInRes {
   nhip_match_t rec[DROPIN_PARTS_MAX];
   int32_t sums[DROPIN_PARTS_MAX];
 };
 static_assert(sizeof(DropInRes) == 160 && offsetof(DropInRes, sums) == 128, "DropInRes layout");
+static_assert(sizeof(DropInRes) <= DROPIN_DOWN_RES2 && DROPIN_DOWN_RES2 + sizeof(DropInRes) <= DROPIN_DOWN_ORIGIN &&
+              DROPIN_DOWN_ORIGIN + 2 * sizeof(int32_t) <= DROPIN_DOWN_BYTES, "download block layout");
 
 // One level of a call: its search on grids `g` and the plan for it.  The branch-and-bound matcher computes a pair's bounds
 // in the pair's ONE workgroup, eight rotations at a time: a search of 21 rotations is three rounds on one CU while 255 idle.
@@ -1600,14 +1654,27 @@ int dropin_enqueue(DropInScratch &S, int32_t n_a, const DropInLevel &v, const nh
   part.n_theta = v.per;
   // (the host holds the cloud: a source that fits the matcher's by-rotation form saves the launch of the other instantiation)
   if (n_a <= NHIP_SHORT_SCAN_POINTS) part.flags |= NHIP_SEARCH_SHORT_SCANS;
-  const IdBounds idb = {1, v.g->n, dev_status()};  // (the scratch holds one scan; every part reads scan 0, slot 0)
-  return launch_csm_match(static_cast<const float *>(S.xy.p), reinterpret_cast<const int32_t *>(dp), idb,
-                          static_cast<const uint8_t *>(v.g->grids.p), &spec_now, v.g->L, static_cast<const int32_t *>(S.idx.p),
-                          static_cast<const int32_t *>(S.idx.p) + DROPIN_PARTS_MAX, reinterpret_cast<const double *>(dp + 16),
-                          static_cast<const double *>(d_delta), with_origin ? reinterpret_cast<const int32_t *>(dp + 144) : nullptr,
-                          v.parts, &part, v.plan, -INFINITY, static_cast<uint64_t *>(d_keys), reinterpret_cast<nhip_match_t *>(dr),
-                          reinterpret_cast<int32_t *>(dr + 128), nullptr, d_ws, (int64_t)ws_bytes,
-                          v.parts > 1 ? reinterpret_cast<const int32_t *>(dp + 208) : nullptr);
+  MatchJob job;
+  job.xy = static_cast<const float *>(S.xy.p);
+  job.offsets = reinterpret_cast<const int32_t *>(dp + offsetof(DropInPar, off));
+  job.ids = {1, v.g->n, dev_status()};  // (the scratch holds one scan; every part reads scan 0, slot 0)
+  job.grids = static_cast<const uint8_t *>(v.g->grids.p);
+  job.spec = &spec_now;
+  job.L = &v.g->L;
+  job.pair_src = static_cast<const int32_t *>(S.idx.p);
+  job.pair_slot = static_cast<const int32_t *>(S.idx.p) + DROPIN_PARTS_MAX;
+  job.rot0_cs = reinterpret_cast<const double *>(dp + offsetof(DropInPar, cs));
+  job.delta_cs = static_cast<const double *>(d_delta);
+  if (with_origin) job.pair_origin = reinterpret_cast<const int32_t *>(dp + offsetof(DropInPar, org));
+  if (v.parts > 1) job.pair_kbase = reinterpret_cast<const int32_t *>(dp + offsetof(DropInPar, kb));
+  job.n_pairs = v.parts;
+  job.search = &part;
+  job.keys = static_cast<uint64_t *>(d_keys);
+  job.out = reinterpret_cast<nhip_match_t *>(dr + offsetof(DropInRes, rec));
+  job.sums = reinterpret_cast<int32_t *>(dr + offsetof(DropInRes, sums));
+  job.workspace = d_ws;
+  job.workspace_bytes = (int64_t)ws_bytes;
+  return launch_csm_match(job, v.plan);
 }
 
 // the best of the parts' records
@@ -1727,13 +1794,13 @@ int match_chained(DropInScratch &S, const float *pc_a, int32_t n_a, const DropIn
   par1->off[1] = n_a;
   if ((rc = nhip_csm_rot0(&theta0, nullptr, 1, par1->cs))) return rc;
   // what the host would hand the fine level for each coarse rotation k: theta1 = (double)(float)(theta0 + (k - half) * step)
-  double *rot = reinterpret_cast<double *>(up + 256);
+  double *rot = reinterpret_cast<double *>(up + DROPIN_UP_TABLE);
   const int32_t half1 = (s1.n_theta - 1) / 2;
   for (int32_t k = 0; k < s1.n_theta; k++) {
     const double theta1 = (double)(float)(theta0 + (double)(k - half1) * s1.theta_step);
     if ((rc = nhip_csm_rot0(&theta1, nullptr, 1, rot + 2 * k))) return rc;
   }
-  const size_t up_bytes = 256 + 16 * (size_t)s1.n_theta;
+  const size_t up_bytes = DROPIN_UP_TABLE + 16 * (size_t)s1.n_theta;
   if (n_a) NHIP_TRY_HIP(hipMemcpyAsync(S.xy.p, pc_a, sizeof(float) * 2 * (size_t)n_a, hipMemcpyHostToDevice, nullptr));
   NHIP_TRY_HIP(hipMemcpyAsync(S.rot1.p, up, up_bytes, hipMemcpyHostToDevice, nullptr));
   uint8_t *dres = static_cast<uint8_t *>(S.res.p);
@@ -1744,21 +1811,22 @@ int match_chained(DropInScratch &S, const float *pc_a, int32_t n_a, const DropIn
   v1.plan.keys_undecoded = v2.plan.keys_zeroed = v2.plan.keys_undecoded = fused;
   if ((rc = dropin_enqueue(S, n_a, v1, spec1_now, S.delta1.p, S.rot1.p, false, S.keys.p, S.ws.p, S.ws.bytes, dres))) return rc;
   hipLaunchKernelGGL(dropin_bridge_kernel, dim3(1), dim3(64), 0, nullptr, reinterpret_cast<const nhip_match_t *>(dres),
-                     reinterpret_cast<const double *>(static_cast<uint8_t *>(S.rot1.p) + 256), (s1.nx - 1) / 2, (s1.ny - 1) / 2,
+                     reinterpret_cast<const double *>(static_cast<uint8_t *>(S.rot1.p) + DROPIN_UP_TABLE), (s1.nx - 1) / 2, (s1.ny - 1) / 2,
                      low_res, high_res, n_a, c2.parts, c2.per, static_cast<DropInPar *>(S.par2.p),
-                     reinterpret_cast<int32_t *>(dres + 480),
+                     reinterpret_cast<int32_t *>(dres + DROPIN_DOWN_ORIGIN),
                      fused ? static_cast<const unsigned long long *>(S.keys.p) : nullptr, s1.nx, s1.ny, c1.g->L.Lf, c1.g->L.step,
-                     reinterpret_cast<nhip_match_t *>(dres), reinterpret_cast<int32_t *>(dres + 128),
+                     reinterpret_cast<nhip_match_t *>(dres + offsetof(DropInRes, rec)),
+                     reinterpret_cast<int32_t *>(dres + offsetof(DropInRes, sums)),
                      static_cast<unsigned long long *>(S.keys2.p));
   NHIP_TRY_HIP(hipGetLastError());
-  if ((rc = dropin_enqueue(S, n_a, v2, spec2_now, S.delta2.p, S.par2.p, true, S.keys2.p, S.ws2.p, S.ws2.bytes, dres + 256)))
+  if ((rc = dropin_enqueue(S, n_a, v2, spec2_now, S.delta2.p, S.par2.p, true, S.keys2.p, S.ws2.p, S.ws2.bytes, dres + DROPIN_DOWN_RES2)))
     return rc;
   NHIP_TRY_HIP(hipMemcpyAsync(down, dres, DROPIN_DOWN_BYTES, hipMemcpyDeviceToHost, nullptr));
   NHIP_TRY_HIP(hipStreamSynchronize(nullptr));
   DropInRes r1, r2;
   memcpy(&r1, down, sizeof(r1));
-  memcpy(&r2, down + 256, sizeof(r2));
-  memcpy(dev_origin, down + 480, 2 * sizeof(int32_t));
+  memcpy(&r2, down + DROPIN_DOWN_RES2, sizeof(r2));
+  memcpy(dev_origin, down + DROPIN_DOWN_ORIGIN, 2 * sizeof(int32_t));
   dropin_pick(r1, c1, m1);
   dropin_pick(r2, c2, m2);
   return NHIP_OK;

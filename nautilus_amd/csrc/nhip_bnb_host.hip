@@ -212,41 +212,29 @@ void bnb_last_launch(int32_t out[8]) {
   memcpy(out, info, sizeof(info));
 }
 
-// The kernels' parameters that follow from the lattice, the layout and the plan (the caller sets the arrays)
-static void fill_bnb_params(BnbParams &P, const nhip_grid_spec_t *spec, const GridLayout &L, const nhip_search_t *search,
-                            const BnbPlan &plan) {
-  memset(&P, 0, sizeof(P));
-  P.n_pairs = plan.n_pairs;
-  P.n_theta = search->n_theta;
-  P.nx = search->nx;
-  P.ny = search->ny;
-  P.hx = (search->nx - 1) / 2;
-  P.hy = (search->ny - 1) / 2;
-  P.nbx = (search->nx + BNB_B - 1) / BNB_B;
-  P.nby = (search->ny + BNB_B - 1) / BNB_B;
-  P.S = L.S;
-  P.pad = L.pad;
-  P.pitch = L.pitch;
-  P.rows = L.S + 2 * L.pad;
-  P.max_shift = spec->max_shift;
+// The kernels' parameters: the job's, then what follows from the layout and the plan
+static void fill_bnb_params(BnbParams &P, const MatchJob &job, const BnbPlan &plan) {
+  const GridLayout &L = *job.L;
+  fill_job_params(P, job);
+  P.pair_kbase = job.pair_kbase;
+  P.keys = reinterpret_cast<unsigned long long *>(job.keys);
+  P.gate = job_gate(job);  // (a kernel parameter only: the plan does not read it)
+  P.nbx = (P.nx + BNB_B - 1) / BNB_B;
+  P.nby = (P.ny + BNB_B - 1) / BNB_B;
   P.pool_pitch = L.pool_pitch;
   P.pool_rows = L.pool_rows;
   P.pairs_per_xcd = (plan.n_pairs + 7) / 8;
-  P.grid_bytes = L.grid_bytes;
   P.skip_bytes = L.skip_bytes;
-  P.slot_bytes = L.slot_bytes;
   P.pool_bytes = L.pool_bytes;
   P.pool4_bytes = L.pool4_bytes;
   P.pool4_pitch = L.pool4_pitch;
-  P.hi_offset = L.grid_bytes + L.skip_bytes + L.pool_bytes + L.pool4_bytes;
+  P.hi_offset = L.hi_offset;
   P.hi_bytes = L.hi_bytes;
   P.hi_pitch = L.hi_pitch;
   P.hi_tpr = L.hi_tpr;
   P.hi_copy_bytes = L.hi_copy_bytes;
   P.t16_bytes = L.t16_bytes;
   P.t16_tpr = L.t16_tpr;
-  P.res = spec->res;
-  P.inv_res = 1.0 / spec->res;
   P.inv_res_f = (float)P.inv_res;
   P.levels = plan.levels;
   P.general_all = plan.general_all;
@@ -350,39 +338,24 @@ static int run_rounds(const BnbParams &P, const BnbPlan &plan, const BnbLauncher
   return NHIP_OK;
 }
 
-int launch_csm_bnb(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
-                   const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
-                   const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                   const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, double min_score,
-                   uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
-                   void *d_workspace, int64_t workspace_bytes, const int32_t *d_pair_kbase) {
-  NHIP_REQUIRE(bnb_fits(L, search), "csm_match: lattice %d x %d x %d beyond the branch-and-bound matcher's envelope",
-               search->n_theta, search->nx, search->ny);
-  if (n_pairs == 0) return NHIP_OK;
-  const BnbPlan plan = bnb_plan(L, search, n_pairs, d_workspace ? workspace_bytes : 0);
+int launch_csm_bnb(const MatchJob &job) {
+  const GridLayout &L = *job.L;
+  const hipStream_t s = job.stream;
+  NHIP_REQUIRE(bnb_fits(L, job.search), "csm_match: lattice %d x %d x %d beyond the branch-and-bound matcher's envelope",
+               job.search->n_theta, job.search->nx, job.search->ny);
+  if (job.n_pairs == 0) return NHIP_OK;
+  const BnbPlan plan = bnb_plan(L, job.search, job.n_pairs, job.workspace ? job.workspace_bytes : 0);
   // (the general instantiation -- scans of more than 1088 points, NHIP_BNB_QUEUE=1 -- takes its exact sums on the row-major image)
   NHIP_REQUIRE(L.has_image || plan.short_scans, "csm_match: grids built with NHIP_GRID_NO_IMAGE serve lists whose scans all have at most %d "
                "points, and the caller must say so (NHIP_SEARCH_SHORT_SCANS; the handle API sets it itself)", NHIP_SHORT_SCAN_POINTS);
   BnbParams P;
-  fill_bnb_params(P, spec, L, search, plan);
-  P.xy = reinterpret_cast<const float2 *>(d_xy);
-  P.offsets = d_offsets;
-  P.grids = d_grids;
-  P.pair_src = d_pair_src;
-  P.pair_slot = d_pair_slot;
-  P.ids = ids;
-  P.rot0_cs = d_rot0_cs;
-  P.delta_cs = d_delta_cs;
-  P.pair_origin = d_pair_origin;
-  P.pair_kbase = d_pair_kbase;
-  P.keys = reinterpret_cast<unsigned long long *>(d_keys);
-  P.gate = {min_score, L.Lf, L.step};  // (a kernel parameter only: the plan does not read it)
+  fill_bnb_params(P, job, plan);
   int rc = instr_buffers(plan, P, s);
   if (rc) return rc;
   if (plan.second) {  // (the hand-over lists in the workspace)
-    P.rot_count = static_cast<uint32_t *>(d_workspace);
-    P.rot_list = reinterpret_cast<RotEntry *>(static_cast<uint8_t *>(d_workspace) + BNB_WS_HEADER);
-    NHIP_TRY_HIP(hipMemsetAsync(d_workspace, 0, BNB_WS_HEADER, s));
+    P.rot_count = static_cast<uint32_t *>(job.workspace);
+    P.rot_list = reinterpret_cast<RotEntry *>(static_cast<uint8_t *>(job.workspace) + BNB_WS_HEADER);
+    NHIP_TRY_HIP(hipMemsetAsync(job.workspace, 0, BNB_WS_HEADER, s));
   }
   const BnbLaunchers K = plan.instrumented ? launchers_instr() : launchers_product();
   t_last_plan = plan;
@@ -390,11 +363,11 @@ int launch_csm_bnb(const float *d_xy, const int32_t *d_offsets, const IdBounds &
     TimerScope t_all(NHIP_TIMER_CSM, s);
     // (Tried and removed: the fused form's batch as K launches on K streams, so that one hardware queue's in-order
     //  dispatch does not keep free slots empty -- 2 / 4 / 8 queues took 10 / 30 / 45 % longer, profiles/r03_matcher_experiments.txt.)
-    rc = plan.form == BNB_FUSED ? K.fused(P, plan, s) : run_rounds(P, plan, K, d_workspace, workspace_bytes, s);
+    rc = plan.form == BNB_FUSED ? K.fused(P, plan, s) : run_rounds(P, plan, K, job.workspace, job.workspace_bytes, s);
   }
   if (rc) return rc;
   NHIP_TRY_HIP(hipGetLastError());
-  launch_csm_finalize(d_keys, d_pair_src, d_offsets, ids.n_scans, n_pairs, search, L, min_score, d_out, d_sums, s);
+  launch_csm_finalize(job);
   NHIP_TRY_HIP(hipGetLastError());
   return NHIP_OK;
 }

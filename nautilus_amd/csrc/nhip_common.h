@@ -95,7 +95,15 @@ struct GridLayout {
   int64_t hits_bytes;  // after the matcher's planes: the HIT RASTER, one bit per cell (rows S + 2 * HIT_PAD, hits_pitch bytes each):
   int32_t hits_pitch;  // what the table was blurred from.  The exact-score pass (NHIP_SEARCH_EXACT_SCORE) recomputes the
                        // integer blur sums of the 1081 cells the winning pose reads from it, and their logarithms in double
-  int64_t slot_bytes;  // grid_bytes + skip_bytes + pool_bytes + pool4_bytes + hi_bytes + hits_bytes: stride between grids
+  int64_t slot_bytes;  // the sum of the parts above: stride between grids
+  // Byte offset of each part inside a slot, in the order above (make_layout pads pool4_bytes and hits_bytes so that the
+  // tiled planes and every slot start on a 128-byte line); the image is at 0
+  int64_t skip_offset;   // the skip map (= grid_bytes)
+  int64_t pool_offset;   // the max-pooled table
+  int64_t pool4_offset;  // the stride-4 pooled table
+  int64_t hi_offset;     // the matcher's tiled planes (hi_bytes): first the two copies of the 8-bit plane
+  int64_t t16_offset;    // the tiled copy of the 16-bit image inside them: hi_offset + 2 * hi_copy_bytes
+  int64_t hits_offset;   // the hit raster
   int32_t pool_pitch, pool_rows;
   int32_t pool4_pitch, pool4_rows;
   double Lf, step;
@@ -215,20 +223,36 @@ struct BnbPlan {
 };
 BnbPlan bnb_plan(const GridLayout &L, const nhip_search_t *search, int32_t n_pairs, int64_t workspace_bytes);
 
-int launch_csm_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
-                     const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
-                     const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                     const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, const MatchPlan &plan,
-                     double min_score, uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
-                     void *d_workspace = nullptr, int64_t workspace_bytes = 0, const int32_t *d_pair_kbase = nullptr);
+// One search of a list of pairs, as every launcher of the matcher takes it (the entry points of nhip_api.hip fill one, by
+// field name).  The plan is not part of it: the caller decides it, and the chained GetTransformation edits it per level.
+struct MatchJob {
+  const float *xy = nullptr;         // the points of all scans, (x, y) each
+  const int32_t *offsets = nullptr;  // index of each scan's first point (ids.n_scans + 1 entries)
+  IdBounds ids = {0, 0, nullptr};
+  const uint8_t *grids = nullptr;
+  const nhip_grid_spec_t *spec = nullptr;
+  const GridLayout *L = nullptr;
+  // per pair: source scan, grid slot, (cos, sin) theta0, optional (x, y) cell offset of the search centre, optional entry
+  // of delta_cs that is the pair's rotation 0 (the branch-and-bound matcher's: BnbParams::pair_kbase)
+  const int32_t *pair_src = nullptr, *pair_slot = nullptr;
+  const double *rot0_cs = nullptr;
+  const double *delta_cs = nullptr;  // (cos, sin) of the search's rotations
+  const int32_t *pair_origin = nullptr, *pair_kbase = nullptr;
+  int32_t n_pairs = 0;
+  const nhip_search_t *search = nullptr;
+  double min_score = -INFINITY;  // the score gate (-INFINITY: off)
+  uint64_t *keys = nullptr;
+  nhip_match_t *out = nullptr;
+  int32_t *sums = nullptr;  // may be null
+  hipStream_t stream = nullptr;
+  void *workspace = nullptr;  // the branch-and-bound matcher's (bnb_workspace_bytes)
+  int64_t workspace_bytes = 0;
+};
+
+int launch_csm_match(const MatchJob &job, const MatchPlan &plan);
 
 // branch-and-bound matcher (nhip_bnb.hip); the lattice is one bnb_fits takes (csm_plan chose it)
-int launch_csm_bnb(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
-                   const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
-                   const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                   const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, double min_score,
-                   uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
-                   void *d_workspace = nullptr, int64_t workspace_bytes = 0, const int32_t *d_pair_kbase = nullptr);
+int launch_csm_bnb(const MatchJob &job);
 int64_t bnb_workspace_bytes(int32_t n_pairs);
 int64_t bnb_workspace_bytes_lists(int32_t n_pairs);
 void bnb_last_launch(int32_t out[8]);
@@ -239,34 +263,19 @@ int bnb_timeline_cand_read(unsigned long long *out, int32_t n);
 int bnb_stats_per_pair(unsigned long long *out, int32_t n);
 // decodes the keys into records and sums and applies the score gate (min_score -INFINITY: off); with NHIP_SEARCH_EXACT_SCORE
 // in search->flags only the floor on the sums, the exact-score pass gates the scores
-void launch_csm_finalize(const uint64_t *d_keys, const int32_t *d_pair_src, const int32_t *d_offsets, int32_t n_scans, int32_t n_pairs,
-                         const nhip_search_t *search, const GridLayout &L, double min_score, nhip_match_t *d_out, int32_t *d_sums,
-                         hipStream_t s);
+void launch_csm_finalize(const MatchJob &job);
 
-int launch_csm_scores(const float *d_xy, const int32_t *d_offsets, const uint8_t *d_grids,
-                      const nhip_grid_spec_t *spec, const GridLayout &L, int32_t src, int32_t slot,
-                      const double *d_rot0_cs, const double *d_delta_cs, int32_t origin_x,
-                      int32_t origin_y, const nhip_search_t *search, int32_t *d_sums,
-                      hipStream_t s);
+// the score volume of ONE pair (scan src against grid slot, search centre (origin_x, origin_y)) from the strip kernels;
+// of the job it reads the scans, the grids, rot0_cs (one entry), delta_cs, the search and the stream
+int launch_csm_scores(const MatchJob &job, int32_t src, int32_t slot, int32_t origin_x, int32_t origin_y, int32_t *d_volume);
 
 // the kernel that performs every add, 16-bit cells (nhip_csm16.hip); called by launch_csm_match / launch_csm_scores
-int launch_csm16_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
-                       const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
-                       const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                       const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, double min_score,
-                       uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s);
-int launch_csm16_scores(const float *d_xy, const int32_t *d_offsets, const uint8_t *d_grids,
-                        const nhip_grid_spec_t *spec, const GridLayout &L, int32_t src, int32_t slot,
-                        const double *d_rot0_cs, const double *d_delta_cs, int32_t origin_x, int32_t origin_y,
-                        const nhip_search_t *search, int32_t *d_sums, hipStream_t s);
+int launch_csm16_match(const MatchJob &job);
+int launch_csm16_scores(const MatchJob &job, int32_t src, int32_t slot, int32_t origin_x, int32_t origin_y, int32_t *d_volume);
 // every add for lattices of few translations (nx * ny <= 256), both cell widths (nhip_csm_small.hip); tiling from the plan
 bool csm_small_plane_fits(const nhip_search_t *search);
 bool csm_small_tiled_fits(const nhip_search_t *search, int32_t n_pairs, int32_t *tile_rows, int32_t *n_tiles);
-int launch_csm_small_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
-                           const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
-                           const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                           const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, const MatchPlan &plan,
-                           double min_score, uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s);
+int launch_csm_small_match(const MatchJob &job, const MatchPlan &plan);
 // skip maps of n finished 16-bit grids (the handle API's late build; occupancy unknown: every map tile is computed)
 int launch_skipmap_build(uint8_t *d_grids, int32_t n_grids, const GridLayout &L, hipStream_t s);
 

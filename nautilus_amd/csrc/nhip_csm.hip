@@ -589,49 +589,28 @@ __global__ __launch_bounds__(EX_THREADS) void csm_exact_score_kernel(ExactParams
   }
 }
 
-int launch_csm_exact_score(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
-                           const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
-                           const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                           const int32_t *d_pair_origin, const int32_t *d_pair_kbase, int32_t n_pairs,
-                           const nhip_search_t *search, double min_score, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
-                           const uint64_t *d_keys_to_decode = nullptr) {
+int launch_csm_exact_score(const MatchJob &job, const MatchPlan &plan) {
+  const nhip_grid_spec_t *spec = job.spec;
+  const GridLayout &L = *job.L;
+  const hipStream_t s = job.stream;
   NHIP_REQUIRE(L.R <= 15, "exact score: blur radius %d > 15", L.R);
   GridTables T;
   int rc = make_tables(spec, L, &T);
   if (rc) return rc;
   ExactParams P;
-  memset(&P, 0, sizeof(P));
-  P.xy = reinterpret_cast<const float2 *>(d_xy);
-  P.offsets = d_offsets;
-  P.grids = d_grids;
-  P.pair_src = d_pair_src;
-  P.pair_slot = d_pair_slot;
-  P.rot0_cs = d_rot0_cs;
-  P.delta_cs = d_delta_cs;
-  P.pair_origin = d_pair_origin;
-  P.pair_kbase = d_pair_kbase;
-  P.out = d_out;
-  P.keys = reinterpret_cast<const unsigned long long *>(d_keys_to_decode);
-  P.sums = d_sums;
-  P.ids = ids;
-  P.n_pairs = n_pairs;
-  P.pairs_per_xcd = (n_pairs + 7) / 8;
-  P.nx = search->nx;
-  P.ny = search->ny;
-  P.hx = (search->nx - 1) / 2;
-  P.hy = (search->ny - 1) / 2;
-  P.S = L.S;
+  fill_job_common(P, job);
+  P.pair_kbase = job.pair_kbase;
+  P.out = job.out;
+  if (plan.keys_undecoded) P.keys = reinterpret_cast<const unsigned long long *>(job.keys);
+  P.sums = job.sums;
+  P.pairs_per_xcd = (job.n_pairs + 7) / 8;
   P.R = L.R;
-  P.max_shift = spec->max_shift;
   P.hits_pitch = L.hits_pitch;
-  P.slot_bytes = L.slot_bytes;
-  P.hits_offset = L.grid_bytes + L.skip_bytes + L.pool_bytes + L.pool4_bytes + L.hi_bytes;
-  P.res = spec->res;
-  P.inv_res = 1.0 / spec->res;
+  P.hits_offset = L.hits_offset;
   P.K2 = (double)L.K * (double)L.K;
   P.floor_p = spec->floor_p;
   P.Lf = L.Lf;
-  P.gate = {min_score, L.Lf, L.step};
+  P.gate = job_gate(job);
   for (int i = 0; i <= 2 * L.R; i++) P.taps[i] = T.taps[i];
   timer_begin(NHIP_TIMER_EXACT_SCORE, s);
   if (L.R == 6) hipLaunchKernelGGL(csm_exact_score_kernel<13>, dim3(8u * (uint32_t)P.pairs_per_xcd), dim3(EX_THREADS), 0, s, P);  // sigma = 2
@@ -657,28 +636,15 @@ int check_search(const nhip_grid_spec_t *spec, const GridLayout &L, const nhip_s
   return NHIP_OK;
 }
 
-void fill_params(CsmParams &P, const nhip_grid_spec_t *spec, const GridLayout &L,
-                 const nhip_search_t *search) {
-  memset(&P, 0, sizeof(P));
-  P.n_theta = search->n_theta;
-  P.nx = search->nx;
-  P.ny = search->ny;
-  P.hx = (search->nx - 1) / 2;
-  P.hy = (search->ny - 1) / 2;
-  P.npbx = (search->nx + PB_NX - 1) / PB_NX;
-  P.npby = (search->ny + PB_NY - 1) / PB_NY;
-  P.S = L.S;
-  P.pad = L.pad;
-  P.pitch = L.pitch;
-  P.rows = L.S + 2 * L.pad;
-  P.max_shift = spec->max_shift;
-  P.grid_bytes = L.grid_bytes;
-  P.slot_bytes = L.slot_bytes;
+// the strip kernels' parameters (8-bit cells): the job's, the blocks of the plane and the dense rule
+// (nhip_csm16.hip has a function of the same name for its kernels: its own PB_NX / PB_NY and a dense rule of its own)
+void fill_params(CsmParams &P, const MatchJob &job) {
+  fill_job_params(P, job);
+  P.npbx = (P.nx + PB_NX - 1) / PB_NX;
+  P.npby = (P.ny + PB_NY - 1) / PB_NY;
   // NHIP_CSM_DENSE=1 switches the zero-strip skipping off (measurement: the same kernel, every add done)
   const char *dense = tunable("NHIP_CSM_DENSE");
-  P.dense = ((dense && dense[0] == '1') || (search->flags & NHIP_SEARCH_DENSE)) ? 1 : 0;
-  P.res = spec->res;
-  P.inv_res = 1.0 / spec->res;
+  P.dense = ((dense && dense[0] == '1') || (job.search->flags & NHIP_SEARCH_DENSE)) ? 1 : 0;
 }
 
 }  // namespace
@@ -706,111 +672,69 @@ MatchPlan csm_plan(const GridLayout &L, const nhip_search_t *search, int32_t n_p
   return plan;
 }
 
-void launch_csm_finalize(const uint64_t *d_keys, const int32_t *d_pair_src, const int32_t *d_offsets, int32_t n_scans, int32_t n_pairs,
-                         const nhip_search_t *search, const GridLayout &L, double min_score, nhip_match_t *d_out, int32_t *d_sums,
-                         hipStream_t s) {
-  const ScoreGate gate = {min_score, L.Lf, L.step};
-  hipLaunchKernelGGL(csm_finalize_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, s,
-                     reinterpret_cast<const unsigned long long *>(d_keys), d_pair_src, d_offsets, n_scans, n_pairs, search->nx,
-                     search->ny, gate, (search->flags & NHIP_SEARCH_EXACT_SCORE) != 0, d_out, d_sums);
+void launch_csm_finalize(const MatchJob &job) {
+  hipLaunchKernelGGL(csm_finalize_kernel, dim3((job.n_pairs + 255) / 256), dim3(256), 0, job.stream,
+                     reinterpret_cast<const unsigned long long *>(job.keys), job.pair_src, job.offsets, job.ids.n_scans, job.n_pairs,
+                     job.search->nx, job.search->ny, job_gate(job), (job.search->flags & NHIP_SEARCH_EXACT_SCORE) != 0, job.out,
+                     job.sums);
 }
 
 // the strip kernels, 8-bit cells (the 16-bit ones: nhip_csm16.hip)
-static int launch_csm8_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
-                             const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
-                             const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                             const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, double min_score,
-                             uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s) {
+static int launch_csm8_match(const MatchJob &job) {
+  const hipStream_t s = job.stream;
   CsmParams P;
-  fill_params(P, spec, L, search);
-  P.xy = reinterpret_cast<const float2 *>(d_xy);
-  P.offsets = d_offsets;
-  P.grids = d_grids;
-  P.pair_src = d_pair_src;
-  P.pair_slot = d_pair_slot;
-  P.ids = ids;
-  P.rot0_cs = d_rot0_cs;
-  P.delta_cs = d_delta_cs;
-  P.pair_origin = d_pair_origin;
-  P.keys = reinterpret_cast<unsigned long long *>(d_keys);
-  P.n_pairs = n_pairs;
+  fill_params(P, job);
+  P.keys = reinterpret_cast<unsigned long long *>(job.keys);
   const int64_t per_pair = (int64_t)P.n_theta * P.npbx * P.npby;
-  const int64_t blocks = ((int64_t)(n_pairs + 7) / 8) * 8 * per_pair;
+  const int64_t blocks = ((int64_t)(job.n_pairs + 7) / 8) * 8 * per_pair;
   NHIP_REQUIRE(blocks < 0x7fffffffll, "csm_match: %lld workgroups exceed one launch; split the batch",
                (long long)blocks);
-  NHIP_TRY_HIP(hipMemsetAsync(d_keys, 0, sizeof(uint64_t) * (size_t)n_pairs, s));
+  NHIP_TRY_HIP(hipMemsetAsync(job.keys, 0, sizeof(uint64_t) * (size_t)job.n_pairs, s));
   timer_begin(NHIP_TIMER_CSM, s);
   if (P.dense)
     hipLaunchKernelGGL((csm_correlate_kernel<false, true>), dim3((uint32_t)blocks), dim3(CSM_THREADS), 0, s, P);
   else
     hipLaunchKernelGGL((csm_correlate_kernel<false, false>), dim3((uint32_t)blocks), dim3(CSM_THREADS), 0, s, P);
   timer_end(NHIP_TIMER_CSM, s);
-  launch_csm_finalize(d_keys, d_pair_src, d_offsets, ids.n_scans, n_pairs, search, L, min_score, d_out, d_sums, s);
+  launch_csm_finalize(job);
   NHIP_TRY_HIP(hipGetLastError());
   return NHIP_OK;
 }
 
-int launch_csm_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
-                     const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
-                     const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                     const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, const MatchPlan &plan,
-                     double min_score, uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s,
-                     void *d_workspace, int64_t workspace_bytes, const int32_t *d_pair_kbase) {
+int launch_csm_match(const MatchJob &job, const MatchPlan &plan) {
+  const GridLayout &L = *job.L;
   // (per-pair offsets into the rotation table are the branch-and-bound matcher's: an internal caller that passes them has
   //  made sure the lattice is one it takes)
-  NHIP_REQUIRE(!d_pair_kbase || plan.form == MATCH_BNB, "csm_match: rotation offsets per pair with a lattice the matcher does not take");
-  int rc = check_search(spec, L, search);
+  NHIP_REQUIRE(!job.pair_kbase || plan.form == MATCH_BNB, "csm_match: rotation offsets per pair with a lattice the matcher does not take");
+  int rc = check_search(job.spec, L, job.search);
   if (rc) return rc;
   NHIP_REQUIRE(L.has_image || plan.form == MATCH_BNB, "csm_match: this search takes the kernel that performs every add "
                "(NHIP_SEARCH_EXHAUSTIVE, or a lattice beyond the branch-and-bound matcher's envelope), which reads the row-major "
                "image the grids were built without (NHIP_GRID_NO_IMAGE)");
-  if (n_pairs == 0) return NHIP_OK;
+  if (job.n_pairs == 0) return NHIP_OK;
   switch (plan.form) {
-    case MATCH_BNB:  // the same records, most adds never performed (nhip_bnb.hip)
-      rc = launch_csm_bnb(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs, d_pair_origin,
-                          n_pairs, search, min_score, d_keys, d_out, d_sums, s, d_workspace, workspace_bytes, d_pair_kbase);
-      break;
-    case MATCH_POSES:
-      rc = launch_csm_small_match(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
-                                  d_pair_origin, n_pairs, search, plan, min_score, d_keys, d_out, d_sums, s);
-      break;
-    case MATCH_STRIPS16:
-      rc = launch_csm16_match(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
-                              d_pair_origin, n_pairs, search, min_score, d_keys, d_out, d_sums, s);
-      break;
-    case MATCH_STRIPS8:
-      rc = launch_csm8_match(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
-                             d_pair_origin, n_pairs, search, min_score, d_keys, d_out, d_sums, s);
-      break;
+    case MATCH_BNB: rc = launch_csm_bnb(job); break;  // the same records, most adds never performed (nhip_bnb.hip)
+    case MATCH_POSES: rc = launch_csm_small_match(job, plan); break;
+    case MATCH_STRIPS16: rc = launch_csm16_match(job); break;
+    case MATCH_STRIPS8: rc = launch_csm8_match(job); break;
   }
-  if (rc || !(search->flags & NHIP_SEARCH_EXACT_SCORE)) return rc;
+  if (rc || !(job.search->flags & NHIP_SEARCH_EXACT_SCORE)) return rc;
   // (the records are final -- indices and integer sums; the pass replaces their score field.  A search that left its keys
   //  undecoded -- the fine level of a chained call -- has them decoded by this pass.)
-  return launch_csm_exact_score(d_xy, d_offsets, ids, d_grids, spec, L, d_pair_src, d_pair_slot, d_rot0_cs, d_delta_cs,
-                                d_pair_origin, d_pair_kbase, n_pairs, search, min_score, d_out, d_sums, s,
-                                plan.keys_undecoded ? d_keys : nullptr);
+  return launch_csm_exact_score(job, plan);
 }
 
-int launch_csm_scores(const float *d_xy, const int32_t *d_offsets, const uint8_t *d_grids,
-                      const nhip_grid_spec_t *spec, const GridLayout &L, int32_t src, int32_t slot,
-                      const double *d_rot0_cs, const double *d_delta_cs, int32_t origin_x,
-                      int32_t origin_y, const nhip_search_t *search, int32_t *d_sums,
-                      hipStream_t s) {
-  int rc = check_search(spec, L, search);
+int launch_csm_scores(const MatchJob &job, int32_t src, int32_t slot, int32_t origin_x, int32_t origin_y, int32_t *d_volume) {
+  const GridLayout &L = *job.L;
+  int rc = check_search(job.spec, L, job.search);
   if (rc) return rc;
   NHIP_REQUIRE(L.has_image, "csm_scores: the score volume comes from the kernel that performs every add, which reads the row-major "
                "image the grids were built without (NHIP_GRID_NO_IMAGE)");
-  if (L.cb == 2)
-    return launch_csm16_scores(d_xy, d_offsets, d_grids, spec, L, src, slot, d_rot0_cs, d_delta_cs, origin_x, origin_y,
-                               search, d_sums, s);
+  if (L.cb == 2) return launch_csm16_scores(job, src, slot, origin_x, origin_y, d_volume);
+  const hipStream_t s = job.stream;
   CsmParams P;
-  fill_params(P, spec, L, search);
-  P.xy = reinterpret_cast<const float2 *>(d_xy);
-  P.offsets = d_offsets;
-  P.grids = d_grids;
-  P.rot0_cs = d_rot0_cs;
-  P.delta_cs = d_delta_cs;
-  P.volume = d_sums;
+  fill_params(P, job);  // (the job's pair arrays, ids and keys are null: the one pair is the single_* fields below)
+  P.volume = d_volume;
   P.n_pairs = 1;
   P.single_src = src;
   P.single_slot = slot;

@@ -381,77 +381,46 @@ __global__ __launch_bounds__(THREADS, NHIP_C16_WAVES_PER_SIMD) void csm_correlat
   if (lane == 0) atomicMax(&P.keys[pair], best);
 }
 
-void fill_params16(CsmParams &P, const nhip_grid_spec_t *spec, const GridLayout &L, const nhip_search_t *search) {
-  memset(&P, 0, sizeof(P));
-  P.n_theta = search->n_theta;
-  P.nx = search->nx;
-  P.ny = search->ny;
-  P.hx = (search->nx - 1) / 2;
-  P.hy = (search->ny - 1) / 2;
-  P.npbx = (search->nx + PB_NX - 1) / PB_NX;
-  P.npby = (search->ny + PB_NY - 1) / PB_NY;
-  P.S = L.S;
-  P.pad = L.pad;
-  P.pitch = L.pitch;
-  P.rows = L.S + 2 * L.pad;
-  P.max_shift = spec->max_shift;
-  P.grid_bytes = L.grid_bytes;
-  P.slot_bytes = L.slot_bytes;
+// the strip kernels' parameters (16-bit cells): the job's, the blocks of the plane and the dense rule
+// (nhip_csm.hip has a function of the same name for the 8-bit kernels: its own PB_NX / PB_NY, and a dense rule that does
+//  not ask for NHIP_GRID_SKIP_MAP)
+void fill_params(CsmParams &P, const MatchJob &job) {
+  fill_job_params(P, job);
+  P.npbx = (P.nx + PB_NX - 1) / PB_NX;
+  P.npby = (P.ny + PB_NY - 1) / PB_NY;
   // without a skip map in the slots (spec->flags) every strip is added; NHIP_CSM_DENSE=1 asks for that too
   const char *dense = tunable("NHIP_CSM_DENSE");
-  P.dense = ((dense && dense[0] == '1') || (search->flags & NHIP_SEARCH_DENSE) || !(spec->flags & NHIP_GRID_SKIP_MAP)) ? 1 : 0;
-  P.res = spec->res;
-  P.inv_res = 1.0 / spec->res;
+  P.dense = ((dense && dense[0] == '1') || (job.search->flags & NHIP_SEARCH_DENSE) || !(job.spec->flags & NHIP_GRID_SKIP_MAP)) ? 1 : 0;
 }
 
 }  // namespace
 
-int launch_csm16_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
-                       const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
-                       const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                       const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, double min_score,
-                       uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s) {
+int launch_csm16_match(const MatchJob &job) {
+  const hipStream_t s = job.stream;
   CsmParams P;
-  fill_params16(P, spec, L, search);
-  P.xy = reinterpret_cast<const float2 *>(d_xy);
-  P.offsets = d_offsets;
-  P.grids = d_grids;
-  P.pair_src = d_pair_src;
-  P.pair_slot = d_pair_slot;
-  P.ids = ids;
-  P.rot0_cs = d_rot0_cs;
-  P.delta_cs = d_delta_cs;
-  P.pair_origin = d_pair_origin;
-  P.keys = reinterpret_cast<unsigned long long *>(d_keys);
-  P.n_pairs = n_pairs;
+  fill_params(P, job);
+  P.keys = reinterpret_cast<unsigned long long *>(job.keys);
   const int64_t per_pair = (int64_t)P.n_theta * P.npbx * P.npby;
-  const int64_t blocks = ((int64_t)(n_pairs + 7) / 8) * 8 * per_pair;
+  const int64_t blocks = ((int64_t)(job.n_pairs + 7) / 8) * 8 * per_pair;
   NHIP_REQUIRE(blocks < 0x7fffffffll, "csm_match: %lld workgroups exceed one launch; split the batch",
                (long long)blocks);
-  NHIP_TRY_HIP(hipMemsetAsync(d_keys, 0, sizeof(uint64_t) * (size_t)n_pairs, s));
+  NHIP_TRY_HIP(hipMemsetAsync(job.keys, 0, sizeof(uint64_t) * (size_t)job.n_pairs, s));
   timer_begin(NHIP_TIMER_CSM, s);
   if (P.dense)
     hipLaunchKernelGGL((csm_correlate16_kernel<false, true>), dim3((uint32_t)blocks), dim3(THREADS), 0, s, P);
   else
     hipLaunchKernelGGL((csm_correlate16_kernel<false, false>), dim3((uint32_t)blocks), dim3(THREADS), 0, s, P);
   timer_end(NHIP_TIMER_CSM, s);
-  launch_csm_finalize(d_keys, d_pair_src, d_offsets, ids.n_scans, n_pairs, search, L, min_score, d_out, d_sums, s);
+  launch_csm_finalize(job);
   NHIP_TRY_HIP(hipGetLastError());
   return NHIP_OK;
 }
 
-int launch_csm16_scores(const float *d_xy, const int32_t *d_offsets, const uint8_t *d_grids,
-                        const nhip_grid_spec_t *spec, const GridLayout &L, int32_t src, int32_t slot,
-                        const double *d_rot0_cs, const double *d_delta_cs, int32_t origin_x, int32_t origin_y,
-                        const nhip_search_t *search, int32_t *d_sums, hipStream_t s) {
+int launch_csm16_scores(const MatchJob &job, int32_t src, int32_t slot, int32_t origin_x, int32_t origin_y, int32_t *d_volume) {
+  const hipStream_t s = job.stream;
   CsmParams P;
-  fill_params16(P, spec, L, search);
-  P.xy = reinterpret_cast<const float2 *>(d_xy);
-  P.offsets = d_offsets;
-  P.grids = d_grids;
-  P.rot0_cs = d_rot0_cs;
-  P.delta_cs = d_delta_cs;
-  P.volume = d_sums;
+  fill_params(P, job);  // (the job's pair arrays, ids and keys are null: the one pair is the single_* fields below)
+  P.volume = d_volume;
   P.n_pairs = 1;
   P.single_src = src;
   P.single_slot = slot;

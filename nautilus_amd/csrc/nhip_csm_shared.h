@@ -39,6 +39,47 @@ __host__ __device__ inline nhip_match_t gate_rejected_record() {
   return m;
 }
 
+inline ScoreGate job_gate(const MatchJob &job) { return {job.min_score, job.L->Lf, job.L->step}; }
+
+// ---- what the kernels' parameter blocks share (CsmParams below, bnb::BnbParams, ExactParams of nhip_csm.hip), from a job:
+// the fields have one name in all three.  What differs per kernel -- keys, the blocks of the plane, the dense rule, the
+// plan's fields -- its launcher sets after these.
+// What all three hold (the block is zeroed first): the scans, the grids, the per-pair arrays and their counts, the plane
+// of translations, what places a point's window in a slot
+template <class Params>
+void fill_job_common(Params &P, const MatchJob &job) {
+  memset(&P, 0, sizeof(P));
+  P.xy = reinterpret_cast<const float2 *>(job.xy);
+  P.offsets = job.offsets;
+  P.grids = job.grids;
+  P.pair_src = job.pair_src;
+  P.pair_slot = job.pair_slot;
+  P.ids = job.ids;
+  P.rot0_cs = job.rot0_cs;
+  P.delta_cs = job.delta_cs;
+  P.pair_origin = job.pair_origin;
+  P.n_pairs = job.n_pairs;
+  P.nx = job.search->nx;
+  P.ny = job.search->ny;
+  P.hx = (job.search->nx - 1) / 2;
+  P.hy = (job.search->ny - 1) / 2;
+  P.S = job.L->S;
+  P.max_shift = job.spec->max_shift;
+  P.slot_bytes = job.L->slot_bytes;
+  P.res = job.spec->res;
+  P.inv_res = 1.0 / job.spec->res;
+}
+// ... and what the kernels that search add: the rotations and the stored image's geometry
+template <class Params>
+void fill_job_params(Params &P, const MatchJob &job) {
+  fill_job_common(P, job);
+  P.n_theta = job.search->n_theta;
+  P.pad = job.L->pad;
+  P.pitch = job.L->pitch;
+  P.rows = job.L->S + 2 * job.L->pad;
+  P.grid_bytes = job.L->grid_bytes;
+}
+
 namespace csm {
 
 struct CsmParams {

@@ -173,50 +173,23 @@ bool csm_small_tiled_fits(const nhip_search_t *search, int32_t n_pairs, int32_t 
   return (int64_t)n_pairs * search->n_theta * tiles <= SMALL_TILED_MAX_BLOCKS;
 }
 
-int launch_csm_small_match(const float *d_xy, const int32_t *d_offsets, const IdBounds &ids, const uint8_t *d_grids,
-                           const nhip_grid_spec_t *spec, const GridLayout &L, const int32_t *d_pair_src,
-                           const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
-                           const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, const MatchPlan &plan,
-                           double min_score, uint64_t *d_keys, nhip_match_t *d_out, int32_t *d_sums, hipStream_t s) {
+int launch_csm_small_match(const MatchJob &job, const MatchPlan &plan) {
+  const hipStream_t s = job.stream;
   CsmParams P;
-  memset(&P, 0, sizeof(P));
-  P.xy = reinterpret_cast<const float2 *>(d_xy);
-  P.offsets = d_offsets;
-  P.grids = d_grids;
-  P.pair_src = d_pair_src;
-  P.pair_slot = d_pair_slot;
-  P.ids = ids;
-  P.rot0_cs = d_rot0_cs;
-  P.delta_cs = d_delta_cs;
-  P.pair_origin = d_pair_origin;
-  P.keys = reinterpret_cast<unsigned long long *>(d_keys);
-  P.n_pairs = n_pairs;
-  P.n_theta = search->n_theta;
-  P.nx = search->nx;
-  P.ny = search->ny;
-  P.hx = (search->nx - 1) / 2;
-  P.hy = (search->ny - 1) / 2;
-  P.S = L.S;
-  P.pad = L.pad;
-  P.pitch = L.pitch;
-  P.rows = L.S + 2 * L.pad;
-  P.max_shift = spec->max_shift;
-  P.grid_bytes = L.grid_bytes;
-  P.slot_bytes = L.slot_bytes;
-  P.res = spec->res;
-  P.inv_res = 1.0 / spec->res;
+  fill_job_params(P, job);
+  P.keys = reinterpret_cast<unsigned long long *>(job.keys);
   P.tile_rows = plan.tile_rows;
   P.n_tiles = plan.n_tiles;
   NHIP_REQUIRE(P.tile_rows >= 1 && (int64_t)P.tile_rows * P.nx <= 64 * SMALL_PASSES && (int64_t)P.tile_rows * P.n_tiles >= P.ny,
                "csm_match: a tiling of %d x %d rows does not cover the %d x %d plane in the small-plane kernel", P.n_tiles, P.tile_rows,
                P.nx, P.ny);
-  const int64_t blocks = (int64_t)n_pairs * (int64_t)P.n_theta * (int64_t)P.n_tiles;
+  const int64_t blocks = (int64_t)job.n_pairs * (int64_t)P.n_theta * (int64_t)P.n_tiles;
   NHIP_REQUIRE(blocks < 0x7fffffffll, "csm_match: %lld workgroups exceed one launch; split the batch", (long long)blocks);
-  if (!plan.keys_zeroed) NHIP_TRY_HIP(hipMemsetAsync(d_keys, 0, sizeof(uint64_t) * (size_t)n_pairs, s));
+  if (!plan.keys_zeroed) NHIP_TRY_HIP(hipMemsetAsync(job.keys, 0, sizeof(uint64_t) * (size_t)job.n_pairs, s));
   timer_begin(NHIP_TIMER_CSM, s);
   const int passes = (P.tile_rows * P.nx + 63) / 64;
 #define NHIP_SMALL_LAUNCH(CB_, PS_) hipLaunchKernelGGL((csm_small_plane_kernel<CB_, PS_>), dim3((uint32_t)blocks), dim3(SMALL_THREADS), 0, s, P)
-  if (L.cb == 1) {
+  if (job.L->cb == 1) {
     if (passes == 1) NHIP_SMALL_LAUNCH(1, 1); else if (passes == 2) NHIP_SMALL_LAUNCH(1, 2);
     else if (passes == 3) NHIP_SMALL_LAUNCH(1, 3); else NHIP_SMALL_LAUNCH(1, 4);
   } else {
@@ -225,8 +198,7 @@ int launch_csm_small_match(const float *d_xy, const int32_t *d_offsets, const Id
   }
 #undef NHIP_SMALL_LAUNCH
   timer_end(NHIP_TIMER_CSM, s);
-  if (!plan.keys_undecoded)
-    launch_csm_finalize(d_keys, d_pair_src, d_offsets, ids.n_scans, n_pairs, search, L, min_score, d_out, d_sums, s);
+  if (!plan.keys_undecoded) launch_csm_finalize(job);
   NHIP_TRY_HIP(hipGetLastError());
   return NHIP_OK;
 }

@@ -883,7 +883,7 @@ template <int CB, int ST>
 void launch_pool(const uint8_t *occ, uint8_t *g, const GridLayout &L, int32_t tiles, int32_t n, hipStream_t s) {
   const int32_t rows = L.S + 2 * L.pad, mpitch = L.pitch / 4;
   const int32_t pooled_rows = (rows + ST - 1) / ST;
-  const int64_t off = L.grid_bytes + L.skip_bytes + (ST == BNB_B ? 0 : L.pool_bytes);
+  const int64_t off = ST == BNB_B ? L.pool_offset : L.pool4_offset;
   const int32_t pp = ST == BNB_B ? L.pool_pitch : L.pool4_pitch;
   for (int32_t z0 = 0; z0 < n; z0 += 65535) {  // gridDim.z is limited to 65,535
     const int32_t nz = n - z0 < 65535 ? n - z0 : 65535;
@@ -895,11 +895,10 @@ void launch_pool(const uint8_t *occ, uint8_t *g, const GridLayout &L, int32_t ti
 
 void launch_pool8_from_pool4(uint8_t *g, const GridLayout &L, int32_t n, hipStream_t s) {
   const int32_t rows = L.S + 2 * L.pad, n8 = (rows + BNB_B - 1) / BNB_B;
-  const int64_t off8 = L.grid_bytes + L.skip_bytes, off4 = off8 + L.pool_bytes;
   for (int32_t z0 = 0; z0 < n; z0 += 65535) {  // gridDim.z is limited to 65,535
     const int32_t nz = n - z0 < 65535 ? n - z0 : 65535;
-    hipLaunchKernelGGL(grid_pool8_from_pool4_kernel, dim3((n8 + 255) / 256, (n8 + 3) / 4, nz), dim3(256), 0, s, g, rows, off8, off4,
-                       L.slot_bytes, L.pool_pitch, L.pool4_pitch, z0);
+    hipLaunchKernelGGL(grid_pool8_from_pool4_kernel, dim3((n8 + 255) / 256, (n8 + 3) / 4, nz), dim3(256), 0, s, g, rows, L.pool_offset,
+                       L.pool4_offset, L.slot_bytes, L.pool_pitch, L.pool4_pitch, z0);
   }
 }
 
@@ -962,17 +961,15 @@ int launch_grid_build(const float *d_xy, const int32_t *d_offsets, int32_t n_sca
       // (without a skip map -- 16-bit grids unless the spec asks for one -- only the second-level table: nothing reads
       //  the map's space, and the first-level table is rewritten entry by entry from the second)
       const bool with_map = L.has_image && (L.cb == 1 || (spec->flags & NHIP_GRID_SKIP_MAP));
-      const int64_t hio = L.grid_bytes + L.skip_bytes + L.pool_bytes + L.pool4_bytes;
       // (without a map the second-level table is cleared tile by tile: p4p > 0)
-      const int64_t tb = with_map ? L.skip_bytes + L.pool_bytes + L.pool4_bytes : 0;
-      const int64_t to = with_map ? L.grid_bytes : L.grid_bytes + L.skip_bytes + L.pool_bytes;
-      const int64_t p4o = L.grid_bytes + L.skip_bytes + L.pool_bytes;
+      const int64_t tb = with_map ? L.hi_offset - L.skip_offset : 0;
+      const int64_t to = with_map ? L.skip_offset : L.pool4_offset;
       const int32_t p4p = with_map ? 0 : L.pool4_pitch;
       const int w = (L.pad * L.cb) % 16 == 0 ? 16 : ((L.pad * L.cb) % 8 == 0 ? 8 : 4), wh = L.pad % 16 == 0 ? 16 : (L.pad % 8 == 0 ? 8 : 4);
 #define NHIP_CLEAR(W, WH)                                                                                             \
   hipLaunchKernelGGL((grid_clear_kernel<W, WH>), dim3(4096), dim3(256), 0, s, count, tag, list, g, n, L.S, tiles, L.pad, \
-                     L.pitch, L.cb, L.slot_bytes, to, tb, hio, L.hi_tpr, L.hi_copy_bytes, L.t16_tpr, p4o, p4p, \
-                     L.grid_bytes + L.skip_bytes, L.pool_pitch, hio + L.hi_bytes, L.hits_bytes, L.has_image ? 1 : 0, masks)
+                     L.pitch, L.cb, L.slot_bytes, to, tb, L.hi_offset, L.hi_tpr, L.hi_copy_bytes, L.t16_tpr, L.pool4_offset, p4p, \
+                     L.pool_offset, L.pool_pitch, L.hits_offset, L.hits_bytes, L.has_image ? 1 : 0, masks)
       if (w == 16 && wh == 16) NHIP_CLEAR(16, 16);
       else if (w == 16) NHIP_CLEAR(16, 4);
       else if (w == 8) NHIP_CLEAR(8, 4);
@@ -1005,14 +1002,12 @@ int launch_grid_build(const float *d_xy, const int32_t *d_offsets, int32_t n_sca
       hipLaunchKernelGGL(grid_blur_kernel<1>, dim3(blur_blocks), dim3(256), 0, s,
                          reinterpret_cast<const float2 *>(d_xy), d_offsets, d_target_ids, (int32_t)t0, count, list,
                          tiles, g, L.S, L.pad, L.pitch, L.slot_bytes, L.R, spec->res, inv_res, kt, d_thr16,
-                         L.grid_bytes + L.skip_bytes + L.pool_bytes + L.pool4_bytes, L.hi_tpr, L.hi_copy_bytes, 0, n_scans,
-                         L.grid_bytes + L.skip_bytes + L.pool_bytes + L.pool4_bytes + L.hi_bytes, L.hits_pitch, L.has_image ? 1 : 0, masks);
+                         L.hi_offset, L.hi_tpr, L.hi_copy_bytes, 0, n_scans, L.hits_offset, L.hits_pitch, L.has_image ? 1 : 0, masks);
     else
       hipLaunchKernelGGL(grid_blur_kernel<2>, dim3(blur_blocks), dim3(256), 0, s,
                          reinterpret_cast<const float2 *>(d_xy), d_offsets, d_target_ids, (int32_t)t0, count, list,
                          tiles, g, L.S, L.pad, L.pitch, L.slot_bytes, L.R, spec->res, inv_res, kt, d_thr16,
-                         L.grid_bytes + L.skip_bytes + L.pool_bytes + L.pool4_bytes, L.hi_tpr, L.hi_copy_bytes, L.t16_tpr, n_scans,
-                         L.grid_bytes + L.skip_bytes + L.pool_bytes + L.pool4_bytes + L.hi_bytes, L.hits_pitch, L.has_image ? 1 : 0, masks);
+                         L.hi_offset, L.hi_tpr, L.hi_copy_bytes, L.t16_tpr, n_scans, L.hits_offset, L.hits_pitch, L.has_image ? 1 : 0, masks);
     // gridDim.z is limited to 65,535: the targets of a chunk go in slices.  (The skip map serves the kernels that
     // perform every add; the branch-and-bound matcher never reads it, so 16-bit grids -- its product path -- carry
     // one only when the spec asks.)
@@ -1030,17 +1025,16 @@ int launch_grid_build(const float *d_xy, const int32_t *d_offsets, int32_t n_sca
     {
       // second-level table from the listed tiles (NHIP_GRID_POOL=bands: the band kernel, measurement), first from second
       const char *pk = tunable("NHIP_GRID_POOL");
-      const int64_t off4 = L.grid_bytes + L.skip_bytes + L.pool_bytes;
       if (pk && pk[0] == 'b' && L.has_image) {  // (the band kernels walk the image)
         if (L.cb == 1) launch_pool<1, BNB_B4>(occ, g, L, tiles, n, s);
         else launch_pool<2, BNB_B4>(occ, g, L, tiles, n, s);
       } else if (L.cb == 1) {
         hipLaunchKernelGGL(grid_pool4_tiles_kernel<1>, dim3(blur_blocks), dim3(256), 0, s, count, list, tiles, g, L.pad, rows,
-                           L.pitch, off4, L.slot_bytes, L.pool4_pitch, L.has_image ? 1 : 0, off4 + L.pool4_bytes, L.hi_tpr,
+                           L.pitch, L.pool4_offset, L.slot_bytes, L.pool4_pitch, L.has_image ? 1 : 0, L.hi_offset, L.hi_tpr,
                            L.hi_copy_bytes, L.t16_tpr);
       } else {
         hipLaunchKernelGGL(grid_pool4_tiles_kernel<2>, dim3(blur_blocks), dim3(256), 0, s, count, list, tiles, g, L.pad, rows,
-                           L.pitch, off4, L.slot_bytes, L.pool4_pitch, L.has_image ? 1 : 0, off4 + L.pool4_bytes, L.hi_tpr,
+                           L.pitch, L.pool4_offset, L.slot_bytes, L.pool4_pitch, L.has_image ? 1 : 0, L.hi_offset, L.hi_tpr,
                            L.hi_copy_bytes, L.t16_tpr);
       }
       const bool want_map8 = L.has_image && (L.cb == 1 || (spec->flags & NHIP_GRID_SKIP_MAP));
@@ -1050,7 +1044,7 @@ int launch_grid_build(const float *d_xy, const int32_t *d_offsets, int32_t n_sca
         launch_pool8_from_pool4(g, L, n, s);
       } else {
         hipLaunchKernelGGL(grid_pool8_tiles_kernel, dim3(blur_blocks), dim3(128), 0, s, count, list, tiles, g, L.pad, rows,
-                           L.grid_bytes + L.skip_bytes, off4, L.slot_bytes, L.pool_pitch, L.pool4_pitch);
+                           L.pool_offset, L.pool4_offset, L.slot_bytes, L.pool_pitch, L.pool4_pitch);
       }
     }
     if (one_pass) hipLaunchKernelGGL(grid_tag_kernel, dim3(1), dim3(1), 0, s, count, tag);
