@@ -83,9 +83,15 @@ def test_bad_specs_are_rejected_with_message():
         assert len(lib.nhip_last_error()) > 0
 
 
-def test_threshold_table_reproduces_direct_quantiser():
+# the blur widths and floors the table build is tested at (tests/test_grid_targets_cpu.py): end taps of 1 (sigma 0.7), the
+# largest radius (5.3), a floor that many sums fall below (1e-3) and one that leaves only the table's top in reach (1e-30)
+SIGMA_FLOOR = [(2.0, 1e-10), (0.7, 1e-10), (1.0, 1e-10), (5.3, 1e-10), (2.0, 1e-3), (2.0, 1e-30), (0.7, 1e-3), (0.7, 1e-30)]
+
+
+@pytest.mark.parametrize("sigma,floor_p", SIGMA_FLOOR)
+def test_threshold_table_reproduces_direct_quantiser(sigma, floor_p):
     """thr[k] <= V  <=>  q(V) >= k, against the oracle's direct libm quantiser on a 1-point grid."""
-    spec = csm.grid_spec(1.0, 0.05, 2.0, 1e-10, 2, cell_bits=8)
+    spec = csm.grid_spec(1.0, 0.05, sigma, floor_p, 2, cell_bits=8)
     L = csm.grid_layout(spec)
     taps = np.zeros(2 * L.blur_radius + 1, dtype=np.int32)
     thr = np.zeros(256, dtype=np.uint32)
@@ -93,7 +99,7 @@ def test_threshold_table_reproduces_direct_quantiser():
     assert taps.sum() == L.tap_sum and np.all(taps == taps[::-1]) and taps.argmax() == L.blur_radius
     assert np.all(np.diff(thr.astype(np.int64)) >= 0)
     # one hit in the middle of a 40x40 grid: V[r][c] = taps[i]*taps[j] exactly
-    g = O.grid_build(np.array([[0.01, 0.01]], dtype=np.float32), O.grid_spec(1.0, 0.05, 2.0, 1e-10, 8))
+    g = O.grid_build(np.array([[0.01, 0.01]], dtype=np.float32), O.grid_spec(1.0, 0.05, sigma, floor_p, 8))
     R = L.blur_radius
     for i in range(-R, R + 1):
         for j in range(-R, R + 1):
@@ -102,10 +108,11 @@ def test_threshold_table_reproduces_direct_quantiser():
             assert q == g[20 + i, 20 + j], (i, j, V, q, g[20 + i, 20 + j])
 
 
-def test_threshold_table_16bit_reproduces_direct_quantiser():
+@pytest.mark.parametrize("sigma,floor_p", SIGMA_FLOOR)
+def test_threshold_table_16bit_reproduces_direct_quantiser(sigma, floor_p):
     """The 65536-entry table of the 16-bit cells: thr[k] <= V  <=>  q16(V) >= k, checked against the oracle's direct
     quantiser on every blur sum a single hit produces and on random sums around the table's entries."""
-    spec = csm.grid_spec(1.0, 0.05, 2.0, 1e-10, 2, cell_bits=16)
+    spec = csm.grid_spec(1.0, 0.05, sigma, floor_p, 2, cell_bits=16)
     L = csm.grid_layout(spec)
     assert L.cell_bytes == 2 and abs(L.score_step + L.score_floor / 65535.0) < 1e-18
     taps = np.zeros(2 * L.blur_radius + 1, dtype=np.int32)
@@ -113,7 +120,7 @@ def test_threshold_table_16bit_reproduces_direct_quantiser():
     _lib.check(_lib.load().nhip_grid_tables(C.byref(spec), _lib.ptr(taps), _lib.ptr(thr)))
     reach = thr[thr != 0xffffffff].astype(np.int64)
     assert np.all(np.diff(reach) >= 0) and len(reach) > 60000
-    g = O.grid_build(np.array([[0.01, 0.01]], dtype=np.float32), O.grid_spec(1.0, 0.05, 2.0, 1e-10, 16))
+    g = O.grid_build(np.array([[0.01, 0.01]], dtype=np.float32), O.grid_spec(1.0, 0.05, sigma, floor_p, 16))
     assert g.dtype == np.uint16
     R = L.blur_radius
     for i in range(-R, R + 1):
@@ -123,10 +130,10 @@ def test_threshold_table_16bit_reproduces_direct_quantiser():
             assert q == g[20 + i, 20 + j], (i, j, V, q, g[20 + i, 20 + j])
     # the entries themselves: q(thr[k]) >= k and q(thr[k] - 1) < k (numpy restatement of the quantiser)
     K2 = float(L.tap_sum) ** 2
-    Lf = math.log(1e-10)
+    Lf = math.log(floor_p)
 
     def q16(V):
-        v = np.maximum(V.astype(np.float64) / K2, 1e-10)
+        v = np.maximum(V.astype(np.float64) / K2, floor_p)
         return np.clip(np.floor((np.log(v) - Lf) / (-Lf / 65535.0) + 0.5), 0, 65535)
     ks = np.nonzero((thr != 0xffffffff) & (thr > 0))[0][::37]
     assert np.all(q16(thr[ks].astype(np.int64)) >= ks) and np.all(q16(thr[ks].astype(np.int64) - 1) < ks)

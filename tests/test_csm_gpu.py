@@ -7,6 +7,7 @@ import math
 import numpy as np
 import pytest
 
+from tests.grid_reference import _pool_numpy, skip_map_definition
 from nautilus_amd import _lib, csm, synth
 from oracle import oracle as O
 
@@ -822,21 +823,6 @@ def test_device_pointer_api_on_torch_stream(gpu, small_bag):
         assert not np.unpackbits(got_map, axis=1, bitorder="little")[:, L.pitch // 4:].any()
 
 
-def skip_map_definition(stored, width=21):
-    """include/nautilus_hip.h (nhip_grid_layout_t.skip_bytes): bit (r, c) = any non-zero cell in stored rows
-    [r, r + 21) x aligned dwords [c, c + 21 * cell_bytes), clipped to the image.  stored: (rows, pitch) bytes."""
-    rows, pitch = stored.shape
-    nz = stored.reshape(rows, pitch // 4, 4).any(axis=2)
-    big = np.zeros((rows + 21, pitch // 4 + width), dtype=np.int64)
-    big[:rows, :pitch // 4] = nz
-    I = np.zeros((big.shape[0] + 1, big.shape[1] + 1), dtype=np.int64)
-    I[1:, 1:] = big.cumsum(0).cumsum(1)
-    r = np.arange(rows)[:, None]
-    c = np.arange(pitch // 4)[None, :]
-    cnt = I[r + 21, c + width] - I[r, c + width] - I[r + 21, c] + I[r, c]
-    return (cnt > 0).astype(np.uint8)
-
-
 @pytest.mark.parametrize("cell_bits", [16, 8])
 def test_zero_strip_skipping_changes_nothing(gpu, small_bag, monkeypatch, cell_bits):
     """The kernels that perform every add (NHIP_SEARCH_EXHAUSTIVE): NHIP_CSM_DENSE=1 adds every strip, zero or not;
@@ -868,20 +854,6 @@ def test_zero_strip_skipping_changes_nothing(gpu, small_bag, monkeypatch, cell_b
 
 
 # ---------------------------------------------------------------------------- branch and bound, 16-bit cells
-def _pool_numpy(stored, cell_bits, stride=8):
-    """pool[i][j] = max of stored[8i : 8i + 15, 8j : 8j + 15] (clipped; stride 4: [4i : 4i + 7, 4j : 4j + 7]);
-    16-bit cells scaled by ceil(max / 257)."""
-    rows = stored.shape[0]
-    n = (rows + stride - 1) // stride
-    win = 2 * stride - 1
-    out = np.zeros((n, n), dtype=np.int64)
-    for i in range(n):
-        band = stored[stride * i:stride * i + win, :rows].max(axis=0).astype(np.int64)
-        for j in range(n):
-            out[i, j] = band[stride * j:stride * j + win].max()
-    return out if cell_bits == 8 else (out + 256) // 257
-
-
 @pytest.mark.parametrize("cell_bits", [8, 16])
 def test_pooled_table_matches_its_definition(gpu, small_bag, cell_bits):
     spec, _ = _specs(10.0, 0.05, 2.0, 12, cell_bits)
