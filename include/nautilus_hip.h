@@ -33,6 +33,8 @@
  * Handle entry points take HOST pointers, own their device memory and synchronise.
  * There is no CPU fallback anywhere: without a gfx950 device compute calls fail with
  * NHIP_ERR_NODEV.
+ * The instruments -- counters, timers, launch reports, downloads of the matcher's private planes -- are declared in
+ * nautilus_hip_debug.h, not here.
  */
 #ifndef NAUTILUS_HIP_H_
 #define NAUTILUS_HIP_H_
@@ -234,13 +236,6 @@ int nhip_device_pool_configure(int64_t max_bytes);
 int nhip_device_pool_release(void);
 int nhip_device_pool_stats(int64_t *entries, int64_t *bytes);
 
-/* Wall-clock seconds of the calling thread's last handle-API call (nhip_scans_upload, nhip_grids_build, nhip_csm_match and
- * the _free calls), by what the host waited for: out[0] hipMalloc, [1] zero-fill + host-to-device copies, [2] from the first
- * kernel launch to the end of the call (nhip_grids_build: the launches alone), [3] waiting for the kernels, [4] device-to-host
- * copies, [5] hipFree, [6] the whole call (nhip_csm_match), [7] unused.  Diagnostic: bench.py prints it per run of its
- * host-buffer leg, so that a slow call says where it was slow. */
-int nhip_host_phases(double out[8]);
-
 /* Host helpers: (cos, sin) of theta0 per pair and of the lattice offsets, in double. */
 int nhip_csm_rot0(const double *rot_a, const double *rot_b, int32_t n, double *cs_out /* 2n */);
 int nhip_csm_delta_table(const nhip_search_t *search, double *cs_out /* 2*n_theta */);
@@ -322,35 +317,6 @@ int nhip_csm_match_gated_dev(const float *d_xy, const int32_t *d_offsets, int32_
                              const nhip_search_t *search, uint64_t *d_keys, nhip_match_t *d_out,
                              int32_t *d_sums, void *d_workspace, int64_t workspace_bytes, void *stream, double min_score);
 int64_t nhip_csm_workspace_bytes(int32_t n_pairs);
-/* The form the calling thread's last branch-and-bound match took (diagnostic; every form returns the same records):
- * out[0] = 0 one kernel per pair from start to end (+ the hand-over kernel when out[5]), 1 split form in one round,
- * 2 split form in several rounds on the caller's stream, 3 split form in rounds with the candidates on the library's
- * helper stream of the current device; out[1] pairs per round; out[2] rounds' state the workspace holds; out[3] rounds;
- * out[4] 1 when NHIP_SEARCH_SHORT_SCANS was honoured; out[5] hand-over kernel launched; out[6] instrumented build;
- * out[7] n_pairs. */
-int nhip_csm_last_launch(int32_t out[8]);
-
-/* With NHIP_BNB_STATS=1 in the environment the branch-and-bound matcher counts its work: blocks of 8 x 8
- * translations whose sums it evaluated exactly (four 4 x 4 sub-blocks count as one block), and blocks in all, since
- * the last call (synchronises; resets). */
-int nhip_bnb_stats(uint64_t *evaluated, uint64_t *total);
-/* ... by level: out[0..3] = {blocks evaluated whole, blocks in all, candidate blocks refined through their four
- * sub-block bounds, 4 x 4 sub-blocks evaluated exactly}; out[4..10] = shader-clock sums of the matcher's kernel:
- * wave time in the candidate phase, of which window origins / sub-block bounds / exact sums, the slowest wave of
- * each pair, seed phase and bound phase (per workgroup); out[11..13] further clocks, out[14] = poses of 16-bit grids whose exact
- * sums were read from the 16-bit image (the rest was settled on the plane of high bytes); out[15] = pairs a score gate
- * settled right after their bounds (nhip_csm_match_gated); (synchronises; resets) */
-int nhip_bnb_stats_levels(uint64_t out[16]);
-/* ... and per pair of the last launch (4 x 4 sub-blocks evaluated exactly, a whole block counting four), before
- * nhip_bnb_stats resets the totals */
-int nhip_bnb_stats_per_pair(uint64_t *evaluated, int32_t n_pairs);
-/* With NHIP_BNB_TIMELINE=1: per pair of the last launch four 100 MHz timestamps of its workgroup -- start, bounds
- * done, seeds done, end (the top 16 bits of the last one hold the hardware id of the CU it ran on); after the
- * n_pairs records two more values: first start and last end of the second kernel.  ticks: 4*n_pairs + 2 values */
-int nhip_bnb_timeline(uint64_t *ticks, int32_t n_pairs);
-/* ... and of the candidates' launch of the split form: ticks[i] = first start, ticks[n_pairs + i] = last end over the
- * workgroups that worked pair i of the last round (~0 / 0: none did).  ticks: 2*n_pairs values */
-int nhip_bnb_timeline_candidates(uint64_t *ticks, int32_t n_pairs);
 
 /* Full score volume of ONE pair (tests / debugging): sums[(k*nx + ix)*ny + iy]. */
 int nhip_csm_scores_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const uint8_t *d_grids,
@@ -472,30 +438,8 @@ int nhip_scans_free(nhip_scans_t *scans);
 int nhip_grids_build(const nhip_scans_t *scans, const int32_t *target_ids, int32_t n_targets,
                      const nhip_grid_spec_t *spec, nhip_grids_t **out);
 int nhip_grids_free(nhip_grids_t *grids);
-/* 1 when this handle's tables were built by an incremental REBUILD: nhip_grids_free hands the table buffer and its build
- * workspace back to the device buffer pool together, contents known; while nobody else has taken either, the next
- * nhip_grids_build of the same spec and target count takes the pair and clears what the previous build wrote (as
- * nhip_grid_rebuild_dev does, the workspace's tag checked on the device) instead of zero-filling every slot.  Same
- * tables, bit for bit.  0: a fresh allocation or a buffer of unknown contents, zero-filled (diagnostic). */
-int nhip_grids_was_rebuilt(const nhip_grids_t *grids);
 /* copy stored (padded) grid `slot` to host: layout.grid_bytes bytes (uint8 or uint16 cells) */
 int nhip_grids_download(const nhip_grids_t *grids, int32_t slot, uint8_t *out);
-/* copy the plane of high bytes of grid `slot` (16-bit cells) to host in plain row-major form: rows x hi_pitch bytes.
- * On the device the plane is stored as two copies tiled 8 rows x 16 bytes (layout.hi_bytes bytes in all; the second
- * copy's tiles are shifted by 8 columns); `_copy` selects the copy that is read back (0 / 1: both hold the same bytes). */
-int nhip_grids_download_hi_plane(const nhip_grids_t *grids, int32_t slot, uint8_t *out);
-int nhip_grids_download_hi_plane_copy(const nhip_grids_t *grids, int32_t slot, int32_t copy, uint8_t *out);
-/* 16-bit cells: the matcher's copy of the 16-bit image (tiled 8 rows x 8 cells on the device; it follows the two copies
- * of the plane of high bytes inside layout.hi_bytes) in the plain form of nhip_grids_download: layout.grid_bytes bytes */
-int nhip_grids_download_tiled16(const nhip_grids_t *grids, int32_t slot, uint8_t *out);
-/* copy the skip map of grid `slot` to host: layout.skip_bytes bytes (rows x 8*ceil(pitch/256) bytes, then padding) */
-int nhip_grids_download_skip_map(const nhip_grids_t *grids, int32_t slot, uint8_t *out);
-/* copy the max-pooled table of grid `slot` to host: layout.pool_bytes bytes (pool_rows x pool_pitch) */
-int nhip_grids_download_pool(const nhip_grids_t *grids, int32_t slot, uint8_t *out);
-/* the same for the second-level table: layout.pool4_bytes bytes (pool4_rows x pool4_pitch) */
-int nhip_grids_download_pool4(const nhip_grids_t *grids, int32_t slot, uint8_t *out);
-/* the hit raster of grid `slot`: layout.hits_bytes bytes (bit rows of hits_pitch bytes; see nhip_grid_layout_t.hits_bytes) */
-int nhip_grids_download_hits(const nhip_grids_t *grids, int32_t slot, uint8_t *out);
 
 /* Batched GetTransformation: theta0[i] = AngleMod(rot_a - rot_b) of pair i;
  * pair_origin: NULL or 2 int32 per pair (search centre in cells). */
@@ -551,11 +495,6 @@ int nhip_csm_cache_stats(int64_t *entries, int64_t *bytes, int64_t *hits, int64_
 int nhip_csm_get_transformation(const nhip_csm_params_t *params, const float *pc_a, int32_t n_a, const float *pc_b,
                                 int32_t n_b, double rot_a, double rot_b, double rot_restriction, double *score,
                                 float *tx, float *ty, float *theta);
-/* What the calling thread's last nhip_csm_get_transformation did: {the coarse optimum's score, the form the fine level ran in
- * (0: the branch-and-bound matcher, 1: every add by the strip kernels -- a fine plane too large for the tiles of rows, 2: every
- * add by the kernel whose lanes are poses -- the default), 1 if the two levels were chained on the device (a cached target),
- * the coarse optimum's rotation index}.  (Measurement / tests.) */
-int nhip_csm_get_transformation_info(double out[4]);
 
 /* Residual batch: all LIDAR residual blocks of one ceres::Problem build (immutable after
  * creation, like the functors' copied vectors, slam_residuals.h:117-120). */
@@ -622,25 +561,6 @@ int nhip_resid_point_to_line(const float *segments, const float *points, const i
  * never need it.  A Python host does the same with torch.distributed (nautilus_amd/sharding.py). */
 int nhip_allgather_matches(void *comm, const nhip_match_t *d_local, int32_t n_local,
                            nhip_match_t *d_all, void *stream);
-
-/* ------------------------------------------------------------------ in-stream kernel timing
- * When enabled, the dominant kernels are bracketed by hipEvents on their own stream.
- * ids: 0 = csm match (bounds, candidates, exact sums), 1 = grid build (everything nhip_grid_build_dev enqueues),
- *      2 = resid_lidar, 3 = corr_search, 4 = resid_normal_eq, 5 = the clearing part of a grid build (inside 1). */
-#define NHIP_TIMER_CSM 0
-#define NHIP_TIMER_GRID 1
-#define NHIP_TIMER_RESID 2
-#define NHIP_TIMER_CORR 3
-#define NHIP_TIMER_NORMEQ 4
-#define NHIP_TIMER_GRID_CLEAR 5
-#define NHIP_TIMER_CSM_BOUNDS 6 /* split form of the matcher: bounds + seeds (csm_bnb_kernel<., ., true, true>) ... */
-#define NHIP_TIMER_CSM_CAND 7   /* ... and the candidates (csm_bnb_cand_kernel); both inside NHIP_TIMER_CSM */
-#define NHIP_TIMER_EXACT_SCORE 8 /* the pass of NHIP_SEARCH_EXACT_SCORE (after, not inside, NHIP_TIMER_CSM) */
-#define NHIP_TIMER_COUNT 9
-int nhip_timing_enable(int on);
-int nhip_timing_reset(void);
-/* synchronises the recorded events; total_ms / launches since the last reset */
-int nhip_timing_get(int id, double *total_ms, int32_t *launches);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@
 #include <rccl/rccl.h>
 
 #include "CorrelativeScanMatcher.h"
+#include "nautilus_hip_debug.h"  // (nhip_csm_last_launch: which form a match took)
 #include "slam_residuals_hip.h"
 
 using nautilus_hip::Vec2f;

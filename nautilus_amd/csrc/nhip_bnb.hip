@@ -511,7 +511,7 @@ __device__ __forceinline__ unsigned long long eval_block(const BnbParams &P, con
                                                          int32_t k, int32_t Y, int32_t X, int lane) {
   uint32_t total = 0u;  // this lane's pose: (dy, dx) below
   int dy, dx;
-  // (stored image + skip map: every offset the evaluation can form lies inside; see nhip_api.hip make_layout)
+  // (stored image + skip map: every offset the evaluation can form lies inside; see nhip_layout.hip make_layout)
   const __amdgpu_buffer_rsrc_t rsrc = uniform_rsrc(grid, P.grid_bytes + P.skip_bytes);
   if (CB == 1) {
     const float2 none = make_float2(0.f, 0.f);
@@ -1332,7 +1332,7 @@ __device__ __forceinline__ void rotation_pass(const BnbParams &P, const PairCtx 
   if (BNB_STATS(P)) t_mark = clock64();
   const int32_t nch = cache_origins(P, C.pts, C.n_pts, cf, sf, C.cx, C.cy, lane, org, true);
   if (BNB_STATS(P)) clk.org += clock64() - t_mark;
-  // (stored image + skip map: every offset an evaluation can form lies inside; see nhip_api.hip make_layout)
+  // (stored image + skip map: every offset an evaluation can form lies inside; see nhip_layout.hip make_layout)
   // (8-bit grids: the image, on which the exact sums run; 16-bit grids: the tiled copy of the image, for pose_sum16)
   const __amdgpu_buffer_rsrc_t rsrc16 = CB == 1 ? uniform_rsrc(C.grid, P.grid_bytes + P.skip_bytes)
                                                 : uniform_rsrc(C.grid + P.hi_offset + 2 * P.hi_copy_bytes, P.t16_bytes);

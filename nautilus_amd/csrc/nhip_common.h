@@ -9,7 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/nautilus_hip.h"
+#include "../../include/nautilus_hip_debug.h"  // (the contract, nautilus_hip.h, and the timer ids)
 
 namespace nhip {
 
@@ -223,7 +223,7 @@ struct BnbPlan {
 };
 BnbPlan bnb_plan(const GridLayout &L, const nhip_search_t *search, int32_t n_pairs, int64_t workspace_bytes);
 
-// One search of a list of pairs, as every launcher of the matcher takes it (the entry points of nhip_api.hip fill one, by
+// One search of a list of pairs, as every launcher of the matcher takes it (the entry points of the C ABI fill one, by
 // field name).  The plan is not part of it: the caller decides it, and the chained GetTransformation edits it per level.
 struct MatchJob {
   const float *xy = nullptr;         // the points of all scans, (x, y) each

@@ -1,0 +1,84 @@
+// nhip_host.h -- what the host units of the C ABI share (nhip_runtime, nhip_host_csm, nhip_dropin, nhip_host_solver): the
+// pooled device buffer, the in-flight guard, the phase clocks, the scan and grid handles.  Host only: no kernel unit
+// includes it.
+#pragma once
+#include <atomic>
+#include <chrono>
+#include <mutex>
+
+#include "nhip_common.h"
+
+namespace nhip {
+
+// ---- host phases of the handle API (nhip_host_phases; nhip_runtime.hip) ----
+enum { PH_ALLOC = 0, PH_UPLOAD, PH_ENQUEUE, PH_WAIT, PH_DOWNLOAD, PH_FREE, PH_HOST, PH_COUNT };
+struct PhaseClock {  // its lifetime is added to phase `id` of the calling thread
+  int id;
+  std::chrono::steady_clock::time_point t0;
+  explicit PhaseClock(int i) : id(i), t0(std::chrono::steady_clock::now()) {}
+  ~PhaseClock();
+};
+void phases_reset();
+
+// ---- device buffers of the handle API (the pool behind them: nhip_runtime.hip) ----
+struct InFlight {  // work this thread's call enqueued may still run: a DevBuf released meanwhile waits for the device first
+  InFlight();
+  static void done();  // (the caller has synchronised)
+};
+
+struct DevBuf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  int device = -1;  // the device the memory lives on
+  int alloc(size_t n);
+  void free(uint64_t key = 0, uint64_t meta = 0);  // (key, meta: the contents stay known to the pool, see PoolEntry)
+  void adopt(void *q, size_t n);                   // (a buffer pool_take_pair returned: filed under the current device)
+  template <class T> T *as() const { return static_cast<T *>(p); }
+  ~DevBuf() { free(); }
+};
+// the two buffers of one keyed release (metas `meta_a`, `meta_b`), if both are still in the pool
+bool pool_take_pair(uint64_t meta_a, uint64_t meta_b, size_t need_a, size_t need_b, void **pa, size_t *ba, void **pb, size_t *bb);
+extern std::atomic<uint64_t> g_pool_key;
+
+}  // namespace nhip
+
+// ---- the handles ----
+struct nhip_scans {
+  nhip::DevBuf xy, offsets;
+  int32_t n_scans = 0;
+  int64_t n_points = 0;
+  std::vector<int32_t> h_offsets;
+};
+
+struct nhip_grids {
+  nhip::DevBuf grids;
+  nhip::DevBuf ws;         // the build's workspace: its tile list and line masks describe what `grids` holds
+  uint64_t shape = 0;      // digest of (spec as built, targets): what a later build must equal to rebuild into these buffers
+  bool dirty = false;      // something besides the build wrote into `grids` (a late skip-map build): contents no longer the list's
+  bool rebuilt = false;    // this handle's build was an incremental rebuild into a kept pair
+  nhip_grid_spec_t spec;
+  nhip::GridLayout L;
+  int32_t n = 0;
+  std::mutex mu;  // (the late skip-map build)
+};
+
+namespace nhip {
+
+// 16-bit grids are built without skip maps unless their spec asks (only the 16-bit strip kernels read them).
+// The first search on a handle whose plan takes those kernels builds them, once.  (nhip_host_csm.hip)
+int ensure_skip_maps(const nhip_grids_t *grids, const MatchPlan &plan);
+// the handle's spec as it is now (the flags may be written by a concurrent call's ensure_skip_maps: read under the same lock)
+int spec_under_lock(nhip_grids_t *g, nhip_grid_spec_t *out);
+
+// a job on scans and grids of the handle API: the five fields every such search takes from them; the rest by name, per call
+inline MatchJob job_on(const DevBuf &xy, const DevBuf &offsets, const nhip_grids &g, const nhip_grid_spec_t &spec_now) {
+  MatchJob job;
+  job.xy = xy.as<const float>();
+  job.offsets = offsets.as<const int32_t>();
+  job.grids = g.grids.as<const uint8_t>();
+  job.spec = &spec_now;
+  job.L = &g.L;
+  return job;
+}
+
+}  // namespace nhip

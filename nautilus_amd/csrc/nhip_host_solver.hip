@@ -1,0 +1,542 @@
+// nhip_host_solver.hip -- the solver-side entry points of the C ABI: residuals, correspondences and loop-closure gates in
+// their `_dev` and host-buffer forms, the residual batch handle, the all-gather of match records (RCCL, bound at run time).
+#include <dlfcn.h>
+
+#include "nhip_common.h"
+#include "nhip_host.h"
+
+// the residual batch handle (this unit's alone; the scan and grid handles are in nhip_host.h)
+struct nhip_resid_batch {
+  nhip::DevBuf corr, corr_block, block_src, block_tgt, consts, poses, res, jsrc, jtgt, jtt;  // (jtt also holds q: nhip_resid_batch_eval_q)
+  nhip::DevBuf one_poses, one_consts, one_idx;  // single-block evaluation: 2 poses, 8 constants, {0, 1}
+  std::vector<int32_t> h_offsets;
+  std::mutex one_mu;
+  int kind = 0;
+  int32_t n_blocks = 0, n_poses = 0;
+  int64_t n_corr = 0;
+};
+
+using namespace nhip;
+
+extern "C" {
+
+// ---------------------------------------------------------------- residuals and correspondences, device pointers
+int nhip_resid_lidar_dev(int kind, const float *d_corr, const int32_t *d_corr_block,
+                         int64_t n_corr, const int32_t *d_block_src, const int32_t *d_block_tgt,
+                         int32_t n_blocks, const double *d_poses, int32_t n_poses,
+                         double *d_block_consts, double *d_residuals, double *d_jac_src,
+                         double *d_jac_tgt, void *stream) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(d_corr && d_corr_block && d_block_src && d_block_tgt && d_poses && d_block_consts &&
+                   d_residuals,
+               "resid_lidar_dev: null pointer");
+  return launch_resid_lidar(kind, d_corr, d_corr_block, n_corr, d_block_src, d_block_tgt, n_blocks,
+                            d_poses, n_poses, d_block_consts, d_residuals, d_jac_src, d_jac_tgt,
+                            static_cast<hipStream_t>(stream));
+}
+
+int nhip_resid_lidar_normal_eq_dev(int kind, const float *d_corr, const int32_t *d_block_offsets,
+                                   const int32_t *d_block_src, const int32_t *d_block_tgt,
+                                   int32_t n_blocks, const double *d_poses, int32_t n_poses,
+                                   double *d_block_consts, double *d_out, void *stream) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(d_corr && d_block_offsets && d_block_src && d_block_tgt && d_poses && d_block_consts && d_out,
+               "resid_lidar_normal_eq_dev: null pointer");
+  NHIP_REQUIRE(n_poses >= 0, "resid_lidar_normal_eq_dev: negative size");
+  return launch_resid_normal_eq(kind, d_corr, d_block_offsets, d_block_src, d_block_tgt, n_blocks, d_poses, n_poses,
+                                d_block_consts, d_out, static_cast<hipStream_t>(stream));
+}
+
+int nhip_pose_affines(const double *poses, int32_t n, float *out) {
+  NHIP_REQUIRE(poses && out && n >= 0, "pose_affines: bad arguments");
+  for (int32_t i = 0; i < n; i++) {
+    // entries of PoseArrayToAffine<double>(pose).cast<float>() (slam_util.h:20-28, 37-40)
+    out[4 * i + 0] = (float)cos(poses[3 * i + 2]);
+    out[4 * i + 1] = (float)sin(poses[3 * i + 2]);
+    out[4 * i + 2] = (float)poses[3 * i + 0];
+    out[4 * i + 3] = (float)poses[3 * i + 1];
+  }
+  return NHIP_OK;
+}
+
+int nhip_corr_search_dev(const float *d_xy, const float *d_normals, const int32_t *d_offsets, int32_t n_scans,
+                         const int32_t *d_block_src, const int32_t *d_block_tgt, int32_t n_blocks,
+                         const float *d_pose_aff, float outlier_threshold,
+                         const int64_t *d_cap_offsets, float *d_corr_padded, int32_t *d_counts,
+                         void *stream) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(d_xy && d_normals && d_offsets && d_block_src && d_block_tgt && d_pose_aff && d_cap_offsets &&
+                   d_corr_padded && d_counts,
+               "corr_search_dev: null pointer");
+  NHIP_REQUIRE(n_blocks >= 0 && n_scans >= 0 && outlier_threshold > 0, "corr_search_dev: bad size or threshold");
+  return launch_corr_search(d_xy, d_normals, d_offsets, n_scans, d_block_src, d_block_tgt, n_blocks, d_pose_aff,
+                            outlier_threshold, 0.f, false, d_cap_offsets, d_corr_padded, d_counts,
+                            static_cast<hipStream_t>(stream));
+}
+
+int nhip_corr_search_normals_dev(const float *d_xy, const float *d_normals, const int32_t *d_offsets, int32_t n_scans,
+                                 const int32_t *d_block_src, const int32_t *d_block_tgt, int32_t n_blocks,
+                                 const float *d_pose_aff, float outlier_threshold, float min_abs_cosine,
+                                 const int64_t *d_cap_offsets, float *d_corr_padded, int32_t *d_counts,
+                                 void *stream) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(d_xy && d_normals && d_offsets && d_block_src && d_block_tgt && d_pose_aff && d_cap_offsets &&
+                   d_corr_padded && d_counts,
+               "corr_search_normals_dev: null pointer");
+  NHIP_REQUIRE(n_blocks >= 0 && n_scans >= 0 && outlier_threshold > 0, "corr_search_normals_dev: bad size or threshold");
+  NHIP_REQUIRE(min_abs_cosine >= 0.f && min_abs_cosine <= 1.f, "corr_search_normals_dev: min_abs_cosine outside [0, 1]");
+  return launch_corr_search(d_xy, d_normals, d_offsets, n_scans, d_block_src, d_block_tgt, n_blocks, d_pose_aff,
+                            outlier_threshold, min_abs_cosine, true, d_cap_offsets, d_corr_padded, d_counts,
+                            static_cast<hipStream_t>(stream));
+}
+
+int nhip_corr_compact_dev(const float *d_corr_padded, const int64_t *d_cap_offsets,
+                          const int32_t *d_counts, int32_t n_blocks, int32_t *d_block_offsets,
+                          float *d_corr, int32_t *d_corr_block, void *stream) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(d_corr_padded && d_cap_offsets && d_counts && d_block_offsets && d_corr && d_corr_block,
+               "corr_compact_dev: null pointer");
+  NHIP_REQUIRE(n_blocks >= 0, "corr_compact_dev: n_blocks < 0");
+  return launch_corr_compact(d_corr_padded, d_cap_offsets, d_counts, n_blocks, d_block_offsets, d_corr,
+                             d_corr_block, static_cast<hipStream_t>(stream));
+}
+
+int nhip_resid_point_to_line_dev(const float *d_segments, const float *d_points,
+                                 const int32_t *d_point_block, int64_t n_points,
+                                 const int32_t *d_block_pose, const int32_t *d_block_line,
+                                 int32_t n_blocks, const double *d_poses, int32_t n_poses,
+                                 const double *d_line_poses, int32_t n_line_poses, double *d_residuals,
+                                 double *d_jac_pose, double *d_jac_line, void *stream) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(d_segments && d_points && d_point_block && d_block_pose && d_block_line && d_poses &&
+                   d_line_poses && d_residuals,
+               "resid_point_to_line_dev: null pointer");
+  return launch_resid_point_to_line(d_segments, d_points, d_point_block, n_points, d_block_pose,
+                                    d_block_line, n_blocks, d_poses, n_poses, d_line_poses, n_line_poses, d_residuals,
+                                    d_jac_pose, d_jac_line, static_cast<hipStream_t>(stream));
+}
+
+int nhip_resid_odometry_dev(const float *d_t_odom, const float *d_r_odom, const int32_t *d_pose_i,
+                            const int32_t *d_pose_j, int32_t n_factors, double translation_weight,
+                            double rotation_weight, const double *d_poses, int32_t n_poses, double *d_residuals,
+                            double *d_jac_i, double *d_jac_j, void *stream) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(d_t_odom && d_r_odom && d_pose_i && d_pose_j && d_poses && d_residuals,
+               "resid_odometry_dev: null pointer");
+  return launch_resid_odometry(d_t_odom, d_r_odom, d_pose_i, d_pose_j, n_factors,
+                               translation_weight, rotation_weight, d_poses, n_poses, d_residuals, d_jac_i,
+                               d_jac_j, static_cast<hipStream_t>(stream));
+}
+
+// ---------------------------------------------------------------- loop-closure gates
+int nhip_lc_scatter_scores_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, double *d_scores,
+                               void *stream) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(n_scans >= 0 && (n_scans == 0 || (d_xy && d_offsets && d_scores)), "lc_scatter_scores_dev: bad arguments");
+  return launch_lc_scatter_scores(d_xy, d_offsets, n_scans, d_scores, static_cast<hipStream_t>(stream));
+}
+
+int nhip_lc_pair_gate_dev(const double *d_poses, int32_t n_poses, const int32_t *d_candidates, int32_t n_candidates,
+                          double max_range, int32_t min_separation, uint8_t *d_flags, void *stream) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(n_candidates >= 0 && n_poses >= 0 && (n_candidates == 0 || (d_poses && d_candidates && d_flags)),
+               "lc_pair_gate_dev: bad arguments");
+  return launch_lc_pair_gate(d_poses, n_poses, d_candidates, n_candidates, max_range, min_separation, d_flags,
+                             static_cast<hipStream_t>(stream));
+}
+
+int nhip_lc_chi_square_gate_dev(const double *d_poses, int32_t n_poses, const int32_t *d_pair_src, const int32_t *d_pair_tgt,
+                                const float *d_cov, int32_t n_pairs, double max_score, double *d_scores,
+                                uint8_t *d_flags, void *stream) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(n_pairs >= 0 && n_poses >= 0 && (n_pairs == 0 || (d_poses && d_pair_src && d_pair_tgt && d_cov && d_scores && d_flags)),
+               "lc_chi_square_gate_dev: bad arguments");
+  NHIP_REQUIRE((reinterpret_cast<uintptr_t>(d_cov) & 15) == 0, "lc_chi_square_gate_dev: d_cov must be 16-byte aligned");
+  return launch_lc_chi_square(d_poses, n_poses, d_pair_src, d_pair_tgt, d_cov, n_pairs, max_score, d_scores, d_flags,
+                              static_cast<hipStream_t>(stream));
+}
+
+int nhip_lc_chi_square_gate(const double *poses, int32_t n_poses, const int32_t *pair_src, const int32_t *pair_tgt,
+                            const float *cov, int32_t n, double max_score, double *scores, uint8_t *flags) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(n >= 0 && n_poses >= 0 && (n == 0 || (poses && pair_src && pair_tgt && cov && scores && flags)),
+               "lc_chi_square_gate: bad arguments");
+  for (int32_t i = 0; i < n; i++)
+    NHIP_REQUIRE(pair_src[i] >= 0 && pair_src[i] < n_poses && pair_tgt[i] >= 0 && pair_tgt[i] < n_poses,
+                 "lc_chi_square_gate: pair %d (%d, %d) out of range", i, pair_src[i], pair_tgt[i]);
+  if (n == 0) return NHIP_OK;
+  const size_t N = (size_t)n;
+  DevBuf dp, ds, dt, dc, dsc, df;
+  if ((rc = dp.alloc(sizeof(double) * 3 * (size_t)n_poses)) || (rc = ds.alloc(4 * N)) || (rc = dt.alloc(4 * N)) ||
+      (rc = dc.alloc(16 * N)) || (rc = dsc.alloc(8 * N)) || (rc = df.alloc(N)))
+    return rc;
+  NHIP_TRY_HIP(hipMemcpy(dp.p, poses, sizeof(double) * 3 * (size_t)n_poses, hipMemcpyHostToDevice));
+  NHIP_TRY_HIP(hipMemcpy(ds.p, pair_src, 4 * N, hipMemcpyHostToDevice));
+  NHIP_TRY_HIP(hipMemcpy(dt.p, pair_tgt, 4 * N, hipMemcpyHostToDevice));
+  NHIP_TRY_HIP(hipMemcpy(dc.p, cov, 16 * N, hipMemcpyHostToDevice));
+  InFlight inflight;
+  rc = launch_lc_chi_square(dp.as<const double>(), n_poses, ds.as<const int32_t>(), dt.as<const int32_t>(), dc.as<const float>(), n,
+                            max_score, dsc.as<double>(), df.as<uint8_t>(), nullptr);
+  if (rc) return rc;
+  NHIP_TRY_HIP(hipMemcpy(scores, dsc.p, 8 * N, hipMemcpyDeviceToHost));
+  NHIP_TRY_HIP(hipMemcpy(flags, df.p, N, hipMemcpyDeviceToHost));
+  InFlight::done();  // (the downloads above synchronised the null stream)
+  return NHIP_OK;
+}
+
+int nhip_lc_scatter_scores(const nhip_scans_t *scans, double *scores) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(scans && (scores || scans->n_scans == 0), "lc_scatter_scores: bad arguments");
+  if (scans->n_scans == 0) return NHIP_OK;
+  DevBuf d;
+  if ((rc = d.alloc(sizeof(double) * (size_t)scans->n_scans))) return rc;
+  InFlight inflight;
+  rc = launch_lc_scatter_scores(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), scans->n_scans, d.as<double>(), nullptr);
+  if (rc) return rc;
+  NHIP_TRY_HIP(hipMemcpy(scores, d.p, sizeof(double) * (size_t)scans->n_scans, hipMemcpyDeviceToHost));
+  InFlight::done();  // (the downloads above synchronised the null stream)
+  return NHIP_OK;
+}
+
+int nhip_lc_pair_gate(const double *poses, int32_t n_poses, const int32_t *candidates, int32_t n, double max_range,
+                      int32_t min_separation, uint8_t *flags) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(n >= 0 && n_poses >= 0 && (n == 0 || (poses && candidates && flags)), "lc_pair_gate: bad arguments");
+  for (int32_t i = 0; i < n; i++)
+    NHIP_REQUIRE(candidates[i] >= 0 && candidates[i] < n_poses, "lc_pair_gate: candidate %d out of range", candidates[i]);
+  if (n == 0) return NHIP_OK;
+  DevBuf dp, dc, df;
+  if ((rc = dp.alloc(sizeof(double) * 3 * (size_t)n_poses)) || (rc = dc.alloc(sizeof(int32_t) * (size_t)n)) ||
+      (rc = df.alloc((size_t)n * n)))
+    return rc;
+  NHIP_TRY_HIP(hipMemcpy(dp.p, poses, sizeof(double) * 3 * (size_t)n_poses, hipMemcpyHostToDevice));
+  NHIP_TRY_HIP(hipMemcpy(dc.p, candidates, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+  InFlight inflight;
+  rc = launch_lc_pair_gate(dp.as<const double>(), n_poses, dc.as<const int32_t>(), n, max_range, min_separation, df.as<uint8_t>(), nullptr);
+  if (rc) return rc;
+  NHIP_TRY_HIP(hipMemcpy(flags, df.p, (size_t)n * n, hipMemcpyDeviceToHost));
+  InFlight::done();  // (the downloads above synchronised the null stream)
+  return NHIP_OK;
+}
+
+// ---------------------------------------------------------------- residual batches and the host-buffer residual forms
+int nhip_resid_batch_create(int kind, const float *corr, const int32_t *block_offsets,
+                            const int32_t *block_src, const int32_t *block_tgt, int32_t n_blocks,
+                            int32_t n_poses, nhip_resid_batch_t **out) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(kind == NHIP_LIDAR_NORMAL || kind == NHIP_LIDAR_POINT, "resid_batch_create: bad kind %d", kind);
+  NHIP_REQUIRE(block_offsets && block_src && block_tgt && out && n_blocks >= 0 && n_poses >= 0,
+               "resid_batch_create: bad arguments");
+  NHIP_REQUIRE(block_offsets[0] == 0, "resid_batch_create: block_offsets[0] must be 0");
+  for (int32_t b = 0; b < n_blocks; b++) {
+    // slam_residuals.h:109 CHECK_GT(source_points.size(), 0)
+    NHIP_REQUIRE(block_offsets[b + 1] > block_offsets[b], "resid_batch_create: block %d is empty", b);
+    NHIP_REQUIRE(block_src[b] >= 0 && block_src[b] < n_poses && block_tgt[b] >= 0 && block_tgt[b] < n_poses,
+                 "resid_batch_create: block %d pose index out of range", b);
+  }
+  const int64_t n_corr = block_offsets[n_blocks];
+  NHIP_REQUIRE(n_corr == 0 || corr, "resid_batch_create: null corr");
+  std::vector<int32_t> cb((size_t)n_corr);
+  for (int32_t b = 0; b < n_blocks; b++)
+    for (int32_t i = block_offsets[b]; i < block_offsets[b + 1]; i++) cb[i] = b;
+  nhip_resid_batch *B = new nhip_resid_batch();
+  B->kind = kind;
+  B->n_blocks = n_blocks;
+  B->n_poses = n_poses;
+  B->n_corr = n_corr;
+  B->h_offsets.assign(block_offsets, block_offsets + n_blocks + 1);
+  if ((rc = B->jtt.alloc(sizeof(double) * 2 * (size_t)n_corr)) || (rc = B->one_poses.alloc(sizeof(double) * 6)) ||
+      (rc = B->one_consts.alloc(sizeof(double) * 8)) || (rc = B->one_idx.alloc(sizeof(int32_t) * 2))) {
+    delete B;
+    return rc;
+  }
+  {
+    const int32_t idx[2] = {0, 1};
+    hipError_t e0 = hipMemcpy(B->one_idx.p, idx, sizeof(idx), hipMemcpyHostToDevice);
+    if (e0 != hipSuccess) {
+      delete B;
+      return hip_fail(e0, "resid_batch_create memcpy", __FILE__, __LINE__);
+    }
+  }
+  if ((rc = B->corr.alloc(sizeof(float) * 8 * (size_t)n_corr)) || (rc = B->corr_block.alloc(sizeof(int32_t) * (size_t)n_corr)) ||
+      (rc = B->block_src.alloc(sizeof(int32_t) * (size_t)n_blocks)) || (rc = B->block_tgt.alloc(sizeof(int32_t) * (size_t)n_blocks)) ||
+      (rc = B->consts.alloc(sizeof(double) * 8 * (size_t)n_blocks)) || (rc = B->poses.alloc(sizeof(double) * 3 * (size_t)n_poses)) ||
+      (rc = B->res.alloc(sizeof(double) * 2 * (size_t)n_corr)) || (rc = B->jsrc.alloc(sizeof(double) * 6 * (size_t)n_corr)) ||
+      (rc = B->jtgt.alloc(sizeof(double) * 6 * (size_t)n_corr))) {
+    delete B;
+    return rc;
+  }
+  hipError_t e = hipSuccess;
+  if (n_corr) {
+    e = hipMemcpy(B->corr.p, corr, sizeof(float) * 8 * (size_t)n_corr, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(B->corr_block.p, cb.data(), sizeof(int32_t) * (size_t)n_corr, hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess && n_blocks) {
+    e = hipMemcpy(B->block_src.p, block_src, sizeof(int32_t) * (size_t)n_blocks, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(B->block_tgt.p, block_tgt, sizeof(int32_t) * (size_t)n_blocks, hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    delete B;
+    return hip_fail(e, "resid_batch_create memcpy", __FILE__, __LINE__);
+  }
+  *out = B;
+  return NHIP_OK;
+}
+
+// the whole batch at `poses`, on the null stream: the pose upload and the launch the three evaluations share.  jsrc, jtgt,
+// jtt, q: which of the outputs beside the residuals the kernel writes (jtt and q into B->jtt, one of them at a time)
+static int batch_launch(nhip_resid_batch_t *B, const double *poses, bool jsrc, bool jtgt, bool jtt, bool q) {
+  NHIP_TRY_HIP(hipMemcpy(B->poses.p, poses, sizeof(double) * 3 * (size_t)B->n_poses, hipMemcpyHostToDevice));
+  return launch_resid_lidar(B->kind, B->corr.as<const float>(), B->corr_block.as<const int32_t>(), B->n_corr,
+                            B->block_src.as<const int32_t>(), B->block_tgt.as<const int32_t>(), B->n_blocks, B->poses.as<const double>(),
+                            B->n_poses, B->consts.as<double>(), B->res.as<double>(), jsrc ? B->jsrc.as<double>() : nullptr,
+                            jtgt ? B->jtgt.as<double>() : nullptr, nullptr, jtt ? B->jtt.as<double>() : nullptr, 0,
+                            q ? B->jtt.as<double>() : nullptr);
+}
+
+int nhip_resid_batch_eval(nhip_resid_batch_t *B, const double *poses, double *residuals,
+                          double *jac_src, double *jac_tgt) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(B && poses && residuals, "resid_batch_eval: bad arguments");
+  if (B->n_corr == 0) return NHIP_OK;
+  if ((rc = batch_launch(B, poses, jac_src != nullptr, jac_tgt != nullptr, false, false))) return rc;
+  NHIP_TRY_HIP(hipMemcpy(residuals, B->res.p, sizeof(double) * 2 * (size_t)B->n_corr, hipMemcpyDeviceToHost));
+  if (jac_src) NHIP_TRY_HIP(hipMemcpy(jac_src, B->jsrc.p, sizeof(double) * 6 * (size_t)B->n_corr, hipMemcpyDeviceToHost));
+  if (jac_tgt) NHIP_TRY_HIP(hipMemcpy(jac_tgt, B->jtgt.p, sizeof(double) * 6 * (size_t)B->n_corr, hipMemcpyDeviceToHost));
+  return NHIP_OK;
+}
+
+int nhip_resid_batch_eval_compact(nhip_resid_batch_t *B, const double *poses, double *residuals, double *jac_src,
+                                  double *jac_tgt_theta) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(B && poses && residuals && jac_src && jac_tgt_theta, "resid_batch_eval_compact: bad arguments");
+  if (B->n_corr == 0) return NHIP_OK;
+  if ((rc = batch_launch(B, poses, true, false, true, false))) return rc;
+  // three copies on the stream the kernel ran on; into pinned memory (nhip_host_alloc) they run at the PCIe rate
+  NHIP_TRY_HIP(hipMemcpyAsync(residuals, B->res.p, sizeof(double) * 2 * (size_t)B->n_corr, hipMemcpyDeviceToHost, nullptr));
+  NHIP_TRY_HIP(hipMemcpyAsync(jac_src, B->jsrc.p, sizeof(double) * 6 * (size_t)B->n_corr, hipMemcpyDeviceToHost, nullptr));
+  NHIP_TRY_HIP(hipMemcpyAsync(jac_tgt_theta, B->jtt.p, sizeof(double) * 2 * (size_t)B->n_corr, hipMemcpyDeviceToHost, nullptr));
+  NHIP_TRY_HIP(hipStreamSynchronize(nullptr));
+  return NHIP_OK;
+}
+
+int nhip_resid_batch_eval_q(nhip_resid_batch_t *B, const double *poses, double *residuals, double *q, double *block_consts) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(B && poses && residuals && q && block_consts, "resid_batch_eval_q: bad arguments");
+  if (B->n_corr == 0) return NHIP_OK;
+  // (residual-only instantiation + one more 16-byte store per correspondence; q goes where the compact form keeps J_tgt's
+  //  theta column: the two forms of one batch are not in flight together -- the handle's calls synchronise)
+  if ((rc = batch_launch(B, poses, false, false, false, true))) return rc;
+  NHIP_TRY_HIP(hipMemcpyAsync(residuals, B->res.p, sizeof(double) * 2 * (size_t)B->n_corr, hipMemcpyDeviceToHost, nullptr));
+  NHIP_TRY_HIP(hipMemcpyAsync(q, B->jtt.p, sizeof(double) * 2 * (size_t)B->n_corr, hipMemcpyDeviceToHost, nullptr));
+  NHIP_TRY_HIP(hipMemcpyAsync(block_consts, B->consts.p, sizeof(double) * 8 * (size_t)B->n_blocks, hipMemcpyDeviceToHost, nullptr));
+  NHIP_TRY_HIP(hipStreamSynchronize(nullptr));
+  return NHIP_OK;
+}
+
+int nhip_resid_jacobians_from_q(int kind, const float *corr, const double *q, const double *block_consts, int64_t n,
+                                double *jac_src, double *jac_tgt) {
+  NHIP_REQUIRE(kind == NHIP_LIDAR_NORMAL || kind == NHIP_LIDAR_POINT, "resid_jacobians_from_q: bad kind %d", kind);
+  NHIP_REQUIRE(n >= 0 && (n == 0 || (corr && q && block_consts)), "resid_jacobians_from_q: bad arguments");
+  // the closed forms of resid_lidar_kernel (nhip_resid.hip) with u = q - t; consts = {l00, l01, l10, l11, tx, ty, i00, i01}
+  const double tx = block_consts[4], ty = block_consts[5], i00 = block_consts[6], i01 = block_consts[7], i10 = -i01, i11 = i00;
+  for (int64_t i = 0; i < n; i++) {
+    const double qx = q[2 * i], qy = q[2 * i + 1], ux = qx - tx, uy = qy - ty;
+    double js[6], jt[6];
+    if (kind == NHIP_LIDAR_NORMAL) {
+      const double nsx = corr[8 * i + 4], nsy = corr[8 * i + 5], ntx = corr[8 * i + 6], nty = corr[8 * i + 7];
+      js[0] = ntx * i00 + nty * i10;
+      js[1] = ntx * i01 + nty * i11;
+      js[2] = ntx * (-uy) + nty * ux;
+      js[3] = -(nsx * i00 + nsy * i10);
+      js[4] = -(nsx * i01 + nsy * i11);
+      js[5] = -(nsx * (-uy) + nsy * ux);
+      jt[0] = -js[0];
+      jt[1] = -js[1];
+      jt[2] = ntx * qy - nty * qx;
+      jt[3] = -js[3];
+      jt[4] = -js[4];
+      jt[5] = -(nsx * qy - nsy * qx);
+    } else {
+      js[0] = -i00; js[1] = -i01; js[2] = uy;
+      js[3] = -i10; js[4] = -i11; js[5] = -ux;
+      jt[0] = i00;  jt[1] = i01;  jt[2] = -qy;
+      jt[3] = i10;  jt[4] = i11;  jt[5] = qx;
+    }
+    if (jac_src) memcpy(jac_src + 6 * i, js, sizeof(js));
+    if (jac_tgt) memcpy(jac_tgt + 6 * i, jt, sizeof(jt));
+  }
+  return NHIP_OK;
+}
+
+int nhip_resid_batch_eval_block(nhip_resid_batch_t *B, int32_t block, const double *source_pose,
+                                const double *target_pose, double *residuals, double *jac_src, double *jac_tgt) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(B && source_pose && target_pose && residuals, "resid_batch_eval_block: bad arguments");
+  NHIP_REQUIRE(block >= 0 && block < B->n_blocks, "resid_batch_eval_block: block %d out of range", block);
+  const int64_t o = B->h_offsets[block], n = B->h_offsets[block + 1] - o;
+  double two[6];
+  memcpy(two, source_pose, 3 * sizeof(double));
+  memcpy(two + 3, target_pose, 3 * sizeof(double));
+  std::lock_guard<std::mutex> lk(B->one_mu);  // one scratch set per batch: callers on several threads take turns
+  NHIP_TRY_HIP(hipMemcpy(B->one_poses.p, two, sizeof(two), hipMemcpyHostToDevice));
+  // the block's slice of the batch; its rows carry block id `block`, the one set of constants sits at index 0
+  rc = launch_resid_lidar(B->kind, B->corr.as<const float>() + 8 * o, B->corr_block.as<const int32_t>() + o, n,
+                          B->one_idx.as<const int32_t>(), B->one_idx.as<const int32_t>() + 1, 1, B->one_poses.as<const double>(), 2,
+                          B->one_consts.as<double>(), B->res.as<double>() + 2 * o, jac_src ? B->jsrc.as<double>() + 6 * o : nullptr,
+                          jac_tgt ? B->jtgt.as<double>() + 6 * o : nullptr, nullptr, nullptr, block);
+  if (rc) return rc;
+  NHIP_TRY_HIP(hipMemcpy(residuals, B->res.as<double>() + 2 * o, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost));
+  if (jac_src) NHIP_TRY_HIP(hipMemcpy(jac_src, B->jsrc.as<double>() + 6 * o, sizeof(double) * 6 * (size_t)n, hipMemcpyDeviceToHost));
+  if (jac_tgt) NHIP_TRY_HIP(hipMemcpy(jac_tgt, B->jtgt.as<double>() + 6 * o, sizeof(double) * 6 * (size_t)n, hipMemcpyDeviceToHost));
+  return NHIP_OK;
+}
+
+int nhip_resid_batch_free(nhip_resid_batch_t *batch) {
+  delete batch;
+  return NHIP_OK;
+}
+
+// upload n bytes (n may be 0)
+static int up(DevBuf &d, const void *h, size_t n) {
+  int rc = d.alloc(n);
+  if (rc) return rc;
+  if (n) NHIP_TRY_HIP(hipMemcpy(d.p, h, n, hipMemcpyHostToDevice));
+  return NHIP_OK;
+}
+
+int nhip_resid_odometry(const float *t_odom, const float *r_odom, const int32_t *pose_i,
+                        const int32_t *pose_j, int32_t n, double tw, double rw, const double *poses,
+                        int32_t n_poses, double *residuals, double *jac_i, double *jac_j) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(n >= 0 && n_poses >= 0, "resid_odometry: negative size");
+  if (n == 0) return NHIP_OK;
+  NHIP_REQUIRE(t_odom && r_odom && pose_i && pose_j && poses && residuals, "resid_odometry: null pointer");
+  for (int32_t f = 0; f < n; f++)
+    NHIP_REQUIRE(pose_i[f] >= 0 && pose_i[f] < n_poses && pose_j[f] >= 0 && pose_j[f] < n_poses,
+                 "resid_odometry: factor %d pose index out of range", f);
+  DevBuf dt, dr, di, dj, dp, res, ji, jj;
+  if ((rc = up(dt, t_odom, sizeof(float) * 2 * (size_t)n)) || (rc = up(dr, r_odom, sizeof(float) * (size_t)n)) ||
+      (rc = up(di, pose_i, sizeof(int32_t) * (size_t)n)) || (rc = up(dj, pose_j, sizeof(int32_t) * (size_t)n)) ||
+      (rc = up(dp, poses, sizeof(double) * 3 * (size_t)n_poses)) || (rc = res.alloc(sizeof(double) * 3 * (size_t)n)) ||
+      (rc = ji.alloc(sizeof(double) * 9 * (size_t)n)) || (rc = jj.alloc(sizeof(double) * 9 * (size_t)n)))
+    return rc;
+  InFlight inflight;
+  rc = launch_resid_odometry(dt.as<const float>(), dr.as<const float>(), di.as<const int32_t>(), dj.as<const int32_t>(), n, tw, rw,
+                             dp.as<const double>(), n_poses, res.as<double>(), jac_i ? ji.as<double>() : nullptr,
+                             jac_j ? jj.as<double>() : nullptr, nullptr);
+  if (rc) return rc;
+  NHIP_TRY_HIP(hipMemcpy(residuals, res.p, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost));
+  if (jac_i) NHIP_TRY_HIP(hipMemcpy(jac_i, ji.p, sizeof(double) * 9 * (size_t)n, hipMemcpyDeviceToHost));
+  if (jac_j) NHIP_TRY_HIP(hipMemcpy(jac_j, jj.p, sizeof(double) * 9 * (size_t)n, hipMemcpyDeviceToHost));
+  InFlight::done();  // (the downloads above synchronised the null stream)
+  return NHIP_OK;
+}
+
+int nhip_resid_point_to_line(const float *segments, const float *points, const int32_t *point_block,
+                             int64_t n_points, const int32_t *block_pose, const int32_t *block_line,
+                             int32_t n_blocks, const double *poses, int32_t n_poses,
+                             const double *line_poses, int32_t n_line_poses, double *residuals,
+                             double *jac_pose, double *jac_line) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(n_points >= 0 && n_blocks >= 0 && n_poses >= 0 && n_line_poses >= 0, "resid_point_to_line: negative size");
+  if (n_points == 0) return NHIP_OK;
+  NHIP_REQUIRE(segments && points && point_block && block_pose && block_line && poses && line_poses && residuals,
+               "resid_point_to_line: null pointer");
+  for (int32_t b = 0; b < n_blocks; b++)
+    NHIP_REQUIRE(block_pose[b] >= 0 && block_pose[b] < n_poses && block_line[b] >= 0 && block_line[b] < n_line_poses,
+                 "resid_point_to_line: block %d parameter index out of range", b);
+  for (int64_t i = 0; i < n_points; i++)
+    NHIP_REQUIRE(point_block[i] >= 0 && point_block[i] < n_blocks, "resid_point_to_line: point %lld block out of range",
+                 (long long)i);
+  DevBuf ds, dpt, dpb, dbp, dbl, dp, dl, res, j0, j1;
+  if ((rc = up(ds, segments, sizeof(float) * 4 * (size_t)n_blocks)) || (rc = up(dpt, points, sizeof(float) * 2 * (size_t)n_points)) ||
+      (rc = up(dpb, point_block, sizeof(int32_t) * (size_t)n_points)) || (rc = up(dbp, block_pose, sizeof(int32_t) * (size_t)n_blocks)) ||
+      (rc = up(dbl, block_line, sizeof(int32_t) * (size_t)n_blocks)) || (rc = up(dp, poses, sizeof(double) * 3 * (size_t)n_poses)) ||
+      (rc = up(dl, line_poses, sizeof(double) * 3 * (size_t)n_line_poses)) || (rc = res.alloc(sizeof(double) * (size_t)n_points)) ||
+      (rc = j0.alloc(sizeof(double) * 3 * (size_t)n_points)) || (rc = j1.alloc(sizeof(double) * 3 * (size_t)n_points)))
+    return rc;
+  InFlight inflight;
+  rc = launch_resid_point_to_line(ds.as<const float>(), dpt.as<const float>(), dpb.as<const int32_t>(), n_points,
+                                  dbp.as<const int32_t>(), dbl.as<const int32_t>(), n_blocks, dp.as<const double>(), n_poses,
+                                  dl.as<const double>(), n_line_poses, res.as<double>(), jac_pose ? j0.as<double>() : nullptr,
+                                  jac_line ? j1.as<double>() : nullptr, nullptr);
+  if (rc) return rc;
+  NHIP_TRY_HIP(hipMemcpy(residuals, res.p, sizeof(double) * (size_t)n_points, hipMemcpyDeviceToHost));
+  if (jac_pose) NHIP_TRY_HIP(hipMemcpy(jac_pose, j0.p, sizeof(double) * 3 * (size_t)n_points, hipMemcpyDeviceToHost));
+  if (jac_line) NHIP_TRY_HIP(hipMemcpy(jac_line, j1.p, sizeof(double) * 3 * (size_t)n_points, hipMemcpyDeviceToHost));
+  InFlight::done();  // (the downloads above synchronised the null stream)
+  return NHIP_OK;
+}
+
+// ---------------------------------------------------------------- multi-GPU all-gather
+namespace {
+// ncclAllGather(sendbuff, recvbuff, sendcount, datatype, comm, stream); ncclInt8 = 0 (rccl.h)
+typedef int (*nccl_allgather_fn)(const void *, void *, size_t, int, void *, hipStream_t);
+typedef const char *(*nccl_errstr_fn)(int);
+nccl_allgather_fn g_allgather = nullptr;
+nccl_errstr_fn g_errstr = nullptr;
+std::once_flag g_rccl_once;
+
+void bind_rccl() {
+  // RTLD_NOLOAD first: a process that already holds an RCCL (PyTorch ships its own copy) must
+  // keep using that one, since the communicator came from it
+  void *h = nullptr;
+  for (const char *name : {"librccl.so.1", "librccl.so"}) {
+    h = dlopen(name, RTLD_NOW | RTLD_NOLOAD);
+    if (h) break;
+  }
+  for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
+    if (h) break;
+    h = dlopen(name, RTLD_NOW | RTLD_LOCAL);
+  }
+  if (!h) return;
+  g_allgather = reinterpret_cast<nccl_allgather_fn>(dlsym(h, "ncclAllGather"));
+  g_errstr = reinterpret_cast<nccl_errstr_fn>(dlsym(h, "ncclGetErrorString"));
+}
+}  // namespace
+
+int nhip_allgather_matches(void *comm, const nhip_match_t *d_local, int32_t n_local, nhip_match_t *d_all,
+                           void *stream) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(n_local >= 0, "allgather_matches: negative count");
+  if (n_local == 0) return NHIP_OK;
+  NHIP_REQUIRE(comm && d_local && d_all, "allgather_matches: null pointer");
+  std::call_once(g_rccl_once, bind_rccl);
+  if (!g_allgather) {
+    const char *why = dlerror();
+    set_error("allgather_matches: librccl.so could not be loaded (%s)", why ? why : "no ncclAllGather symbol");
+    return NHIP_ERR_STATE;
+  }
+  const int st = g_allgather(d_local, d_all, sizeof(nhip_match_t) * (size_t)n_local, /*ncclInt8=*/0, comm,
+                             static_cast<hipStream_t>(stream));
+  if (st != 0) {
+    set_error("allgather_matches: ncclAllGather failed: %s", g_errstr ? g_errstr(st) : "unknown");
+    return NHIP_ERR_HIP;
+  }
+  return NHIP_OK;
+}
+
+
+}  // extern "C"

@@ -524,7 +524,7 @@ int orc_csm_match_f64_batch(const float *xy, const int32_t *offsets, const int32
  * build defines it: exhaustive search on the low_res grid over
  * +-trans_range and +-rot_restriction in 1 degree steps, then exhaustive search on the high_res grid
  * over +-low_res around the coarse optimum in 0.1 degree steps.  Restated independently of
- * nhip_csm_get_transformation (csrc/nhip_api.hip), which tests compare with this, float for float.
+ * nhip_csm_get_transformation (csrc/nhip_dropin.hip), which tests compare with this, float for float.
  */
 int orc_two_level_match(const float *pc_a, int32_t n_a, const float *pc_b, int32_t n_b, double rot_a,
                         double rot_b, double rot_restriction, double range, double trans_range,

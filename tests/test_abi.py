@@ -1,5 +1,5 @@
-"""CPU-side checks of the C-ABI boundary: the library loads, exports every symbol the header
-declares, its pure-host helpers agree with the oracle's formulas, and compute entry points
+"""CPU-side checks of the C-ABI boundary: the library loads, exports every symbol the two headers
+declare, its pure-host helpers agree with the oracle's formulas, and compute entry points
 fail loudly (NHIP_ERR_NODEV) instead of falling back when no GPU is present."""
 import ctypes as C
 import math
@@ -15,19 +15,36 @@ from oracle import oracle as O
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def header_symbols():
-    txt = open(os.path.join(ROOT, "include", "nautilus_hip.h")).read()
+def header_symbols(name="nautilus_hip.h"):
+    txt = open(os.path.join(ROOT, "include", name)).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(nhip_[a-z0-9_]+)\s*\(", txt)))
 
 
+# The instruments: what include/nautilus_hip_debug.h declares, and nothing else does.  Moving a name between the two
+# headers is an edit of this list.
+DEBUG_SYMBOLS = [
+    "nhip_bnb_stats", "nhip_bnb_stats_levels", "nhip_bnb_stats_per_pair", "nhip_bnb_timeline", "nhip_bnb_timeline_candidates",
+    "nhip_host_phases",
+    "nhip_timing_enable", "nhip_timing_reset", "nhip_timing_get",
+    "nhip_csm_last_launch", "nhip_csm_get_transformation_info", "nhip_grids_was_rebuilt",
+    "nhip_grids_download_skip_map", "nhip_grids_download_hi_plane", "nhip_grids_download_hi_plane_copy",
+    "nhip_grids_download_tiled16", "nhip_grids_download_pool", "nhip_grids_download_pool4", "nhip_grids_download_hits",
+]
+
+
 def test_library_exports_every_declared_symbol():
     lib = _lib.load()
-    syms = header_symbols()
+    contract, debug = header_symbols(), header_symbols("nautilus_hip_debug.h")
+    syms = sorted(contract + debug)
     assert len(syms) >= 30
-    for s in syms:
+    for s in contract:
         assert hasattr(lib, s), "symbol %s declared in include/nautilus_hip.h is not exported" % s
-    assert sorted(_lib.PROTOTYPES) == syms, "python prototypes and header disagree"
+    for s in debug:
+        assert hasattr(lib, s), "symbol %s declared in include/nautilus_hip_debug.h is not exported" % s
+    assert not set(contract) & set(debug), "declared in both headers: %s" % sorted(set(contract) & set(debug))
+    assert sorted(_lib.PROTOTYPES) == syms, "python prototypes and headers disagree"
+    assert debug == sorted(DEBUG_SYMBOLS), "include/nautilus_hip_debug.h and the list of instruments above disagree"
 
 
 def test_struct_sizes_match_header():
