@@ -65,13 +65,25 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     xy, off = csm.pack_scans(bag.scans)
     nrm = np.concatenate(bag.normals).astype(np.float32)
     kind = _lib.NHIP_LIDAR_NORMAL if residual == "normal" else _lib.NHIP_LIDAR_POINT
+    if residual not in ("normal", "point", "feature"):
+        raise ValueError("run: residual %r" % (residual,))
     out = {"backend": backend.name, "n_scans": n_scans, "window": window, "residual": residual,
            "err_odometry_m": posegraph.trajectory_error(odom, bag.truth)}
     posegraph.clock_reset()
 
+    feats = None
+    if residual == "feature":
+        # the reference's FEATURE mode (the only one SolveSLAM runs, solver.cc:363): <= 20 planar and <= 10 edge points per
+        # scan, extracted once per run on the GPU (FeatureExtractor, slam_types.h:66-69)
+        t0 = time.perf_counter()
+        with posegraph.clocked("path"):
+            feats = backend.features(xy, nrm, off)
+        out["t_features_s"] = time.perf_counter() - t0
+        out["planar_points"], out["edge_points"] = int(feats[0][2][-1]), int(feats[1][2][-1])
+
     t0 = time.perf_counter()
     pg, poses = posegraph.solve_growing_window(xy, nrm, off, odom, 1, window, iterations=iterations, kind=kind,
-                                               device=device, verbose=verbose, backend=backend)
+                                               device=device, verbose=verbose, backend=backend, features=feats)
     out["t_icp_solve_s"] = time.perf_counter() - t0
     out["err_icp_m"] = posegraph.trajectory_error(poses, bag.truth)
     out["icp_correspondences"] = pg.icp.n_corr
@@ -153,7 +165,7 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         # residuals in every pass
         pg, poses = posegraph.solve_growing_window(xy, nrm, off, poses.copy(), max(1, window - 1), window, iterations=iterations, kind=kind,
                                                    device=device, verbose=verbose, backend=backend, initial=poses,
-                                                   hitl=[con] if con.blocks else [], loop_closures=lc)
+                                                   hitl=[con] if con.blocks else [], loop_closures=lc, features=feats)
         out["t_hitl_solve_s"] = time.perf_counter() - t0
         out["err_hitl_m"] = posegraph.trajectory_error(poses, bag.truth)
         out["hitl_chosen_line_pose"] = [float(v) for v in con.chosen_line_pose]
@@ -182,9 +194,10 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--scans", type=int, default=320)
     ap.add_argument("--window", type=int, default=10)
-    ap.add_argument("--residual", choices=["point", "normal"], default="normal",
-                    help="LIDARPointResidual on all points (the reference's non-FEATURE mode, solver.cc:308-314) or "
-                         "LIDARNormalResidual (its planar-feature mode, solver.cc:298-303)")
+    ap.add_argument("--residual", choices=["point", "normal", "feature"], default="normal",
+                    help="LIDARPointResidual on all points (the reference's non-FEATURE mode, solver.cc:308-314), "
+                         "LIDARNormalResidual on all points, or the reference's FEATURE mode (solver.cc:297-318): planar "
+                         "feature points as LIDARNormalResidual blocks and edge points as LIDARPointResidual blocks")
     ap.add_argument("-v", action="store_true")
     a = ap.parse_args()
     rank, world, local = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), \

@@ -62,7 +62,8 @@ const char *nhip_version(void);
  * memory that was out of range (see "Ids in device memory" above): NHIP_OK, or NHIP_ERR_ARG with the message in
  * nhip_last_error().  info (may be NULL): {OR of the kinds seen, kind, value, index of the first one reported}; kinds:
  * 1 target scan id of a grid build, 2 source scan id of a pair, 4 grid slot of a pair, 8 block id of a correspondence,
- * 16 pose index of a block, 32 scan id of a correspondence-search block.  Clears the record (in the order of `stream`).
+ * 16 pose index of a block, 32 scan id of a correspondence-search block, 64 feature index and 128 feature count of
+ * nhip_features_pack_dev.  Clears the record (in the order of `stream`).
  * ONE record per DEVICE, shared by every stream and host thread that uses the library on it: a host with several streams
  * on one device learns THAT an id was bad and which, not on which stream; a call that finds a record consumes it -- reports
  * of kernels still running on OTHER streams at that moment can be reported by this call or wiped by its clear.  Clients
@@ -426,6 +427,45 @@ int nhip_lc_chi_square_gate_dev(const double *d_poses, int32_t n_poses, const in
                                 const float *d_cov, int32_t n_pairs, double max_score, double *d_scores,
                                 uint8_t *d_flags, void *stream);
 
+/* Scan features: the planar and the edge points Solver::SolveSLAM's FEATURE mode builds its residual blocks from
+ * (solver.cc:297-318) -- FeatureExtractor(pointcloud, 0.008, 2.0, 10, 10, 20, 10) of every scan at once
+ * (src/util/slam_types.h:66-69, src/input/feature_extracter.{h,cc}; the spec, quirks included: DESIGN.md section 3,
+ * "Scan features").  Per point a smoothness score from its index neighbours (min / max eigenvalue of their float scatter
+ * matrix, closed form in double as nhip_lc_scatter_scores; NaN = the point has no score); the planar points are the
+ * greedy walk over ascending (score, index) that accepts what is not above `threshold` and not closer than
+ * `distance_threshold` to an accepted point, up to max_planar; the edge points the same walk over descending (score, index),
+ * not below `threshold`, up to max_edge.  Accepted ranges: neighbors_per_side 1..NHIP_FEATURE_MAX, min_neighbors
+ * 1..2 * neighbors_per_side - 1, max_planar and max_edge 1..NHIP_FEATURE_MAX, threshold finite, the two distances finite
+ * and >= 0; anything else is NHIP_ERR_ARG before anything is launched. */
+#define NHIP_FEATURE_MAX 64
+typedef struct nhip_feature_spec {
+  double threshold;             /* planar: score <= threshold; edge: score >= threshold (0.008) */
+  double distance_threshold;    /* accepted points of one set are at least this far apart [m] (2.0) */
+  double max_neighbor_distance; /* a LEFT neighbour further away than this is dropped (feature_extracter.h:28: 0.8) */
+  int32_t neighbors_per_side;   /* P: left neighbours i - P .. i - 1 (none for i < P), right i + 1 .. i + P - 1 (10) */
+  int32_t min_neighbors;        /* fewer neighbours: the point has no score (10) */
+  int32_t max_planar;           /* (20) */
+  int32_t max_edge;             /* (10) */
+} nhip_feature_spec_t;
+/* the reference's values, as listed above; pure host */
+int nhip_feature_spec_default(nhip_feature_spec_t *out);
+/* d_xy, d_offsets: the scans as everywhere (d_offsets: n_scans + 1 entries).  Outputs, per scan s, scan-local indices IN
+ * ACCEPTANCE ORDER (the order of planar_points / edge_points, hence of the rows of the residual blocks), -1 padded:
+ * d_planar_idx[s][max_planar], d_planar_count[s], d_edge_idx[s][max_edge], d_edge_count[s]; d_scores (may be NULL): one
+ * double per point of d_xy, NaN where a point has no score.  Scans of any length, empty ones included. */
+int nhip_features_extract_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const nhip_feature_spec_t *spec,
+                              int32_t *d_planar_idx, int32_t *d_planar_count, int32_t *d_edge_idx, int32_t *d_edge_count,
+                              double *d_scores, void *stream);
+/* Gathers the points d_idx[s][0 .. d_count[s]) (rows of `cap` entries, 1 <= cap <= NHIP_FEATURE_MAX) of every scan, and
+ * their normals if d_normals is not NULL (then d_normals_out must not be either: a feature point keeps its own normal, as
+ * GetPointNormal's lookup gives it, solver.cc:67-77, 164-166), into packed clouds: d_xy_out / d_normals_out (room for
+ * n_scans * cap points) and d_offsets_out[n_scans + 1] -- the layout nhip_corr_search_dev takes.  d_idx and d_count are
+ * checked by the kernels ("Ids in device memory" above): a count outside [0, cap] makes its scan contribute nothing, an
+ * index outside its scan is left out, and nhip_dev_status() reports either. */
+int nhip_features_pack_dev(const float *d_xy, const float *d_normals, const int32_t *d_offsets, int32_t n_scans,
+                           const int32_t *d_idx, const int32_t *d_count, int32_t cap, float *d_xy_out,
+                           float *d_normals_out, int32_t *d_offsets_out, void *stream);
+
 /* ------------------------------------------------------------------ handle API (host pointers) */
 typedef struct nhip_scans nhip_scans_t;
 typedef struct nhip_grids nhip_grids_t;
@@ -464,6 +504,10 @@ int nhip_lc_pair_gate(const double *poses, int32_t n_poses, const int32_t *candi
 int nhip_lc_chi_square_gate(const double *poses, int32_t n_poses, const int32_t *pair_src, const int32_t *pair_tgt,
                             const float *cov /* n_pairs x 4 */, int32_t n_pairs, double max_score,
                             double *scores /* n_pairs */, uint8_t *flags /* n_pairs */);
+
+/* nhip_features_extract_dev on uploaded scans; host outputs of the same shapes (scores: n_points doubles, may be NULL). */
+int nhip_features_extract(const nhip_scans_t *scans, const nhip_feature_spec_t *spec, int32_t *planar_idx,
+                          int32_t *planar_count, int32_t *edge_idx, int32_t *edge_count, double *scores);
 
 /* The reference-shaped single-pair call: CorrelativeScanMatcher(scanner_range, trans_range, low_res, high_res)
  * .GetTransformation(pc_a, pc_b, rot_a, rot_b, rot_restriction) -> (score, ((tx, ty), theta))

@@ -15,6 +15,7 @@ NHIP_OK, NHIP_ERR_ARG, NHIP_ERR_NODEV, NHIP_ERR_HIP, NHIP_ERR_ALLOC, NHIP_ERR_ST
 NHIP_LIDAR_NORMAL, NHIP_LIDAR_POINT = 0, 1
 NHIP_SEARCH_EXHAUSTIVE, NHIP_SEARCH_DENSE, NHIP_SEARCH_SHORT_SCANS, NHIP_SEARCH_EXACT_SCORE, NHIP_SEARCH_LATENCY = 1, 2, 4, 8, 16
 NHIP_SHORT_SCAN_POINTS = 1088
+NHIP_FEATURE_MAX = 64
 NHIP_GRID_SKIP_MAP, NHIP_GRID_NO_IMAGE = 1, 2
 NHIP_TIMER_CSM, NHIP_TIMER_GRID, NHIP_TIMER_RESID, NHIP_TIMER_CORR, NHIP_TIMER_NORMEQ, NHIP_TIMER_GRID_CLEAR = 0, 1, 2, 3, 4, 5
 NHIP_TIMER_CSM_BOUNDS, NHIP_TIMER_CSM_CAND, NHIP_TIMER_EXACT_SCORE = 6, 7, 8
@@ -51,6 +52,12 @@ class CsmParams(C.Structure):
     _fields_ = [("scanner_range", C.c_double), ("trans_range", C.c_double), ("low_res", C.c_double),
                 ("high_res", C.c_double), ("sigma", C.c_double), ("floor_p", C.c_double), ("cell_bits", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class FeatureSpec(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("distance_threshold", C.c_double), ("max_neighbor_distance", C.c_double),
+                ("neighbors_per_side", C.c_int32), ("min_neighbors", C.c_int32), ("max_planar", C.c_int32),
+                ("max_edge", C.c_int32)]
 
 
 class Match(C.Structure):
@@ -128,6 +135,10 @@ PROTOTYPES = {
     "nhip_lc_scatter_scores_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp]),
     "nhip_lc_pair_gate_dev": (C.c_int, [_vp, _i32, _vp, _i32, _f64, _i32, _vp, _vp]),
     "nhip_lc_chi_square_gate_dev": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _f64, _vp, _vp, _vp]),
+    "nhip_feature_spec_default": (C.c_int, [_P(FeatureSpec)]),
+    "nhip_features_extract_dev": (C.c_int, [_vp, _vp, _i32, _P(FeatureSpec), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nhip_features_pack_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "nhip_features_extract": (C.c_int, [_vp, _P(FeatureSpec), _vp, _vp, _vp, _vp, _vp]),
     "nhip_lc_chi_square_gate": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _f64, _vp, _vp]),
     "nhip_lc_scatter_scores": (C.c_int, [_vp, _vp]),
     "nhip_lc_pair_gate": (C.c_int, [_vp, _i32, _vp, _i32, _f64, _i32, _vp]),

@@ -62,7 +62,9 @@ class IcpBatch:
         self.dev = torch.device(device)
         self.lib = _lib.load()
         self.arena = arena
-        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.dev)
+        # (an empty array -- feature clouds of scans without features -- still gets an address: the entry points refuse NULL)
+        t = lambda a, dt: (torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.dev) if np.size(a)
+                           else torch.zeros(2, dtype=torch.from_numpy(np.zeros(0, dt)).dtype, device=self.dev))
         self.offsets_h = np.ascontiguousarray(offsets, dtype=np.int32)
         self.n_scans = len(self.offsets_h) - 1
         # the clouds: uploaded once per arena (the same host arrays, by identity and size, every window pass)

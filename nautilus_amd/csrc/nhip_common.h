@@ -52,7 +52,7 @@ struct IdBounds {          // (plain data: it travels inside the kernels' parame
   uint32_t *status;        // the device's status words, or null (ids are still checked, nothing is reported)
 };
 constexpr uint32_t BAD_TARGET_ID = 1u, BAD_PAIR_SRC = 2u, BAD_PAIR_SLOT = 4u, BAD_BLOCK_ID = 8u, BAD_POSE_ID = 16u,
-                   BAD_SCAN_ID = 32u;
+                   BAD_SCAN_ID = 32u, BAD_FEATURE_IDX = 64u, BAD_FEATURE_COUNT = 128u;
 constexpr int DEV_STATUS_WORDS = 4;  // {OR of the kinds seen, kind / value / index of the first report}
 uint32_t *dev_status();              // of the current device (allocated on the device's first use; null if that failed)
 #ifdef __HIPCC__
@@ -304,6 +304,14 @@ int launch_lc_chi_square(const double *d_poses, int32_t n_poses, const int32_t *
                          int32_t n, double max_score, double *d_scores, uint8_t *d_flags, hipStream_t s);
 int launch_lc_pair_gate(const double *d_poses, int32_t n_poses, const int32_t *d_cand, int32_t n, double max_range,
                         int32_t min_sep, uint8_t *d_flags, hipStream_t s);
+
+// scan features (nhip_feat.hip); the spec has passed feature_spec_check (nhip_host_features.hip)
+int launch_feat_extract(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const nhip_feature_spec_t &spec,
+                        int32_t *d_planar_idx, int32_t *d_planar_count, int32_t *d_edge_idx, int32_t *d_edge_count,
+                        double *d_scores, hipStream_t s);
+int launch_feat_pack(const float *d_xy, const float *d_normals, const int32_t *d_offsets, int32_t n_scans, const int32_t *d_idx,
+                     const int32_t *d_count, int32_t cap, float *d_xy_out, float *d_normals_out, int32_t *d_offsets_out,
+                     hipStream_t s);
 
 int launch_resid_point_to_line(const float *d_segments, const float *d_points,
                                const int32_t *d_point_block, int64_t n_points,

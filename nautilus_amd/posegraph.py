@@ -70,9 +70,25 @@ class HipBackend:
         self.torch, self.dev, self.lib = torch, torch.device(device), _lib.load()
         from .correspondence import DeviceArena
         self.arena = DeviceArena()  # the clouds and the work buffers of the ICP batches, kept across problem builds
+        self._dedicated = {}        # id(xy) -> (xy, DeviceArena): clouds whose batches do not share `arena` (dedicate())
 
     def icp(self, xy, normals, offsets, block_src, block_tgt, outlier_threshold):
-        return _HipIcp(IcpBatch(xy, normals, offsets, block_src, block_tgt, str(self.dev), outlier_threshold, arena=self.arena))
+        arena = self._dedicated.get(id(xy), (None, self.arena))[1]
+        return _HipIcp(IcpBatch(xy, normals, offsets, block_src, block_tgt, str(self.dev), outlier_threshold, arena=arena))
+
+    def dedicate(self, xy):
+        """Batches on the cloud `xy` (by identity) get an arena of their own from now on.  One batch owns an arena at a time
+        (DeviceArena): two batches that are evaluated in turn -- the planar and the edge batch of a FEATURE-mode graph -- would
+        take a shared one from each other at every evaluation and search again each time.  Feature clouds are tiny."""
+        from .correspondence import DeviceArena
+        if id(xy) not in self._dedicated:
+            self._dedicated[id(xy)] = (xy, DeviceArena())  # (the reference to xy keeps its id its own)
+
+    def features(self, xy, normals, offsets, spec=None):
+        """The planar and the edge points of every scan, extracted on the GPU (features.extract), as the pair of packed clouds
+        ((xy_p, nrm_p, off_p), (xy_e, nrm_e, off_e)) that PoseGraph(..., features=) takes."""
+        from . import features
+        return features.extract(xy, offsets, spec, device=str(self.dev)).clouds(xy, normals, offsets)
 
     def reserve_icp(self, offsets, window):
         """Work buffers for the largest problem of a growing-window solve (all (i, j), j in [i - window, i)): allocated once."""
@@ -197,6 +213,36 @@ class _HipIcp:
         return self.b.n_corr
 
 
+class _FeatureIcp:
+    """FEATURE mode (Solver::AddLidarResiduals, solver.cc:297-318): per window pair a LIDARNormalResidual block on the planar
+    points and a LIDARPointResidual block on the edge points -- two batches over the same pairs, each through
+    backend.icp(); their per-block normal equations add."""
+
+    def __init__(self, backend, features, block_src, block_tgt, outlier_threshold):
+        (xy_p, nrm_p, off_p), (xy_e, nrm_e, off_e) = features
+        if hasattr(backend, "dedicate"):
+            backend.dedicate(xy_p)
+            backend.dedicate(xy_e)
+        self.planar = backend.icp(xy_p, nrm_p, off_p, block_src, block_tgt, outlier_threshold)
+        self.edge = backend.icp(xy_e, nrm_e, off_e, block_src, block_tgt, outlier_threshold)
+        self.block_src, self.block_tgt = self.planar.block_src, self.planar.block_tgt
+
+    def set_poses(self, poses):
+        self.planar.set_poses(poses)
+        self.edge.set_poses(poses)
+
+    def search(self):
+        return self.planar.search() + self.edge.search()
+
+    def normal_equations(self, kind):
+        """(kind is the all-points graph's choice: a FEATURE graph's kinds are fixed by the reference)"""
+        return self.planar.normal_equations(_lib.NHIP_LIDAR_NORMAL) + self.edge.normal_equations(_lib.NHIP_LIDAR_POINT)
+
+    @property
+    def n_corr(self):
+        return self.planar.n_corr + self.edge.n_corr
+
+
 class OdometryFactors:
     """Batched OdometryResidual blocks: r = (w_t (T_i + T_odom - T_j), w_r wrap(th_i + R_odom - th_j))."""
 
@@ -264,14 +310,20 @@ class HitlConstraint:
 
 class PoseGraph:
     def __init__(self, xy, normals, offsets, odom, window=10, kind=_lib.NHIP_LIDAR_POINT, outlier_threshold=0.25,
-                 odom_weights=(1.0, 1.0), device="cuda:0", initial=None, backend=None):
+                 odom_weights=(1.0, 1.0), device="cuda:0", initial=None, backend=None, features=None):
+        """features: None -- every point of scan i against scan j, evaluated as `kind`; or the pair of packed clouds
+        ((xy_p, nrm_p, off_p), (xy_e, nrm_e, off_e)) of HipBackend.features(): the reference's FEATURE mode, planar points as
+        LIDARNormalResidual blocks and edge points as LIDARPointResidual blocks (xy, normals, offsets and kind are then unused)."""
         self.n = len(odom)
         self.kind = kind
         self.backend = backend if backend is not None else HipBackend(device)
         with clocked("marshal"):
             bs, bt = window_pairs(self.n, window)
         with clocked("path"), clocked("path_setup"):  # (uploads of the clouds and block lists, device allocations: part of "path")
-            self.icp = self.backend.icp(xy, normals, offsets, bs, bt, outlier_threshold)
+            if features is None:
+                self.icp = self.backend.icp(xy, normals, offsets, bs, bt, outlier_threshold)
+            else:
+                self.icp = _FeatureIcp(self.backend, features, bs, bt, outlier_threshold)
         self.odo = odometry_factors_from_poses(odom, tw=odom_weights[0], rw=odom_weights[1])
         self.lc = None
         self.hitl = []
@@ -417,20 +469,20 @@ class PoseGraph:
 
 def solve_growing_window(xy, normals, offsets, odom, window_min=1, window_max=10, iterations=4,
                          kind=_lib.NHIP_LIDAR_POINT, outlier_threshold=0.25, odom_weights=(1.0, 1.0),
-                         device="cuda:0", verbose=False, backend=None, initial=None, hitl=(), loop_closures=None):
+                         device="cuda:0", verbose=False, backend=None, initial=None, hitl=(), loop_closures=None, features=None):
     """Solver::OptimizeOverGrowingWindow (solver.cc:339-355): for every window size from
     lidar_constraint_amount_min to _max the problem is rebuilt -- odometry factors, HITL residuals
     (AddHITLResiduals) plus fresh correspondences for all (i, j) blocks of the window, searched at the current
-    estimate -- and solved.  Returns (PoseGraph of the last pass, poses)."""
+    estimate -- and solved.  features: as PoseGraph's (FEATURE mode).  Returns (PoseGraph of the last pass, poses)."""
     poses = np.array(odom if initial is None else initial, dtype=np.float64)
     backend = backend if backend is not None else HipBackend(device)
-    if hasattr(backend, "reserve_icp"):
+    if features is None and hasattr(backend, "reserve_icp"):  # (feature clouds: a few points per scan, nothing to reserve)
         with clocked("path"), clocked("path_setup"):
             backend.reserve_icp(offsets, window_max)
     pg = None
     for w in range(window_min, window_max + 1):
         pg = PoseGraph(xy, normals, offsets, odom, window=w, kind=kind, outlier_threshold=outlier_threshold,
-                       odom_weights=odom_weights, device=device, initial=poses, backend=backend)
+                       odom_weights=odom_weights, device=device, initial=poses, backend=backend, features=features)
         for con in hitl:
             pg.add_hitl(con)
         if loop_closures is not None:
