@@ -561,8 +561,8 @@ int nhip_resid_batch_eval_compact(nhip_resid_batch_t *batch, const double *poses
  * constants and the correspondence's own points / normals, which the host holds: a consumer rebuilds the
  * rows of its block while it copies its slice -- nhip_resid_jacobians_from_q does exactly that, on the host, for `n` rows
  * of ONE block (corr: its n x 8 floats; q: its n x 2 doubles; block_consts: its 8 doubles; jac_src / jac_tgt: 6 n doubles
- * or NULL).  32 instead of 80 (compact) / 112 (full) bytes per correspondence cross PCIe; the Jacobians agree with
- * nhip_resid_batch_eval's to 1e-14 relative (u is recovered as q - t). */
+ * or NULL).  32 instead of 80 (compact) / 112 (full) bytes per correspondence cross PCIe; the Jacobians are
+ * nhip_resid_batch_eval's bit for bit (u = L p_s is formed from the source point as the kernel forms it). */
 int nhip_resid_batch_eval_q(nhip_resid_batch_t *batch, const double *poses, double *residuals, double *q, double *block_consts);
 int nhip_resid_jacobians_from_q(int kind, const float *corr, const double *q, const double *block_consts, int64_t n,
                                 double *jac_src, double *jac_tgt);

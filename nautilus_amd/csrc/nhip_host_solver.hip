@@ -355,10 +355,14 @@ int nhip_resid_jacobians_from_q(int kind, const float *corr, const double *q, co
                                 double *jac_src, double *jac_tgt) {
   NHIP_REQUIRE(kind == NHIP_LIDAR_NORMAL || kind == NHIP_LIDAR_POINT, "resid_jacobians_from_q: bad kind %d", kind);
   NHIP_REQUIRE(n >= 0 && (n == 0 || (corr && q && block_consts)), "resid_jacobians_from_q: bad arguments");
-  // the closed forms of resid_lidar_kernel (nhip_resid.hip) with u = q - t; consts = {l00, l01, l10, l11, tx, ty, i00, i01}
-  const double tx = block_consts[4], ty = block_consts[5], i00 = block_consts[6], i01 = block_consts[7], i10 = -i01, i11 = i00;
+  // the closed forms of resid_lidar_kernel (nhip_resid.hip); consts = {l00, l01, l10, l11, tx, ty, i00, i01}.  u = L p_s is
+  // formed as the kernel forms it, from the source point the caller holds: q - t would leave it with the rounding of q, which
+  // beside a point near its scanner's origin is hundreds of ulps of u
+  const double l00 = block_consts[0], l01 = block_consts[1], l10 = block_consts[2], l11 = block_consts[3];
+  const double i00 = block_consts[6], i01 = block_consts[7], i10 = -i01, i11 = i00;
   for (int64_t i = 0; i < n; i++) {
-    const double qx = q[2 * i], qy = q[2 * i + 1], ux = qx - tx, uy = qy - ty;
+    const double px = corr[8 * i], py = corr[8 * i + 1];
+    const double qx = q[2 * i], qy = q[2 * i + 1], ux = l00 * px + l01 * py, uy = l10 * px + l11 * py;
     double js[6], jt[6];
     if (kind == NHIP_LIDAR_NORMAL) {
       const double nsx = corr[8 * i + 4], nsy = corr[8 * i + 5], ntx = corr[8 * i + 6], nty = corr[8 * i + 7];

@@ -74,8 +74,8 @@ __global__ __launch_bounds__(RT) void resid_lidar_kernel(
     const double *__restrict__ consts, double2 *__restrict__ residuals,
     double2 *__restrict__ jac_src, double2 *__restrict__ jac_tgt, double2 *__restrict__ jac_tgt_theta,
     int32_t block_base, int32_t n_blocks, uint32_t *__restrict__ status, double2 *__restrict__ q_out) {
-  // q_out (optional): the transformed source point q = S2T p_s per correspondence.  With the block's constants (Linv, t) it
-  // determines every Jacobian entry (u = q - t; the closed forms below), so a host that holds the correspondences rebuilds
+  // q_out (optional): the transformed source point q = S2T p_s per correspondence.  With the block's constants (L, Linv) it
+  // determines every Jacobian entry (u = L p_s; the closed forms below), so a host that holds the correspondences rebuilds
   // both Jacobians while it copies its slice: 32 instead of 80 bytes per correspondence cross PCIe (nhip_resid_batch_eval_q)
   __shared__ double2 s_j[WANT_J ? 2 * 3 * RT : 1];
   const int64_t i0 = (int64_t)blockIdx.x * RT;

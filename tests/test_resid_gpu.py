@@ -59,7 +59,7 @@ def test_lidar_blocks_match_autodiff_oracle(gpu, small_bag, kind):
     assert b4 is None and np.array_equal(a4, js)
     # the smallest form over PCIe (nhip_resid_batch_eval_q): residuals + q + 8 constants per block come down, both Jacobians
     # are rebuilt on the host from them and the correspondences (nhip_resid_jacobians_from_q): same residuals bit for bit,
-    # Jacobians equal to the device's to rounding (u is recovered as q - t) and to the autodiff oracle's like the device's
+    # Jacobians equal to the device's (u = L p_s is formed as the kernel forms it) and to the autodiff oracle's like the device's
     rq, jsq, jtq = batch.evaluate_q(poses)
     assert np.array_equal(rq, res)
     assert np.allclose(jsq, js, rtol=1e-12, atol=1e-12) and np.allclose(jtq, jt, rtol=1e-12, atol=1e-12)
@@ -138,12 +138,29 @@ def test_point_to_line_matches_autodiff_oracle(gpu):
     torch.cuda.synchronize()
     res, j0, j1 = d_res.cpu().numpy(), d_j0.cpu().numpy().reshape(n, 3), d_j1.cpu().numpy().reshape(n, 3)
     o = 0
-    seen_inside = seen_end = 0
+    seen_inside = seen_start = seen_end = 0
     for b in range(8):
         wr, w0, w1 = O.point_to_line_block(bseg[b], pts[b], poses[bpose[b]], lines[bline[b]])
         k = len(pts[b])
         close(res[o:o + k], wr), close(j0[o:o + k], w0, 10.0), close(j1[o:o + k], w1, 10.0)
+        # which branch each point took: the oracle's residual is its signed distance to the line (in magnitude) or its
+        # distance to one end, and the kernel's must be the same one
+        (px, py, pth), (lx, ly, lth) = poses[bpose[b]], lines[bline[b]]
+        sg = bseg[b].astype(np.float64)
+        S = [np.array([math.cos(lth) * sg[i] - math.sin(lth) * sg[i + 1] + lx, math.sin(lth) * sg[i] + math.cos(lth) * sg[i + 1] + ly]) for i in (0, 2)]
+        p = pts[b].astype(np.float64)
+        P = np.stack([math.cos(pth) * p[:, 0] - math.sin(pth) * p[:, 1] + px, math.sin(pth) * p[:, 0] + math.cos(pth) * p[:, 1] + py], axis=1)
+        e = S[1] - S[0]
+        sd = np.abs(((P - S[0]) @ np.array([-e[1], e[0]])) / np.hypot(*e))
+        cand = np.stack([sd, np.hypot(*(P - S[0]).T), np.hypot(*(P - S[1]).T)], axis=1)
+        took = np.argmin(np.abs(cand - wr[:, None]), axis=1)
+        assert np.all(np.abs(cand[np.arange(k), took] - wr) < 1e-9)
+        assert np.array_equal(np.argmin(np.abs(cand - res[o:o + k, None]), axis=1), took)
+        seen_inside += int((took == 0).sum())
+        seen_start += int((took == 1).sum())
+        seen_end += int((took == 2).sum())
         o += k
+    assert seen_inside > 0 and seen_start > 0 and seen_end > 0, (seen_inside, seen_start, seen_end)
     assert np.all(res >= 0)
 
 
