@@ -114,25 +114,45 @@ __device__ __forceinline__ void window_origin(float2 q, float cf, float sf, cons
     // position of a point that scores nothing (column -hx - 1, row -hy - 1: the lower clamp bounds), and the straight-line
     // code needs neither the two magnitude compares nor the selects -- one constant per coordinate after the clamp.
     const float rx = __fsub_rn(mx, fx), ry = __fsub_rn(my, fy);  // exact
-    const bool slow = !(fminf(rx, __fsub_rn(1.0f, rx)) > __fmul_rn(fabsf(mx), 0x1p-22f)) ||
-                      !(fminf(ry, __fsub_rn(1.0f, ry)) > __fmul_rn(fabsf(my), 0x1p-22f));
+    const float dx = fminf(rx, __fsub_rn(1.0f, rx)), dy = fminf(ry, __fsub_rn(1.0f, ry));
+    const float tx = __fmul_rn(fabsf(mx), 0x1p-22f), ty = __fmul_rn(fabsf(my), 0x1p-22f);
+    // (the lane mask straight from the compares, "unordered or <=": a ballot of the bool goes through a 0 / 1 register)
+    const unsigned long long slow = __builtin_amdgcn_fcmpf(dx, tx, 13 /* ule */) | __builtin_amdgcn_fcmpf(dy, ty, 13 /* ule */);
     ix = (int32_t)fx;
     iy = (int32_t)fy;
-    if (__builtin_amdgcn_ballot_w64(slow) != 0ull) {
-      if (slow) {
-        // (the magnitude test on the promoted values -- 1e9 is a float -- so that it stays on this path)
-        const double xd = (double)xr, yd = (double)yr;
-        const bool fin = (fabs(xd) < 1e9) && (fabs(yd) < 1e9);
-        ix = (int32_t)fmin(fmax(floor_quotient(xd, P.res, P.inv_res), -2147483000.0), 2147483000.0);
-        iy = (int32_t)fmin(fmax(floor_quotient(yd, P.res, P.inv_res), -2147483000.0), 2147483000.0);
-        if (!fin) ix = iy = -2147483000;
+    const int32_t kx = half + cx - P.hx + P.pad, ky = half + cy - P.hy + P.pad;  // (added after the clamp, below)
+    if (slow != 0ull) {
+      // Second stage, off the straight path.  The bounds phase uses only pcol >> 3 and prow >> 3 (the pooled entry), not
+      // the cell.  For a near coordinate with |m| < 2^22 the quotient and m lie within |m| * 2^-23 < 1 / 2 of each other,
+      // so the only integer that can separate them is n = rint(m): the spec's floor and the float floor are both n - 1 or
+      // n.  The clamp c() is monotone with steps of 0 or 1: c(n - 1) and c(n) are equal, or they are n - 1 and n
+      // themselves -- it creates no crossing that the unclamped values do not have -- and (n - 1 + K) >> 3 differs from
+      // (n + K) >> 3 only where n + K is a multiple of 8 (K: the constant added after the clamp).  So a near coordinate
+      // needs the double-precision floor only in that bucket, one time in eight; everywhere else the lane keeps
+      // (int)floorf(m): its cell may be off by one, its pooled entry is not.  A coordinate that is not near has the
+      // spec's floor already.  What stays: quotients that are not numbers and |m| >= 2^22 (which includes every point the
+      // spec calls non-finite, see above) -- "!(|m| < 2^22)" holds for both.
+      // (bitwise: straight-line code on lane masks, no short-circuit branches)
+      const bool near_x = !(dx > tx), near_y = !(dy > ty);
+      const bool big = (int)!(fabsf(mx) < 0x1p22f) | (int)!(fabsf(my) < 0x1p22f);
+      const int32_t nx = (int32_t)rintf(mx), ny = (int32_t)rintf(my);  // (saturating; `big` covers what does not fit)
+      const bool stay = (int)big | ((int)near_x & (int)(((nx + kx) & 7) == 0)) | ((int)near_y & (int)(((ny + ky) & 7) == 0));
+      if (__builtin_amdgcn_ballot_w64(stay) != 0ull) {
+        if (stay) {
+          // (the magnitude test on the promoted values -- 1e9 is a float -- so that it stays on this path)
+          const double xd = (double)xr, yd = (double)yr;
+          const bool fin = (fabs(xd) < 1e9) && (fabs(yd) < 1e9);
+          ix = (int32_t)fmin(fmax(floor_quotient(xd, P.res, P.inv_res), -2147483000.0), 2147483000.0);
+          iy = (int32_t)fmin(fmax(floor_quotient(yd, P.res, P.inv_res), -2147483000.0), 2147483000.0);
+          if (!fin) ix = iy = -2147483000;
+        }
       }
     }
     const int32_t lo_x = -P.hx - 1 - half - cx, lo_y = -P.hy - 1 - half - cy;
     ix = min(max(ix, lo_x), P.S + P.hx - half - cx);
     iy = min(max(iy, lo_y), P.S + P.hy - half - cy);
-    *pcol = ix + (half + cx - P.hx + P.pad);
-    *prow = iy + (half + cy - P.hy + P.pad);
+    *pcol = ix + kx;
+    *prow = iy + ky;
     return;
   }
   const float rx = __fsub_rn(mx, fx), ry = __fsub_rn(my, fy);  // exact
@@ -292,6 +312,16 @@ __device__ __forceinline__ uint32_t add_xor(uint32_t v) {
 // gather a total run length of at most LANE_WEIGHT = 64 between two reductions (4 lanes * 64 * 255 = 65,280); the
 // wave reduces early when a pass would take some lane past that, otherwise once per rotation.
 constexpr uint32_t LANE_WEIGHT = 64u;
+
+// acc + a * b on 24-bit factors as ONE v_mad_u32_u24, whatever the compiler learns about the bits of the result that are
+// used: where only part of a packed sum is read later (the fields O[y][2] of the gather below, whose high halves are
+// unused or carry block row 10) hipcc narrows `acc += __umul24(a, b)` and then selects the quarter-rate v_mad_u64_u32.
+__device__ __forceinline__ uint32_t mad24(uint32_t a, uint32_t b, uint32_t acc) {
+  uint32_t r;
+  asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(acc));
+  return r;
+}
+
 constexpr int LIST_ENTRIES = 128; // ring of pending entries per wave (a chunk appends <= 64, 64 are consumed at a time)
 
 template <bool POOL_LDS>
@@ -307,7 +337,7 @@ __device__ __forceinline__ void coarse_rotation(const BnbParams &P, const uint8_
 #pragma unroll
     for (int d = 0; d < 3; d++) E[y][d] = O[y][d] = 0u;
   uint32_t head = 0u, tail = 0u;  // ring positions (wave-uniform)
-  bool pending = false;           // passes gathered since the last reduction
+  uint32_t reduced = 0u;          // `head` at the last reduction: passes were gathered since iff head != reduced (scalar)
   uint32_t weight = 0u;           // this lane's run lengths gathered since the last reduction
 
   // 64 list entries: every lane gathers the 11 x 12 bytes of its entry, weighted by the run length.  The bytes of dword d
@@ -329,7 +359,7 @@ __device__ __forceinline__ void coarse_rotation(const BnbParams &P, const uint8_
       }
       E[y][0] += __umul24(__builtin_amdgcn_perm(w1, w0, se), cnt); O[y][0] += __umul24(__builtin_amdgcn_perm(w1, w0, so), cnt);
       E[y][1] += __umul24(__builtin_amdgcn_perm(w2, w1, se), cnt); O[y][1] += __umul24(__builtin_amdgcn_perm(w2, w1, so), cnt);
-      E[y][2] += __umul24(__builtin_amdgcn_perm(w3, w2, se), cnt); O[y][2] += __umul24(__builtin_amdgcn_perm(w3, w2, so), cnt);
+      E[y][2] += __umul24(__builtin_amdgcn_perm(w3, w2, se), cnt); O[y][2] = mad24(__builtin_amdgcn_perm(w3, w2, so), cnt, O[y][2]);
     }
   };
   // the transposing reduction of the 128 packed sums (see the layout above); clears the accumulators
@@ -419,15 +449,18 @@ __device__ __forceinline__ void coarse_rotation(const BnbParams &P, const uint8_
       const uint32_t next = mine ? list[(head + (uint32_t)lane + 1u) & (LIST_ENTRIES - 1)] : 0u;
       const uint32_t cnt = mine ? ((next >> RUN_SHIFT) - (entry >> RUN_SHIFT)) & 127u : 0u;
       // (also before a pass that could overflow some lane's fields)
-      if (pending && (last || __ballot(weight + cnt > LANE_WEIGHT) != 0ull)) {
+      // (the lane mask straight from the compare; `last` tested on a scalar register the compiler knows nothing about:
+      //  as the bool above, which also ends the loop, it is inverted here through a 0 / 1 vector register)
+      uint32_t left = avail;
+      asm("" : "+s"(left));
+      if (head != reduced && (left == 0u || __builtin_amdgcn_uicmp(weight + cnt, LANE_WEIGHT, 34 /* ugt */) != 0ull)) {
         reduce();
-        pending = false;
+        reduced = head;
         weight = 0u;
       }
       if (last) break;
       gather(ea, cnt);
       weight += cnt;
-      pending = true;
       head += avail < 64u ? avail : 64u;
       __builtin_amdgcn_wave_barrier();
     }
@@ -824,6 +857,21 @@ __device__ __forceinline__ uint32_t org_cnt(uint32_t o) { return (o & 63u) + 1u;
 //  cells lie in the zero border)
 __device__ __forceinline__ uint32_t origin_of(const uint32_t *org, int c) { return c < OCL ? org[64 * c] : 0u; }
 
+// sum over each aligned group of 8 lanes, in all of them
+__device__ __forceinline__ uint32_t sum8(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1, 0, 3, 2]
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2, 3, 0, 1]
+  return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false);  // row_half_mirror
+}
+// sum over the wave of a value that is the same in each aligned group of 8 lanes, counted once per group (wave-uniform)
+__device__ __forceinline__ uint32_t wave_total_of8(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false);  // row_mirror: the row's other half
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xF, 0xF, false);  // row_bcast:15: the row above's sum
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xF, 0xF, false);  // row_bcast:31: rows 0 + 1 into 2, 3
+  // (lane 63 holds the total whatever the rows without a source lane received: its own two sources do have one)
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+
 // Returns the number of 64-entry chunks of the list (wave-uniform).  The packed sums of the bounds and exact sums hold
 // 16-bit fields that are added over 8 lanes before they are unpacked: the points of every aligned group of 8 lanes,
 // over all chunks, must not exceed 257 (257 * 255 = 65,535).  One point per entry keeps that by construction (<= 18
@@ -893,9 +941,7 @@ __device__ __forceinline__ int32_t cache_origins(const BnbParams &P, const float
       const uint32_t e = org[64 * c];
       w += 64u * (uint32_t)c + (uint32_t)lane < tail ? org_cnt(e) : 0u;
     }
-    w += shfl_xor_u32(w, 1);
-    w += shfl_xor_u32(w, 2);
-    w += shfl_xor_u32(w, 4);
+    w = sum8(w);
     if (__ballot(w > 257u) == 0ull) return nch;
     __builtin_amdgcn_wave_barrier();
   }
@@ -956,13 +1002,13 @@ __device__ __forceinline__ void strip_bounds_c(const BnbParams &P, __amdgpu_buff
       E[2] += __umul24(n2 & M8, cn[j]); O[2] += __umul24((n2 >> 8) & M8, cn[j]);
     }
   }
+  // sums over the wave without LDS: the packed fields over groups of 8 lanes (quad permutations, then the mirror image
+  // of the half row holds the other quad's sum), unpacked, over the row of 16 (its mirror image), then down the rows
+  // (row_bcast:15 / :31 -- lane 63 ends with the total) and into a scalar register
 #pragma unroll
-  for (int m = 1; m < 8; m <<= 1) {
-#pragma unroll
-    for (int t = 0; t < 3; t++) {
-      E[t] += shfl_xor_u32(E[t], m);
-      O[t] += shfl_xor_u32(O[t], m);
-    }
+  for (int t = 0; t < 3; t++) {
+    E[t] = sum8(E[t]);
+    O[t] = sum8(O[t]);
   }
 #pragma unroll
   for (int t = 0; t < 3; t++) {
@@ -972,12 +1018,7 @@ __device__ __forceinline__ void strip_bounds_c(const BnbParams &P, __amdgpu_buff
     out[4 * t + 3] = O[t] >> 16;      // (1, 1)
   }
 #pragma unroll
-  for (int m = 8; m < 64; m <<= 1) {
-#pragma unroll
-    for (int q = 0; q < 12; q++) out[q] += shfl_xor_u32(out[q], m);
-  }
-#pragma unroll
-  for (int q = 0; q < 12; q++) out[q] *= scale;
+  for (int q = 0; q < 12; q++) out[q] = wave_total_of8(out[q]) * scale;
 }
 
 // ---- the pair's running best
@@ -1164,8 +1205,34 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
   v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false));
   v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xF, 0xF, false));
   v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, false));
-  v = max(v, shfl_xor_u32(v, 16));
-  return max(v, shfl_xor_u32(v, 32));
+  const auto s16 = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+  v = max(s16[0], s16[1]);
+  const auto s32 = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+  return max(s32[0], s32[1]);
+}
+// the same over 64-bit keys (both halves take the same route; every lane ends with the wave's maximum)
+template <int CTRL>
+__device__ __forceinline__ unsigned long long max_dpp_u64(unsigned long long v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, 0xF, 0xF, false);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, 0xF, 0xF, false);
+  const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+  return o > v ? o : v;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+  v = max_dpp_u64<0xB1>(v);
+  v = max_dpp_u64<0x4E>(v);
+  v = max_dpp_u64<0x124>(v);
+  v = max_dpp_u64<0x128>(v);
+  {
+    const auto l = __builtin_amdgcn_permlane16_swap((uint32_t)v, (uint32_t)v, false, false);
+    const auto h = __builtin_amdgcn_permlane16_swap((uint32_t)(v >> 32), (uint32_t)(v >> 32), false, false);
+    const unsigned long long a = ((unsigned long long)h[0] << 32) | l[0], b = ((unsigned long long)h[1] << 32) | l[1];
+    v = a > b ? a : b;
+  }
+  const auto l = __builtin_amdgcn_permlane32_swap((uint32_t)v, (uint32_t)v, false, false);
+  const auto h = __builtin_amdgcn_permlane32_swap((uint32_t)(v >> 32), (uint32_t)(v >> 32), false, false);
+  const unsigned long long a = ((unsigned long long)h[0] << 32) | l[0], b = ((unsigned long long)h[1] << 32) | l[1];
+  return a > b ? a : b;
 }
 
 // sum over the scan's points of the 16-bit cell that pose (ix, iy) of the rotation reads: one 2-byte load per point
@@ -1515,19 +1582,11 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : BNB_THREADS, SPLIT ? SPL
       wbest = cand > wbest ? cand : wbest;
     }
     if (BY_ROT) {
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) {
-        const uint32_t o = shfl_xor_u32(umax, m);
-        umax = o > umax ? o : umax;
-      }
+      umax = wave_max(umax);  // (no LDS round trips)
       if (wave_leader(lane)) s_kmax[k] = ((unsigned long long)umax << 32) | (uint32_t)k;
     }
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const unsigned long long o = shfl_xor_u64b(wbest, m);
-    wbest = o > wbest ? o : wbest;
-  }
+  wbest = wave_max_u64(wbest);
   if (gfloor > 0) {  // (score gate; uniform over the workgroup)
     // no bound of the pair reaches the floor: no pose can be kept, the pair is settled -- no seeds, nothing handed over,
     // no candidates left for the split form's second kernel (its counts stay the zeros the host wrote)
