@@ -20,7 +20,8 @@ size_t bnb_lds_first(const GridLayout &L, bool pool_lds) {
   return pool > (size_t)ORG_LDS ? pool : (size_t)ORG_LDS;
 }
 size_t bnb_lds_bytes(const GridLayout &L, const nhip_search_t *search, bool pool_lds) {
-  return bnb_lds_first(L, pool_lds) + (size_t)search->n_theta * 128 * 4 + (size_t)QCAP * 8 + 64;
+  // (the fused form's size; the split form's is no larger: nhip_bnb_params.h)
+  return lds_bytes(bnb_lds_first(L, pool_lds), search->n_theta, false);
 }
 constexpr size_t LDS_MAX = 160 * 1024;
 
@@ -152,7 +153,6 @@ BnbPlan bnb_plan(const GridLayout &L, const nhip_search_t *search, int32_t n_pai
   if (p.second)  // (entries per XCD list)
     p.rot_cap = (uint32_t)std::min<int64_t>((workspace_bytes - BNB_WS_HEADER) / (int64_t)sizeof(RotEntry) / 8, 0x0fffffff);
   p.pool_lds = bnb_lds_bytes(L, search, true) <= LDS_MAX;
-  p.lds = (int64_t)bnb_lds_bytes(L, search, p.pool_lds);
   p.lds_first = (int64_t)bnb_lds_first(L, p.pool_lds);
   return p;
 }

@@ -12,12 +12,46 @@ constexpr int BNB_WAVES = 8;          // waves per workgroup of csm_bnb_kernel
 constexpr int NB = BNB_MAX_NB;        // blocks per axis held in registers (11: nx, ny <= 88)
 constexpr int MAX_ROT = 340;          // rotations per search: QCAP * 4 bytes hold their 12 bytes of ordering data
 constexpr int QCAP = 1024;            // candidate queue entries per workgroup (overflow is evaluated by the wave that found it)
+// Waves per workgroup of the split form's first kernel (bounds + seeds).  What bounds that kernel is the latency of a
+// wave's own instruction chain more than issue slots: with ONE workgroup per CU (two waves per SIMD) it takes 1.63x the
+// time of two.  Five waves per SIMD would need workgroups of ten waves at 96 registers; built and twice as slow -- ten
+// waves spread 3 + 3 + 2 + 2 over the SIMDs, a second workgroup's would make six on two of them, which 96 registers do
+// not allow, so ONE workgroup was resident per CU.  Twelve waves need 80 registers, a third workgroup of eight also 53 KB
+// of LDS (profiles/r04_bounds_variants.txt).
+constexpr int SPLIT_WAVES = 8;
+constexpr int LIST_ENTRIES = 128;     // ring of pending run-list entries per wave (a chunk appends <= 64, 64 are consumed at a time)
 constexpr int RUN_SHIFT = 25;         // run-list entry = pooled offset | (index of the run's first point mod 128) << RUN_SHIFT
 constexpr int OC = 18;                // 64-entry chunks the by-rotation passes are unrolled for
 constexpr int OCL = 17;               // chunks of window origins a wave holds: 1088 points (a 1081-beam scan)
 constexpr int ORG_WAVE = OCL * 64;    // words of LDS per wave
 constexpr int ORG_LDS = BNB_WAVES * ORG_WAVE * 4;  // bytes per workgroup (34,816: the 1200 x 1200 grid's pooled table is 35,712)
 constexpr uint32_t ORG_LIMIT = 1u << 13;           // rows / columns of a stored grid the packed origins hold
+
+// ---- the dynamic LDS of csm_bnb_kernel, in this order (the kernel carves it, bnb_plan and launch_main size it):
+//   first region   the pooled table while the bounds are computed (if staged), then the waves' window origins
+//   bounds         n_theta rows of 128 words
+//   queue's space  words of 8 bytes: QCAP entries of the candidate queue -- or, in the split form, which has no queue,
+//                  QSPACE_SPLIT words for the run lists of its SPLIT_WAVES waves and the rotations' maxima and order
+//                  (the fused form keeps those in the queue's two halves)
+//   LdsTail        in LDS_TAIL_BYTES
+constexpr int QSPACE_SPLIT = (SPLIT_WAVES * LIST_ENTRIES * 4 + MAX_ROT * 12 + 15) / 16 * 2;
+constexpr int lds_qspace(bool split) { return split ? QSPACE_SPLIT : QCAP; }
+// bnb_fits() checks the fused form's size only: it holds for the split form because that form's is no larger
+static_assert(QSPACE_SPLIT <= QCAP, "the split form's LDS must not exceed the fused form's, which bnb_fits() checks");
+struct LdsTail {
+  unsigned long long best;  // the pair's running best key
+  uint32_t cnt[6];          // [0], [3..5]: work counters (instrumented build); [LDS_QN]: candidates counted / queued;
+                            // [LDS_QHEAD]: next queue entry or rank to hand out
+  unsigned long long slow;  // (stats: the slowest wave's time in the candidate phase)
+  uint32_t top;             // (score gate: the workgroup's highest bound)
+};
+constexpr int LDS_QN = 1, LDS_QHEAD = 2, LDS_TAIL_BYTES = 64;
+static_assert(sizeof(LdsTail) <= LDS_TAIL_BYTES, "the tail fits its 64 bytes");
+// bytes of dynamic LDS of a launch whose first region has `first` bytes (a multiple of 16)
+constexpr size_t lds_bytes(size_t first, int32_t n_theta, bool split) {
+  return first + (size_t)n_theta * 128 * 4 + (size_t)lds_qspace(split) * 8 + LDS_TAIL_BYTES;
+}
+
 constexpr int BNB_STATS_PAIRS = 1 << 20;           // per-pair counters kept by NHIP_BNB_STATS=1
 constexpr int BNB_STATS_HEAD = 16;    // totals: 4 counts, then shader-clock sums of the by-rotation kernel (see nhip_bnb_stats_levels)
 

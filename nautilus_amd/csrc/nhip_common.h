@@ -219,7 +219,7 @@ struct BnbPlan {
   bool sized_split;  // the size rule (bnb_workspace_bytes) gives this list room for the split form
   uint32_t rot_cap, heavy_min, keep_ranks, split_min, split_max;  // split_max 0: by the round's length
   int64_t batch, slots, slot_bytes, rounds;  // pairs per round (0: fused), rounds' state the workspace holds, bytes of one
-  int64_t lds, lds_first;
+  int64_t lds_first;  // bytes of the main kernel's first LDS region (bnb::lds_bytes gives a launch's total from it)
 };
 BnbPlan bnb_plan(const GridLayout &L, const nhip_search_t *search, int32_t n_pairs, int64_t workspace_bytes);
 

@@ -68,7 +68,7 @@ int make_layout(const nhip_grid_spec_t *spec, GridLayout *L) {
   L->hi_offset = L->pool4_offset + L->pool4_bytes;
   // 16-bit cells: the plane of their high bytes, one byte per cell at the 8-bit pitch.  The matcher sums exact 8 x 8
   // and 4 x 4 blocks on this plane at the cost of 8-bit cells (256 * sum(hi) + 255 * points bounds a pose's sum from
-  // above) and reads 16-bit cells only for the poses that bound still admits (nhip_bnb.hip)
+  // above) and reads 16-bit cells only for the poses that bound still admits (nhip_bnb_exact.h refine16)
   // (8-bit cells: the same two tiled copies hold the cells themselves -- the image's bytes)
   L->hi_pitch = ((L->S + 2 * L->pad) + 15) & ~15;
   L->hi_tpr = L->hi_pitch / 16 + 1;  // (+ 1: the shifted copy's last tile)

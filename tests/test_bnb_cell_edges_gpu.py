@@ -1,6 +1,6 @@
 """Points on cell edges through the branch-and-bound matcher.  A point whose quotient x / res lies on or one float step
 beside an integer is where the bounds phase's single-precision window origins hand over to the double-precision path
-(nhip_bnb.hip, window_origin): the records must be the oracle's in the fused form, the split form (bounds + seeds, then
+(nhip_bnb_origin.h, window_origin): the records must be the oracle's in the fused form, the split form (bounds + seeds, then
 candidates) and the form that keeps every rotation in the pair's workgroup -- for scans of fewer than 64 points, of one
 workgroup's held origins (<= 1088 points) and longer ones, 8- and 16-bit cells."""
 import math

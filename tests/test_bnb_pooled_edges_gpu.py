@@ -2,7 +2,7 @@
 wave-wide reductions end.
 
 The bounds phase needs only the pooled entry of a point's window origin, (floor(m) + K) >> 3 per coordinate (m: the
-single-precision quotient v / res, K: the constant added after the clamp, nhip_bnb.hip window_origin<true>).  A quotient
+single-precision quotient v / res, K: the constant added after the clamp, nhip_bnb_origin.h window_origin<true>).  A quotient
 that lies on or one float step beside an integer n takes the double-precision floor only where n + K is a multiple of
 8 -- the one bucket in which n - 1 and n fall into different entries; in the other seven the lane keeps the float floor.
 Here the scans hold such points for every residue of n + K, in x alone, in y alone and in both, next to points that
@@ -221,7 +221,7 @@ def test_best_block_in_last_rotation_and_in_lane_63(gpu, cell_bits):
     xy, off, src, slot, th0, want = _order_case(cell_bits)
     # CPU precondition: the optimum is where the case wants it
     assert want["itheta"][0] == 60
-    assert (want["iy"][1] // 8, want["ix"][1] // 8) == (5, 6)   # slot 63 of the bounds' layout (nhip_bnb.hip slot_block)
+    assert (want["iy"][1] // 8, want["ix"][1] // 8) == (5, 6)   # slot 63 of the bounds' layout (nhip_bnb_bounds.h slot_block)
     spec = csm.grid_spec(RANGE, RES, 2.0, 1e-10, 40, cell_bits)
     assert csm.grid_layout(spec).side <= 256
     search = csm.search_spec(61, 81, 81, DEG)
