@@ -50,9 +50,11 @@ def synthetic_hitl_message(bag, poses, early, late):
 
 def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, verbose=False, residual="normal",
         rank=0, world=1, device="cuda:0", backend=None, iterations=4, hitl=True, cell_bits=16, gate="scatter",
-        min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25):
+        min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False):
     """min_scatter_score: LCCandidateFilter's threshold is 0.70 (lc_candidate_filter.cc:76); scans of the synthetic
     24 m x 16 m room score ~0.4, so callers on that world pass a lower one.
+    hitl_device: the HITL constraint's points are selected and packed on the GPU (hitl.select, under the "path" clock) and
+    its blocks reduced there to normal equations, instead of hostside.hitl_relevant_poses + per-point evaluation.
     With world > 1 (one process per GPU under torch.distributed): the window ICP solve is replicated -- its
     consumer, the solver, is host-side -- and the loop-closure pairs are sharded by target across the ranks,
     matched, and all-gathered (nautilus_amd/sharding.py); every rank ends with the same trajectory."""
@@ -154,18 +156,22 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         early, late = n_scans // 20, n_scans - 1 - n_scans // 20
         msg = synthetic_hitl_message(bag, poses, early, late)
         lines = hostside.hitl_segments(msg)
-        with posegraph.clocked("hitl_select"):
-            a_poses, b_poses = hostside.hitl_relevant_poses(poses, bag.scans, lines[0], lines[1])
-        with posegraph.clocked("marshal"):
-            con = posegraph.HitlConstraint(lines[0], lines[1], a_poses, b_poses)
+        if hitl_device:
+            with posegraph.clocked("path"):
+                con = backend.hitl_select(xy, off, poses, lines[0], lines[1])
+        else:
+            with posegraph.clocked("hitl_select"):
+                a_poses, b_poses = hostside.hitl_relevant_poses(poses, bag.scans, lines[0], lines[1])
+            with posegraph.clocked("marshal"):
+                con = posegraph.HitlConstraint(lines[0], lines[1], a_poses, b_poses)
         out["hitl_line_a_poses"], out["hitl_line_b_poses"] = con.n_a, con.n_b
-        out["hitl_points"] = int(sum(len(p) for _, p in con.blocks))
+        out["hitl_points"] = con.n_points if hitl_device else int(sum(len(p) for _, p in con.blocks))
         # state_->problem.odometry_factors = GetSolvedOdomFactors() (solver.cc:535, 406-427): the solved trajectory
         # becomes the odometry; then SolveSLAM() with the constraint (:550): the growing-window solve again, HITL
         # residuals in every pass
         pg, poses = posegraph.solve_growing_window(xy, nrm, off, poses.copy(), max(1, window - 1), window, iterations=iterations, kind=kind,
                                                    device=device, verbose=verbose, backend=backend, initial=poses,
-                                                   hitl=[con] if con.blocks else [], loop_closures=lc, features=feats)
+                                                   hitl=[con] if con.n_a + con.n_b else [], loop_closures=lc, features=feats)
         out["t_hitl_solve_s"] = time.perf_counter() - t0
         out["err_hitl_m"] = posegraph.trajectory_error(poses, bag.truth)
         out["hitl_chosen_line_pose"] = [float(v) for v in con.chosen_line_pose]
@@ -186,6 +192,7 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     out["path_setup_s"] = posegraph.CLOCK["path_setup"]  # (of the path seconds: uploads + device allocations of the per-pass batches)
     out["host_assembly_s"] = posegraph.CLOCK["assemble"]
     out["hitl_select_s"] = posegraph.CLOCK["hitl_select"]
+    out["hitl_device"] = bool(hitl_device)
     out["harness_s"] = out["host_other_s"] - out["marshal_s"] - out["host_assembly_s"] - out["hitl_select_s"]
     return out
 
@@ -198,6 +205,8 @@ if __name__ == "__main__":
                     help="LIDARPointResidual on all points (the reference's non-FEATURE mode, solver.cc:308-314), "
                          "LIDARNormalResidual on all points, or the reference's FEATURE mode (solver.cc:297-318): planar "
                          "feature points as LIDARNormalResidual blocks and edge points as LIDARPointResidual blocks")
+    ap.add_argument("--hitl-device", action="store_true",
+                    help="select the HITL constraint's points and reduce its blocks to normal equations on the GPU")
     ap.add_argument("-v", action="store_true")
     a = ap.parse_args()
     rank, world, local = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), \
@@ -214,7 +223,7 @@ if __name__ == "__main__":
         dist.barrier()
         os.dup2(saved, 1)
     res = run(a.scans, a.window, verbose=a.v and rank == 0, residual=a.residual, rank=rank, world=world,
-              device="cuda:%d" % local)
+              device="cuda:%d" % local, hitl_device=a.hitl_device)
     res["world_size"] = world
     if rank == 0:
         print(json.dumps(res))

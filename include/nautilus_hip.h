@@ -367,6 +367,22 @@ int nhip_resid_point_to_line_dev(const float *d_segments, const float *d_points,
                                  const double *d_line_poses, int32_t n_line_poses, double *d_residuals,
                                  double *d_jac_pose, double *d_jac_line, void *stream);
 
+/* The normal equations of PointToLineResidual blocks, the point-to-line counterpart of nhip_resid_lidar_normal_eq_dev: block b
+ * holds the points d_points[2 * d_block_offsets[b] .. 2 * d_block_offsets[b + 1]) (blocks are contiguous: the packed layout
+ * of nhip_hitl_pack_dev; d_block_offsets has n_blocks + 1 entries), its segment, pose and line pose as above.  With one
+ * residual per point and J = [d r / d pose | d r / d line_pose] (n x 6), the same functor and Jet rules as
+ * nhip_resid_point_to_line_dev:
+ *   d_out[28*b +  0..20] = upper triangle of J^T J, row-major (i <= j)
+ *   d_out[28*b + 21..26] = J^T r
+ *   d_out[28*b + 27]     = r^T r
+ * An empty block gives 28 zeros.  A block whose pose or line-pose index is out of range gives 28 zeros and makes
+ * nhip_dev_status() report it (kind 16, the index, the block).  A point whose Jet is NaN (a zero-length segment under the
+ * point) makes the sums it enters NaN, as on the host.  The same input gives the same bits. */
+int nhip_resid_point_to_line_normal_eq_dev(const float *d_segments, const float *d_points, const int32_t *d_block_offsets,
+                                           const int32_t *d_block_pose, const int32_t *d_block_line, int32_t n_blocks,
+                                           const double *d_poses, int32_t n_poses, const double *d_line_poses,
+                                           int32_t n_line_poses, double *d_out, void *stream);
+
 /* OdometryResidual (slam_residuals.h:18-40): factor f has T_odom d_t_odom[2f..] (Vector2f),
  * R_odom d_r_odom[f] (float), poses d_pose_i[f], d_pose_j[f].  3 residuals, 3x3 Jacobians. */
 int nhip_resid_odometry_dev(const float *d_t_odom, const float *d_r_odom, const int32_t *d_pose_i,
@@ -465,6 +481,42 @@ int nhip_features_extract_dev(const float *d_xy, const int32_t *d_offsets, int32
 int nhip_features_pack_dev(const float *d_xy, const float *d_normals, const int32_t *d_offsets, int32_t n_scans,
                            const int32_t *d_idx, const int32_t *d_count, int32_t cap, float *d_xy_out,
                            float *d_normals_out, int32_t *d_offsets_out, void *stream);
+
+/* HITL point selection: GetRelevantPosesForHITL (solver.cc:479-513) for every scan at once.  A point p of scan s goes to
+ * the world as w = (c px - s py + tx, s px + c py + ty) with (c, s, tx, ty) = d_pose_f32[4s ..], the entries of
+ * PoseArrayToAffine(pose).cast<float>() (nhip_pose_affines forms them), every operation a float operation rounded on its
+ * own; DistanceToLineSegment<float> (slam_util.h:92-110) against line a, and for a point not on a against line b; a point
+ * is ON a line iff (double)distance <= line_width -- the reference's comparison of a float with CONFIG_DOUBLE
+ * hitl_line_width, under which a distance of exactly float(0.05) is NOT on the line.  A non-finite point is on no line.
+ * A scan with at least point_threshold points on a is an a-node and contributes its a-points only; otherwise one with at
+ * least point_threshold points on b is a b-node and contributes its b-points only.  Blocks: all a-nodes in node order, then
+ * all b-nodes in node order; points inside a block in scan order.
+ * A non-finite or negative line_width, a point_threshold below 1 or a negative n_scans is NHIP_ERR_ARG before anything is
+ * launched (with or without a device).  Scans of any length, empty ones included. */
+typedef struct nhip_hitl_spec {
+  float line_a[4];         /* x0 y0 x1 y1, LineSegment<float> (LineSegmentsFromHitlMsg, solver.cc:467-478) */
+  float line_b[4];
+  double line_width;       /* hitl_line_width (0.05) */
+  int32_t point_threshold; /* hitl_pose_point_threshold (10) */
+  int32_t reserved;        /* 0 */
+} nhip_hitl_spec_t;
+/* both lines zero, line_width 0.05, point_threshold 10; pure host */
+int nhip_hitl_spec_default(nhip_hitl_spec_t *out);
+/* Classifies and counts.  Outputs: d_class, one byte per point of d_xy (0: on neither line, 1: on a, 2: on b); d_counts[2s],
+ * d_counts[2s + 1]: the points of scan s on a and on b; d_scan_block[s]: the block of scan s (-1: it joins neither line);
+ * d_scan_offset[s]: the index of its first point in the packed array; d_totals = {n_a, n_b, n_points}: the a-nodes, the
+ * b-nodes and the points of all blocks (zeros for n_scans == 0 or when nothing is selected). */
+int nhip_hitl_select_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const float *d_pose_f32,
+                         const nhip_hitl_spec_t *spec, uint8_t *d_class, int32_t *d_counts, int32_t *d_scan_block,
+                         int32_t *d_scan_offset, int32_t *d_totals, void *stream);
+/* Packs what nhip_hitl_select_dev selected into buffers the caller sized from the totals it downloaded: n_blocks = n_a + n_b,
+ * n_points; d_points (2 floats per point, scan frame), d_block_offsets[n_blocks + 1], d_block_pose[n_blocks] (the node of
+ * every block) -- the layout nhip_resid_point_to_line_normal_eq_dev takes.  Sizes that are not the totals behind d_totals
+ * write nothing and make nhip_dev_status() report it (kind 8). */
+int nhip_hitl_pack_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const uint8_t *d_class,
+                       const int32_t *d_counts, const int32_t *d_scan_block, const int32_t *d_scan_offset,
+                       const int32_t *d_totals, int32_t n_blocks, int32_t n_points, float *d_points,
+                       int32_t *d_block_offsets, int32_t *d_block_pose, void *stream);
 
 /* ------------------------------------------------------------------ handle API (host pointers) */
 typedef struct nhip_scans nhip_scans_t;

@@ -60,6 +60,11 @@ class FeatureSpec(C.Structure):
                 ("max_edge", C.c_int32)]
 
 
+class HitlSpec(C.Structure):
+    _fields_ = [("line_a", C.c_float * 4), ("line_b", C.c_float * 4), ("line_width", C.c_double),
+                ("point_threshold", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Match(C.Structure):
     _fields_ = [("itheta", C.c_int32), ("ix", C.c_int32), ("iy", C.c_int32), ("score", C.c_float)]
 
@@ -114,6 +119,7 @@ PROTOTYPES = {
     "nhip_corr_compact_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "nhip_resid_point_to_line_dev": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i32, _vp, _i32,
                                                _vp, _vp, _vp, _vp]),
+    "nhip_resid_point_to_line_normal_eq_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp]),
     "nhip_resid_odometry_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f64, _f64, _vp, _i32, _vp, _vp,
                                           _vp, _vp]),
     "nhip_scans_upload": (C.c_int, [_vp, _vp, _i32, _P(_vp)]),
@@ -138,6 +144,9 @@ PROTOTYPES = {
     "nhip_feature_spec_default": (C.c_int, [_P(FeatureSpec)]),
     "nhip_features_extract_dev": (C.c_int, [_vp, _vp, _i32, _P(FeatureSpec), _vp, _vp, _vp, _vp, _vp, _vp]),
     "nhip_features_pack_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "nhip_hitl_spec_default": (C.c_int, [_P(HitlSpec)]),
+    "nhip_hitl_select_dev": (C.c_int, [_vp, _vp, _i32, _vp, _P(HitlSpec), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nhip_hitl_pack_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "nhip_features_extract": (C.c_int, [_vp, _P(FeatureSpec), _vp, _vp, _vp, _vp, _vp]),
     "nhip_lc_chi_square_gate": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _f64, _vp, _vp]),
     "nhip_lc_scatter_scores": (C.c_int, [_vp, _vp]),

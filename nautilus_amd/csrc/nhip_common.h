@@ -319,6 +319,20 @@ int launch_resid_point_to_line(const float *d_segments, const float *d_points,
                                int32_t n_blocks, const double *d_poses, int32_t n_poses, const double *d_line_poses,
                                int32_t n_line_poses, double *d_res, double *d_jpose, double *d_jline, hipStream_t s);
 
+// point-to-line blocks reduced to their normal equations (nhip_resid.hip): 28 doubles per block, blocks contiguous in d_points
+int launch_resid_point_to_line_normal_eq(const float *d_segments, const float *d_points, const int32_t *d_block_offsets,
+                                         const int32_t *d_block_pose, const int32_t *d_block_line, int32_t n_blocks,
+                                         const double *d_poses, int32_t n_poses, const double *d_line_poses, int32_t n_line_poses,
+                                         double *d_out, hipStream_t s);
+
+// HITL point selection (nhip_hitl.hip); the spec has passed hitl_spec_check (nhip_host_solver.hip)
+int launch_hitl_select(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const float *d_pose_f32,
+                       const nhip_hitl_spec_t &spec, uint8_t *d_class, int32_t *d_counts, int32_t *d_scan_block,
+                       int32_t *d_scan_offset, int32_t *d_totals, hipStream_t s);
+int launch_hitl_pack(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const uint8_t *d_class, const int32_t *d_counts,
+                     const int32_t *d_scan_block, const int32_t *d_scan_offset, const int32_t *d_totals, int32_t n_blocks,
+                     int32_t n_points, float *d_points, int32_t *d_block_offsets, int32_t *d_block_pose, hipStream_t s);
+
 int launch_resid_odometry(const float *d_t_odom, const float *d_r_odom, const int32_t *d_pose_i,
                           const int32_t *d_pose_j, int32_t n_factors, double tw, double rw,
                           const double *d_poses, int32_t n_poses, double *d_res, double *d_ji, double *d_jj,

@@ -1,5 +1,5 @@
-// nhip_host_solver.hip -- the solver-side entry points of the C ABI: residuals, correspondences and loop-closure gates in
-// their `_dev` and host-buffer forms, the residual batch handle, the all-gather of match records (RCCL, bound at run time).
+// nhip_host_solver.hip -- the solver-side entry points of the C ABI: residuals, correspondences, HITL point selection and
+// loop-closure gates in their `_dev` and host-buffer forms, the residual batch handle, the all-gather of match records (RCCL, bound at run time).
 #include <dlfcn.h>
 
 #include "nhip_common.h"
@@ -122,6 +122,21 @@ int nhip_resid_point_to_line_dev(const float *d_segments, const float *d_points,
                                     d_jac_pose, d_jac_line, static_cast<hipStream_t>(stream));
 }
 
+int nhip_resid_point_to_line_normal_eq_dev(const float *d_segments, const float *d_points, const int32_t *d_block_offsets,
+                                           const int32_t *d_block_pose, const int32_t *d_block_line, int32_t n_blocks,
+                                           const double *d_poses, int32_t n_poses, const double *d_line_poses,
+                                           int32_t n_line_poses, double *d_out, void *stream) {
+  // (sizes are an argument error with or without a device)
+  NHIP_REQUIRE(n_blocks >= 0 && n_poses >= 0 && n_line_poses >= 0, "resid_point_to_line_normal_eq_dev: negative size");
+  int rc = require_device();
+  if (rc) return rc;
+  if (n_blocks == 0) return NHIP_OK;
+  NHIP_REQUIRE(d_segments && d_points && d_block_offsets && d_block_pose && d_block_line && d_poses && d_line_poses && d_out,
+               "resid_point_to_line_normal_eq_dev: null pointer");
+  return launch_resid_point_to_line_normal_eq(d_segments, d_points, d_block_offsets, d_block_pose, d_block_line, n_blocks, d_poses,
+                                              n_poses, d_line_poses, n_line_poses, d_out, static_cast<hipStream_t>(stream));
+}
+
 int nhip_resid_odometry_dev(const float *d_t_odom, const float *d_r_odom, const int32_t *d_pose_i,
                             const int32_t *d_pose_j, int32_t n_factors, double translation_weight,
                             double rotation_weight, const double *d_poses, int32_t n_poses, double *d_residuals,
@@ -133,6 +148,52 @@ int nhip_resid_odometry_dev(const float *d_t_odom, const float *d_r_odom, const 
   return launch_resid_odometry(d_t_odom, d_r_odom, d_pose_i, d_pose_j, n_factors,
                                translation_weight, rotation_weight, d_poses, n_poses, d_residuals, d_jac_i,
                                d_jac_j, static_cast<hipStream_t>(stream));
+}
+
+// ---------------------------------------------------------------- HITL point selection
+// the accepted ranges of include/nautilus_hip.h
+static int hitl_spec_check(const nhip_hitl_spec_t *s, const char *who) {
+  NHIP_REQUIRE(s, "%s: null spec", who);
+  NHIP_REQUIRE(std::isfinite(s->line_width) && s->line_width >= 0, "%s: line_width must be finite and >= 0", who);
+  NHIP_REQUIRE(s->point_threshold >= 1, "%s: point_threshold %d below 1", who, s->point_threshold);
+  return NHIP_OK;
+}
+
+int nhip_hitl_spec_default(nhip_hitl_spec_t *out) {
+  NHIP_REQUIRE(out, "hitl_spec_default: null pointer");
+  memset(out, 0, sizeof(*out));
+  out->line_width = 0.05;     // hitl_line_width, default_config.lua:88
+  out->point_threshold = 10;  // hitl_pose_point_threshold, default_config.lua:91
+  return NHIP_OK;
+}
+
+int nhip_hitl_select_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const float *d_pose_f32,
+                         const nhip_hitl_spec_t *spec, uint8_t *d_class, int32_t *d_counts, int32_t *d_scan_block,
+                         int32_t *d_scan_offset, int32_t *d_totals, void *stream) {
+  int rc = hitl_spec_check(spec, "hitl_select_dev");  // (a bad spec or size is an argument error with or without a device)
+  if (rc) return rc;
+  NHIP_REQUIRE(n_scans >= 0, "hitl_select_dev: n_scans < 0");
+  if ((rc = require_device())) return rc;
+  NHIP_REQUIRE(d_totals && (n_scans == 0 || (d_xy && d_offsets && d_pose_f32 && d_class && d_counts && d_scan_block && d_scan_offset)),
+               "hitl_select_dev: null pointer");
+  NHIP_REQUIRE((reinterpret_cast<uintptr_t>(d_pose_f32) & 15) == 0, "hitl_select_dev: d_pose_f32 must be 16-byte aligned");
+  return launch_hitl_select(d_xy, d_offsets, n_scans, d_pose_f32, *spec, d_class, d_counts, d_scan_block, d_scan_offset, d_totals,
+                            static_cast<hipStream_t>(stream));
+}
+
+int nhip_hitl_pack_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const uint8_t *d_class,
+                       const int32_t *d_counts, const int32_t *d_scan_block, const int32_t *d_scan_offset,
+                       const int32_t *d_totals, int32_t n_blocks, int32_t n_points, float *d_points,
+                       int32_t *d_block_offsets, int32_t *d_block_pose, void *stream) {
+  NHIP_REQUIRE(n_scans >= 0 && n_blocks >= 0 && n_points >= 0, "hitl_pack_dev: negative size");
+  NHIP_REQUIRE(n_blocks <= n_scans, "hitl_pack_dev: %d blocks of %d scans", n_blocks, n_scans);
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(d_totals && d_block_offsets && (n_scans == 0 || (d_xy && d_offsets && d_class && d_counts && d_scan_block && d_scan_offset)) &&
+                   (n_blocks == 0 || d_block_pose) && (n_points == 0 || d_points),
+               "hitl_pack_dev: null pointer");
+  return launch_hitl_pack(d_xy, d_offsets, n_scans, d_class, d_counts, d_scan_block, d_scan_offset, d_totals, n_blocks, n_points, d_points,
+                          d_block_offsets, d_block_pose, static_cast<hipStream_t>(stream));
 }
 
 // ---------------------------------------------------------------- loop-closure gates

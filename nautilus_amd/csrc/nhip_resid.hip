@@ -168,9 +168,47 @@ __global__ __launch_bounds__(RT) void resid_lidar_kernel(
   }
 }
 
+// The 28 sums of a workgroup from its lanes' partial sums, written to out[0..28): a wave reduction as a reduce-scatter -- at
+// each butterfly step a lane hands half of its values to its partner and keeps the other half, so 32 -> 16 -> 8 -> 4 -> 2 -> 1
+// values per lane and 32 fp64 shuffles in all (a plain all-reduce of 28 values takes 168); lane l ends with value l >> 1 --
+// then LDS across the RT / 64 waves.  Every lane of the workgroup calls it.
+__device__ __forceinline__ void reduce28_store(const double (&acc)[28], double (*s_part)[28], double *__restrict__ out) {
+  const int tid = threadIdx.x;
+  {
+    double v[32];
+#pragma unroll
+    for (int k = 0; k < 32; k++) v[k] = k < 28 ? acc[k] : 0.0;
+    const int lane = tid & 63;
+#define NHIP_RS_STEP(M, N)                                          \
+  {                                                                 \
+    const bool lo = (lane & (M)) == 0;                              \
+    _Pragma("unroll") for (int j = 0; j < (N) / 2; j++) {           \
+      const double send = lo ? v[j + (N) / 2] : v[j];               \
+      const double recv = __shfl_xor(send, (M), 64);                \
+      v[j] = (lo ? v[j] : v[j + (N) / 2]) + recv;                   \
+    }                                                               \
+  }
+    NHIP_RS_STEP(32, 32)
+    NHIP_RS_STEP(16, 16)
+    NHIP_RS_STEP(8, 8)
+    NHIP_RS_STEP(4, 4)
+    NHIP_RS_STEP(2, 2)
+#undef NHIP_RS_STEP
+    const double total = v[0] + __shfl_xor(v[0], 1, 64);
+    if ((lane & 1) == 0 && (lane >> 1) < 28) s_part[tid >> 6][lane >> 1] = total;
+  }
+  __syncthreads();
+  if (tid < 28) {
+    double v = 0.0;
+#pragma unroll
+    for (int w = 0; w < RT / 64; w++) v += s_part[w][tid];
+    out[tid] = v;
+  }
+}
+
 // Per-block normal equations: one workgroup per block, every lane runs the
 // same per-correspondence math as resid_lidar_kernel and keeps 28 fp64 partial sums (upper
-// triangle of J^T J, J^T r, r^T r); wave64 shuffles, then LDS across the 4 waves.  Output is
+// triangle of J^T J, J^T r, r^T r), reduced by reduce28_store.  Output is
 // 224 B per block instead of 112 B per correspondence.
 template <int KIND>
 __global__ __launch_bounds__(RT) void resid_normal_eq_kernel(const float4 *__restrict__ corr,
@@ -242,39 +280,7 @@ __global__ __launch_bounds__(RT) void resid_normal_eq_kernel(const float4 *__res
     acc[27] += r[0] * r[0] + r[1] * r[1];
     }
   }
-  // wave reduction as a reduce-scatter: at each butterfly step a lane hands half of its values to
-  // its partner and keeps the other half, so 32 -> 16 -> 8 -> 4 -> 2 -> 1 values per lane and 32
-  // fp64 shuffles in all (a plain all-reduce of 28 values takes 168); lane l ends with value l >> 1.
-  {
-    double v[32];
-#pragma unroll
-    for (int k = 0; k < 32; k++) v[k] = k < 28 ? acc[k] : 0.0;
-    const int lane = tid & 63;
-#define NHIP_RS_STEP(M, N)                                          \
-  {                                                                 \
-    const bool lo = (lane & (M)) == 0;                              \
-    _Pragma("unroll") for (int j = 0; j < (N) / 2; j++) {           \
-      const double send = lo ? v[j + (N) / 2] : v[j];               \
-      const double recv = __shfl_xor(send, (M), 64);                \
-      v[j] = (lo ? v[j] : v[j + (N) / 2]) + recv;                   \
-    }                                                               \
-  }
-    NHIP_RS_STEP(32, 32)
-    NHIP_RS_STEP(16, 16)
-    NHIP_RS_STEP(8, 8)
-    NHIP_RS_STEP(4, 4)
-    NHIP_RS_STEP(2, 2)
-#undef NHIP_RS_STEP
-    const double total = v[0] + __shfl_xor(v[0], 1, 64);
-    if ((lane & 1) == 0 && (lane >> 1) < 28) s_part[tid >> 6][lane >> 1] = total;
-  }
-  __syncthreads();
-  if (tid < 28) {
-    double v = 0.0;
-#pragma unroll
-    for (int w = 0; w < RT / 64; w++) v += s_part[w][tid];
-    out[28 * (size_t)b + tid] = v;
-  }
+  reduce28_store(acc, s_part, out + 28 * (size_t)b);
 }
 
 // ---------------------------------------------------------------- forward-mode duals
@@ -332,6 +338,44 @@ __device__ __forceinline__ bool between(double v, double a, double b) {  // slam
   return (v >= a && v <= b) || (v >= b && v <= a);
 }
 
+// PointToLineResidual::operator() (slam_residuals.h:180-200) in two halves.  What a block's pose, line pose and segment
+// determine -- the same for every point of the block:
+struct P2LFrame {
+  Dual6 x, y, c, s;            // pose_to_world = T(x, y) * R(theta), slam_util.h:20-28; partials 0..2 = pose, 3..5 = line_pose
+  Dual6 sx0, sy0, sx1, sy1;    // line_start, line_end under line_pose, :186-188
+  Dual6 nx, ny, off;           // Hyperplane::Through(start, end): n = unitOrthogonal(end - start), offset = -n . start
+};
+__device__ __forceinline__ P2LFrame p2l_frame(const double *__restrict__ pp, const double *__restrict__ lp, const float4 sg) {
+  P2LFrame F;
+  F.x = dvar(pp[0], 0); F.y = dvar(pp[1], 1);
+  F.c = dconst(cos(pp[2])); F.s = dconst(sin(pp[2]));
+  F.c.v[2] = -F.s.a; F.s.v[2] = F.c.a;
+  const Dual6 lx = dvar(lp[0], 3), ly = dvar(lp[1], 4);
+  Dual6 lc = dconst(cos(lp[2])), ls = dconst(sin(lp[2]));
+  lc.v[5] = -ls.a; ls.v[5] = lc.a;
+  F.sx0 = lc * dconst(sg.x) - ls * dconst(sg.y) + lx;
+  F.sy0 = ls * dconst(sg.x) + lc * dconst(sg.y) + ly;
+  F.sx1 = lc * dconst(sg.z) - ls * dconst(sg.w) + lx;
+  F.sy1 = ls * dconst(sg.z) + lc * dconst(sg.w) + ly;
+  const Dual6 dx = F.sx1 - F.sx0, dy = F.sy1 - F.sy0;
+  Dual6 nx = -dy, ny = dx;
+  const Dual6 len = dsqrt(nx * nx + ny * ny);
+  F.nx = nx / len; F.ny = ny / len;
+  F.off = -(F.sx0 * F.nx + F.sy0 * F.ny);
+  return F;
+}
+// ... and the point's part: DistanceToLineSegment (slam_util.h:92-110) of pointT (:194); .a the residual, .v its six partials
+__device__ __forceinline__ Dual6 p2l_distance(const P2LFrame &F, const float2 pt) {
+  const Dual6 px = F.c * dconst(pt.x) - F.s * dconst(pt.y) + F.x;
+  const Dual6 py = F.s * dconst(pt.x) + F.c * dconst(pt.y) + F.y;
+  const Dual6 sd = F.nx * px + F.ny * py + F.off;  // signedDistance
+  const Dual6 prx = px - sd * F.nx, pry = py - sd * F.ny;  // projection
+  if (between(prx.a, F.sx0.a, F.sx1.a) && between(pry.a, F.sy0.a, F.sy1.a)) return sd.a < 0.0 ? -sd : sd;  // absDistance
+  const Dual6 ax = px - F.sx0, ay = py - F.sy0, bx = px - F.sx1, by = py - F.sy1;
+  const Dual6 ds = dsqrt(ax * ax + ay * ay), de = dsqrt(bx * bx + by * by);
+  return (de.a < ds.a) ? de : ds;  // std::min<T>(dist_to_start, dist_to_endpoint)
+}
+
 __global__ __launch_bounds__(RT) void resid_point_to_line_kernel(
     const float4 *__restrict__ segments, const float2 *__restrict__ points,
     const int32_t *__restrict__ point_block, int64_t n_points,
@@ -353,42 +397,61 @@ __global__ __launch_bounds__(RT) void resid_point_to_line_kernel(
     if (jac_line) { jac_line[3 * i] = 0.0; jac_line[3 * i + 1] = 0.0; jac_line[3 * i + 2] = 0.0; }
     return;
   }
-  const double *pp = poses + 3 * (size_t)ip;
-  const double *lp = line_poses + 3 * (size_t)il;
-  const float4 sg = segments[b];
-  const float2 pt = points[i];
-  // pose_to_world = T(x, y) * R(theta), slam_util.h:20-28; partials 0..2 = pose, 3..5 = line_pose
-  const Dual6 x = dvar(pp[0], 0), y = dvar(pp[1], 1);
-  Dual6 c = dconst(cos(pp[2])), s = dconst(sin(pp[2]));
-  c.v[2] = -s.a; s.v[2] = c.a;
-  const Dual6 lx = dvar(lp[0], 3), ly = dvar(lp[1], 4);
-  Dual6 lc = dconst(cos(lp[2])), ls = dconst(sin(lp[2]));
-  lc.v[5] = -ls.a; ls.v[5] = lc.a;
-  const Dual6 sx0 = lc * dconst(sg.x) - ls * dconst(sg.y) + lx;  // line_start, :186-187
-  const Dual6 sy0 = ls * dconst(sg.x) + lc * dconst(sg.y) + ly;
-  const Dual6 sx1 = lc * dconst(sg.z) - ls * dconst(sg.w) + lx;  // line_end, :188
-  const Dual6 sy1 = ls * dconst(sg.z) + lc * dconst(sg.w) + ly;
-  const Dual6 px = c * dconst(pt.x) - s * dconst(pt.y) + x;      // pointT, :194
-  const Dual6 py = s * dconst(pt.x) + c * dconst(pt.y) + y;
-  // Hyperplane::Through(start, end): n = unitOrthogonal(end - start), offset = -n . start
-  const Dual6 dx = sx1 - sx0, dy = sy1 - sy0;
-  Dual6 nx = -dy, ny = dx;
-  const Dual6 len = dsqrt(nx * nx + ny * ny);
-  nx = nx / len; ny = ny / len;
-  const Dual6 off = -(sx0 * nx + sy0 * ny);
-  const Dual6 sd = nx * px + ny * py + off;  // signedDistance
-  const Dual6 prx = px - sd * nx, pry = py - sd * ny;  // projection
-  Dual6 d;
-  if (between(prx.a, sx0.a, sx1.a) && between(pry.a, sy0.a, sy1.a)) {
-    d = sd.a < 0.0 ? -sd : sd;  // absDistance
-  } else {
-    const Dual6 ax = px - sx0, ay = py - sy0, bx = px - sx1, by = py - sy1;
-    const Dual6 ds = dsqrt(ax * ax + ay * ay), de = dsqrt(bx * bx + by * by);
-    d = (de.a < ds.a) ? de : ds;  // std::min<T>(dist_to_start, dist_to_endpoint)
-  }
+  const P2LFrame F = p2l_frame(poses + 3 * (size_t)ip, line_poses + 3 * (size_t)il, segments[b]);
+  const Dual6 d = p2l_distance(F, points[i]);
   residuals[i] = d.a;
   if (jac_pose) { jac_pose[3 * i] = d.v[0]; jac_pose[3 * i + 1] = d.v[1]; jac_pose[3 * i + 2] = d.v[2]; }
   if (jac_line) { jac_line[3 * i] = d.v[3]; jac_line[3 * i + 1] = d.v[4]; jac_line[3 * i + 2] = d.v[5]; }
+}
+
+// The normal equations of point-to-line blocks: one workgroup per block, the block's points contiguous from
+// block_offsets[b].  The block's frame is formed once per lane; every lane then runs p2l_distance on its points and keeps the
+// 28 partial sums over the six parameters [pose | line_pose], one residual per point.  A NaN Jet stays NaN in the sums.
+__global__ __launch_bounds__(RT) void resid_p2l_normal_eq_kernel(
+    const float4 *__restrict__ segments, const float2 *__restrict__ points, const int32_t *__restrict__ block_offsets,
+    const int32_t *__restrict__ block_pose, const int32_t *__restrict__ block_line, const double *__restrict__ poses,
+    const double *__restrict__ line_poses, double *__restrict__ out, int32_t n_poses, int32_t n_line_poses,
+    uint32_t *__restrict__ status) {
+  __shared__ double s_part[RT / 64][28];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int32_t o = block_offsets[b];
+  int32_t n = block_offsets[b + 1] - o;
+  if (n < 0) n = 0;
+  // (indices from device memory: one outside its array is reported, and the block's 28 numbers are zero)
+  const int32_t ip = block_pose[b], il = block_line[b];
+  if (!id_in(ip, n_poses) || !id_in(il, n_line_poses)) {
+    if (tid == 0) flag_bad_id(status, BAD_POSE_ID, id_in(ip, n_poses) ? il : ip, b);
+    if (tid < 28) out[28 * (size_t)b + tid] = 0.0;
+    return;
+  }
+  const P2LFrame F = p2l_frame(poses + 3 * (size_t)ip, line_poses + 3 * (size_t)il, segments[b]);
+  double acc[28];
+#pragma unroll
+  for (int k = 0; k < 28; k++) acc[k] = 0.0;
+  // (the points of a trip are loaded ahead of the fp64 math, as the LIDAR kernel loads its rows)
+  constexpr int LOADS = 4;
+  for (int32_t i0 = tid; i0 < n; i0 += RT * LOADS) {
+    float2 pv[LOADS];
+#pragma unroll
+    for (int u = 0; u < LOADS; u++) {
+      const int32_t i = i0 + u * RT;
+      if (i < n) pv[u] = points[(size_t)o + i];
+    }
+#pragma unroll
+    for (int u = 0; u < LOADS; u++) {
+      if (i0 + u * RT >= n) break;
+      const Dual6 d = p2l_distance(F, pv[u]);
+      int k = 0;
+#pragma unroll
+      for (int p = 0; p < 6; p++)
+#pragma unroll
+        for (int q = p; q < 6; q++) acc[k++] += d.v[p] * d.v[q];
+#pragma unroll
+      for (int p = 0; p < 6; p++) acc[21 + p] += d.v[p] * d.a;
+      acc[27] += d.a * d.a;
+    }
+  }
+  reduce28_store(acc, s_part, out + 28 * (size_t)b);
 }
 
 // OdometryResidual: r = (tw (Ti + T_odom - Tj), rw atan2(sin d, cos d)), d = th_i + R_odom - th_j.
@@ -508,6 +571,19 @@ int launch_resid_point_to_line(const float *d_segments, const float *d_points,
                      reinterpret_cast<const float2 *>(d_points), d_point_block, n_points,
                      d_block_pose, d_block_line, d_poses, d_line_poses, d_res, d_jpose, d_jline, n_blocks, n_poses,
                      n_line_poses, dev_status());
+  NHIP_TRY_HIP(hipGetLastError());
+  return NHIP_OK;
+}
+
+int launch_resid_point_to_line_normal_eq(const float *d_segments, const float *d_points, const int32_t *d_block_offsets,
+                                         const int32_t *d_block_pose, const int32_t *d_block_line, int32_t n_blocks,
+                                         const double *d_poses, int32_t n_poses, const double *d_line_poses, int32_t n_line_poses,
+                                         double *d_out, hipStream_t s) {
+  NHIP_REQUIRE(n_blocks >= 0 && n_poses >= 0 && n_line_poses >= 0, "resid_point_to_line_normal_eq: negative size");
+  if (n_blocks == 0) return NHIP_OK;
+  hipLaunchKernelGGL(resid_p2l_normal_eq_kernel, dim3((uint32_t)n_blocks), dim3(RT), 0, s,
+                     reinterpret_cast<const float4 *>(d_segments), reinterpret_cast<const float2 *>(d_points), d_block_offsets,
+                     d_block_pose, d_block_line, d_poses, d_line_poses, d_out, n_poses, n_line_poses, dev_status());
   NHIP_TRY_HIP(hipGetLastError());
   return NHIP_OK;
 }

@@ -10,7 +10,8 @@ batched API instead:
     relative transform", the TODO at solver.cc:651-660), both evaluated by nhip_resid_odometry_dev;
   * HITL constraints (solver.cc:479-559): PointToLineResidual blocks of the points the user's two
     segments select, every block against line_a and one shared `chosen_line_pose` parameter block
-    (AddHITLResiduals, solver.cc:515-532), evaluated by nhip_resid_point_to_line;
+    (AddHITLResiduals, solver.cc:515-532), evaluated by nhip_resid_point_to_line -- or, for a constraint selected on
+    the GPU (hitl.select), reduced there to per-block normal equations (nhip_resid_point_to_line_normal_eq_dev);
   * Gauss-Newton with Levenberg damping on the assembled sparse system (scipy.sparse on the
     host: N poses x 3 + 3 per HITL constraint), first pose held constant (solver.cc:384-386).
 Only the linear solve and the bookkeeping are host work; every residual, Jacobian and nearest
@@ -114,6 +115,29 @@ class HipBackend:
                                                 _lib.ptr(block_pose), _lib.ptr(block_line), len(block_pose), _lib.ptr(P), len(P),
                                                 _lib.ptr(Lp), len(Lp), _lib.ptr(r), _lib.ptr(j0), _lib.ptr(j1)))
         return r, j0, j1
+
+    def hitl_select(self, xy, offsets, poses, line_a, line_b, line_width=0.05, point_threshold=10):
+        """GetRelevantPosesForHITL on the GPU (hitl.select): a DeviceHitlConstraint, its points packed on the device."""
+        from . import hitl
+        return hitl.select(self, xy, offsets, poses, line_a, line_b, line_width, point_threshold)
+
+    def point_to_line_normal_eq(self, constraint, poses, line_poses, line_index):
+        """The normal equations of a DeviceHitlConstraint's blocks at `poses`, every block against line a under
+        line_poses[line_index]: (n_blocks, 28) float64 in the layout of the ICP blocks' (nhip_resid_point_to_line_normal_eq_dev)."""
+        torch, con = self.torch, constraint
+        if con.n_blocks == 0:
+            return np.zeros((0, 28))
+        P, Lp = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3), np.ascontiguousarray(line_poses, dtype=np.float64).reshape(-1, 3)
+        d_p, d_l = torch.from_numpy(P).to(self.dev), torch.from_numpy(Lp).to(self.dev)
+        d_out = torch.empty((con.n_blocks, 28), dtype=torch.float64, device=self.dev)
+        sp = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        check(self.lib.nhip_resid_point_to_line_normal_eq_dev(con.d_segments.data_ptr(), con.d_points.data_ptr(),
+                                                              con.d_block_offsets.data_ptr(), con.d_block_pose.data_ptr(),
+                                                              con.d_block_line(line_index).data_ptr(), con.n_blocks, d_p.data_ptr(), len(P),
+                                                              d_l.data_ptr(), len(Lp), d_out.data_ptr(), sp))
+        out = d_out.cpu().numpy()
+        check(self.lib.nhip_dev_status(sp, None))
+        return out
 
     def scatter_scores(self, xy, offsets):
         """LCCandidateFilter's scatter-matrix score of every scan (nhip_lc_scatter_scores)."""
@@ -308,6 +332,16 @@ class HitlConstraint:
         return self._arrays[1]
 
 
+def _blocks_from_normal_equations(neq, idx):
+    """(n, 28) rows -- upper triangle of a 6 x 6 J^T J, J^T r, r^T r -- and the (n, 6) unknowns of every block -> the COO
+    rows, columns and values of the full symmetric blocks."""
+    iu = np.triu_indices(6)
+    H6 = np.zeros((len(neq), 6, 6))
+    H6[:, iu[0], iu[1]] = neq[:, :21]
+    H6 = H6 + np.transpose(H6, (0, 2, 1)) - np.einsum("bij,ij->bij", H6, np.eye(6))
+    return np.repeat(idx, 6, axis=1).ravel(), np.tile(idx, (1, 6)).ravel(), H6.ravel()
+
+
 class PoseGraph:
     def __init__(self, xy, normals, offsets, odom, window=10, kind=_lib.NHIP_LIDAR_POINT, outlier_threshold=0.25,
                  odom_weights=(1.0, 1.0), device="cuda:0", initial=None, backend=None, features=None):
@@ -334,6 +368,11 @@ class PoseGraph:
         self.lc = loop_closure_factors(self.poses, pairs_src, pairs_tgt, rel, tw=weights[0], rw=weights[1])
 
     def add_hitl(self, constraint):
+        """A HitlConstraint (points on the host, evaluated point by point through backend.point_to_line) or a
+        hitl.DeviceHitlConstraint (points on the device, reduced there to 28 doubles per block: needs a backend with
+        point_to_line_normal_eq)."""
+        if hasattr(constraint, "d_points") and not hasattr(self.backend, "point_to_line_normal_eq"):
+            raise TypeError("add_hitl: backend %r cannot evaluate a device constraint; pass a HitlConstraint" % self.backend.name)
         self.hitl.append(constraint)
 
     @property
@@ -360,15 +399,10 @@ class PoseGraph:
         rows, cols, vals = [], [], []
         g = np.zeros(NU)
         cost = 0.5 * float(neq[:, 27].sum()) if len(neq) else 0.0
-        iu = np.triu_indices(6)
         bs, bt = self.icp.block_src, self.icp.block_tgt
-        H6 = np.zeros((len(neq), 6, 6))
-        H6[:, iu[0], iu[1]] = neq[:, :21]
-        H6 = H6 + np.transpose(H6, (0, 2, 1)) - np.einsum("bij,ij->bij", H6, np.eye(6))
         idx = np.concatenate([3 * bs[:, None] + np.arange(3), 3 * bt[:, None] + np.arange(3)], axis=1)  # (B, 6)
-        rows.append(np.repeat(idx, 6, axis=1).ravel())
-        cols.append(np.tile(idx, (1, 6)).ravel())
-        vals.append(H6.ravel())
+        for out, v in zip((rows, cols, vals), _blocks_from_normal_equations(neq, idx)):
+            out.append(v)
         np.add.at(g, idx.ravel(), neq[:, 21:27].ravel())
         for fac in (self.odo, self.lc):
             if fac is None or fac.n == 0:
@@ -385,6 +419,19 @@ class PoseGraph:
             np.add.at(g, idf.ravel(), gf.ravel())
             cost += 0.5 * float((r * r).sum())
         for c, con in enumerate(self.hitl):
+            if hasattr(con, "d_points"):
+                # a DeviceHitlConstraint: 28 doubles per block from the device, over [the block's pose | chosen_line_pose c]
+                if con.n_points == 0:
+                    continue
+                with clocked("path"):
+                    neq = self.backend.point_to_line_normal_eq(con, poses, lines, c)
+                idh = np.concatenate([3 * con.block_pose.astype(np.int64)[:, None] + np.arange(3),
+                                      np.full((con.n_blocks, 1), 3 * N + 3 * c) + np.arange(3)], axis=1)
+                for out, v in zip((rows, cols, vals), _blocks_from_normal_equations(neq, idh)):
+                    out.append(v)
+                np.add.at(g, idh.ravel(), neq[:, 21:27].ravel())
+                cost += 0.5 * float(neq[:, 27].sum())
+                continue
             with clocked("marshal"):
                 seg, pts, pb, bp, bl = con.arrays(c)
             if len(pts) == 0:
