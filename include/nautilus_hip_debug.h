@@ -80,6 +80,14 @@ int nhip_grids_download_pool4(const nhip_grids_t *grids, int32_t slot, uint8_t *
 /* the hit raster of grid `slot`: layout.hits_bytes bytes (bit rows of hits_pitch bytes; see nhip_grid_layout_t.hits_bytes) */
 int nhip_grids_download_hits(const nhip_grids_t *grids, int32_t slot, uint8_t *out);
 
+/* ------------------------------------------------------------------ the float norm of the distance gates
+ * The correspondence search, the loop-closure pair gate and the scan features decide by comparing ONE device function with
+ * a threshold: norm(dx, dy) = sqrt(fl(fl(dx * dx) + fl(dy * dy))), every operation rounded to nearest on its own.  This runs
+ * exactly that function on n device inputs on the caller's stream: d_out[i] = norm(d_dx[i], d_dy[i]), or with root_only
+ * != 0 its last step alone, d_out[i] = sqrt(d_dx[i]) (d_dy is not read and may be null).  (Tests: the output must equal a
+ * correctly rounded float chain as bit patterns.) */
+int nhip_round_norm_dev(const float *d_dx, const float *d_dy, int64_t n, int32_t root_only, float *d_out, void *stream);
+
 /* ------------------------------------------------------------------ in-stream kernel timing
  * When enabled, the dominant kernels are bracketed by hipEvents on their own stream.
  * ids: 0 = csm match (bounds, candidates, exact sums), 1 = grid build (everything nhip_grid_build_dev enqueues),

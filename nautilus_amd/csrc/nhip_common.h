@@ -64,6 +64,19 @@ __device__ __forceinline__ void flag_bad_id(uint32_t *status, uint32_t kind, int
   status[3] = (uint32_t)index;
 }
 __device__ __forceinline__ bool id_in(int32_t id, int32_t n) { return (uint32_t)id < (uint32_t)n; }
+// ---- the float norm of the distance gates ----
+// Vector2f::norm() as Eigen evaluates it on baseline x86-64, and as the oracles restate it: two rounded products, one
+// rounded add, a CORRECTLY ROUNDED root.  The correspondence search (nhip_corr.hip), the loop-closure pair gate
+// (nhip_lc.hip) and the scan features (nhip_feat.hip) compare this value with a threshold and promise the reference's
+// decision bit for bit, so the root must round as std::sqrt does: a root one ulp off flips the decision for the d2
+// values next to the threshold (tests/threshold_edges.py designs them; tests/test_round_ops_gpu.py holds this helper to
+// numpy's float32 chain over every binade).  float_norm_root takes the d2 a caller already holds.  sqrtf, not the
+// intrinsic whose name promises round-to-nearest: on gfx950 that one compiles to the bare hardware root, which is off
+// by one ulp for a share of its inputs (measured: DESIGN.md section 5, K5); sqrtf adds the correction step.
+__device__ __forceinline__ float float_norm_root(float d2) { return sqrtf(d2); }
+__device__ __forceinline__ float float_norm(float dx, float dy) {
+  return float_norm_root(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+}
 // a pair's source scan and grid slot; false: the pair scores nothing (and is reported)
 __device__ __forceinline__ bool pair_ids_ok(const IdBounds &B, int32_t src, int32_t slot, int32_t pair, bool report) {
   const bool s_ok = id_in(src, B.n_scans), g_ok = id_in(slot, B.n_slots);
@@ -304,6 +317,9 @@ int launch_lc_chi_square(const double *d_poses, int32_t n_poses, const int32_t *
                          int32_t n, double max_score, double *d_scores, uint8_t *d_flags, hipStream_t s);
 int launch_lc_pair_gate(const double *d_poses, int32_t n_poses, const int32_t *d_cand, int32_t n, double max_range,
                         int32_t min_sep, uint8_t *d_flags, hipStream_t s);
+
+// the float norm of the distance gates on n inputs (nhip_lc.hip; the instrument nhip_round_norm_dev)
+int launch_round_norm(const float *d_dx, const float *d_dy, int64_t n, int32_t root_only, float *d_out, hipStream_t s);
 
 // scan features (nhip_feat.hip); the spec has passed feature_spec_check (nhip_host_features.hip)
 int launch_feat_extract(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const nhip_feature_spec_t &spec,

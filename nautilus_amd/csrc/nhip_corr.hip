@@ -266,7 +266,7 @@ __global__ __launch_bounds__(CT) void corr_search_kernel(
               bool ok = true;
               if (GATE) {
                 const float2 gn = s_tgn[i];
-                ok = __fsqrt_rn(d2) < thr && fabsf(dot2(gn.x, snx[k], gn.y, sny[k])) > min_cos;
+                ok = float_norm_root(d2) < thr && fabsf(dot2(gn.x, snx[k], gn.y, sny[k])) > min_cos;
               }
               // the order of visits is arbitrary: (d2, index) lexicographic = "lowest index wins ties".  bi[k] holds the
               // SLOT of the best so far; the indices are fetched only on an exact tie of the squared distances
@@ -300,7 +300,7 @@ __global__ __launch_bounds__(CT) void corr_search_kernel(
             bool ok = true;
             if (GATE) {
               const float2 gn = s_tgn[i];
-              ok = __fsqrt_rn(d2) < thr && fabsf(dot2(gn.x, snx[GATE ? k : 0], gn.y, sny[GATE ? k : 0])) > min_cos;
+              ok = float_norm_root(d2) < thr && fabsf(dot2(gn.x, snx[GATE ? k : 0], gn.y, sny[GATE ? k : 0])) > min_cos;
             }
             const bool better = ok && (d2 < best[k] || (d2 == best[k] && (uint32_t)idx < (uint32_t)bi[k]));  // the lowest index wins ties
             best[k] = better ? d2 : best[k];
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(CT) void corr_search_kernel(
     __syncthreads();  // s_scan is free again (previous pass / bucket scan)
 #pragma unroll
     for (int k = 0; k < MAX_PER_LANE; k++) {
-      keep[k] = (SRC_INDEX(k) < hi) && bi[k] >= 0 && (__fsqrt_rn(best[k]) < thr);
+      keep[k] = (SRC_INDEX(k) < hi) && bi[k] >= 0 && (float_norm_root(best[k]) < thr);
       const unsigned long long m = __ballot(keep[k]);
       rank[k] = __builtin_popcountll(m & ((1ull << lane) - 1ull));
       if (lane == 0) s_scan[k * (CT / 64) + wv] = __builtin_popcountll(m);

@@ -34,8 +34,7 @@ __device__ __forceinline__ double feat_nan() { return __longlong_as_double(0x7ff
 
 // (a - b).norm() as Eigen evaluates it for Vector2f: every float operation rounded on its own
 __device__ __forceinline__ float norm2f(float2 a, float2 b) {
-  const float dx = __fsub_rn(a.x, b.x), dy = __fsub_rn(a.y, b.y);
-  return __fsqrt_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+  return float_norm(__fsub_rn(a.x, b.x), __fsub_rn(a.y, b.y));  // (nhip_common.h: the root is correctly rounded)
 }
 
 // The smoothness score of point i of a scan of n points, NaN for "no score" (too few neighbours, or 0 / 0).

@@ -215,6 +215,13 @@ int nhip_lc_pair_gate_dev(const double *d_poses, int32_t n_poses, const int32_t 
                              static_cast<hipStream_t>(stream));
 }
 
+int nhip_round_norm_dev(const float *d_dx, const float *d_dy, int64_t n, int32_t root_only, float *d_out, void *stream) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(n >= 0 && (n == 0 || (d_dx && d_out && (root_only || d_dy))), "round_norm_dev: bad arguments");
+  return launch_round_norm(d_dx, d_dy, n, root_only, d_out, static_cast<hipStream_t>(stream));
+}
+
 int nhip_lc_chi_square_gate_dev(const double *d_poses, int32_t n_poses, const int32_t *d_pair_src, const int32_t *d_pair_tgt,
                                 const float *d_cov, int32_t n_pairs, double max_score, double *d_scores,
                                 uint8_t *d_flags, void *stream) {

@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void lc_pair_gate_kernel(const double *__restr
   }
   // GetPoseTranslation returns a Vector2f (slam_util.h:48-53): the distance is a float norm
   const float dx = __fsub_rn((float)poses[3 * b], (float)poses[3 * a]), dy = __fsub_rn((float)poses[3 * b + 1], (float)poses[3 * a + 1]);
-  const float dist = __fsqrt_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+  const float dist = float_norm(dx, dy);
   const int32_t sep = a > b ? a - b : b - a;
   flags[t] = (a != b && sep > min_sep && dist < max_range) ? 1 : 0;
 }
@@ -107,7 +107,23 @@ __global__ __launch_bounds__(256) void lc_chi_square_kernel(const double *__rest
   flags[t] = (a != b && score < max_score) ? 1 : 0;  // `match.node_idx == source.node_idx` is skipped (:64-66); NaN fails
 }
 
+// The instrument of include/nautilus_hip_debug.h: the shared float norm (nhip_common.h) on n inputs, one lane each.
+__global__ __launch_bounds__(256) void round_norm_kernel(const float *__restrict__ dx, const float *__restrict__ dy, int64_t n,
+                                                         int32_t root_only, float *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  out[i] = root_only ? float_norm_root(dx[i]) : float_norm(dx[i], dy[i]);
+}
+
 }  // namespace
+
+int launch_round_norm(const float *d_dx, const float *d_dy, int64_t n, int32_t root_only, float *d_out, hipStream_t s) {
+  if (n == 0) return NHIP_OK;
+  NHIP_REQUIRE(n < (int64_t)0x7fffffff * 256, "round_norm: too many inputs");
+  hipLaunchKernelGGL(round_norm_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, d_dx, d_dy, n, root_only, d_out);
+  NHIP_TRY_HIP(hipGetLastError());
+  return NHIP_OK;
+}
 
 int launch_lc_chi_square(const double *d_poses, int32_t n_poses, const int32_t *d_src, const int32_t *d_tgt, const float *d_cov,
                          int32_t n, double max_score, double *d_scores, uint8_t *d_flags, hipStream_t s) {

@@ -27,6 +27,7 @@ DEBUG_SYMBOLS = [
     "nhip_bnb_stats", "nhip_bnb_stats_levels", "nhip_bnb_stats_per_pair", "nhip_bnb_timeline", "nhip_bnb_timeline_candidates",
     "nhip_host_phases",
     "nhip_timing_enable", "nhip_timing_reset", "nhip_timing_get",
+    "nhip_round_norm_dev",
     "nhip_csm_last_launch", "nhip_csm_get_transformation_info", "nhip_grids_was_rebuilt",
     "nhip_grids_download_skip_map", "nhip_grids_download_hi_plane", "nhip_grids_download_hi_plane_copy",
     "nhip_grids_download_tiled16", "nhip_grids_download_pool", "nhip_grids_download_pool4", "nhip_grids_download_hits",
