@@ -153,7 +153,7 @@ constexpr int BNB_MAX_NB = 11;  // blocks per axis the kernel's register layout 
 constexpr int BNB_B4 = 4;
 constexpr int BNB_POOL4 = 2 * BNB_B4 - 1;
 // Geometry the skip map shares with the correlation kernel: a wave of csm_correlate_kernel owns
-// CSM_WAVE_ROWS plane rows and reads CSM_ROW_DW aligned dwords of each (nhip_csm.hip).
+// CSM_WAVE_ROWS plane rows and reads CSM_ROW_DW aligned dwords of each (nhip_csm_strip.h).
 constexpr int CSM_WAVE_ROWS = 21;
 constexpr int CSM_ROW_DW = 21;  // per cell byte: a 16-bit-cell strip spans 2 * CSM_ROW_DW dwords
 #ifdef __HIPCC__
@@ -202,7 +202,7 @@ int launch_grid_build(const float *d_xy, const int32_t *d_offsets, int32_t n_sca
                       int32_t n_targets, const nhip_grid_spec_t *spec, const GridLayout &L,
                       uint8_t *d_grids, void *d_ws, int64_t ws_bytes, hipStream_t s, bool incremental = false);
 
-// Which kernel matches a list: decided by csm_plan (nhip_csm.hip) and nowhere else; launch_csm_match dispatches on it.
+// Which kernel matches a list: decided by csm_plan (nhip_csm_plan.hip) and nowhere else; launch_csm_match dispatches on it.
 // For MATCH_BNB, the form of the branch-and-bound run is decided by bnb_plan (nhip_bnb_host.hip) and nowhere else.
 enum MatchForm : int32_t {
   MATCH_BNB,       // the branch-and-bound matcher (nhip_bnb.hip)
@@ -282,9 +282,9 @@ void launch_csm_finalize(const MatchJob &job);
 // of the job it reads the scans, the grids, rot0_cs (one entry), delta_cs, the search and the stream
 int launch_csm_scores(const MatchJob &job, int32_t src, int32_t slot, int32_t origin_x, int32_t origin_y, int32_t *d_volume);
 
-// the kernel that performs every add, 16-bit cells (nhip_csm16.hip); called by launch_csm_match / launch_csm_scores
-int launch_csm16_match(const MatchJob &job);
-int launch_csm16_scores(const MatchJob &job, int32_t src, int32_t slot, int32_t origin_x, int32_t origin_y, int32_t *d_volume);
+// NHIP_SEARCH_EXACT_SCORE: replaces the records' scores by the winners' scores on the unquantised table and gates them
+// (nhip_csm_score.hip); called by launch_csm_match
+int launch_csm_exact_score(const MatchJob &job, const MatchPlan &plan);
 // every add for lattices of few translations (nx * ny <= 256), both cell widths (nhip_csm_small.hip); tiling from the plan
 bool csm_small_plane_fits(const nhip_search_t *search);
 bool csm_small_tiled_fits(const nhip_search_t *search, int32_t n_pairs, int32_t *tile_rows, int32_t *n_tiles);

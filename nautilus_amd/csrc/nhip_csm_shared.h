@@ -1,5 +1,6 @@
-// nhip_csm_shared.h -- what the two kernels that perform every add of the (theta, x, y) correlation share:
-// csm_correlate_kernel (8-bit cells, nhip_csm.hip) and csm_correlate16_kernel (16-bit cells, nhip_csm16.hip).
+// nhip_csm_shared.h -- what the kernels that perform every add of the (theta, x, y) correlation share with each other
+// (the strip kernels of nhip_csm_strip.h, csm_small_plane_kernel) and with the kernels that turn keys into records
+// (nhip_csm_score.hip): the score gate, the parameter block, a point's window cell, the rotation, the key.
 #pragma once
 #include "nhip_common.h"
 
@@ -39,9 +40,18 @@ __host__ __device__ inline nhip_match_t gate_rejected_record() {
   return m;
 }
 
+// A key is (sum << 32) | ~lin with lin = (itheta * nx + ix) * ny + iy, so that the maximum key is the largest sum at the
+// smallest linear index.  The indices of the record a key stands for:
+__device__ __forceinline__ void decode_key(unsigned long long key, int32_t nx, int32_t ny, nhip_match_t &m) {
+  const uint32_t lin = 0xffffffffu - (uint32_t)key;
+  m.iy = (int32_t)(lin % (uint32_t)ny);
+  m.ix = (int32_t)((lin / (uint32_t)ny) % (uint32_t)nx);
+  m.itheta = (int32_t)(lin / ((uint32_t)ny * (uint32_t)nx));
+}
+
 inline ScoreGate job_gate(const MatchJob &job) { return {job.min_score, job.L->Lf, job.L->step}; }
 
-// ---- what the kernels' parameter blocks share (CsmParams below, bnb::BnbParams, ExactParams of nhip_csm.hip), from a job:
+// ---- what the kernels' parameter blocks share (CsmParams below, bnb::BnbParams, ExactParams of nhip_csm_score.hip), from a job:
 // the fields have one name in all three.  What differs per kernel -- keys, the blocks of the plane, the dense rule, the
 // plan's fields -- its launcher sets after these.
 // What all three hold (the block is zeroed first): the scans, the grids, the per-pair arrays and their counts, the plane
@@ -104,6 +114,16 @@ struct CsmParams {
   double res, inv_res;
 };
 
+// The strip kernels of one cell width (nhip_csm_strip.h), as their launchers take them (nhip_csm_plan.hip)
+struct StripKernels {
+  void (*match[2])(CsmParams);   // the keys of a list of pairs; [1]: DENSE
+  void (*scores[2])(CsmParams);  // the score volume of one pair (VOLUME); [1]: DENSE
+  int32_t threads;               // per workgroup
+  int32_t pb_nx, pb_ny;          // translations per plane block
+};
+const StripKernels &strip_kernels8();   // nhip_csm.hip
+const StripKernels &strip_kernels16();  // nhip_csm16.hip
+
 // Stored-grid coordinates (row, col) of the top-left cell of point q's window under rotation
 // (cf, sf), packed (row << 16) | col.  Spec: rotate in float with individually rounded
 // products (Eigen Affine2f * Vector2f on baseline x86-64: no FMA), cell = S/2 +
@@ -126,11 +146,35 @@ __device__ __forceinline__ uint32_t window_cell(float2 q, float cf, float sf, co
   return (prow << 16) | pcol;
 }
 
+// Rotation k of a pair: R(theta0) * R(delta_k), composed in double with individually rounded ops.  (cos, sin) of theta0
+// is entry `pair` of rot0_cs, of delta_k entry k of delta_cs.
+__device__ __forceinline__ void compose_rotation(const double *rot0_cs, const double *delta_cs, int32_t pair, int32_t k,
+                                                 float &cf, float &sf) {
+  const double c0 = rot0_cs[2 * pair], s0 = rot0_cs[2 * pair + 1];
+  const double cd = delta_cs[2 * k], sd = delta_cs[2 * k + 1];
+  cf = __double2float_rn(__dsub_rn(__dmul_rn(c0, cd), __dmul_rn(s0, sd)));
+  sf = __double2float_rn(__dadd_rn(__dmul_rn(s0, cd), __dmul_rn(c0, sd)));
+}
+
 __device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int m) {
   uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
   lo = __shfl_xor(lo, m, 64);
   hi = __shfl_xor(hi, m, 64);
   return ((unsigned long long)hi << 32) | lo;
+}
+
+// K3: argmax with deterministic tie-break (smallest linear index wins).  `best` is the largest of the lane's keys
+// (sum << 32) | ~lin; the wave's largest goes to the pair's key.
+__device__ __forceinline__ unsigned long long pose_key(uint32_t sum, uint32_t lin) {
+  return ((unsigned long long)sum << 32) | (0xffffffffu - lin);
+}
+__device__ __forceinline__ void wave_max_to_key(unsigned long long best, int lane, unsigned long long *key) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const unsigned long long o = shfl_xor_u64(best, m);
+    best = o > best ? o : best;
+  }
+  if (lane == 0) atomicMax(key, best);
 }
 
 // Where to put point j inside a fresh tile: ahead of the direction the beam sweep is moving.

@@ -2,7 +2,7 @@
 //
 // The coarse level of CorrelativeScanMatcher::GetTransformation (call site src/optimization/solver.cc:633-638; DESIGN.md
 // section 3, item 7) is 181 rotations of 13 x 13 translations on a 200 x 200 table.  The two kernels that perform every
-// add (nhip_csm.hip, nhip_csm16.hip) are built for planes of 81 x 81: a workgroup owns a 21-row strip of ONE rotation's
+// add (nhip_csm_strip.h) are built for planes of 81 x 81: a workgroup owns a 21-row strip of ONE rotation's
 // plane and walks all of the scan's points through LDS tiles -- on a 13 x 13 plane most of its lanes idle and its
 // lifetime (0.2 ms) is the whole call's.  The branch-and-bound matcher computes the bounds of all 181 rotations in the
 // pair's one workgroup (23 rounds of its eight waves).  Here:
@@ -72,11 +72,8 @@ __global__ __launch_bounds__(SMALL_THREADS) void csm_small_plane_kernel(CsmParam
   // (a centre the stored border cannot cover scores nothing: every sum stays 0 and pose 0 wins, as in the other kernels)
   const bool centre_ok = (abs(cx) + P.hx <= P.max_shift) && (abs(cy) + P.hy <= P.max_shift);
 
-  // rotation k: R(theta0) * R(delta_k), composed in double with individually rounded ops
-  const double c0 = P.rot0_cs[2 * pair], s0 = P.rot0_cs[2 * pair + 1];
-  const double cd = P.delta_cs[2 * k], sd = P.delta_cs[2 * k + 1];
-  const float cf = __double2float_rn(__dsub_rn(__dmul_rn(c0, cd), __dmul_rn(s0, sd)));
-  const float sf = __double2float_rn(__dadd_rn(__dmul_rn(s0, cd), __dmul_rn(c0, sd)));
+  float cf, sf;
+  compose_rotation(P.rot0_cs, P.delta_cs, pair, k, cf, sf);
 
   // this lane's poses: slot = pass * 64 + lane = iy * nx + ix -- ROW-major in the table, so that the 64 lookups of one load
   // instruction fall into ~5 rows of 13 consecutive cells (5 cache lines) and a point's three loads touch each of its 13
@@ -144,16 +141,10 @@ __global__ __launch_bounds__(SMALL_THREADS) void csm_small_plane_kernel(CsmParam
 #pragma unroll
     for (int p = 0; p < PASSES; p++) {
       if (!valid[p]) continue;
-      const uint32_t lin = (uint32_t)(k * n_poses + lin_pose[p]);  // (k * nx + ix) * ny + iy
-      const unsigned long long key = ((unsigned long long)s_sum[p * 64 + lane] << 32) | (0xffffffffu - lin);
+      const unsigned long long key = pose_key(s_sum[p * 64 + lane], (uint32_t)(k * n_poses + lin_pose[p]));  // (k * nx + ix) * ny + iy
       best = key > best ? key : best;
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      const unsigned long long o = shfl_xor_u64(best, m);
-      best = o > best ? o : best;
-    }
-    if (lane == 0) atomicMax(&P.keys[pair], best);
+    wave_max_to_key(best, lane, &P.keys[pair]);
   }
 }
 

@@ -5,6 +5,7 @@
 #include <memory>
 
 #include "nhip_common.h"
+#include "nhip_csm_shared.h"  // (decode_key)
 #include "nhip_host.h"
 
 using namespace nhip;
@@ -298,10 +299,8 @@ extern "C" __global__ void dropin_bridge_kernel(const nhip_match_t *rec1, const 
     // the coarse search left its keys undecoded (MatchPlan::keys_undecoded): csm_finalize_kernel's decoding, here, and the
     // fine search's keys zeroed for it (keys_zeroed) -- two small launches and a memset fewer per call
     const unsigned long long key = keys1[0];
-    const uint32_t sum = (uint32_t)(key >> 32), lin = 0xffffffffu - (uint32_t)key;
-    m.iy = (int32_t)(lin % (uint32_t)ny1);
-    m.ix = (int32_t)((lin / (uint32_t)ny1) % (uint32_t)nx1);
-    m.itheta = (int32_t)(lin / ((uint32_t)ny1 * (uint32_t)nx1));
+    const uint32_t sum = (uint32_t)(key >> 32);
+    decode_key(key, nx1, ny1, m);
     double sc = Lf1;
     if (n_a > 0) sc = __dadd_rn(Lf1, __ddiv_rn(__dmul_rn(step1, (double)sum), (double)n_a));
     m.score = __double2float_rn(sc);

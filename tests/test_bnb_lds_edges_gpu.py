@@ -12,7 +12,7 @@ sit on both sides of each threshold.  The constants, as they stand in nhip_bnb_p
 On the 1,200-cell grid of _specs() (30 m at 0.05 m, max_shift 40) the pooled table has 35,712 bytes, so
     staged:      35,712 + 512 n + 8,256 <= 163,840  <=>  n <= 234  (234: 163,776 bytes; 235: 164,288)
     not staged:  34,816 + 512 n + 8,256 <= 163,840  <=>  n <= 235  (235: 163,392 bytes; 236: 163,904)
-A search has an odd number of rotations (nhip_csm.hip requires it, and so does the oracle), so the cases are the odd counts
+A search has an odd number of rotations (check_search of nhip_csm_plan.hip requires it, and so does the oracle), so the cases are the odd counts
 on either side: 233 rotations are the last that run with POOL_LDS = true (163,264 bytes), 235 the last the matcher admits
 and the first with POOL_LDS = false (163,392 bytes, the largest launch there is), 237 go to the kernel that performs every
 add.  Three pairs, a 9 x 9 lattice of translations, both cell widths; every form through the environment hooks, the

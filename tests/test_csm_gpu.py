@@ -199,28 +199,67 @@ def test_score_volume_bit_exact(gpu, small_bag):
         st.close()
 
 
-def test_score_volume_16bit_full_plane_every_alignment_class(gpu, small_bag):
+_CLASS_ORIGINS = ((0, 0), (1, -2), (2, 3), (3, 1))  # search centres whose windows start in each column class mod 4
+
+
+@pytest.mark.parametrize("cell_bits", (16, 8))
+def test_score_volume_16bit_full_plane_every_alignment_class(gpu, small_bag, cell_bits):
     """csm_correlate16_kernel keeps two parity sets of (raw, hi) accumulators and four alignment classes (window start
-    column mod 4), with the cells left of a lane's 28 travelling to its neighbour: EVERY sum of full 81 x 81 planes
-    (all three lanes of a row, the neighbour exchanges, rows up to 80 = four strips) against the oracle, for search
-    centres that put the windows into each class, with the skip map and with every strip added."""
+    column mod 4), with the cells left of a lane's 28 travelling to its neighbour; csm_correlate_kernel (8-bit cells) a
+    packed register set per class, unpacked into the lane's sums with the same exchange.  Both are one skeleton
+    (nhip_csm_strip.h): EVERY sum of full 81 x 81 planes (all three lanes of a row, the neighbour exchanges, rows up to
+    80 = four strips) against the oracle, for search centres that put the windows into each class, with the skip map
+    and with every strip added.  The sums are beyond what a 16-bit field holds (8-bit cells), 50 times that (16-bit)."""
     import os
-    spec, ospec = _specs(max_shift=44, cell_bits=16)
+    spec, ospec = _specs(max_shift=44, cell_bits=cell_bits)
     st = csm.ScanTable.from_list(small_bag.scans)
     grids = csm.LikelihoodGrids(st, [12], spec)
     og = O.grid_build(small_bag.scans[12], ospec)
     search, oss = csm.search_spec(3, 81, 81, 2 * DEG), O.search_spec(3, 81, 81, 2 * DEG)
-    for origin in ((0, 0), (1, -2), (2, 3), (3, 1)):
+    for origin in _CLASS_ORIGINS:
         want = O.csm_scores(small_bag.scans[14], og, ospec, -0.02, oss, origin)
         got = csm.score_volume(st, grids, 14, 0, -0.02, search, origin)
         assert np.array_equal(got, want), origin
-        assert want.max() > 65535 * 50
+        assert want.max() > (65535 * 50 if cell_bits == 16 else 65535)
     os.environ["NHIP_CSM_DENSE"] = "1"
     try:
         got = csm.score_volume(st, grids, 14, 0, -0.02, search, (3, 1))
     finally:
         os.environ.pop("NHIP_CSM_DENSE", None)
     assert np.array_equal(got, want)
+    grids.close()
+    st.close()
+
+
+@pytest.mark.parametrize("cell_bits", (8, 16))
+def test_score_volume_at_plane_block_seams(gpu, small_bag, cell_bits):
+    """A plane of 83 x 85 translations is more than one plane block of the strip kernels on both axes: 81 + 2 columns,
+    and 4 x 21 + 1 rows of one-wave workgroups (8-bit cells) or 84 + 1 rows of a four-wave workgroup (16-bit).  EVERY sum
+    against the oracle, for search centres in each alignment class, with the skip map and with every strip added.  (The
+    columns and the row past the first blocks hold no zero and column 82 as many values as it has rows: a seam block
+    left at zero, or written to another block's place, cannot pass.)"""
+    import os
+    ospec = O.grid_spec(30.0, 0.05, 2.0, 1e-10, cell_bits)
+    # (max_shift 45: the centre (2, 3) of a plane of 85 rows needs |3| + 42 cells of border; a centre beyond the border
+    #  scores nothing by the kernels' contract.  8-bit grids carry the map anyway)
+    spec = csm.grid_spec(30.0, 0.05, 2.0, 1e-10, 45, cell_bits, skip_map=True)
+    st = csm.ScanTable.from_list(small_bag.scans)
+    grids = csm.LikelihoodGrids(st, [12], spec)
+    og = O.grid_build(small_bag.scans[12], ospec)
+    search, oss = csm.search_spec(1, 83, 85, 2 * DEG), O.search_spec(1, 83, 85, 2 * DEG)
+    for origin in _CLASS_ORIGINS:
+        want = O.csm_scores(small_bag.scans[14], og, ospec, -0.02, oss, origin)
+        assert want.shape == (1, 83, 85)
+        assert (want[0, 81:, :] != 0).all() and (want[0, :, 84] != 0).all()
+        assert len(np.unique(want[0, 82, :])) == 85
+        for dense in (False, True):
+            if dense:
+                os.environ["NHIP_CSM_DENSE"] = "1"
+            try:
+                got = csm.score_volume(st, grids, 14, 0, -0.02, search, origin)
+            finally:
+                os.environ.pop("NHIP_CSM_DENSE", None)
+            assert np.array_equal(got, want), (origin, dense)
     grids.close()
     st.close()
 

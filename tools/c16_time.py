@@ -1,6 +1,8 @@
-"""Times the kernel that performs every add on 16-bit cells (csm_correlate16_kernel) for every library under
-build/variants/ (tools/c16_variants.sh), one subprocess each (NHIP_LIB), interleaved over `rounds`.
-  python tools/c16_time.py [--scans 300] [--rounds 3]        -> JSON lines on stdout"""
+"""Times the strip kernel that performs every add (csm_correlate16_kernel, or csm_correlate_kernel with --cell-bits 8) on
+the bench workload, with the skip map and dense, for the libraries given -- by default every one under build/variants/
+(tools/c16_variants.sh) --, one child process per library and round (NHIP_LIB), interleaved over `rounds`, each under its
+own time limit; the first child that fails ends the run.
+  python tools/c16_time.py [--cell-bits 16] [--scans 300] [--rounds 3] [LIB.so ...]        -> JSON lines on stdout"""
 import argparse
 import glob
 import json
@@ -12,7 +14,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def child(scans, steps):
+def child(scans, steps, cell_bits):
     sys.path.insert(0, ROOT)
     import ctypes as C
     import torch
@@ -25,7 +27,7 @@ def child(scans, steps):
     out = {}
     for dense in ("0", "1"):
         os.environ["NHIP_CSM_DENSE"] = dense
-        m = bench.HipMatcher(wl, plan.shard(0), dev, 16, exhaustive=True)
+        m = bench.HipMatcher(wl, plan.shard(0), dev, cell_bits, exhaustive=True)
         m.step()
         torch.cuda.synchronize()
         lib.nhip_timing_reset()
@@ -48,16 +50,23 @@ if __name__ == "__main__":
     ap.add_argument("--scans", type=int, default=300)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--cell-bits", type=int, choices=(8, 16), default=16)
+    ap.add_argument("--timeout", type=int, default=240, help="seconds a child may take")
     ap.add_argument("--child", action="store_true")
+    ap.add_argument("libs", nargs="*", help="libraries to time (default: build/variants/lib_*.so)")
     a = ap.parse_args()
     if a.child:
-        child(a.scans, a.steps)
+        child(a.scans, a.steps, a.cell_bits)
         sys.exit(0)
-    libs = sorted(glob.glob(os.path.join(ROOT, "build", "variants", "lib_*.so")))
+    libs = [os.path.abspath(lp) for lp in a.libs] or sorted(glob.glob(os.path.join(ROOT, "build", "variants", "lib_*.so")))
     for r in range(a.rounds):
         for lp in libs:
             env = dict(os.environ, NHIP_LIB=lp)
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--scans", str(a.scans), "--steps", str(a.steps)],
+            p = subprocess.run(["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--child",
+                                "--scans", str(a.scans), "--steps", str(a.steps), "--cell-bits", str(a.cell_bits)],
                                env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
             line = p.stdout.decode().strip().splitlines()[-1] if p.stdout.strip() else p.stderr.decode()[-400:]
-            print(json.dumps({"lib": os.path.basename(lp), "round": r, "result": line}), flush=True)
+            print(json.dumps({"lib": lp if a.libs else os.path.basename(lp), "cell_bits": a.cell_bits, "round": r, "exit": p.returncode,
+                              "result": line}), flush=True)
+            if p.returncode != 0:  # (a fault, an abort or the time limit: nothing more is started on that GPU)
+                sys.exit(p.returncode)
