@@ -8,7 +8,7 @@
 // Bound: the plane of translations of one rotation is cut into 8 x 8 blocks (Y, X).  A point whose window origin
 // (top-left lookup cell) is (r, c) reads, for the 64 poses of block (Y, X), stored cells in rows
 // [r + 8Y, r + 8Y + 8) and columns [c + 8X, c + 8X + 8), all inside the 15 x 15 cells that the pooled entry
-// pool[(r >> 3) + Y][(c >> 3) + X] covers (nhip_grid.hip).  So U(k, Y, X) = sum over points of that entry is an
+// pool[(r >> 3) + Y][(c >> 3) + X] covers (nhip_grid_tables.hip).  So U(k, Y, X) = sum over points of that entry is an
 // upper bound of every sum in the block (16-bit cells: 257 * U, the pool holds ceil(max / 257)).
 // Search: (1) U for all blocks of all rotations -- a gather of 11 x 11 bytes per RUN of points that share a pooled
 // entry (consecutive beams do: run-length compression cuts the gathers ~5x) from the LDS-resident pooled table;

@@ -4,9 +4,9 @@
 // points that share a pooled entry (the run lists: LIST_ENTRIES words of LDS per wave) -- with slot_block, the layout its
 // totals come out in; sub_bounds -- the four 4 x 4 sub-block bounds of one block, from the points; strip_bounds_c -- the
 // same for a strip of up to three blocks, from the origins a wave holds.
-// Assumes: the pooled tables behind the stored image as nhip_grid.hip builds them (zero rows below the pooled image, a
-// pitch that is a multiple of 16, offsets below 1 << RUN_SHIFT), 16-bit packed fields (LANE_WEIGHT, 18 chunks of 64
-// points).  Every bound is at least the largest sum of the poses it covers; nothing here reads the stored cells.
+// Assumes: the pooled tables behind the stored image as the table build leaves them (nhip_grid_blur.hip,
+// nhip_grid_tables.hip: zero rows below the pooled image, a pitch that is a multiple of 16, offsets below
+// 1 << RUN_SHIFT), 16-bit packed fields (LANE_WEIGHT, 18 chunks of 64 points).  Every bound is at least the largest sum of the poses it covers; nothing here reads the stored cells.
 // Included by nhip_bnb.hip only.
 #pragma once
 #include "nhip_bnb_origin.h"

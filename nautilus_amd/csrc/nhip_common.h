@@ -87,6 +87,7 @@ __device__ __forceinline__ bool pair_ids_ok(const IdBounds &B, int32_t src, int3
 #endif
 
 // ---- grid layout (host) ----
+constexpr int32_t GRID_MAX_SIDE = 16384;  // cells per axis make_layout admits (the table build sizes its tile bitmap by it: nhip_grid.h)
 struct GridLayout {
   int32_t S, pad, pitch, R;
   int32_t cb;      // bytes per cell: 1 or 2
@@ -198,6 +199,7 @@ void timer_begin(int id, hipStream_t s);
 void timer_end(int id, hipStream_t s);
 
 // ---- kernel launchers (defined in the .hip files) ----
+// the table build (nhip_grid.hip; its kernels: nhip_grid_blur.hip, nhip_grid_tables.hip, nhip_grid_clear.hip)
 int launch_grid_build(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const int32_t *d_target_ids,
                       int32_t n_targets, const nhip_grid_spec_t *spec, const GridLayout &L,
                       uint8_t *d_grids, void *d_ws, int64_t ws_bytes, hipStream_t s, bool incremental = false);

@@ -7,7 +7,7 @@
 // rotation k of one pair and keeps its integer accumulators in registers -- three lanes per y-shift, 28 consecutive
 // x-shifts each.  A point's contribution to the strip is the (81 x 21) window of the target grid anchored at its rotated
 // cell.  Per lane-chunk of 64 points the wave computes the rotated cells (one point per lane) and looks up the target's
-// skip map (nhip_grid.hip): points whose window strip holds only zeros are dropped -- they would add nothing, so the sums
+// skip map (nhip_grid_tables.hip): points whose window strip holds only zeros are dropped -- they would add nothing, so the sums
 // are unchanged.  The others are visited in beam order; consecutive beams hit neighbouring cells, so a run of points
 // shares one grid tile: the workgroup stages a tile of the grid in LDS (16-byte reads of HBM/L2, once per run), then
 // every point of the run is a wave-uniform LDS offset (v_readlane) from which each lane reads its 28 cells as seven
@@ -62,7 +62,7 @@ struct Strip {
   static constexpr int CHUNK_W = 16 / (int)sizeof(typename C::Word);
   static_assert(sizeof(typename C::Word) == 4 * C::CB, "an aligned read is four cells");
   static_assert(WAVE_ROWS == CSM_WAVE_ROWS && ROW_BYTES == 4 * C::CB * CSM_ROW_DW,
-                "the skip map (nhip_grid.hip) is built for this wave footprint");
+                "the skip map (nhip_grid_tables.hip) is built for this wave footprint");
   static_assert(C::TILE_ROWS % STEP_ROWS == 0, "tile rows must be a whole number of fill steps");
 };
 

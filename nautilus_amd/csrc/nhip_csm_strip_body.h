@@ -77,7 +77,7 @@
     for (; C::UNPACKS ? c64 < n_pts && max(max(added0, added1), max(added2, added3)) <= C::FLUSH_START_MAX : c64 == c0; c64 += 64) {
       const int32_t n = min(n_pts - c64, 64);
       // one point per lane: rotated window cell, and whether this block's strip of its window
-      // holds anything but zeros (skip map, nhip_grid.hip)
+      // holds anything but zeros (skip map, nhip_grid_tables.hip)
       uint32_t vcell = 0u, vwork = 0u;  // vwork bit u: strip u of this plane block has work for the point
       if (lane < n) {
         vcell = window_cell(P.xy[beg + c64 + lane], cf, sf, P, ox, oy, cx, cy);

@@ -34,7 +34,7 @@ int make_layout(const nhip_grid_spec_t *spec, GridLayout *L) {
   NHIP_REQUIRE((spec->flags & (NHIP_GRID_SKIP_MAP | NHIP_GRID_NO_IMAGE)) != (NHIP_GRID_SKIP_MAP | NHIP_GRID_NO_IMAGE),
                "grid spec: a skip map (the every-add kernels') needs the image NHIP_GRID_NO_IMAGE leaves out");
   const double side = floor((spec->range * 2.0) / spec->res);  // cimg_debug.h:21-22
-  NHIP_REQUIRE(side >= 1 && side <= 16384, "grid spec: side %g out of range [1, 16384]", side);
+  NHIP_REQUIRE(side >= 1 && side <= GRID_MAX_SIDE, "grid spec: side %g out of range [1, %d]", side, GRID_MAX_SIDE);
   L->S = (int32_t)side;
   L->cb = spec->cell_bits == 8 ? 1 : 2;  // (0 = the default: 16-bit cells, in every struct of the ABI)
   L->levels = L->cb == 2 ? 65535 : 255;

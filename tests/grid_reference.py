@@ -16,7 +16,7 @@ import numpy as np
 from nautilus_amd import _lib, csm
 from oracle import oracle as O
 
-TILE = 64        # the build works in 64 x 64 tiles (nhip_grid.hip)
+TILE = 64        # the build works in 64 x 64 tiles (nhip_grid.h)
 HIT_PAD = 32     # zero border of the hit raster, in cells (include/nautilus_hip.h, hits_bytes)
 LINE = 128       # bytes of one tile of the matcher's tiled planes
 
@@ -117,8 +117,9 @@ def grid_tables(spec):
 
 
 def first_guess(sums, thr):
-    """Where the 16-bit quantiser of the build starts its search of the table for a blur sum (nhip_grid.hip,
-    launch_grid_build): the line through (ln thr[57344], 57344) and (ln thr[65535], 65535), evaluated in single precision.
+    """Where the 16-bit quantiser of the build (grid_blur_kernel<2>, nhip_grid_blur.hip) starts its search of the table for
+    a blur sum: the line through (ln thr[57344], 57344) and (ln thr[65535], 65535) that launch_grid_build (nhip_grid.hip)
+    fits, evaluated in single precision.
     Within 6 levels of the answer a few table steps settle the cell; further off, a binary search of the whole table
     does.  Only to state which of the two an INPUT reaches (numpy's float32 log stands in for the device's)."""
     t1, t2 = float(thr[57344]), float(thr[65535])

@@ -1,5 +1,5 @@
-"""The likelihood-table build (nhip_grid.hip) on targets chosen to break it, every plane of every slot against its
-definition (tests/grid_reference.py; tests/test_grid_targets_cpu.py ties the definitions to the CPU oracle and holds the
+"""The likelihood-table build (nhip_grid.h and its units) on targets chosen to break it, every plane of every slot against
+its definition (tests/grid_reference.py; tests/test_grid_targets_cpu.py ties the definitions to the CPU oracle and holds the
 inputs' preconditions).  Hits in the grid's corners and on its rim, on both sides of tile seams and where four tiles meet,
 in the partial last tile; tile neighbourhoods with every cell a hit (blur radius 16: the build's LDS lists at capacity); a
 density ramp (thousands of distinct 16-bit values, blur sums from 1 upwards at sigma 0.7); points on cell edges; piles;
@@ -137,6 +137,66 @@ def test_chunked_builds_rebuilds_and_band_kernels_give_the_same_bytes(gpu, small
         os.environ.pop("NHIP_GRID_POOL", None)
     assert np.array_equal(bands, fresh), "NHIP_GRID_POOL=bands"
     assert np.array_equal(bands_rebuilt, fresh), "NHIP_GRID_POOL=bands, rebuild"
+
+
+# ------------------------------------------------------------------------------------------------ more than one z-slice
+N_SLICED = 65537  # a launch's z dimension holds 65,535 targets: two slices, the second of two targets
+
+
+def test_more_targets_than_one_z_slice_in_one_pass(gpu):
+    """65,537 targets in one pass of nhip_grid_build_dev: the kernels launched in z-slices (skip map, level 1 from level
+    2, and with NHIP_GRID_POOL=bands the band kernel) run a second slice, whose slots are t_base + blockIdx.z.  The
+    smallest geometry with a tile and a blur: side 4 (one tile), border 16, blur radius 2, 8-bit cells with the skip
+    map -- under 16 KB a slot, so the buffer stays under 1 GB.  Target ids cycle through five scans of a few points (one
+    empty): every slot i must equal slot i mod 5 (compared on the device), and slots 0 .. 4, 65,535 and 65,536 are held
+    to the definitions plane by plane."""
+    import torch
+    dev = torch.device("cuda:0")
+    lib = _lib.load()
+    range_m, res, sigma = 0.1, 0.05, 0.5
+    spec = csm.grid_spec(range_m, res, sigma, 1e-10, 0, 8)
+    ospec, L = O.grid_spec(range_m, res, sigma, 1e-10, 8), csm.grid_layout(spec)
+    S = L.side
+    assert S == 4 and L.blur_radius == 2 and L.pad == 16 and L.cell_bytes == 1 and G.has_map(spec, L)
+    assert L.slot_bytes < 16384 and L.slot_bytes % 8 == 0, "a slot of the geometry the test is sized for"
+    every_cell = [(c, r) for r in range(S) for c in range(S)]
+    clouds = [G.cell_centres(cells, S, res) for cells in ([(0, 0)], [(3, 3), (0, 3), (2, 1)], every_cell)]
+    clouds += [np.zeros((0, 2), np.float32), G.cell_centres([(3, 0), (1, 2)], S, res)]
+    k = len(clouds)
+    expected = [G.expected_slot(c, spec, ospec, L) for c in clouds]
+    n = N_SLICED
+    xy, off = csm.pack_scans(clouds)
+    ids = (np.arange(n) % k).astype(np.int32)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d_xy, d_off, d_ids = t(xy), t(off), t(ids)
+    nbytes = lib.nhip_grids_bytes(C.byref(spec), n)
+    ws = lib.nhip_grid_workspace_bytes(C.byref(spec), n)
+    assert nbytes < (1 << 30) and ws < (2 << 20)
+    sp = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    d_grids = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    d_ws = torch.empty(ws, dtype=torch.uint8, device=dev)
+    held = list(range(k)) + [n - 2, n - 1]
+
+    def build_and_check(what):
+        d_grids.fill_(255)
+        d_ws.fill_(255)
+        _lib.check(lib.nhip_grid_build_dev(d_xy.data_ptr(), d_off.data_ptr(), k, d_ids.data_ptr(), n, C.byref(spec),
+                                           d_grids.data_ptr(), d_ws.data_ptr(), ws, sp))
+        torch.cuda.synchronize()
+        slots = d_grids[:n * L.slot_bytes].view(torch.int64).view(n, L.slot_bytes // 8)
+        for j in range(k):
+            same = (slots[j::k] == slots[j]).all(dim=1)
+            assert bool(same.all()), "%s: slot %d differs from slot %d" % (what, j + k * int((~same).nonzero()[0]), j)
+        for slot in held:
+            raw = slots[slot].view(torch.uint8).cpu().numpy()
+            G.assert_raw_slot(raw, spec, L, expected[slot % k], "%s, slot %d:" % (what, slot))
+
+    build_and_check("one pass of %d targets" % n)
+    os.environ["NHIP_GRID_POOL"] = "bands"
+    try:
+        build_and_check("one pass of %d targets, NHIP_GRID_POOL=bands" % n)
+    finally:
+        os.environ.pop("NHIP_GRID_POOL", None)
 
 
 # ------------------------------------------------------------------------------------------------ the consumer
