@@ -50,11 +50,14 @@ def synthetic_hitl_message(bag, poses, early, late):
 
 def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, verbose=False, residual="normal",
         rank=0, world=1, device="cuda:0", backend=None, iterations=4, hitl=True, cell_bits=16, gate="scatter",
-        min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False):
+        min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False, normals="bag"):
     """min_scatter_score: LCCandidateFilter's threshold is 0.70 (lc_candidate_filter.cc:76); scans of the synthetic
     24 m x 16 m room score ~0.4, so callers on that world pass a lower one.
     hitl_device: the HITL constraint's points are selected and packed on the GPU (hitl.select, under the "path" clock) and
     its blocks reduced there to normal equations, instead of hostside.hitl_relevant_poses + per-point evaluation.
+    normals: "bag" takes the synthetic world's analytic normals; "device" estimates them from the clouds on the GPU
+    (backend.normals: NormalComputation::GetNormals, once, before the first solve, under the "path" clock) -- what a real
+    bag, which brings none, needs.
     With world > 1 (one process per GPU under torch.distributed): the window ICP solve is replicated -- its
     consumer, the solver, is host-side -- and the loop-closure pairs are sharded by target across the ranks,
     matched, and all-gathered (nautilus_amd/sharding.py); every rank ends with the same trajectory."""
@@ -69,9 +72,18 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     kind = _lib.NHIP_LIDAR_NORMAL if residual == "normal" else _lib.NHIP_LIDAR_POINT
     if residual not in ("normal", "point", "feature"):
         raise ValueError("run: residual %r" % (residual,))
+    if normals not in ("bag", "device"):
+        raise ValueError("run: normals %r" % (normals,))
     out = {"backend": backend.name, "n_scans": n_scans, "window": window, "residual": residual,
            "err_odometry_m": posegraph.trajectory_error(odom, bag.truth)}
     posegraph.clock_reset()
+
+    if normals == "device":
+        t0 = time.perf_counter()
+        with posegraph.clocked("path"):
+            nrm = backend.normals(xy, off)
+        out["t_normals_s"] = time.perf_counter() - t0
+        out["normals"] = "device"
 
     feats = None
     if residual == "feature":
@@ -207,6 +219,8 @@ if __name__ == "__main__":
                          "feature points as LIDARNormalResidual blocks and edge points as LIDARPointResidual blocks")
     ap.add_argument("--hitl-device", action="store_true",
                     help="select the HITL constraint's points and reduce its blocks to normal equations on the GPU")
+    ap.add_argument("--normals", choices=["bag", "device"], default="bag",
+                    help="the synthetic bag's analytic normals, or normals estimated from the clouds on the GPU")
     ap.add_argument("-v", action="store_true")
     a = ap.parse_args()
     rank, world, local = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), \
@@ -223,7 +237,7 @@ if __name__ == "__main__":
         dist.barrier()
         os.dup2(saved, 1)
     res = run(a.scans, a.window, verbose=a.v and rank == 0, residual=a.residual, rank=rank, world=world,
-              device="cuda:%d" % local, hitl_device=a.hitl_device)
+              device="cuda:%d" % local, hitl_device=a.hitl_device, normals=a.normals)
     res["world_size"] = world
     if rank == 0:
         print(json.dumps(res))

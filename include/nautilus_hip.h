@@ -63,7 +63,7 @@ const char *nhip_version(void);
  * nhip_last_error().  info (may be NULL): {OR of the kinds seen, kind, value, index of the first one reported}; kinds:
  * 1 target scan id of a grid build, 2 source scan id of a pair, 4 grid slot of a pair, 8 block id of a correspondence,
  * 16 pose index of a block, 32 scan id of a correspondence-search block, 64 feature index and 128 feature count of
- * nhip_features_pack_dev.  Clears the record (in the order of `stream`).
+ * nhip_features_pack_dev, 256 scan offset of nhip_normals_estimate_dev.  Clears the record (in the order of `stream`).
  * ONE record per DEVICE, shared by every stream and host thread that uses the library on it: a host with several streams
  * on one device learns THAT an id was bad and which, not on which stream; a call that finds a record consumes it -- reports
  * of kernels still running on OTHER streams at that moment can be reported by this call or wiped by its clear.  Clients
@@ -482,6 +482,52 @@ int nhip_features_pack_dev(const float *d_xy, const float *d_normals, const int3
                            const int32_t *d_idx, const int32_t *d_count, int32_t cap, float *d_xy_out,
                            float *d_normals_out, int32_t *d_offsets_out, void *stream);
 
+/* Scan normals: NormalComputation::GetNormals (src/input/normal_computation.{h,cc}) of every scan at once -- the one input
+ * of the correspondence search, the normal residual and the feature clouds that a real bag does not bring.  The randomised
+ * Hough estimate of the reference, stated deterministically (the spec, and every departure from the reference: DESIGN.md
+ * section 3, "Scan normals").  Per point i (scan-local index) of a scan:
+ *   neighbours  the points j of the same scan, i included, in scan order, with sqrtf(dx * dx + dy * dy) < (float)r (float
+ *               operations rounded one by one, strict); r = neighborhood_size, and while there are fewer than two and fewer
+ *               than max_growth_steps growths were made, r += neighborhood_step_size (double) and the list is rebuilt.  Still
+ *               fewer than two: the normal is (0, 0).  A non-finite point has no neighbours and is nobody's.
+ *   samples     limit = min(m (m - 1), (size_t)(1 / (2.0 * mean_distance * mean_distance))) ordered pairs (a, b) of neighbour
+ *               ranks, m the neighbour count; redrawn while a == b or the pair was taken.  The generator is counter based and
+ *               keyed on (seed, i) alone: h(x) = lowbias32 (x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15, x *= 0x846ca68b,
+ *               x ^= x >> 16), s0 = h(seed ^ h(i)), draw k = h(s0 + k), k = 0, 1, ... (a, then b, two per attempt), rank =
+ *               ((uint64_t)draw * m) >> 32.  A scan's normals do not depend on where it sits in a batch.
+ *   vote        n = (-dy, dx) / sqrtf(dx * dx + dy * dy) of p_b - p_a in float, negated if n.y < 0 or (n.y == 0 and n.x < 0);
+ *               angle = acos(clamp((double)n.x, -1, 1)); bin = floor(angle / (2 pi / bin_number) + 0.5).  A pair of zero (or
+ *               not finite) length casts no vote but counts as a sample.  The two leading bins follow
+ *               CircularHoughAccumulator::AddVote.
+ *   stop        after a vote, if votes(most) / B - votes(second) / B >= 2.0 * sqrt(1.0 / B), B = bin_number, the quotients
+ *               INTEGER divisions (BinMean); otherwise the sample is counted, up to limit.
+ *   result      a = (sum of the winning bin's angles in vote order) / votes(most) in double; ((float)cos(a), (float)sin(a));
+ *               no vote at all: (0, 0).
+ * Accepted ranges: the three lengths finite and > 0, bin_number 2..NHIP_NORMALS_MAX_BINS, the sample limit's second term
+ * 1..NHIP_NORMALS_MAX_SAMPLES, max_growth_steps 0..1024, n_scans >= 0; anything else is NHIP_ERR_ARG before anything is
+ * launched, with or without a device. */
+#define NHIP_NORMALS_MAX_BINS 64
+#define NHIP_NORMALS_MAX_SAMPLES 128
+typedef struct nhip_normals_spec {
+  double neighborhood_size;      /* starting radius [m] (nc_neighborhood_size, 0.15) */
+  double neighborhood_step_size; /* radius growth per step [m] (nc_neighborhood_step_size, 0.1) */
+  double mean_distance;          /* sets the sample limit (nc_mean_distance, 0.1: 49 samples) */
+  int32_t bin_number;            /* Hough bins around the circle (nc_bin_number, 32) */
+  int32_t max_growth_steps;      /* cap on the radius growth (32) */
+  uint32_t seed;                 /* of the generator (1) */
+  int32_t flags;                 /* 0 */
+} nhip_normals_spec_t;
+/* config/default_config.lua's nc_* values, as listed above; pure host */
+int nhip_normals_spec_default(nhip_normals_spec_t *out);
+/* d_xy, d_offsets: the scans as everywhere (d_offsets: n_scans + 1 entries); scans of any length, empty ones included.
+ * d_normals: 2 floats per point of d_xy.  d_info (may be NULL): 4 int32 per point -- {neighbour count, growth steps made,
+ * winning bin (-1: none), votes in it | samples counted << 16}.  The offsets are read by the kernels: a scan whose first
+ * offset is negative or whose end lies before its start is treated as empty -- nothing is written for it -- and
+ * nhip_dev_status() reports it (kind 256).  Scans of at most NHIP_SHORT_SCAN_POINTS points and specs whose sample limit is
+ * at most 64 take the fast form; everything else a slow one with the same results. */
+int nhip_normals_estimate_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const nhip_normals_spec_t *spec,
+                              float *d_normals, int32_t *d_info, void *stream);
+
 /* HITL point selection: GetRelevantPosesForHITL (solver.cc:479-513) for every scan at once.  A point p of scan s goes to
  * the world as w = (c px - s py + tx, s px + c py + ty) with (c, s, tx, ty) = d_pose_f32[4s ..], the entries of
  * PoseArrayToAffine(pose).cast<float>() (nhip_pose_affines forms them), every operation a float operation rounded on its
@@ -560,6 +606,10 @@ int nhip_lc_chi_square_gate(const double *poses, int32_t n_poses, const int32_t 
 /* nhip_features_extract_dev on uploaded scans; host outputs of the same shapes (scores: n_points doubles, may be NULL). */
 int nhip_features_extract(const nhip_scans_t *scans, const nhip_feature_spec_t *spec, int32_t *planar_idx,
                           int32_t *planar_count, int32_t *edge_idx, int32_t *edge_count, double *scores);
+
+/* nhip_normals_estimate_dev on uploaded scans; host outputs (normals: 2 floats per point; info: 4 int32 per point, may be
+ * NULL). */
+int nhip_normals_estimate(const nhip_scans_t *scans, const nhip_normals_spec_t *spec, float *normals, int32_t *info);
 
 /* The reference-shaped single-pair call: CorrelativeScanMatcher(scanner_range, trans_range, low_res, high_res)
  * .GetTransformation(pc_a, pc_b, rot_a, rot_b, rot_restriction) -> (score, ((tx, ty), theta))

@@ -16,6 +16,7 @@ NHIP_LIDAR_NORMAL, NHIP_LIDAR_POINT = 0, 1
 NHIP_SEARCH_EXHAUSTIVE, NHIP_SEARCH_DENSE, NHIP_SEARCH_SHORT_SCANS, NHIP_SEARCH_EXACT_SCORE, NHIP_SEARCH_LATENCY = 1, 2, 4, 8, 16
 NHIP_SHORT_SCAN_POINTS = 1088
 NHIP_FEATURE_MAX = 64
+NHIP_NORMALS_MAX_BINS, NHIP_NORMALS_MAX_SAMPLES = 64, 128
 NHIP_GRID_SKIP_MAP, NHIP_GRID_NO_IMAGE = 1, 2
 NHIP_TIMER_CSM, NHIP_TIMER_GRID, NHIP_TIMER_RESID, NHIP_TIMER_CORR, NHIP_TIMER_NORMEQ, NHIP_TIMER_GRID_CLEAR = 0, 1, 2, 3, 4, 5
 NHIP_TIMER_CSM_BOUNDS, NHIP_TIMER_CSM_CAND, NHIP_TIMER_EXACT_SCORE = 6, 7, 8
@@ -58,6 +59,11 @@ class FeatureSpec(C.Structure):
     _fields_ = [("threshold", C.c_double), ("distance_threshold", C.c_double), ("max_neighbor_distance", C.c_double),
                 ("neighbors_per_side", C.c_int32), ("min_neighbors", C.c_int32), ("max_planar", C.c_int32),
                 ("max_edge", C.c_int32)]
+
+
+class NormalsSpec(C.Structure):
+    _fields_ = [("neighborhood_size", C.c_double), ("neighborhood_step_size", C.c_double), ("mean_distance", C.c_double),
+                ("bin_number", C.c_int32), ("max_growth_steps", C.c_int32), ("seed", C.c_uint32), ("flags", C.c_int32)]
 
 
 class HitlSpec(C.Structure):
@@ -144,6 +150,9 @@ PROTOTYPES = {
     "nhip_feature_spec_default": (C.c_int, [_P(FeatureSpec)]),
     "nhip_features_extract_dev": (C.c_int, [_vp, _vp, _i32, _P(FeatureSpec), _vp, _vp, _vp, _vp, _vp, _vp]),
     "nhip_features_pack_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "nhip_normals_spec_default": (C.c_int, [_P(NormalsSpec)]),
+    "nhip_normals_estimate_dev": (C.c_int, [_vp, _vp, _i32, _P(NormalsSpec), _vp, _vp, _vp]),
+    "nhip_normals_estimate": (C.c_int, [_vp, _P(NormalsSpec), _vp, _vp]),
     "nhip_hitl_spec_default": (C.c_int, [_P(HitlSpec)]),
     "nhip_hitl_select_dev": (C.c_int, [_vp, _vp, _i32, _vp, _P(HitlSpec), _vp, _vp, _vp, _vp, _vp, _vp]),
     "nhip_hitl_pack_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),

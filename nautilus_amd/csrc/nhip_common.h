@@ -52,7 +52,7 @@ struct IdBounds {          // (plain data: it travels inside the kernels' parame
   uint32_t *status;        // the device's status words, or null (ids are still checked, nothing is reported)
 };
 constexpr uint32_t BAD_TARGET_ID = 1u, BAD_PAIR_SRC = 2u, BAD_PAIR_SLOT = 4u, BAD_BLOCK_ID = 8u, BAD_POSE_ID = 16u,
-                   BAD_SCAN_ID = 32u, BAD_FEATURE_IDX = 64u, BAD_FEATURE_COUNT = 128u;
+                   BAD_SCAN_ID = 32u, BAD_FEATURE_IDX = 64u, BAD_FEATURE_COUNT = 128u, BAD_SCAN_OFFSETS = 256u;
 constexpr int DEV_STATUS_WORDS = 4;  // {OR of the kinds seen, kind / value / index of the first report}
 uint32_t *dev_status();              // of the current device (allocated on the device's first use; null if that failed)
 #ifdef __HIPCC__
@@ -330,6 +330,11 @@ int launch_feat_extract(const float *d_xy, const int32_t *d_offsets, int32_t n_s
 int launch_feat_pack(const float *d_xy, const float *d_normals, const int32_t *d_offsets, int32_t n_scans, const int32_t *d_idx,
                      const int32_t *d_count, int32_t cap, float *d_xy_out, float *d_normals_out, int32_t *d_offsets_out,
                      hipStream_t s);
+
+// scan normals (nhip_normals.hip); the spec has passed normals_spec_check (nhip_host_normals.hip), which also gives the
+// sample limit's second term
+int launch_normals_estimate(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const nhip_normals_spec_t &spec,
+                            int32_t sample_limit, float *d_normals, int32_t *d_info, hipStream_t s);
 
 int launch_resid_point_to_line(const float *d_segments, const float *d_points,
                                const int32_t *d_point_block, int64_t n_points,

@@ -91,6 +91,11 @@ class HipBackend:
         from . import features
         return features.extract(xy, offsets, spec, device=str(self.dev)).clouds(xy, normals, offsets)
 
+    def normals(self, xy, offsets, spec=None):
+        """The normals of every point of the packed scans, estimated on the GPU (normals.estimate): float32 (n, 2)."""
+        from . import normals
+        return normals.estimate(xy, offsets, spec, device=str(self.dev))
+
     def reserve_icp(self, offsets, window):
         """Work buffers for the largest problem of a growing-window solve (all (i, j), j in [i - window, i)): allocated once."""
         off = np.asarray(offsets, dtype=np.int64)
