@@ -14,6 +14,7 @@ and reports trajectory error and wall-clock per stage.  Every evaluation goes th
 the product's HipBackend by default; tests and bench.py's cpu_baseline inject the oracle's CPU backend to time the
 same loop on the CPU restatement."""
 import argparse
+import inspect
 import json
 import math
 import os
@@ -48,9 +49,12 @@ def synthetic_hitl_message(bag, poses, early, late):
     return {"line_a_start": a[0], "line_a_end": a[1], "line_b_start": b[0], "line_b_end": b[1]}
 
 
+LC_MIN_SEPARATION = 20  # nodes between the two scans of a loop-closure pair (the pair gate below)
+
+
 def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, verbose=False, residual="normal",
         rank=0, world=1, device="cuda:0", backend=None, iterations=4, hitl=True, cell_bits=16, gate="scatter",
-        min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False, normals="bag"):
+        min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False, normals="bag", lc_submap=0):
     """min_scatter_score: LCCandidateFilter's threshold is 0.70 (lc_candidate_filter.cc:76); scans of the synthetic
     24 m x 16 m room score ~0.4, so callers on that world pass a lower one.
     hitl_device: the HITL constraint's points are selected and packed on the GPU (hitl.select, under the "path" clock) and
@@ -58,6 +62,11 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     normals: "bag" takes the synthetic world's analytic normals; "device" estimates them from the clouds on the GPU
     (backend.normals: NormalComputation::GetNormals, once, before the first solve, under the "path" clock) -- what a real
     bag, which brings none, needs.
+    lc_submap K > 0: every loop-closure target's table is built from its SUBMAP, the scans t - K .. t + K placed in t's frame
+    by the current estimate (the poses after the window solve), instead of from scan t alone ("Submaps").
+    A backend whose match() takes submap_radius merges the clouds on the device; any other gets the merged clouds as extra
+    scans (hostside.submap_extra_scans).  K must stay below the pair gate's minimum separation (20): a source is never in
+    its target's submap.  Not with world > 1.
     With world > 1 (one process per GPU under torch.distributed): the window ICP solve is replicated -- its
     consumer, the solver, is host-side -- and the loop-closure pairs are sharded by target across the ranks,
     matched, and all-gathered (nautilus_amd/sharding.py); every rank ends with the same trajectory."""
@@ -74,6 +83,12 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         raise ValueError("run: residual %r" % (residual,))
     if normals not in ("bag", "device"):
         raise ValueError("run: normals %r" % (normals,))
+    lc_submap = int(lc_submap)
+    if not 0 <= lc_submap < LC_MIN_SEPARATION:
+        raise ValueError("run: lc_submap %d: a submap radius is >= 0 and below the pair gate's minimum separation (%d)"
+                         % (lc_submap, LC_MIN_SEPARATION))
+    if lc_submap and world > 1:
+        raise ValueError("run: lc_submap with world > 1 (sharded matching has no submaps)")
     out = {"backend": backend.name, "n_scans": n_scans, "window": window, "residual": residual,
            "err_odometry_m": posegraph.trajectory_error(odom, bag.truth)}
     posegraph.clock_reset()
@@ -112,12 +127,12 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         # ... then the pair gate: |dt| < lc_base_max_range (3.5 m, default_config.lua:122) on the current estimate and
         # more than 20 nodes apart (geometric stand-in for LCMatcher's per-pair ceres::Covariance, lc_matcher.cc:28-74)
         with posegraph.clocked("path"):
-            src, tgt = hostside.geometric_pair_gate(poses, cand, max_range=3.5, min_separation=20, backend=backend)
+            src, tgt = hostside.geometric_pair_gate(poses, cand, max_range=3.5, min_separation=LC_MIN_SEPARATION, backend=backend)
         out["lc_candidate_scans"] = len(cand)
     else:
         idx = np.arange(n_scans)
         d = np.linalg.norm(poses[:, None, :2] - poses[None, :, :2], axis=2)
-        s_, t_ = np.nonzero((d < 3.5) & (np.abs(idx[:, None] - idx[None, :]) > 20))
+        s_, t_ = np.nonzero((d < 3.5) & (np.abs(idx[:, None] - idx[None, :]) > LC_MIN_SEPARATION))
         keep = s_ > t_
         src, tgt = s_[keep].astype(np.int32), t_[keep].astype(np.int32)
     out["t_gate_s"] = time.perf_counter() - t0
@@ -138,6 +153,14 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
             with posegraph.clocked("path"):
                 m = sharding.distributed_match(match_shard, src, tgt, theta0, rank, world, device=device)
             spec, search = csm.grid_spec(30.0, 0.05, 2.0, 1e-10, 40, cell_bits), csm.search_spec()
+        elif lc_submap and "submap_radius" in inspect.signature(backend.match).parameters:
+            with posegraph.clocked("path"):
+                m, spec, search = backend.match(xy, off, src, tgt, theta0, cell_bits, submap_radius=lc_submap, poses=poses)
+        elif lc_submap:
+            with posegraph.clocked("marshal"):
+                xy_m, off_m, tgt_m = hostside.submap_extra_scans(xy, off, poses, tgt, lc_submap)
+            with posegraph.clocked("path"):
+                m, spec, search = backend.match(xy_m, off_m, src, tgt_m, theta0, cell_bits)
         else:
             with posegraph.clocked("path"):
                 m, spec, search = backend.match(xy, off, src, tgt, theta0, cell_bits)
@@ -205,6 +228,7 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     out["host_assembly_s"] = posegraph.CLOCK["assemble"]
     out["hitl_select_s"] = posegraph.CLOCK["hitl_select"]
     out["hitl_device"] = bool(hitl_device)
+    out["lc_submap"] = lc_submap
     out["harness_s"] = out["host_other_s"] - out["marshal_s"] - out["host_assembly_s"] - out["hitl_select_s"]
     return out
 
@@ -221,8 +245,14 @@ if __name__ == "__main__":
                     help="select the HITL constraint's points and reduce its blocks to normal equations on the GPU")
     ap.add_argument("--normals", choices=["bag", "device"], default="bag",
                     help="the synthetic bag's analytic normals, or normals estimated from the clouds on the GPU")
+    ap.add_argument("--lc-submap", type=int, default=0, metavar="K",
+                    help="build every loop-closure target's table from the scans t-K .. t+K under the current estimate "
+                         "(0: from scan t alone); below %d, the pair gate's minimum separation" % LC_MIN_SEPARATION)
     ap.add_argument("-v", action="store_true")
     a = ap.parse_args()
+    if not 0 <= a.lc_submap < LC_MIN_SEPARATION:
+        ap.error("--lc-submap %d: the radius must be in [0, %d): a source must never be in its target's submap"
+                 % (a.lc_submap, LC_MIN_SEPARATION))
     rank, world, local = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), \
         int(os.environ.get("LOCAL_RANK", "0"))
     if "RANK" in os.environ:  # python -m torch.distributed.run --nproc-per-node N examples/slam_loop.py ...
@@ -237,7 +267,7 @@ if __name__ == "__main__":
         dist.barrier()
         os.dup2(saved, 1)
     res = run(a.scans, a.window, verbose=a.v and rank == 0, residual=a.residual, rank=rank, world=world,
-              device="cuda:%d" % local, hitl_device=a.hitl_device, normals=a.normals)
+              device="cuda:%d" % local, hitl_device=a.hitl_device, normals=a.normals, lc_submap=a.lc_submap)
     res["world_size"] = world
     if rank == 0:
         print(json.dumps(res))

@@ -63,7 +63,8 @@ const char *nhip_version(void);
  * nhip_last_error().  info (may be NULL): {OR of the kinds seen, kind, value, index of the first one reported}; kinds:
  * 1 target scan id of a grid build, 2 source scan id of a pair, 4 grid slot of a pair, 8 block id of a correspondence,
  * 16 pose index of a block, 32 scan id of a correspondence-search block, 64 feature index and 128 feature count of
- * nhip_features_pack_dev, 256 scan offset of nhip_normals_estimate_dev.  Clears the record (in the order of `stream`).
+ * nhip_features_pack_dev, 256 scan offset of nhip_normals_estimate_dev, 512 member scan id and 1024 merged point count beyond
+ * the capacity of nhip_submaps_gather_dev.  Clears the record (in the order of `stream`).
  * ONE record per DEVICE, shared by every stream and host thread that uses the library on it: a host with several streams
  * on one device learns THAT an id was bad and which, not on which stream; a call that finds a record consumes it -- reports
  * of kernels still running on OTHER streams at that moment can be reported by this call or wiped by its clear.  Clients
@@ -274,6 +275,32 @@ int nhip_grid_build_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_s
 int nhip_grid_rebuild_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const int32_t *d_target_ids,
                           int32_t n_targets, const nhip_grid_spec_t *spec, uint8_t *d_grids,
                           void *d_workspace, int64_t workspace_bytes, void *stream);
+
+/* K10: SUBMAPS -- the target cloud of a table built from several neighbouring scans instead of one (DESIGN.md section 3,
+ * "Submaps").  Target t has the members member_scan[member_offsets[t] .. member_offsets[t + 1]); member m has four floats
+ * (c, s, tx, ty) at member_affine + 4m, its frame in the target's anchor frame.  A member point (x, y) becomes
+ *   x' = ((c x) + ((-s) y)) + tx,   y' = ((s x) + (c y)) + ty
+ * in float, every operation rounded on its own; the merged cloud of a target is its members' points in member order, then
+ * point order.  Nothing is dropped or deduplicated, non-finite points stay non-finite, points outside the grid are left to
+ * the table build.
+ *
+ * nhip_submap_member_affines: pure host (works without a GPU).  Member m's affine from the poses (x, y, theta: 3 doubles
+ * each) of its anchor anchor_of_member[m] and of its scan member_scan[m], both indices into `poses`: the entries of
+ * inverse(A(anchor)) * A(member) in double, A as PoseArrayToAffine (slam_util.h:20-28) and the inverse the rigid one,
+ *   c = ca cm + sa sm,  s = ca sm - sa cm,  tx = ca dx + sa dy,  ty = ca dy - sa dx   (dx, dy = member - anchor translation),
+ * each rounded to float.  An index outside [0, n_poses) is NHIP_ERR_ARG and nothing is written. */
+int nhip_submap_member_affines(const double *poses, int32_t n_poses, const int32_t *anchor_of_member, const int32_t *member_scan,
+                               int32_t n_members, float *out /* 4 per member */);
+/* The merged clouds of n_targets submaps, on the caller's buffers and stream; never allocates.  Outputs: d_out_offsets
+ * (n_targets + 1 prefix offsets, in points) and d_out_xy (the packed cloud, room for out_capacity points): exactly what
+ * nhip_grid_build_dev / nhip_grid_rebuild_dev take as (d_xy, d_offsets, n_scans = n_targets) with target ids 0 .. n_targets - 1.
+ * d_member_offsets (n_targets + 1, non-decreasing, the caller's like d_offsets) and d_member_scan live in device memory: a
+ * member id outside [0, n_scans) is an EMPTY member -- never dereferenced -- and nhip_dev_status() reports it (kind 512).
+ * If the merged clouds hold more than out_capacity points (or more than 2^31 - 1) NOTHING is stored in d_out_xy, every entry
+ * of d_out_offsets is 0 (every target empty) and nhip_dev_status() reports it (kind 1024, value: the points needed). */
+int nhip_submaps_gather_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const int32_t *d_member_scan,
+                            const float *d_member_affine, const int32_t *d_member_offsets, int32_t n_targets, float *d_out_xy,
+                            int64_t out_capacity, int32_t *d_out_offsets, void *stream);
 
 /* K2+K3: exhaustive (theta, x, y) correlation + argmax for n_pairs candidate pairs.
  * Pair i matches scan d_pair_src[i] (of the n_scans behind d_offsets) against grid slot d_pair_slot[i] (of the n_grids in
@@ -575,6 +602,13 @@ int nhip_scans_free(nhip_scans_t *scans);
 
 int nhip_grids_build(const nhip_scans_t *scans, const int32_t *target_ids, int32_t n_targets,
                      const nhip_grid_spec_t *spec, nhip_grids_t **out);
+/* Tables of n_targets SUBMAPS of the uploaded scans (see nhip_submaps_gather_dev): slot t is the table of target t's merged
+ * cloud, gathered on the device.  member_scan, member_affine (4 floats per member) and member_offsets (n_targets + 1) are
+ * HOST arrays; a member id outside the scans or offsets that are not a prefix from 0 are NHIP_ERR_ARG.  The grids work with
+ * nhip_csm_match, nhip_csm_match_gated, nhip_csm_scores and the downloads exactly as those of nhip_grids_build do. */
+int nhip_grids_build_submaps(const nhip_scans_t *scans, const int32_t *member_scan, const float *member_affine,
+                             const int32_t *member_offsets, int32_t n_targets, const nhip_grid_spec_t *spec,
+                             nhip_grids_t **out);
 int nhip_grids_free(nhip_grids_t *grids);
 /* copy stored (padded) grid `slot` to host: layout.grid_bytes bytes (uint8 or uint16 cells) */
 int nhip_grids_download(const nhip_grids_t *grids, int32_t slot, uint8_t *out);

@@ -105,6 +105,9 @@ PROTOTYPES = {
                                      _P(Search), _vp, _vp, _vp, _vp, _i64, _vp]),
     "nhip_csm_match_gated_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(GridSpec), _vp, _vp, _vp, _vp, _vp, _i32,
                                            _P(Search), _vp, _vp, _vp, _vp, _i64, _vp, _f64]),
+    "nhip_submap_member_affines": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp]),
+    "nhip_submaps_gather_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp]),
+    "nhip_grids_build_submaps": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _P(GridSpec), _P(_vp)]),
     "nhip_csm_workspace_bytes": (_i64, [_i32]),
     "nhip_csm_last_launch": (C.c_int, [_P(_i32)]),
     "nhip_csm_get_transformation_info": (C.c_int, [_vp]),

@@ -112,6 +112,28 @@ class LikelihoodGrids:
         check(_lib.load().nhip_grids_build(scans._h, ptr(self.target_ids), self.target_ids.size,
                                            C.byref(spec), C.byref(self._h)))
 
+    @classmethod
+    def from_submaps(cls, scans, member_scan, member_affine, member_offsets, spec):
+        """Tables of SUBMAPS of the uploaded scans (nhip_grids_build_submaps; DESIGN.md section 3, "Submaps"): slot t is built
+        from the merged cloud of members member_scan[member_offsets[t]:member_offsets[t + 1]], each moved into the target's
+        anchor frame by its (c, s, tx, ty) of member_affine -- gathered on the device.  hostside.submap_members gives the
+        index-window membership, submap_member_affines the affines from poses.  Everything a LikelihoodGrids does works on
+        the result; target_ids is 0 .. n_targets - 1."""
+        self = cls.__new__(cls)
+        self.spec = spec
+        self.layout = grid_layout(spec)
+        self.member_scan = np.ascontiguousarray(member_scan, dtype=np.int32)
+        self.member_affine = np.ascontiguousarray(member_affine, dtype=np.float32).reshape(-1, 4)
+        self.member_offsets = np.ascontiguousarray(member_offsets, dtype=np.int32)
+        if self.member_offsets.size < 1 or len(self.member_affine) != self.member_scan.size:
+            raise ValueError("from_submaps: one affine per member, n_targets + 1 offsets")
+        self.target_ids = np.arange(self.member_offsets.size - 1, dtype=np.int32)
+        self._h = C.c_void_p()
+        check(_lib.load().nhip_grids_build_submaps(scans._h, ptr(self.member_scan), ptr(self.member_affine),
+                                                   ptr(self.member_offsets), self.target_ids.size, C.byref(spec),
+                                                   C.byref(self._h)))
+        return self
+
     def was_rebuilt(self):
         """True when the tables were rebuilt into the buffers a released handle of the same shape left in the library's
         device pool (nhip_grids_was_rebuilt): only what that build wrote was cleared, nothing was zero-filled."""
@@ -181,6 +203,19 @@ class LikelihoodGrids:
             self._h = C.c_void_p()
 
     __del__ = close
+
+
+def submap_member_affines(poses, anchor_of_member, member_scan):
+    """(n_members, 4) float32 (c, s, tx, ty): each member's frame in its anchor's, from the poses (n, 3) of both
+    (nhip_submap_member_affines; pure host)."""
+    P = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    a = np.ascontiguousarray(anchor_of_member, dtype=np.int32)
+    m = np.ascontiguousarray(member_scan, dtype=np.int32)
+    if a.size != m.size:
+        raise ValueError("submap_member_affines: one anchor per member")
+    out = np.empty((m.size, 4), dtype=np.float32)
+    check(_lib.load().nhip_submap_member_affines(ptr(P), len(P), ptr(a), ptr(m), m.size, ptr(out)))
+    return out
 
 
 def match_pairs(scans, grids, pair_src, pair_slot, theta0, search, pair_origin=None, min_score=None):

@@ -52,7 +52,8 @@ struct IdBounds {          // (plain data: it travels inside the kernels' parame
   uint32_t *status;        // the device's status words, or null (ids are still checked, nothing is reported)
 };
 constexpr uint32_t BAD_TARGET_ID = 1u, BAD_PAIR_SRC = 2u, BAD_PAIR_SLOT = 4u, BAD_BLOCK_ID = 8u, BAD_POSE_ID = 16u,
-                   BAD_SCAN_ID = 32u, BAD_FEATURE_IDX = 64u, BAD_FEATURE_COUNT = 128u, BAD_SCAN_OFFSETS = 256u;
+                   BAD_SCAN_ID = 32u, BAD_FEATURE_IDX = 64u, BAD_FEATURE_COUNT = 128u, BAD_SCAN_OFFSETS = 256u,
+                   BAD_MEMBER_ID = 512u, BAD_SUBMAP_CAPACITY = 1024u;
 constexpr int DEV_STATUS_WORDS = 4;  // {OR of the kinds seen, kind / value / index of the first report}
 uint32_t *dev_status();              // of the current device (allocated on the device's first use; null if that failed)
 #ifdef __HIPCC__
@@ -330,6 +331,11 @@ int launch_feat_extract(const float *d_xy, const int32_t *d_offsets, int32_t n_s
 int launch_feat_pack(const float *d_xy, const float *d_normals, const int32_t *d_offsets, int32_t n_scans, const int32_t *d_idx,
                      const int32_t *d_count, int32_t cap, float *d_xy_out, float *d_normals_out, int32_t *d_offsets_out,
                      hipStream_t s);
+
+// submap clouds (nhip_submap.hip): the offsets kernel, then the gather; stores nothing past out_capacity points
+int launch_submap_gather(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const int32_t *d_member_scan,
+                         const float *d_member_affine, const int32_t *d_member_offsets, int32_t n_targets, float *d_out_xy,
+                         int64_t out_capacity, int32_t *d_out_offsets, hipStream_t s);
 
 // scan normals (nhip_normals.hip); the spec has passed normals_spec_check (nhip_host_normals.hip), which also gives the
 // sample limit's second term

@@ -66,6 +66,42 @@ int nhip_grid_rebuild_dev(const float *d_xy, const int32_t *d_offsets, int32_t n
   return grid_build_dev("grid_rebuild_dev", true, d_xy, d_offsets, n_scans, d_target_ids, n_targets, spec, d_grids, d_workspace, workspace_bytes, stream);
 }
 
+int nhip_submap_member_affines(const double *poses, int32_t n_poses, const int32_t *anchor_of_member, const int32_t *member_scan,
+                               int32_t n_members, float *out) {
+  NHIP_REQUIRE(n_poses >= 0 && n_members >= 0, "submap_member_affines: negative count");
+  NHIP_REQUIRE(n_members == 0 || (poses && anchor_of_member && member_scan && out), "submap_member_affines: null pointer");
+  for (int32_t m = 0; m < n_members; m++)
+    NHIP_REQUIRE(anchor_of_member[m] >= 0 && anchor_of_member[m] < n_poses && member_scan[m] >= 0 && member_scan[m] < n_poses,
+                 "submap_member_affines: member %d: anchor %d / scan %d outside the %d poses", m, anchor_of_member[m],
+                 member_scan[m], n_poses);
+  for (int32_t m = 0; m < n_members; m++) {
+    // entries of inverse(A(anchor)) * A(member) in double (A: PoseArrayToAffine, slam_util.h:20-28; the rigid inverse), then
+    // the cast of TransformPointcloud (slam_util.h:55-63).  Compiled without contraction: products and sums round singly.
+    const double *a = poses + 3 * (size_t)anchor_of_member[m], *b = poses + 3 * (size_t)member_scan[m];
+    const double ca = cos(a[2]), sa = sin(a[2]), cm = cos(b[2]), sm = sin(b[2]);
+    const double dx = b[0] - a[0], dy = b[1] - a[1];
+    out[4 * (size_t)m + 0] = (float)(ca * cm + sa * sm);
+    out[4 * (size_t)m + 1] = (float)(ca * sm - sa * cm);
+    out[4 * (size_t)m + 2] = (float)(ca * dx + sa * dy);
+    out[4 * (size_t)m + 3] = (float)(ca * dy - sa * dx);
+  }
+  return NHIP_OK;
+}
+
+int nhip_submaps_gather_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const int32_t *d_member_scan,
+                            const float *d_member_affine, const int32_t *d_member_offsets, int32_t n_targets, float *d_out_xy,
+                            int64_t out_capacity, int32_t *d_out_offsets, void *stream) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(d_offsets && d_member_offsets && d_out_offsets && (d_member_scan || n_targets == 0), "submaps_gather_dev: null pointer");
+  NHIP_REQUIRE(n_targets >= 0 && n_scans >= 0 && out_capacity >= 0, "submaps_gather_dev: n_targets %d / n_scans %d / out_capacity %lld < 0",
+               n_targets, n_scans, (long long)out_capacity);
+  // (without room nothing reads the points or the affines: a caller that only wants the error may pass null for them)
+  NHIP_REQUIRE(out_capacity == 0 || (d_xy && d_member_affine && d_out_xy), "submaps_gather_dev: null pointer");
+  return launch_submap_gather(d_xy, d_offsets, n_scans, d_member_scan, d_member_affine, d_member_offsets, n_targets, d_out_xy,
+                              out_capacity, d_out_offsets, static_cast<hipStream_t>(stream));
+}
+
 int nhip_csm_match_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const uint8_t *d_grids,
                        int32_t n_grids, const nhip_grid_spec_t *spec, const int32_t *d_pair_src,
                        const int32_t *d_pair_slot, const double *d_rot0_cs,
@@ -195,17 +231,12 @@ int nhip_scans_free(nhip_scans_t *scans) {
   return NHIP_OK;
 }
 
-int nhip_grids_build(const nhip_scans_t *scans, const int32_t *target_ids, int32_t n_targets,
-                     const nhip_grid_spec_t *spec, nhip_grids_t **out) {
-  int rc = require_device();
-  if (rc) return rc;
-  NHIP_REQUIRE(scans && out && n_targets >= 0 && (target_ids || n_targets == 0), "grids_build: bad arguments");
-  phases_reset();
-  for (int32_t i = 0; i < n_targets; i++)
-    NHIP_REQUIRE(target_ids[i] >= 0 && target_ids[i] < scans->n_scans,
-                 "grids_build: target id %d out of range", target_ids[i]);
+// the handle builds: the tables of scans `target_ids` (checked by the caller) of the device cloud (d_xy, d_offsets), after
+// whatever the caller enqueued on the null stream; returns with the device idle
+static int grids_build_on(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const int32_t *target_ids,
+                          int32_t n_targets, const nhip_grid_spec_t *spec, nhip_grids_t **out) {
   GridLayout L;
-  rc = make_layout(spec, &L);
+  int rc = make_layout(spec, &L);
   if (rc) return rc;
   nhip_grids *g = new nhip_grids();
   g->spec = *spec;
@@ -251,9 +282,8 @@ int nhip_grids_build(const nhip_scans_t *scans, const int32_t *target_ids, int32
     InFlight inflight;
     {
       PhaseClock pc(PH_ENQUEUE);
-      rc = launch_grid_build(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), scans->n_scans,
-                             ids.as<const int32_t>(), n_targets, spec, L, g->grids.as<uint8_t>(), ws.p, ws_bytes, nullptr,
-                             g->rebuilt);
+      rc = launch_grid_build(d_xy, d_offsets, n_scans, ids.as<const int32_t>(), n_targets, spec, L, g->grids.as<uint8_t>(), ws.p,
+                             ws_bytes, nullptr, g->rebuilt);
     }
     if (rc == NHIP_OK) {
       PhaseClock pc(PH_WAIT);
@@ -268,6 +298,76 @@ int nhip_grids_build(const nhip_scans_t *scans, const int32_t *target_ids, int32
     }
   }
   *out = g;
+  return NHIP_OK;
+}
+
+int nhip_grids_build(const nhip_scans_t *scans, const int32_t *target_ids, int32_t n_targets,
+                     const nhip_grid_spec_t *spec, nhip_grids_t **out) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(scans && out && n_targets >= 0 && (target_ids || n_targets == 0), "grids_build: bad arguments");
+  phases_reset();
+  for (int32_t i = 0; i < n_targets; i++)
+    NHIP_REQUIRE(target_ids[i] >= 0 && target_ids[i] < scans->n_scans,
+                 "grids_build: target id %d out of range", target_ids[i]);
+  return grids_build_on(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), scans->n_scans, target_ids, n_targets,
+                        spec, out);
+}
+
+int nhip_grids_build_submaps(const nhip_scans_t *scans, const int32_t *member_scan, const float *member_affine,
+                             const int32_t *member_offsets, int32_t n_targets, const nhip_grid_spec_t *spec,
+                             nhip_grids_t **out) {
+  int rc = require_device();
+  if (rc) return rc;
+  NHIP_REQUIRE(scans && out && n_targets >= 0 && member_offsets, "grids_build_submaps: bad arguments");
+  phases_reset();
+  NHIP_REQUIRE(member_offsets[0] == 0, "grids_build_submaps: member_offsets[0] must be 0");
+  for (int32_t t = 0; t < n_targets; t++)
+    NHIP_REQUIRE(member_offsets[t + 1] >= member_offsets[t], "grids_build_submaps: member_offsets not monotone at target %d", t);
+  const int32_t n_members = member_offsets[n_targets];
+  NHIP_REQUIRE(n_members == 0 || (member_scan && member_affine), "grids_build_submaps: null member array");
+  int64_t total = 0;  // points of all merged clouds: the host knows the scans' lengths
+  for (int32_t m = 0; m < n_members; m++) {
+    NHIP_REQUIRE(member_scan[m] >= 0 && member_scan[m] < scans->n_scans, "grids_build_submaps: member %d: scan id %d out of range",
+                 m, member_scan[m]);
+    total += scans->h_offsets[member_scan[m] + 1] - scans->h_offsets[member_scan[m]];
+  }
+  NHIP_REQUIRE(total <= 0x7fffffffll, "grids_build_submaps: the merged clouds hold %lld points; offsets are int32", (long long)total);
+  {
+    GridLayout L;  // (a bad spec fails before anything is allocated)
+    if ((rc = make_layout(spec, &L))) return rc;
+  }
+  DevBuf d_scan, d_aff, d_moff, d_xy, d_off;
+  if ((rc = d_scan.alloc(sizeof(int32_t) * (size_t)(n_members > 0 ? n_members : 1))) ||
+      (rc = d_aff.alloc(sizeof(float) * 4 * (size_t)(n_members > 0 ? n_members : 1))) ||
+      (rc = d_moff.alloc(sizeof(int32_t) * (size_t)(n_targets + 1))) ||
+      (rc = d_xy.alloc(sizeof(float) * 2 * (size_t)(total > 0 ? total : 1))) ||
+      (rc = d_off.alloc(sizeof(int32_t) * (size_t)(n_targets + 1))))
+    return rc;
+  {
+    PhaseClock pc(PH_UPLOAD);
+    if (n_members) {
+      NHIP_TRY_HIP(hipMemcpy(d_scan.p, member_scan, sizeof(int32_t) * (size_t)n_members, hipMemcpyHostToDevice));
+      NHIP_TRY_HIP(hipMemcpy(d_aff.p, member_affine, sizeof(float) * 4 * (size_t)n_members, hipMemcpyHostToDevice));
+    }
+    NHIP_TRY_HIP(hipMemcpy(d_moff.p, member_offsets, sizeof(int32_t) * (size_t)(n_targets + 1), hipMemcpyHostToDevice));
+  }
+  std::vector<int32_t> ids((size_t)n_targets);
+  for (int32_t t = 0; t < n_targets; t++) ids[(size_t)t] = t;
+  InFlight inflight;  // (the buffers above outlive the gather: grids_build_on returns with the device idle; a failure waits)
+  {
+    PhaseClock pc(PH_ENQUEUE);
+    rc = launch_submap_gather(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), scans->n_scans,
+                              d_scan.as<const int32_t>(), d_aff.as<const float>(), d_moff.as<const int32_t>(), n_targets,
+                              d_xy.as<float>(), total, d_off.as<int32_t>(), nullptr);
+  }
+  if (rc) return rc;
+  rc = grids_build_on(d_xy.as<const float>(), d_off.as<const int32_t>(), n_targets, ids.data(), n_targets, spec, out);
+  if (rc) return rc;
+  if (n_targets == 0) {
+    NHIP_TRY_HIP(hipStreamSynchronize(nullptr));  // (nothing was built: the offsets kernel alone ran)
+    InFlight::done();
+  }
   return NHIP_OK;
 }
 

@@ -8,6 +8,8 @@ end-to-end test can be driven the way nautilus drives them.  Nothing here is on 
   map file   "x1,y1,x2,y2" per line       solver.cc:608-618
   HitlSlamInputMsg (two line segments)    msg/HitlSlamInputMsg.msg:1-4, solver.cc:467-478
 """
+import math
+
 import numpy as np
 
 
@@ -102,6 +104,80 @@ def lc_possible_matches(source, candidates, poses, covariance_fn, max_score=5000
         if chi_square_score(m, poses[source][:2], poses[c][:2]) < max_score:
             out.append(c)
     return out
+
+
+def submap_members(n_scans, targets, radius):
+    """The index-window membership of a submap ("Submaps"): target t's members are the scans
+    t - radius .. t + radius clipped to [0, n_scans), the anchor among them; radius 0 is one member per target.
+    Returns (member_scan int32, member_offsets int32 (len(targets) + 1))."""
+    radius = int(radius)
+    if radius < 0:
+        raise ValueError("submap_members: radius %d" % radius)
+    targets = np.asarray(targets, dtype=np.int64).reshape(-1)
+    if len(targets) and (targets.min() < 0 or targets.max() >= n_scans):
+        raise ValueError("submap_members: target outside the %d scans" % n_scans)
+    lo, hi = np.maximum(targets - radius, 0), np.minimum(targets + radius, n_scans - 1) + 1
+    member_offsets = np.concatenate([[0], np.cumsum(hi - lo)]).astype(np.int32)
+    member_scan = np.concatenate([np.arange(a, b) for a, b in zip(lo, hi)]) if len(targets) else np.zeros(0)
+    return member_scan.astype(np.int32), member_offsets
+
+
+def submap_member_affines(poses, anchor_of_member, member_scan):
+    """Each member's frame in its anchor's: the entries (c, s, tx, ty) of inverse(A(anchor)) * A(member) in double, A as
+    PoseArrayToAffine (slam_util.h:20-28), rounded to float32 (the cast of TransformPointcloud, slam_util.h:55-63) --
+    the numpy statement of nhip_submap_member_affines (held to it bit for bit in tests/)."""
+    P = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+    out = np.empty((len(member_scan), 4), dtype=np.float32)
+    for m, (a, b) in enumerate(zip(anchor_of_member, member_scan)):
+        ca, sa, cm, sm = math.cos(P[a, 2]), math.sin(P[a, 2]), math.cos(P[b, 2]), math.sin(P[b, 2])
+        dx, dy = float(P[b, 0]) - float(P[a, 0]), float(P[b, 1]) - float(P[a, 1])
+        out[m] = (ca * cm + sa * sm, ca * sm - sa * cm, ca * dx + sa * dy, ca * dy - sa * dx)
+    return out
+
+
+def submap_clouds(xy, offsets, member_scan, member_affine, member_offsets):
+    """The merged clouds of submaps, float32 as the spec has them ("Submaps"; the device form is
+    nhip_submaps_gather_dev): member points (x, y) -> (((c x) + ((-s) y)) + tx, ((s x) + (c y)) + ty), every operation
+    rounded to float32 on its own, in member order then point order; nothing dropped, a member id outside the scans is an
+    empty member.  Returns (xy (n, 2) float32, offsets int32 (n_targets + 1)).  Product code: a backend without a device
+    gather matches against these clouds passed as extra scans (examples/slam_loop.py --lc-submap)."""
+    f = np.float32
+    xy = np.asarray(xy, dtype=f).reshape(-1, 2)
+    off = np.asarray(offsets, dtype=np.int64)
+    member_scan, member_offsets = np.asarray(member_scan, dtype=np.int64), np.asarray(member_offsets, dtype=np.int64)
+    aff = np.asarray(member_affine, dtype=f).reshape(-1, 4)
+    n_scans, parts, out_off = len(off) - 1, [], [0]
+    with np.errstate(invalid="ignore", over="ignore"):
+        for t in range(len(member_offsets) - 1):
+            n = 0
+            for m in range(member_offsets[t], member_offsets[t + 1]):
+                i = member_scan[m]
+                if not 0 <= i < n_scans:
+                    continue
+                p = xy[off[i]:max(off[i + 1], off[i])]
+                c, s, tx, ty = aff[m]
+                x = ((c * p[:, 0]).astype(f) + ((-s) * p[:, 1]).astype(f)).astype(f) + tx
+                y = ((s * p[:, 0]).astype(f) + (c * p[:, 1]).astype(f)).astype(f) + ty
+                parts.append(np.stack([x.astype(f), y.astype(f)], axis=1))
+                n += len(p)
+            out_off.append(out_off[-1] + n)
+    merged = np.concatenate(parts).astype(f) if parts else np.zeros((0, 2), f)
+    return merged, np.asarray(out_off, dtype=np.int32)
+
+
+def submap_extra_scans(xy, offsets, poses, pair_tgt, radius):
+    """The host-merge route to submap tables for a backend whose match() has no submap_radius: the merged cloud of every
+    distinct target of the list (members by submap_members, affines from `poses`) appended to the bag as an extra scan.
+    Returns (xy, offsets, pair_tgt) with every target replaced by the id of its merged scan."""
+    off = np.asarray(offsets, dtype=np.int32)
+    n_scans = len(off) - 1
+    targets = np.unique(np.asarray(pair_tgt))
+    member_scan, member_offsets = submap_members(n_scans, targets, radius)
+    aff = submap_member_affines(poses, np.repeat(targets, np.diff(member_offsets)), member_scan)
+    mxy, moff = submap_clouds(xy, off, member_scan, aff, member_offsets)
+    xy2 = np.concatenate([np.asarray(xy, dtype=np.float32).reshape(-1, 2), mxy])
+    off2 = np.concatenate([off, off[-1] + moff[1:]]).astype(np.int32)
+    return xy2, off2, (n_scans + np.searchsorted(targets, pair_tgt)).astype(np.int32)
 
 
 def distance_to_line_segment_f32(points, seg):

@@ -175,15 +175,27 @@ class HipBackend:
                                                float(max_score), _lib.ptr(scores), _lib.ptr(flags)))
         return scores, flags
 
-    def match(self, xy, offsets, pair_src, pair_tgt, theta0, cell_bits=16):
+    def match(self, xy, offsets, pair_src, pair_tgt, theta0, cell_bits=16, submap_radius=0, poses=None):
         """Batched loop-closure scan matching (BASELINE config #2 lattice): (records, spec, search).
         Only the scans the list names go to the device (the candidate scans of a 10,000-scan bag are ~150: 1.3 MB instead
-        of the bag's 86 MB, whose upload cost more than matching the 3,275 pairs)."""
-        from . import csm
+        of the bag's 86 MB, whose upload cost more than matching the 3,275 pairs).
+        submap_radius K > 0: every target's table is built from its SUBMAP -- the scans t - K .. t + K placed in t's frame
+        by `poses` (n_scans, 3), merged on the device (nhip_submaps_gather_dev) from the same sub-bag, which then holds the
+        members too.  0: the tables of the target scans alone; no gather is launched."""
+        from . import csm, hostside
         spec = csm.grid_spec(30.0, 0.05, 2.0, 1e-10, 40, cell_bits)
         search = csm.search_spec(61, 81, 81, math.radians(1.0))
         pair_src, pair_tgt = np.asarray(pair_src), np.asarray(pair_tgt)
-        used = np.unique(np.concatenate([pair_src, pair_tgt]))
+        submap_radius = int(submap_radius)
+        if submap_radius < 0 or (submap_radius > 0 and poses is None):
+            raise ValueError("match: submap_radius %d needs poses and must not be negative" % submap_radius)
+        members = None
+        if submap_radius > 0 and len(pair_src):
+            targets = np.unique(pair_tgt)
+            member_scan, member_offsets = hostside.submap_members(len(offsets) - 1, targets, submap_radius)
+            member_aff = csm.submap_member_affines(poses, np.repeat(targets, np.diff(member_offsets)), member_scan)
+            members = (targets, member_scan, member_aff, member_offsets)
+        used = np.unique(np.concatenate([pair_src, pair_tgt] + ([members[1]] if members else [])))
         off = np.asarray(offsets, dtype=np.int64)
         xy2 = np.asarray(xy, dtype=np.float32).reshape(-1, 2)
         sub_xy = np.concatenate([xy2[off[i]:off[i + 1]] for i in used]) if len(used) else np.zeros((0, 2), np.float32)
@@ -214,8 +226,22 @@ class HipBackend:
         d_out = torch.empty((n, 4), dtype=torch.int32, device=dev)
         sp = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         n_sub = len(sub_off) - 1
-        check(lib.nhip_grid_build_dev(d_xy.data_ptr(), d_off.data_ptr(), n_sub, d_ids.data_ptr(), len(ids), C.byref(spec),
-                                      d_grids.data_ptr(), d_ws_g.data_ptr(), ws_g, sp))
+        if members:
+            # (ids, the sorted distinct targets in sub-bag numbering, are `targets` in the bag's: slot t is target t's submap)
+            _, member_scan, member_aff, member_offsets = members
+            m_sub = np.searchsorted(used, member_scan).astype(np.int32)
+            total = int((sub_off[m_sub + 1] - sub_off[m_sub]).sum())
+            d_mscan, d_maff, d_moff = t(m_sub), t(member_aff), t(member_offsets)
+            d_gxy = torch.empty((max(total, 1), 2), dtype=torch.float32, device=dev)
+            d_goff = torch.empty(len(ids) + 1, dtype=torch.int32, device=dev)
+            d_gids = torch.arange(len(ids), dtype=torch.int32, device=dev)
+            check(lib.nhip_submaps_gather_dev(d_xy.data_ptr(), d_off.data_ptr(), n_sub, d_mscan.data_ptr(), d_maff.data_ptr(),
+                                              d_moff.data_ptr(), len(ids), d_gxy.data_ptr(), total, d_goff.data_ptr(), sp))
+            check(lib.nhip_grid_build_dev(d_gxy.data_ptr(), d_goff.data_ptr(), len(ids), d_gids.data_ptr(), len(ids),
+                                          C.byref(spec), d_grids.data_ptr(), d_ws_g.data_ptr(), ws_g, sp))
+        else:
+            check(lib.nhip_grid_build_dev(d_xy.data_ptr(), d_off.data_ptr(), n_sub, d_ids.data_ptr(), len(ids), C.byref(spec),
+                                          d_grids.data_ptr(), d_ws_g.data_ptr(), ws_g, sp))
         check(lib.nhip_csm_match_dev(d_xy.data_ptr(), d_off.data_ptr(), n_sub, d_grids.data_ptr(), len(ids), C.byref(spec), d_src.data_ptr(),
                                      d_slot.data_ptr(), d_rot0.data_ptr(), d_delta.data_ptr(), None, n, C.byref(search),
                                      d_keys.data_ptr(), d_out.data_ptr(), None, d_ws_m.data_ptr(), ws_m, sp))
