@@ -1,31 +1,12 @@
 """Scan normals on the GPU (nhip_normals.hip) against the numpy statement of the spec (tests/normals_reference.py): the info
 words equal, the normals within one float ulp at 1.0, on one launch of crafted scans at the lengths where the kernels change
 path; determinism; the three ways in; and the normal-residual solve on estimated normals."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from nautilus_amd import _lib, csm, normals, posegraph, synth
 from tests import normals_reference as R
-
-
-def _estimate_dev(xy, off, spec, want_info=True, fill=0.0):
-    """nhip_normals_estimate_dev, called directly -> (normals (n, 2), info (n, 4) or None, rc and info of nhip_dev_status)."""
-    import torch
-    lib, dev = _lib.load(), torch.device("cuda:0")
-    xy, off = np.ascontiguousarray(xy, np.float32).reshape(-1, 2), np.ascontiguousarray(off, np.int32)
-    n = len(xy)
-    d_xy = torch.from_numpy(xy).to(dev) if n else torch.zeros(2, dtype=torch.float32, device=dev)
-    d_off = torch.from_numpy(off).to(dev)
-    d_nrm = torch.full((max(n, 1), 2), fill, dtype=torch.float32, device=dev)
-    d_info = torch.full((max(n, 1), 4), -7, dtype=torch.int32, device=dev) if want_info else None
-    sp = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    _lib.check(lib.nhip_normals_estimate_dev(d_xy.data_ptr(), d_off.data_ptr(), len(off) - 1, C.byref(spec), d_nrm.data_ptr(),
-                                             None if d_info is None else d_info.data_ptr(), sp))
-    st = (C.c_int32 * 4)()
-    rc = lib.nhip_dev_status(sp, st)
-    return d_nrm.cpu().numpy()[:n], None if d_info is None else d_info.cpu().numpy()[:n], (rc, list(st))
+from tests.normals_device import estimate_dev as _estimate_dev
 
 
 @pytest.fixture(scope="module")
