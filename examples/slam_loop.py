@@ -54,7 +54,8 @@ LC_MIN_SEPARATION = 20  # nodes between the two scans of a loop-closure pair (th
 
 def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, verbose=False, residual="normal",
         rank=0, world=1, device="cuda:0", backend=None, iterations=4, hitl=True, cell_bits=16, gate="scatter",
-        min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False, normals="bag", lc_submap=0):
+        min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False, normals="bag", lc_submap=0,
+        linear_solver="host"):
     """min_scatter_score: LCCandidateFilter's threshold is 0.70 (lc_candidate_filter.cc:76); scans of the synthetic
     24 m x 16 m room score ~0.4, so callers on that world pass a lower one.
     hitl_device: the HITL constraint's points are selected and packed on the GPU (hitl.select, under the "path" clock) and
@@ -67,6 +68,8 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     A backend whose match() takes submap_radius merges the clouds on the device; any other gets the merged clouds as extra
     scans (hostside.submap_extra_scans).  K must stay below the pair gate's minimum separation (20): a source is never in
     its target's submap.  Not with world > 1.
+    linear_solver: "host" -- every solve's linear step in scipy on downloaded rows -- or "device": assembled and solved on the
+    GPU by block-Jacobi PCG (PoseGraph.solve; needs hitl_device for the HITL phase).
     With world > 1 (one process per GPU under torch.distributed): the window ICP solve is replicated -- its
     consumer, the solver, is host-side -- and the loop-closure pairs are sharded by target across the ranks,
     matched, and all-gathered (nautilus_amd/sharding.py); every rank ends with the same trajectory."""
@@ -92,6 +95,13 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     out = {"backend": backend.name, "n_scans": n_scans, "window": window, "residual": residual,
            "err_odometry_m": posegraph.trajectory_error(odom, bag.truth)}
     posegraph.clock_reset()
+    pcg_by_phase, pcg_seen = {}, [0, 0]
+
+    def pcg_phase(name):
+        """[solves, PCG iterations] of the phase that just ended (the device linear solver's; zeros with the host's)"""
+        now = [posegraph.LINEAR_STATS["solves"], posegraph.LINEAR_STATS["iterations"]]
+        pcg_by_phase[name] = [now[0] - pcg_seen[0], now[1] - pcg_seen[1]]
+        pcg_seen[:] = now
 
     if normals == "device":
         t0 = time.perf_counter()
@@ -112,8 +122,10 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
 
     t0 = time.perf_counter()
     pg, poses = posegraph.solve_growing_window(xy, nrm, off, odom, 1, window, iterations=iterations, kind=kind,
-                                               device=device, verbose=verbose, backend=backend, features=feats)
+                                               device=device, verbose=verbose, backend=backend, features=feats,
+                                               linear_solver=linear_solver)
     out["t_icp_solve_s"] = time.perf_counter() - t0
+    pcg_phase("icp")
     out["err_icp_m"] = posegraph.trajectory_error(poses, bag.truth)
     out["icp_correspondences"] = pg.icp.n_corr
 
@@ -181,8 +193,9 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         t0 = time.perf_counter()
         with posegraph.clocked("marshal"):
             pg.add_loop_closures(*lc)
-        poses, _ = pg.solve(iterations=2 * iterations, verbose=verbose)
+        poses, _ = pg.solve(iterations=2 * iterations, verbose=verbose, linear_solver=linear_solver)
         out["t_lc_solve_s"] = time.perf_counter() - t0
+        pcg_phase("lc")
         out["err_lc_m"] = posegraph.trajectory_error(poses, bag.truth)
 
     # ---- HITL: the user marks the same wall twice; HitlCallback re-solves with the point-to-line blocks
@@ -206,8 +219,10 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         # residuals in every pass
         pg, poses = posegraph.solve_growing_window(xy, nrm, off, poses.copy(), max(1, window - 1), window, iterations=iterations, kind=kind,
                                                    device=device, verbose=verbose, backend=backend, initial=poses,
-                                                   hitl=[con] if con.n_a + con.n_b else [], loop_closures=lc, features=feats)
+                                                   hitl=[con] if con.n_a + con.n_b else [], loop_closures=lc, features=feats,
+                                                   linear_solver=linear_solver)
         out["t_hitl_solve_s"] = time.perf_counter() - t0
+        pcg_phase("hitl")
         out["err_hitl_m"] = posegraph.trajectory_error(poses, bag.truth)
         out["hitl_chosen_line_pose"] = [float(v) for v in con.chosen_line_pose]
     out["t_total_s"] = sum(v for k, v in out.items() if k.startswith("t_") and k.endswith("_s"))
@@ -227,6 +242,13 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     out["path_setup_s"] = posegraph.CLOCK["path_setup"]  # (of the path seconds: uploads + device allocations of the per-pass batches)
     out["host_assembly_s"] = posegraph.CLOCK["assemble"]
     out["hitl_select_s"] = posegraph.CLOCK["hitl_select"]
+    # the linear step: with "host" it is host_solver_s + host_assembly_s; with "device" it is
+    # path_linear_s, a part of the path seconds like path_setup_s, and the PCG's counts over all solves
+    out["linear_solver"] = linear_solver
+    out["path_linear_s"] = posegraph.CLOCK["path_linear"]
+    out["pcg_solves"], out["pcg_iterations"] = posegraph.LINEAR_STATS["solves"], posegraph.LINEAR_STATS["iterations"]
+    out["pcg_not_converged"] = posegraph.LINEAR_STATS["not_converged"] + posegraph.LINEAR_STATS["breakdowns"]
+    out["pcg_by_phase"] = pcg_by_phase  # phase -> [solves, iterations]
     out["hitl_device"] = bool(hitl_device)
     out["lc_submap"] = lc_submap
     out["harness_s"] = out["host_other_s"] - out["marshal_s"] - out["host_assembly_s"] - out["hitl_select_s"]
@@ -248,6 +270,9 @@ if __name__ == "__main__":
     ap.add_argument("--lc-submap", type=int, default=0, metavar="K",
                     help="build every loop-closure target's table from the scans t-K .. t+K under the current estimate "
                          "(0: from scan t alone); below %d, the pair gate's minimum separation" % LC_MIN_SEPARATION)
+    ap.add_argument("--linear-solver", choices=["host", "device"], default="host",
+                    help="the linear step of every solve: scipy on the host, or block-Jacobi PCG on the GPU (with HITL: "
+                         "needs --hitl-device)")
     ap.add_argument("-v", action="store_true")
     a = ap.parse_args()
     if not 0 <= a.lc_submap < LC_MIN_SEPARATION:
@@ -267,7 +292,8 @@ if __name__ == "__main__":
         dist.barrier()
         os.dup2(saved, 1)
     res = run(a.scans, a.window, verbose=a.v and rank == 0, residual=a.residual, rank=rank, world=world,
-              device="cuda:%d" % local, hitl_device=a.hitl_device, normals=a.normals, lc_submap=a.lc_submap)
+              device="cuda:%d" % local, hitl_device=a.hitl_device, normals=a.normals, lc_submap=a.lc_submap,
+              linear_solver=a.linear_solver)
     res["world_size"] = world
     if rank == 0:
         print(json.dumps(res))

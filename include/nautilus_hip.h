@@ -64,7 +64,8 @@ const char *nhip_version(void);
  * 1 target scan id of a grid build, 2 source scan id of a pair, 4 grid slot of a pair, 8 block id of a correspondence,
  * 16 pose index of a block, 32 scan id of a correspondence-search block, 64 feature index and 128 feature count of
  * nhip_features_pack_dev, 256 scan offset of nhip_normals_estimate_dev, 512 member scan id and 1024 merged point count beyond
- * the capacity of nhip_submaps_gather_dev.  Clears the record (in the order of `stream`).
+ * the capacity of nhip_submaps_gather_dev, 2048 contributor id of nhip_bsr_assemble_dev, 4096 block column of
+ * nhip_bsr_assemble_dev / nhip_bsr_pcg_dev.  Clears the record (in the order of `stream`).
  * ONE record per DEVICE, shared by every stream and host thread that uses the library on it: a host with several streams
  * on one device learns THAT an id was bad and which, not on which stream; a call that finds a record consumes it -- reports
  * of kernels still running on OTHER streams at that moment can be reported by this call or wiped by its clear.  Clients
@@ -416,6 +417,62 @@ int nhip_resid_odometry_dev(const float *d_t_odom, const float *d_r_odom, const 
                             const int32_t *d_pose_j, int32_t n_factors, double translation_weight,
                             double rotation_weight, const double *d_poses, int32_t n_poses, double *d_residuals,
                             double *d_jac_i, double *d_jac_j, void *stream);
+
+/* The same factors reduced to their normal equations, 28 doubles per factor in the layout of the other *_normal_eq_dev
+ * calls, over the six parameters [pose_i | pose_j] (J = [J_i | J_j], 3 x 6):
+ *   d_out[28*f + 0..20]  = upper triangle of J^T J, row-major     d_out[28*f + 21..26] = J^T r     d_out[28*f + 27] = r^T r
+ * Every sum runs over the three residual rows, products rounded, added in row order 0, 1, 2 (no contraction): bit-equal to
+ * the same sums formed on the host from nhip_resid_odometry_dev's J and r.  A factor whose pose index is out of range gives
+ * 28 zeros and makes nhip_dev_status() report it (kind 16).  n_factors == 0 launches nothing. */
+int nhip_resid_odometry_normal_eq_dev(const float *d_t_odom, const float *d_r_odom, const int32_t *d_pose_i,
+                                      const int32_t *d_pose_j, int32_t n_factors, double translation_weight,
+                                      double rotation_weight, const double *d_poses, int32_t n_poses, double *d_out,
+                                      void *stream);
+
+/* ------------------------------------------------------------------ K11: the pose graph's linear system on the device
+ * The Gauss-Newton system of a pose graph as a block-sparse matrix of 3 x 3 blocks in fp64 (DESIGN.md section 3,
+ * "Block-sparse system").  n_blocks unknown blocks of 3; the sources are 28-double rows (every *_normal_eq_dev call writes
+ * them): row r couples two DIFFERENT unknown blocks u[r], v[r], its 6 x 6 ordered [u | v].  The structure is the caller's,
+ * built once per graph (nautilus_amd/linsolve.py builds it): d_row_ptr[n_blocks + 1] and d_col[nnzb] (block columns,
+ * ascending within a block row, the diagonal block always present, the full symmetric pattern), d_contrib_ptr[nnzb + 1] and
+ * d_contrib[n_contrib]: the contributors of every stored block, ascending, as 4 * r + q -- quadrant q of row r's 6 x 6:
+ * 0 (u,u), 1 (u,v), 2 (v,u) = quadrant 1 transposed, 3 (v,v).  d_row_ptr and d_contrib_ptr are the caller's like every
+ * offsets array (non-decreasing, from 0 to nnzb / n_contrib); d_col and d_contrib are checked by the kernels.
+ *
+ * nhip_bsr_assemble_dev: d_values[9 * nnzb] (every block row-major), d_grad[3 * n_blocks] (block b: the sum over the
+ * contributors of b's diagonal block of row[21..23] for q = 0 and row[24..26] for q = 3) and d_cost[0] = 1/2 the sum of
+ * rows[r][27].  ONE pinned summation order for all three: partial l, l = 0 .. 63, adds terms l, l + 64, l + 128, ... one by
+ * one starting from +0.0; then partial[l] += partial[l + s] for s = 32, 16, ..., 1; the sum is partial[0].  No atomics: the
+ * same input gives the same bits.  A contributor id outside [0, 4 * n_rows) (kind 2048) or a block column outside
+ * [0, n_blocks) (kind 4096) is never dereferenced: the block is zero and nhip_dev_status() reports it.  n_rows == 0 gives
+ * zeros. */
+int nhip_bsr_assemble_dev(const double *d_rows, int32_t n_rows, const int32_t *d_row_ptr, const int32_t *d_col,
+                          const int32_t *d_contrib_ptr, const int32_t *d_contrib, int32_t n_blocks, int32_t nnzb,
+                          int32_t n_contrib, double *d_values, double *d_grad, double *d_cost, void *stream);
+
+/* What a solve reports (host memory). */
+typedef struct {
+  int32_t iterations;        /* CG iterations completed */
+  int32_t flag;              /* 0 converged, 1 max_iters reached, 2 breakdown */
+  double relative_residual;  /* the recursive residual's ||r|| / ||b|| at the end (0 for b = 0) */
+} nhip_pcg_stats_t;
+
+/* Solves (H + lambda * diag(diag(H) + diag_floor)) x = -g over the blocks with d_fixed[b] == 0 by preconditioned CG in
+ * fp64; rows and columns of fixed blocks are skipped and x is exactly 0 there.  The preconditioner is the inverse of every
+ * damped 3 x 3 diagonal block, formed once per solve.  It stops when the recursive residual satisfies
+ * ||r||_2 <= tol * ||b||_2 (flag 0), after max_iters iterations (flag 1), or at a breakdown -- p^T A p <= 0 or a
+ * non-finite scalar (flag 2; x is the last iterate before it).  b = 0: 0 iterations, x = 0.
+ * Two launches per iteration, no grid-wide barrier inside a kernel, no floating-point atomics: the same input gives the same
+ * bits.  This is the one call of the library that reads device memory between its launches: once per `check_every`
+ * iterations it waits for the stream and reads the end words (launches queued behind the end are no-ops, so x and *stats
+ * do not depend on check_every), and once more for *stats -- it returns with the stream drained, and it cannot be captured
+ * into a graph.  d_workspace: nhip_bsr_pcg_workspace_bytes(n_blocks, nnzb) bytes, 16-byte aligned.  A block column outside
+ * [0, n_blocks) is skipped and reported (kind 4096). */
+int64_t nhip_bsr_pcg_workspace_bytes(int32_t n_blocks, int32_t nnzb);
+int nhip_bsr_pcg_dev(const int32_t *d_row_ptr, const int32_t *d_col, const double *d_values, const double *d_grad,
+                     const uint8_t *d_fixed, int32_t n_blocks, int32_t nnzb, double lambda, double diag_floor, double tol,
+                     int32_t max_iters, int32_t check_every, double *d_x, void *d_workspace, int64_t workspace_bytes,
+                     nhip_pcg_stats_t *stats, void *stream);
 
 /* K5: correspondence search, the step that feeds K4 (Solver::GetPointToPointMatching,
  * src/optimization/solver.cc:132-172; KDTree::FindNearestPoint, src/util/kdtree.cc:253-305).

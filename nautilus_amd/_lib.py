@@ -71,6 +71,10 @@ class HitlSpec(C.Structure):
                 ("point_threshold", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PcgStats(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("flag", C.c_int32), ("relative_residual", C.c_double)]
+
+
 class Match(C.Structure):
     _fields_ = [("itheta", C.c_int32), ("ix", C.c_int32), ("iy", C.c_int32), ("score", C.c_float)]
 
@@ -131,6 +135,11 @@ PROTOTYPES = {
     "nhip_resid_point_to_line_normal_eq_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp]),
     "nhip_resid_odometry_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f64, _f64, _vp, _i32, _vp, _vp,
                                           _vp, _vp]),
+    "nhip_resid_odometry_normal_eq_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f64, _f64, _vp, _i32, _vp, _vp]),
+    "nhip_bsr_assemble_dev": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "nhip_bsr_pcg_workspace_bytes": (_i64, [_i32, _i32]),
+    "nhip_bsr_pcg_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64, _f64, _i32, _i32, _vp, _vp, _i64,
+                                   _P(PcgStats), _vp]),
     "nhip_scans_upload": (C.c_int, [_vp, _vp, _i32, _P(_vp)]),
     "nhip_scans_free": (C.c_int, [_vp]),
     "nhip_grids_build": (C.c_int, [_vp, _vp, _i32, _P(GridSpec), _P(_vp)]),

@@ -53,7 +53,7 @@ struct IdBounds {          // (plain data: it travels inside the kernels' parame
 };
 constexpr uint32_t BAD_TARGET_ID = 1u, BAD_PAIR_SRC = 2u, BAD_PAIR_SLOT = 4u, BAD_BLOCK_ID = 8u, BAD_POSE_ID = 16u,
                    BAD_SCAN_ID = 32u, BAD_FEATURE_IDX = 64u, BAD_FEATURE_COUNT = 128u, BAD_SCAN_OFFSETS = 256u,
-                   BAD_MEMBER_ID = 512u, BAD_SUBMAP_CAPACITY = 1024u;
+                   BAD_MEMBER_ID = 512u, BAD_SUBMAP_CAPACITY = 1024u, BAD_CONTRIB_ID = 2048u, BAD_BLOCK_COLUMN = 4096u;
 constexpr int DEV_STATUS_WORDS = 4;  // {OR of the kinds seen, kind / value / index of the first report}
 uint32_t *dev_status();              // of the current device (allocated on the device's first use; null if that failed)
 #ifdef __HIPCC__
@@ -366,5 +366,27 @@ int launch_resid_odometry(const float *d_t_odom, const float *d_r_odom, const in
                           const int32_t *d_pose_j, int32_t n_factors, double tw, double rw,
                           const double *d_poses, int32_t n_poses, double *d_res, double *d_ji, double *d_jj,
                           hipStream_t s);
+
+// odometry factors reduced to their normal equations (nhip_resid.hip): 28 doubles per factor over [pose_i | pose_j]
+int launch_resid_odometry_normal_eq(const float *d_t_odom, const float *d_r_odom, const int32_t *d_pose_i,
+                                    const int32_t *d_pose_j, int32_t n_factors, double tw, double rw,
+                                    const double *d_poses, int32_t n_poses, double *d_out, hipStream_t s);
+
+// the block-sparse linear system of the pose graph (nhip_linsolve.hip, K11): assembly from 28-double rows, and the
+// block-Jacobi preconditioned CG; the arguments have passed the checks of nhip_host_linsolve.hip
+struct PcgStats {  // what pcg_state_kernel leaves in the workspace's first bytes for the host
+  int32_t done_a, done_b;  // set by the direction kernel / the update kernel once the solve has ended
+  int32_t iterations, flag;
+  double relres, bb;
+};
+int launch_bsr_assemble(const double *d_rows, int32_t n_rows, const int32_t *d_row_ptr, const int32_t *d_col,
+                        const int32_t *d_contrib_ptr, const int32_t *d_contrib, int32_t nb, int32_t nnzb, int32_t n_contrib,
+                        double *d_values, double *d_grad, double *d_cost, hipStream_t s);
+int64_t bsr_pcg_workspace_bytes(int32_t nb, int32_t nnzb);
+// enqueues the start of a solve (kernels of iteration `first` .. `last` - 1; first == 0: the set-up in front of them;
+// final: the closing check behind them).  The state in the workspace's first bytes is a PcgStats.
+int launch_bsr_pcg(const int32_t *d_row_ptr, const int32_t *d_col, const double *d_values, const double *d_grad,
+                   const uint8_t *d_fixed, int32_t nb, int32_t nnzb, double lambda, double diag_floor, double tol,
+                   int32_t first, int32_t last, bool final, double *d_x, void *d_ws, hipStream_t s);
 
 }  // namespace nhip

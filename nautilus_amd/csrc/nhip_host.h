@@ -1,4 +1,4 @@
-// nhip_host.h -- what the host units of the C ABI share (nhip_runtime, nhip_host_csm, nhip_dropin, nhip_host_solver): the
+// nhip_host.h -- what the host units of the C ABI share (nhip_runtime, nhip_host_csm, nhip_dropin, nhip_host_solver, nhip_host_linsolve): the
 // pooled device buffer, the in-flight guard, the phase clocks, the scan and grid handles.  Host only: no kernel unit
 // includes it.
 #pragma once

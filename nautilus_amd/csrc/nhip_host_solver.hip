@@ -150,6 +150,19 @@ int nhip_resid_odometry_dev(const float *d_t_odom, const float *d_r_odom, const 
                                d_jac_j, static_cast<hipStream_t>(stream));
 }
 
+int nhip_resid_odometry_normal_eq_dev(const float *d_t_odom, const float *d_r_odom, const int32_t *d_pose_i,
+                                      const int32_t *d_pose_j, int32_t n_factors, double translation_weight,
+                                      double rotation_weight, const double *d_poses, int32_t n_poses, double *d_out,
+                                      void *stream) {
+  NHIP_REQUIRE(n_factors >= 0 && n_poses >= 0, "resid_odometry_normal_eq_dev: negative size");
+  int rc = require_device();
+  if (rc) return rc;
+  if (n_factors == 0) return NHIP_OK;
+  NHIP_REQUIRE(d_t_odom && d_r_odom && d_pose_i && d_pose_j && d_poses && d_out, "resid_odometry_normal_eq_dev: null pointer");
+  return launch_resid_odometry_normal_eq(d_t_odom, d_r_odom, d_pose_i, d_pose_j, n_factors, translation_weight, rotation_weight,
+                                         d_poses, n_poses, d_out, static_cast<hipStream_t>(stream));
+}
+
 // ---------------------------------------------------------------- HITL point selection
 // the accepted ranges of include/nautilus_hip.h
 static int hitl_spec_check(const nhip_hitl_spec_t *s, const char *who) {

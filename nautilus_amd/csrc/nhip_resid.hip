@@ -496,7 +496,56 @@ __global__ void resid_odometry_kernel(const float2 *__restrict__ t_odom,
   }
 }
 
+// The normal equations of odometry factors: one lane per factor, r and J = [J_i | J_j] (3 x 6) exactly as
+// resid_odometry_kernel forms them, then the 28 doubles of the other *_normal_eq kernels.  Every sum runs over the three
+// residual rows: products rounded, added in row order 0, 1, 2 (no contraction: -ffp-contract=off), so the result is
+// bit-equal to the same sums formed on the host from resid_odometry_kernel's outputs.
+__global__ void resid_odometry_normal_eq_kernel(const float2 *__restrict__ t_odom, const float *__restrict__ r_odom,
+                                                const int32_t *__restrict__ pose_i, const int32_t *__restrict__ pose_j,
+                                                int32_t n, double tw, double rw, const double *__restrict__ poses,
+                                                double *__restrict__ out, int32_t n_poses, uint32_t *__restrict__ status) {
+  const int32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n) return;
+  double *o = out + 28 * (size_t)f;
+  const int32_t ii = pose_i[f], ij = pose_j[f];
+  if (!id_in(ii, n_poses) || !id_in(ij, n_poses)) {
+    flag_bad_id(status, BAD_POSE_ID, id_in(ii, n_poses) ? ij : ii, f);
+    for (int q = 0; q < 28; q++) o[q] = 0.0;
+    return;
+  }
+  const double *pi = poses + 3 * (size_t)ii;
+  const double *pj = poses + 3 * (size_t)ij;
+  const float2 t = t_odom[f];
+  const double ex = pi[0] + (double)t.x - pj[0];
+  const double ey = pi[1] + (double)t.y - pj[1];
+  const double d = pi[2] + (double)r_odom[f] - pj[2];
+  const double sd = sin(d), cd = cos(d);
+  const double r[3] = {tw * ex, tw * ey, rw * atan2(sd, cd)};
+  const double g = rw * ((sd * sd + cd * cd) / (cd * cd + sd * sd));
+  const double J[3][6] = {{tw, 0, 0, -tw, 0, 0}, {0, tw, 0, 0, -tw, 0}, {0, 0, g, 0, 0, -g}};
+  int k = 0;
+#pragma unroll
+  for (int p = 0; p < 6; p++)
+#pragma unroll
+    for (int q = p; q < 6; q++) o[k++] = J[0][p] * J[0][q] + J[1][p] * J[1][q] + J[2][p] * J[2][q];
+#pragma unroll
+  for (int p = 0; p < 6; p++) o[21 + p] = J[0][p] * r[0] + J[1][p] * r[1] + J[2][p] * r[2];
+  o[27] = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+}
+
 }  // namespace
+
+int launch_resid_odometry_normal_eq(const float *d_t_odom, const float *d_r_odom, const int32_t *d_pose_i,
+                                    const int32_t *d_pose_j, int32_t n_factors, double tw, double rw,
+                                    const double *d_poses, int32_t n_poses, double *d_out, hipStream_t s) {
+  NHIP_REQUIRE(n_factors >= 0 && n_poses >= 0, "resid_odometry_normal_eq: negative size");
+  if (n_factors == 0) return NHIP_OK;
+  hipLaunchKernelGGL(resid_odometry_normal_eq_kernel, dim3((n_factors + 255) / 256), dim3(256), 0, s,
+                     reinterpret_cast<const float2 *>(d_t_odom), d_r_odom, d_pose_i, d_pose_j, n_factors, tw, rw, d_poses,
+                     d_out, n_poses, dev_status());
+  NHIP_TRY_HIP(hipGetLastError());
+  return NHIP_OK;
+}
 
 int launch_resid_lidar(int kind, const float *d_corr, const int32_t *d_corr_block, int64_t n_corr,
                        const int32_t *d_block_src, const int32_t *d_block_tgt, int32_t n_blocks,

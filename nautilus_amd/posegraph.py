@@ -13,8 +13,10 @@ batched API instead:
     (AddHITLResiduals, solver.cc:515-532), evaluated by nhip_resid_point_to_line -- or, for a constraint selected on
     the GPU (hitl.select), reduced there to per-block normal equations (nhip_resid_point_to_line_normal_eq_dev);
   * Gauss-Newton with Levenberg damping on the assembled sparse system (scipy.sparse on the
-    host: N poses x 3 + 3 per HITL constraint), first pose held constant (solver.cc:384-386).
-Only the linear solve and the bookkeeping are host work; every residual, Jacobian and nearest
+    host: N poses x 3 + 3 per HITL constraint), first pose held constant (solver.cc:384-386) -- or, with
+    solve(linear_solver="device"), on the block-sparse system assembled and solved on the GPU (linsolve.py:
+    nhip_bsr_assemble_dev, nhip_bsr_pcg_dev), every 28-double row staying there.
+By default only the linear solve and the bookkeeping are host work; every residual, Jacobian and nearest
 neighbour comes from the backend -- HipBackend (the product: libnautilus_hip) unless a test or the
 bench's cpu_baseline leg injects another one (oracle/cpu_backend.py times the same loop on the CPU
 restatement; the product never imports it).
@@ -38,13 +40,20 @@ from .correspondence import IcpBatch, window_pairs
 # "marshal" = host work at the path's boundary: building the block lists and input arrays the backend calls take and
 # turning their outputs into what the caller asked for; "assemble" = the sparse system's assembly from the per-block
 # normal equations and factor Jacobians (numpy: what Ceres does inside its solve, like "host_solver"); "hitl_select" =
-# GetRelevantPosesForHITL's point selection (host-side HITL curation, solver.cc:479-513).
-CLOCK = {"path": 0.0, "host_solver": 0.0, "marshal": 0.0, "assemble": 0.0, "hitl_select": 0.0, "path_setup": 0.0}
+# GetRelevantPosesForHITL's point selection (host-side HITL curation, solver.cc:479-513); "path_linear" = of the path
+# seconds, the device linear solver's (structure upload, assembly, PCG: solve(linear_solver="device")).
+CLOCK = {"path": 0.0, "host_solver": 0.0, "marshal": 0.0, "assemble": 0.0, "hitl_select": 0.0, "path_setup": 0.0,
+         "path_linear": 0.0}
+# The device linear solver's solves since the last reset, over every PoseGraph: solves, their PCG iterations, the solves
+# that ended at max_iters (flag 1) and the breakdowns (flag 2).  A PoseGraph keeps its own in .linear_stats.
+LINEAR_STATS = {"solves": 0, "iterations": 0, "not_converged": 0, "breakdowns": 0}
 
 
 def clock_reset():
     for k in CLOCK:
         CLOCK[k] = 0.0
+    for k in LINEAR_STATS:
+        LINEAR_STATS[k] = 0
 
 
 @contextlib.contextmanager
@@ -133,16 +142,47 @@ class HipBackend:
         if con.n_blocks == 0:
             return np.zeros((0, 28))
         P, Lp = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3), np.ascontiguousarray(line_poses, dtype=np.float64).reshape(-1, 3)
-        d_p, d_l = torch.from_numpy(P).to(self.dev), torch.from_numpy(Lp).to(self.dev)
+        d_out = self.point_to_line_normal_eq_dev(con, torch.from_numpy(P).to(self.dev), torch.from_numpy(Lp).to(self.dev), line_index)
+        out = d_out.cpu().numpy()
+        check(self.lib.nhip_dev_status(C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream), None))
+        return out
+
+    def point_to_line_normal_eq_dev(self, constraint, d_poses, d_line_poses, line_index):
+        """The same with everything on the device: d_poses (n, 3) and d_line_poses (m, 3) float64 tensors in, the
+        (n_blocks, 28) tensor out; nothing is downloaded and nhip_dev_status is the caller's to check."""
+        torch, con = self.torch, constraint
         d_out = torch.empty((con.n_blocks, 28), dtype=torch.float64, device=self.dev)
+        if con.n_blocks == 0:
+            return d_out
         sp = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
         check(self.lib.nhip_resid_point_to_line_normal_eq_dev(con.d_segments.data_ptr(), con.d_points.data_ptr(),
                                                               con.d_block_offsets.data_ptr(), con.d_block_pose.data_ptr(),
-                                                              con.d_block_line(line_index).data_ptr(), con.n_blocks, d_p.data_ptr(), len(P),
-                                                              d_l.data_ptr(), len(Lp), d_out.data_ptr(), sp))
-        out = d_out.cpu().numpy()
-        check(self.lib.nhip_dev_status(sp, None))
-        return out
+                                                              con.d_block_line(line_index).data_ptr(), con.n_blocks,
+                                                              d_poses.data_ptr(), d_poses.shape[0], d_line_poses.data_ptr(),
+                                                              d_line_poses.shape[0], d_out.data_ptr(), sp))
+        return d_out
+
+    def odometry_normal_eq_dev(self, factors, d_poses):
+        """The normal equations of OdometryFactors at the (n, 3) float64 device tensor d_poses: (F, 28) float64 on the
+        device over [pose_i | pose_j] (nhip_resid_odometry_normal_eq_dev).  The factors' arrays go up once."""
+        torch, fac = self.torch, factors
+        d_out = torch.empty((fac.n, 28), dtype=torch.float64, device=self.dev)
+        if fac.n == 0:
+            return d_out
+        if getattr(fac, "_dev", None) is None or fac._dev[0] != self.dev:
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+            fac._dev = (self.dev, t(fac.t_odom), t(fac.r_odom), t(fac.pose_i), t(fac.pose_j))
+        _, d_t, d_r, d_i, d_j = fac._dev
+        check(self.lib.nhip_resid_odometry_normal_eq_dev(d_t.data_ptr(), d_r.data_ptr(), d_i.data_ptr(), d_j.data_ptr(), fac.n,
+                                                         fac.tw, fac.rw, d_poses.data_ptr(), d_poses.shape[0], d_out.data_ptr(),
+                                                         C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)))
+        return d_out
+
+    def device_system(self, structure, fixed=()):
+        """The device arrays of a linsolve.BlockStructure -- values, gradient, x, the PCG workspace -- and its two calls
+        (linsolve.DeviceSystem: nhip_bsr_assemble_dev, nhip_bsr_pcg_dev)."""
+        from . import linsolve
+        return linsolve.DeviceSystem(self, structure, fixed)
 
     def scatter_scores(self, xy, offsets):
         """LCCandidateFilter's scatter-matrix score of every scan (nhip_lc_scatter_scores)."""
@@ -263,6 +303,10 @@ class _HipIcp:
     def normal_equations(self, kind):
         return self.b.normal_equations(kind).cpu().numpy()
 
+    def normal_equations_dev(self, kind):
+        """(n_blocks, 28) float64 on the device: the batch's own buffer, overwritten by the next evaluation."""
+        return self.b.normal_equations(kind)
+
     @property
     def n_corr(self):
         return self.b.n_corr
@@ -292,6 +336,9 @@ class _FeatureIcp:
     def normal_equations(self, kind):
         """(kind is the all-points graph's choice: a FEATURE graph's kinds are fixed by the reference)"""
         return self.planar.normal_equations(_lib.NHIP_LIDAR_NORMAL) + self.edge.normal_equations(_lib.NHIP_LIDAR_POINT)
+
+    def normal_equations_dev(self, kind):
+        return self.planar.normal_equations_dev(_lib.NHIP_LIDAR_NORMAL) + self.edge.normal_equations_dev(_lib.NHIP_LIDAR_POINT)
 
     @property
     def n_corr(self):
@@ -392,6 +439,8 @@ class PoseGraph:
         self.odo = odometry_factors_from_poses(odom, tw=odom_weights[0], rw=odom_weights[1])
         self.lc = None
         self.hitl = []
+        self.linear_stats = {k: 0 for k in LINEAR_STATS}  # of this graph's solve(linear_solver="device") calls
+        self._device = None  # (what the system was built from, DeviceSystem): the structure is fixed once the graph is
         # odometry factors always come from `odom`; the estimate may start elsewhere (previous window pass)
         self.poses = np.array(odom if initial is None else initial, dtype=np.float64)
 
@@ -513,8 +562,94 @@ class PoseGraph:
                 out[k] = x[[pos[3 * s_], pos[3 * s_ + 1]], :].astype(np.float32)
         return out
 
-    def solve(self, iterations=8, damping=1e-3, verbose=False):
-        """Gauss-Newton with Levenberg damping; pose 0 constant (SetParameterBlockConstant, solver.cc:384-386)."""
+    def _device_system(self):
+        """The block-sparse system of this graph on the device, built on the first solve(linear_solver="device") and again
+        only if loop closures or HITL constraints were added since.  Unknown blocks: the N poses, then one per HITL
+        constraint.  Rows, in the order _evaluate_device joins them: ICP blocks [source | target], odometry factors
+        [pose_i | pose_j], loop closures likewise, then each device HITL constraint's blocks [pose | chosen_line_pose c]."""
+        if not hasattr(self.backend, "device_system") or not hasattr(self.icp, "normal_equations_dev"):
+            raise TypeError("solve: backend %r has no device linear solver; use linear_solver=\"host\"" % self.backend.name)
+        for con in self.hitl:
+            if not hasattr(con, "d_points"):
+                raise TypeError("solve: linear_solver=\"device\" takes device HITL constraints (hitl.select), not a HitlConstraint")
+        built_from = (id(self.lc), tuple(id(c) for c in self.hitl))
+        if self._device is not None and self._device[0] == built_from:
+            return self._device[1]
+        from . import linsolve
+        with clocked("path"), clocked("path_linear"):
+            u, v = [self.icp.block_src], [self.icp.block_tgt]
+            for fac in (self.odo, self.lc):
+                if fac is not None:
+                    u.append(fac.pose_i)
+                    v.append(fac.pose_j)
+            for c, con in enumerate(self.hitl):
+                u.append(con.block_pose)
+                v.append(np.full(con.n_blocks, self.n + c))
+            structure = linsolve.BlockStructure(self.n + len(self.hitl), np.concatenate(u), np.concatenate(v))
+            system = self.backend.device_system(structure, fixed=[0])  # pose 0 constant
+        self._device = (built_from, system)
+        return system
+
+    def _evaluate_device(self, system, poses, lines, research):
+        """The system at `poses`, assembled on the device from rows that never leave it: the poses go up, the cost comes down."""
+        torch, be = self.backend.torch, self.backend
+        with clocked("path"):
+            self.icp.set_poses(poses)
+            if research:
+                self.icp.search()
+            d_poses = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)).to(be.dev)
+            d_lines = torch.from_numpy(np.ascontiguousarray(lines, dtype=np.float64).reshape(-1, 3)).to(be.dev)
+            parts = [self.icp.normal_equations_dev(self.kind)]
+            parts += [be.odometry_normal_eq_dev(fac, d_poses) for fac in (self.odo, self.lc) if fac is not None]
+            parts += [be.point_to_line_normal_eq_dev(con, d_poses, d_lines, c) for c, con in enumerate(self.hitl)]
+            rows = torch.cat(parts)
+            with clocked("path_linear"):
+                return system.assemble(rows)
+
+    def _solve_device(self, iterations, damping, verbose, cg_tol, cg_max_iters):
+        """solve() with the linear step on the device: the same Levenberg loop; a PCG solve that reached max_iters (flag 1)
+        gives a step like any other -- the cost test accepts or rejects it; a breakdown (flag 2) counts as a rejected step."""
+        system = self._device_system()
+        poses, lines = self.poses.copy(), self._lines()
+        cost = self._evaluate_device(system, poses, lines, research=True)
+        history, lam, N = [cost], damping, self.n
+        for it in range(iterations):
+            with clocked("path"), clocked("path_linear"):
+                step, res = system.solve(lam, 1e-9, cg_tol, cg_max_iters)
+            for stats in (self.linear_stats, LINEAR_STATS):
+                stats["solves"] += 1
+                stats["iterations"] += res.iterations
+                stats["not_converged"] += res.flag == 1
+                stats["breakdowns"] += res.flag == 2
+            accepted = False
+            if res.flag != 2:
+                trial, trial_lines = poses + step[:3 * N].reshape(-1, 3), lines + step[3 * N:].reshape(-1, 3)
+                cost2 = self._evaluate_device(system, trial, trial_lines, research=False)
+                accepted = cost2 < cost
+            if accepted:
+                poses, lines, cost, lam = trial, trial_lines, cost2, max(lam * 0.3, 1e-9)
+            else:
+                lam *= 10.0
+                if res.flag != 2:  # (the system on the device is the trial's: back to the one at `poses`)
+                    cost = self._evaluate_device(system, poses, lines, research=False)
+            history.append(cost)
+            if verbose:
+                print("iter %d cost %.6g lambda %.2g pcg %r" % (it, cost, lam, res))
+        self.poses = poses
+        for c, con in enumerate(self.hitl):
+            con.chosen_line_pose = lines[c].copy()
+        return poses, history
+
+    def solve(self, iterations=8, damping=1e-3, verbose=False, linear_solver="host", cg_tol=1e-10, cg_max_iters=None):
+        """Gauss-Newton with Levenberg damping; pose 0 constant (SetParameterBlockConstant, solver.cc:384-386).
+        linear_solver "host": the system assembled in numpy from downloaded rows, scipy's spsolve.  "device": assembled on
+        the GPU and solved there by block-Jacobi PCG to ||r|| <= cg_tol ||b|| in at most cg_max_iters iterations (None:
+        max(200, 3 x the unknown blocks)); needs a backend with device_system and device HITL constraints (TypeError
+        otherwise); .linear_stats counts the solves."""
+        if linear_solver == "device":
+            return self._solve_device(iterations, damping, verbose, cg_tol, cg_max_iters)
+        if linear_solver != "host":
+            raise ValueError("solve: linear_solver %r (\"host\" or \"device\")" % (linear_solver,))
         import scipy.sparse as sp
         from scipy.sparse.linalg import spsolve
         poses, lines = self.poses.copy(), self._lines()
@@ -547,11 +682,13 @@ class PoseGraph:
 
 def solve_growing_window(xy, normals, offsets, odom, window_min=1, window_max=10, iterations=4,
                          kind=_lib.NHIP_LIDAR_POINT, outlier_threshold=0.25, odom_weights=(1.0, 1.0),
-                         device="cuda:0", verbose=False, backend=None, initial=None, hitl=(), loop_closures=None, features=None):
+                         device="cuda:0", verbose=False, backend=None, initial=None, hitl=(), loop_closures=None, features=None,
+                         linear_solver="host"):
     """Solver::OptimizeOverGrowingWindow (solver.cc:339-355): for every window size from
     lidar_constraint_amount_min to _max the problem is rebuilt -- odometry factors, HITL residuals
     (AddHITLResiduals) plus fresh correspondences for all (i, j) blocks of the window, searched at the current
-    estimate -- and solved.  features: as PoseGraph's (FEATURE mode).  Returns (PoseGraph of the last pass, poses)."""
+    estimate -- and solved.  features: as PoseGraph's (FEATURE mode); linear_solver: as PoseGraph.solve's.  Returns (PoseGraph of the last
+    pass, poses)."""
     poses = np.array(odom if initial is None else initial, dtype=np.float64)
     backend = backend if backend is not None else HipBackend(device)
     if features is None and hasattr(backend, "reserve_icp"):  # (feature clouds: a few points per scan, nothing to reserve)
@@ -565,7 +702,7 @@ def solve_growing_window(xy, normals, offsets, odom, window_min=1, window_max=10
             pg.add_hitl(con)
         if loop_closures is not None:
             pg.add_loop_closures(*loop_closures)
-        poses, hist = pg.solve(iterations=iterations, verbose=verbose)
+        poses, hist = pg.solve(iterations=iterations, verbose=verbose, linear_solver=linear_solver)
         if verbose:
             print("window %d: cost %.6g -> %.6g" % (w, hist[0], hist[-1]))
     return pg, poses

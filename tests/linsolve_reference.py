@@ -1,0 +1,266 @@
+"""The device linear solver's specification in numpy ("Block-sparse system"; kernels nhip_linsolve.hip, the
+odometry rows of nhip_resid.hip): the pinned sums of the assembly, PCG with exactly the stated algorithm, the odometry rows, and
+the systems the CPU and the GPU tests share.  Nothing here runs on a device."""
+import numpy as np
+
+from nautilus_amd import _lib, linsolve, posegraph
+from oracle import oracle as O
+from oracle.cpu_backend import OracleBackend
+
+LD = np.longdouble
+U = 2.0 ** -53
+IU = np.triu_indices(6)
+
+
+# ------------------------------------------------------------------------------------------------ the pinned sum
+def pinned_sum(terms):
+    """The sum over axis 0 in the order the assembly pins: partial l (l = 0 .. 63) adds terms l, l + 64, ... one by one from
+    +0.0, then partial[l] += partial[l + s] for s = 32, 16, ..., 1.  (Padding with +0.0 changes no bit: a partial that
+    started at +0.0 is never -0.0.)"""
+    t = np.asarray(terms, dtype=np.float64)
+    n = t.shape[0]
+    m = (n + 63) // 64
+    pad = np.zeros((64 * max(m, 1),) + t.shape[1:])
+    pad[:n] = t
+    pad = pad.reshape((max(m, 1), 64) + t.shape[1:])
+    partial = np.zeros((64,) + t.shape[1:])
+    for k in range(pad.shape[0]):
+        partial = partial + pad[k]
+    s = 32
+    while s >= 1:
+        partial = partial[:s] + partial[s:2 * s]
+        s //= 2
+    return partial[0]
+
+
+def quadrants(rows):
+    """(R, 28) rows -> (4 R, 9): entry 4 r + q is quadrant q of row r's symmetric 6 x 6, row-major (0 (u,u), 1 (u,v), 2 (v,u), 3 (v,v))."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 28)
+    H6 = np.zeros((len(rows), 6, 6))
+    H6[:, IU[0], IU[1]] = rows[:, :21]
+    H6[:, IU[1], IU[0]] = rows[:, :21]
+    q = np.stack([H6[:, :3, :3], H6[:, :3, 3:], H6[:, 3:, :3], H6[:, 3:, 3:]], axis=1)
+    return q.reshape(-1, 9)
+
+
+def assemble(st, rows):
+    """values (nnzb, 3, 3), grad (3 n_blocks,), cost of nhip_bsr_assemble_dev on a linsolve.BlockStructure."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 28)
+    Q = quadrants(rows)
+    G = np.zeros((len(rows), 4, 3))
+    G[:, 0], G[:, 3] = rows[:, 21:24], rows[:, 24:27]
+    G = G.reshape(-1, 3)
+    values, grad = np.zeros((st.nnzb, 9)), np.zeros((st.n_blocks, 3))
+    for k in range(st.nnzb):
+        ids = st.contrib[st.contrib_ptr[k]:st.contrib_ptr[k + 1]]
+        values[k] = pinned_sum(Q[ids])
+        if st.col[k] == st.block_row[k]:
+            grad[st.col[k]] = pinned_sum(G[ids])
+    return values.reshape(-1, 3, 3), grad.ravel(), 0.5 * float(pinned_sum(rows[:, 27]))
+
+
+def odometry_rows(r, ji, jj):
+    """28 doubles per factor from OdometryResidual's r (F, 3) and Jacobians (F, 3, 3) x 2: every sum over the three residual
+    rows, products rounded, added in row order 0, 1, 2 (numpy's elementwise operations never contract)."""
+    J = np.concatenate([ji, jj], axis=2)
+    out = np.zeros((len(r), 28))
+    for k, (p, q) in enumerate(zip(*IU)):
+        out[:, k] = (J[:, 0, p] * J[:, 0, q] + J[:, 1, p] * J[:, 1, q]) + J[:, 2, p] * J[:, 2, q]
+    for p in range(6):
+        out[:, 21 + p] = (J[:, 0, p] * r[:, 0] + J[:, 1, p] * r[:, 1]) + J[:, 2, p] * r[:, 2]
+    out[:, 27] = (r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1]) + r[:, 2] * r[:, 2]
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ PCG
+def pcg_matrix(A, b, tol, max_iters, precond="block"):
+    """Preconditioned CG on the sparse SPD matrix A (3 n x 3 n) exactly as nhip_bsr_pcg_dev states it: x = 0, r = b,
+    z = M^-1 r; with k iterations complete: beta = r.z / (the r.z before) (k > 0), a non-finite r.r, r.z or beta is a
+    breakdown (flag 2), ||r|| <= tol ||b|| ends the solve (flag 0), k == max_iters too (flag 1); else p = z + beta p
+    (p = z at k = 0), q = A p, breakdown (flag 2) if p.q <= 0 or p.q or alpha = r.z / p.q is not finite, x += alpha p,
+    r -= alpha q, z = M^-1 r.  M: the 3 x 3 diagonal blocks ("block"), the diagonal ("scalar") or I ("none").
+    Returns (x, iterations, ||r|| / ||b||, flag)."""
+    A = A.tocsr()
+    n = A.shape[0]
+    b = np.asarray(b, dtype=np.float64)
+    if precond == "block":
+        D = np.zeros((n // 3, 3, 3))
+        blocks = A.tobsr(blocksize=(3, 3))
+        for row in range(n // 3):
+            for k in range(blocks.indptr[row], blocks.indptr[row + 1]):
+                if blocks.indices[k] == row:
+                    D[row] = blocks.data[k]
+        with np.errstate(all="ignore"):
+            Minv = np.linalg.inv(D)
+        apply = lambda r: np.einsum("bij,bj->bi", Minv, r.reshape(-1, 3)).ravel()
+    elif precond == "scalar":
+        d = A.diagonal()
+        apply = lambda r: r / d
+    else:
+        apply = lambda r: r.copy()
+    x, r = np.zeros(n), b.copy()
+    z = apply(r)
+    p, bb = np.zeros(n), float(b @ b)
+    rr, rz, rz_old, k = bb, float(r @ z), 0.0, 0
+    rel = lambda v: float(np.sqrt(v) / np.sqrt(bb)) if bb > 0 else 0.0
+    with np.errstate(all="ignore"):
+        while True:
+            beta = np.float64(rz) / np.float64(rz_old) if k > 0 else 0.0
+            if not (np.isfinite(rr) and np.isfinite(rz) and np.isfinite(beta)):
+                return x, k, rel(rr), 2
+            if np.sqrt(rr) <= tol * np.sqrt(bb):
+                return x, k, rel(rr), 0
+            if k == max_iters:
+                return x, k, rel(rr), 1
+            p = z.copy() if k == 0 else z + beta * p
+            q = A @ p
+            pq = np.float64(p @ q)
+            alpha = np.float64(rz) / pq
+            if not (pq > 0) or not np.isfinite(pq) or not np.isfinite(alpha):
+                return x, k, rel(rr), 2
+            x = x + alpha * p
+            r = r - alpha * q
+            z = apply(r)
+            rr, rz_old, rz, k = float(r @ r), rz, float(r @ z), k + 1
+
+
+def damped(st, values, fixed, lam, diag_floor):
+    """(A over the free scalars, their indices): H + lam diag(diag(H) + diag_floor) with the fixed blocks' rows and columns removed."""
+    import scipy.sparse as sp
+    H = st.to_scipy(values)
+    mask = np.ones(st.n_blocks, dtype=bool)
+    mask[np.asarray(list(fixed), dtype=np.int64)] = False
+    free = np.nonzero(np.repeat(mask, 3))[0]
+    Hf = H[free][:, free]
+    return (Hf + lam * sp.diags(Hf.diagonal() + diag_floor)).tocsr(), free
+
+
+def pcg(st, values, grad, fixed, lam, diag_floor=1e-9, tol=1e-10, max_iters=1000, precond="block"):
+    """nhip_bsr_pcg_dev on a structure: (x (3 n_blocks,), iterations, relative residual, flag)."""
+    A, free = damped(st, values, fixed, lam, diag_floor)
+    xf, k, rel, flag = pcg_matrix(A, -np.asarray(grad)[free], tol, max_iters, precond)
+    x = np.zeros(3 * st.n_blocks)
+    x[free] = xf
+    return x, k, rel, flag
+
+
+def true_relative_residual(st, values, grad, fixed, lam, diag_floor, x):
+    """||b - A x|| / ||b|| over the free scalars, every product and sum in longdouble."""
+    A, free = damped(st, values, fixed, lam, diag_floor)
+    A = A.tocoo()
+    Ax = np.zeros(len(free), dtype=LD)
+    np.add.at(Ax, A.row, A.data.astype(LD) * np.asarray(x, dtype=LD)[free][A.col])
+    b = -np.asarray(grad, dtype=LD)[free]
+    return float(np.sqrt(np.sum((b - Ax) ** 2)) / np.sqrt(np.sum(b ** 2)))
+
+
+def iteration_cap(k_ref):
+    """What a correct block-Jacobi PCG may take beside the reference's count: reduction orders differ, the algorithm does not.
+    On the three systems of CPU_SYSTEMS the cap stays below scalar-Jacobi's count (tests/test_linsolve_cpu.py checks it), so
+    a wrong preconditioner fails it."""
+    return k_ref + max(4, k_ref // 4)
+
+
+# ------------------------------------------------------------------------------------------------ systems
+def random_rows(u, seed, scale_decades=1.0):
+    """One 28-double row per (u, v) pair: J^T J, J^T r, r^T r of 8 random residuals over 6 parameters, row scales spread over
+    2 * scale_decades decades."""
+    rng = np.random.default_rng(seed)
+    R = len(u)
+    J = rng.normal(size=(R, 8, 6)) * 10.0 ** rng.uniform(-scale_decades, scale_decades, (R, 1, 1))
+    r = rng.normal(size=(R, 8))
+    rows = np.zeros((R, 28))
+    rows[:, :21] = np.einsum("rki,rkj->rij", J, J)[:, IU[0], IU[1]]
+    rows[:, 21:27] = np.einsum("rki,rk->ri", J, r)
+    rows[:, 27] = np.einsum("rk,rk->r", r, r)
+    return rows
+
+
+def arrow_uv():
+    """70 poses tied to one line block (block 70), 130 rows on the pair (5, 70) and 70 on (9, 70): contributor lists of 1, 70
+    (past 64), 130 (past 128) and, on the line block's diagonal, 268 entries."""
+    u = np.concatenate([np.arange(70), np.full(129, 5), np.full(69, 9)])
+    return u, np.full(len(u), 70)
+
+
+def chain_uv(n, window):
+    bs, bt = posegraph.window_pairs(n, window)
+    return np.concatenate([bs, np.arange(n - 1)]), np.concatenate([bt, np.arange(1, n)])
+
+
+class RowsHitl:
+    """A HITL constraint that gives 28-double rows per block, like hitl.DeviceHitlConstraint, with its points on the host
+    (d_points is only what PoseGraph tells the two kinds of constraint apart by)."""
+
+    def __init__(self, line_a, blocks):
+        self.line_a = np.ascontiguousarray(line_a, dtype=np.float32).reshape(4)
+        self.blocks = [(int(i), np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 2)) for i, p in blocks]
+        self.block_pose = np.array([i for i, _ in self.blocks], dtype=np.int32)
+        self.n_blocks = len(self.blocks)
+        self.n_points = int(sum(len(p) for _, p in self.blocks))
+        self.d_points = None
+        self.chosen_line_pose = np.zeros(3)
+
+
+class RowsBackend(OracleBackend):
+    """The oracle's backend with the per-block point-to-line rows a RowsHitl needs."""
+
+    def point_to_line_normal_eq(self, con, poses, line_poses, line_index):
+        out = np.zeros((con.n_blocks, 28))
+        for b, (i, pts) in enumerate(con.blocks):
+            r, j0, j1 = O.point_to_line_block(con.line_a, pts, poses[i], line_poses[line_index])
+            J = np.concatenate([j0, j1], axis=1)
+            out[b, :21] = (J[:, IU[0]] * J[:, IU[1]]).sum(axis=0)
+            out[b, 21:27] = (J * r[:, None]).sum(axis=0)
+            out[b, 27] = (r * r).sum()
+        return out
+
+
+def wall_blocks(bag, every=3, per_scan=40):
+    """(line a, [(scan, points)]): the points of every `every`-th scan that lie on the room's bottom wall (by the true
+    poses), in scan frame -- a HITL constraint over those scans."""
+    seg = np.asarray(bag.segs[0], dtype=np.float64)
+    blocks = []
+    for i in range(0, bag.n_scans, every):
+        p = np.asarray(bag.scans[i], dtype=np.float64)
+        c, s = np.cos(bag.truth[i, 2]), np.sin(bag.truth[i, 2])
+        wx, wy = c * p[:, 0] - s * p[:, 1] + bag.truth[i, 0], s * p[:, 0] + c * p[:, 1] + bag.truth[i, 1]
+        on = (np.abs(wy - seg[1]) < 0.05) & (wx > min(seg[0], seg[2])) & (wx < max(seg[0], seg[2]))
+        if on.sum() >= 4:
+            blocks.append((i, bag.scans[i][np.nonzero(on)[0][:per_scan]]))
+    return seg.astype(np.float32), blocks
+
+
+CPU_SYSTEMS = [(12, 3), (48, 10), (200, 10)]  # scans / window: the issue's table
+
+
+def oracle_graph(n_scans, window):
+    """The PoseGraph of the table's systems on the oracle's backend: SynthBag(dense=True), LIDARNormalResidual blocks, one loop
+    closure between the ends, one HITL constraint over every third scan.  Returns (graph, bag)."""
+    from nautilus_amd import csm, synth
+    bag = synth.SynthBag(n_scans, dense=True)
+    xy, off = csm.pack_scans(bag.scans)
+    nrm = np.concatenate(bag.normals).astype(np.float32)
+    pg = posegraph.PoseGraph(xy, nrm, off, bag.odom, window=window, kind=_lib.NHIP_LIDAR_NORMAL, backend=RowsBackend())
+    pg.add_loop_closures([n_scans - 1], [0], [bag.true_relative(n_scans - 1, 0)])
+    pg.add_hitl(RowsHitl(*wall_blocks(bag)))
+    return pg, bag
+
+
+def graph_rows(pg, poses, lines, research=True):
+    """(u, v, rows) of a graph on a host backend, in the order PoseGraph joins them on the device: ICP blocks, odometry
+    factors, loop closures, each HITL constraint's blocks."""
+    pg.icp.set_poses(poses)
+    if research:
+        pg.icp.search()
+    u, v, rows = [pg.icp.block_src], [pg.icp.block_tgt], [np.asarray(pg.icp.normal_equations(pg.kind))]
+    for fac in (pg.odo, pg.lc):
+        if fac is not None:
+            u.append(fac.pose_i)
+            v.append(fac.pose_j)
+            rows.append(odometry_rows(*fac.evaluate(pg.backend, poses)))
+    for c, con in enumerate(pg.hitl):
+        u.append(con.block_pose)
+        v.append(np.full(con.n_blocks, pg.n + c))
+        rows.append(pg.backend.point_to_line_normal_eq(con, poses, lines, c))
+    return np.concatenate(u), np.concatenate(v), np.concatenate(rows)
