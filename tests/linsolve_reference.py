@@ -73,13 +73,14 @@ def odometry_rows(r, ji, jj):
 
 
 # ------------------------------------------------------------------------------------------------ PCG
-def pcg_matrix(A, b, tol, max_iters, precond="block"):
+def pcg_matrix(A, b, tol, max_iters, precond="block", trace=None):
     """Preconditioned CG on the sparse SPD matrix A (3 n x 3 n) exactly as nhip_bsr_pcg_dev states it: x = 0, r = b,
     z = M^-1 r; with k iterations complete: beta = r.z / (the r.z before) (k > 0), a non-finite r.r, r.z or beta is a
     breakdown (flag 2), ||r|| <= tol ||b|| ends the solve (flag 0), k == max_iters too (flag 1); else p = z + beta p
     (p = z at k = 0), q = A p, breakdown (flag 2) if p.q <= 0 or p.q or alpha = r.z / p.q is not finite, x += alpha p,
     r -= alpha q, z = M^-1 r.  M: the 3 x 3 diagonal blocks ("block"), the diagonal ("scalar") or I ("none").
-    Returns (x, iterations, ||r|| / ||b||, flag)."""
+    Returns (x, iterations, ||r|| / ||b||, flag).  A list given as `trace` receives (x, ||r|| / ||b||) with k = 0, 1, ...
+    iterations complete: entry k is what max_iters = k returns with flag 1."""
     A = A.tocsr()
     n = A.shape[0]
     b = np.asarray(b, dtype=np.float64)
@@ -106,6 +107,8 @@ def pcg_matrix(A, b, tol, max_iters, precond="block"):
     with np.errstate(all="ignore"):
         while True:
             beta = np.float64(rz) / np.float64(rz_old) if k > 0 else 0.0
+            if trace is not None:
+                trace.append((x, rel(rr)))  # (x is rebound below, never written in place)
             if not (np.isfinite(rr) and np.isfinite(rz) and np.isfinite(beta)):
                 return x, k, rel(rr), 2
             if np.sqrt(rr) <= tol * np.sqrt(bb):
@@ -122,6 +125,44 @@ def pcg_matrix(A, b, tol, max_iters, precond="block"):
             r = r - alpha * q
             z = apply(r)
             rr, rz_old, rz, k = float(r @ r), rz, float(r @ z), k + 1
+
+
+def pcg_matrix_longdouble(A, b, max_iters):
+    """pcg_matrix(A, b, 0, max_iters, "block") with every product and sum in longdouble: [(x, ||r|| / ||b||)] with
+    k = 0 .. max_iters iterations complete.  The preconditioner blocks are inverted in float64 and refined by one Newton step
+    X (2 I - D X) in longdouble (the float64 inverse's relative error, squared).  What the float64 restatement's iterates are
+    measured against (tests/test_linsolve_seams_cpu.py)."""
+    A = A.tocoo()
+    A.sum_duplicates()
+    n = A.shape[0]
+    data, b = A.data.astype(LD), np.asarray(b, dtype=LD)
+
+    def mv(p):
+        out = np.zeros(n, dtype=LD)
+        np.add.at(out, A.row, data * p[A.col])
+        return out
+    on = A.row // 3 == A.col // 3
+    D = np.zeros((n // 3, 3, 3), dtype=LD)
+    D[A.row[on] // 3, A.row[on] % 3, A.col[on] % 3] = data[on]
+    X = np.linalg.inv(D.astype(np.float64)).astype(LD)
+    X = np.einsum("bij,bjk->bik", X, 2 * np.eye(3, dtype=LD) - np.einsum("bij,bjk->bik", D, X))
+    apply = lambda r: np.einsum("bij,bj->bi", X, r.reshape(-1, 3)).ravel()
+    dot = lambda a, c: np.sum(a * c)
+    x, r = np.zeros(n, dtype=LD), b.copy()
+    z = apply(r)
+    p, bb = z, dot(b, b)
+    rr, rz, out = bb, dot(r, z), []
+    for k in range(max_iters + 1):
+        out.append((x, np.sqrt(rr) / np.sqrt(bb)))
+        if k == max_iters:
+            break
+        q = mv(p)
+        alpha = rz / dot(p, q)
+        x, r = x + alpha * p, r - alpha * q
+        z = apply(r)
+        rr, rz_old, rz = dot(r, r), rz, dot(r, z)
+        p = z + (rz / rz_old) * p
+    return out
 
 
 def damped(st, values, fixed, lam, diag_floor):
@@ -142,6 +183,25 @@ def pcg(st, values, grad, fixed, lam, diag_floor=1e-9, tol=1e-10, max_iters=1000
     x = np.zeros(3 * st.n_blocks)
     x[free] = xf
     return x, k, rel, flag
+
+
+def pcg_iterates(st, values, grad, fixed, lam, diag_floor, k_max, longdouble=False):
+    """[(x (3 n_blocks,), ||r|| / ||b||)] of the block-Jacobi PCG with k = 0 .. k_max iterations complete: entry k is
+    pcg(..., tol=0, max_iters=k)'s x and residual (one run; pcg_matrix's trace), or the longdouble restatement's."""
+    A, free = damped(st, values, fixed, lam, diag_floor)
+    b = -np.asarray(grad)[free]
+    if longdouble:
+        trace = pcg_matrix_longdouble(A, b, k_max)
+    else:
+        trace = []
+        _, k, _, flag = pcg_matrix(A, b, 0.0, k_max, trace=trace)
+        assert (k, flag) == (k_max, 1) and len(trace) == k_max + 1, "the reference ended before %d iterations" % k_max
+    out = []
+    for xf, rel in trace:
+        x = np.zeros(3 * st.n_blocks, dtype=xf.dtype)
+        x[free] = xf
+        out.append((x, rel))
+    return out
 
 
 def true_relative_residual(st, values, grad, fixed, lam, diag_floor, x):

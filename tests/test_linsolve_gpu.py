@@ -11,6 +11,7 @@ import pytest
 
 from nautilus_amd import _lib, hostside, linsolve, posegraph
 from tests import linsolve_reference as LR
+from tests.linsolve_seams import check_pcg
 
 pytestmark = pytest.mark.gpu
 
@@ -75,7 +76,7 @@ def odometry_on_device(poses, pi, pj, t, r, tw=1.5, rw=0.75):
     return d_out.cpu().numpy(), want
 
 
-@pytest.mark.parametrize("n", [0, 1, 65])
+@pytest.mark.parametrize("n", [0, 1, 65, 256, 257])
 def test_odometry_rows_are_bit_equal_to_numpy_on_the_kernels_own_jacobians(gpu, n):
     out, want = odometry_on_device(*odometry_case(n))
     assert np.array_equal(_bits(out[:28 * n]), _bits(want.ravel()))
@@ -182,21 +183,6 @@ def arrow(backend):
     nb, u, v = assembly_cases()["arrow"]
     st, system, values, grad, cost = assembled(backend, nb, u, v, LR.random_rows(u, 7))
     return st, system, values, grad
-
-
-def check_pcg(st, system, values, grad, fixed, what):
-    """The residual, iteration-cap and fixed-block checks every PCG system gets.  Returns the reference's count."""
-    x, res = system.solve(LAM, FLOOR, TOL, 5000)
-    k_ref = LR.pcg(st, values, grad, fixed, LAM, FLOOR, TOL, 5000)[1]
-    true = LR.true_relative_residual(st, values, grad, fixed, LAM, FLOOR, x)
-    print("PCG %s: %r, k_ref %d (cap %d), true residual / tol %.3g" % (what, res, k_ref, LR.iteration_cap(k_ref), true / TOL))
-    assert res.flag == 0 and res.relative_residual <= TOL
-    assert true <= 10 * TOL
-    assert res.iterations <= LR.iteration_cap(k_ref)
-    for b in fixed:
-        assert np.array_equal(_bits(x[3 * b:3 * b + 3]), _bits(np.zeros(3))), "x is exactly 0 on a fixed block"
-    assert np.abs(x).max() > 0
-    return k_ref
 
 
 def test_pcg_on_the_arrow_system(arrow):
