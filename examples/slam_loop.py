@@ -5,7 +5,8 @@
   synthetic 1081-beam bag
   -> growing-window ICP solve, windows 1..10     Solver::OptimizeOverGrowingWindow   solver.cc:335-356
   -> loop-closure candidates                     LCCandidateFilter (scatter score, GPU) + geometric pair gate
-                                                 (lc_candidate_filter.cc:35-81, in place of lc_matcher.cc:28-74)
+                                                 (lc_candidate_filter.cc:35-81, in place of lc_matcher.cc:28-74),
+                                                 or --lc-gate chi-square: LCMatcher's own covariance gate
   -> batched correlative scan matching           GetRelativeTransform                solver.cc:630-649
   -> loop-closure constraints + re-solve         AddLCConstraints (TODO body)         solver.cc:651-673
   -> a HITL message (two segments on one wall)   HitlCallback: GetRelevantPosesForHITL, AddHITLResiduals, SolveSLAM
@@ -55,7 +56,7 @@ LC_MIN_SEPARATION = 20  # nodes between the two scans of a loop-closure pair (th
 def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, verbose=False, residual="normal",
         rank=0, world=1, device="cuda:0", backend=None, iterations=4, hitl=True, cell_bits=16, gate="scatter",
         min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False, normals="bag", lc_submap=0,
-        linear_solver="host"):
+        linear_solver="host", lc_gate="geometric", lc_max_score=5000.0):
     """min_scatter_score: LCCandidateFilter's threshold is 0.70 (lc_candidate_filter.cc:76); scans of the synthetic
     24 m x 16 m room score ~0.4, so callers on that world pass a lower one.
     hitl_device: the HITL constraint's points are selected and packed on the GPU (hitl.select, under the "path" clock) and
@@ -70,6 +71,12 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     its target's submap.  Not with world > 1.
     linear_solver: "host" -- every solve's linear step in scipy on downloaded rows -- or "device": assembled and solved on the
     GPU by block-Jacobi PCG (PoseGraph.solve; needs hitl_device for the HITL phase).
+    lc_gate: "geometric" -- the distance-and-separation pair gate -- or "chi-square": LCMatcher's own walk (GetPossibleMatches,
+    lc_matcher.cc:59-74), every candidate scan as source against the others by hostside.lc_possible_matches, the covariance
+    blocks of all those pairs from ONE PoseGraph.cross_covariances(linear_solver=linear_solver) call and the scores from the
+    backend's chi_square_gate; what it keeps is intersected with the geometric gate's separation rule (the later scan is the
+    source, more than 20 nodes apart).  Needs gate "scatter".  lc_max_score: the test's threshold (LCMatcher's 5000: on the
+    synthetic room, whose dense scans pin every pose to a fraction of a millimetre, that keeps nothing).
     With world > 1 (one process per GPU under torch.distributed): the window ICP solve is replicated -- its
     consumer, the solver, is host-side -- and the loop-closure pairs are sharded by target across the ranks,
     matched, and all-gathered (nautilus_amd/sharding.py); every rank ends with the same trajectory."""
@@ -87,6 +94,8 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     if normals not in ("bag", "device"):
         raise ValueError("run: normals %r" % (normals,))
     lc_submap = int(lc_submap)
+    if lc_gate not in ("geometric", "chi-square") or (lc_gate == "chi-square" and gate != "scatter"):
+        raise ValueError("run: lc_gate %r (\"geometric\", or \"chi-square\" with gate \"scatter\")" % (lc_gate,))
     if not 0 <= lc_submap < LC_MIN_SEPARATION:
         raise ValueError("run: lc_submap %d: a submap radius is >= 0 and below the pair gate's minimum separation (%d)"
                          % (lc_submap, LC_MIN_SEPARATION))
@@ -138,8 +147,31 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         cand = hostside.lc_candidates_from_scores(poses, scores, min_score=min_scatter_score)
         # ... then the pair gate: |dt| < lc_base_max_range (3.5 m, default_config.lua:122) on the current estimate and
         # more than 20 nodes apart (geometric stand-in for LCMatcher's per-pair ceres::Covariance, lc_matcher.cc:28-74)
-        with posegraph.clocked("path"):
-            src, tgt = hostside.geometric_pair_gate(poses, cand, max_range=3.5, min_separation=LC_MIN_SEPARATION, backend=backend)
+        if lc_gate == "geometric":
+            with posegraph.clocked("path"):
+                src, tgt = hostside.geometric_pair_gate(poses, cand, max_range=3.5, min_separation=LC_MIN_SEPARATION, backend=backend)
+        else:
+            t1 = time.perf_counter()
+            pairs = [(int(s_), int(c)) for s_ in cand for c in cand if c != s_]
+            cov = dict(zip(pairs, pg.cross_covariances(pairs, linear_solver=linear_solver))) if pairs else {}
+            cov_fn = lambda ps: np.stack([cov[(int(s_), int(c))] for s_, c in ps])
+            kept = []
+            for s_ in cand:
+                with posegraph.clocked("path"):
+                    matches = hostside.lc_possible_matches(s_, cand, poses, cov_fn, max_score=lc_max_score, backend=backend)
+                kept += [(s_, c) for c in matches if s_ - c > LC_MIN_SEPARATION]
+            src = np.array([p[0] for p in kept], dtype=np.int32)
+            tgt = np.array([p[1] for p in kept], dtype=np.int32)
+            out["lc_gate"], out["lc_gate_s"], out["lc_gate_pairs"] = lc_gate, time.perf_counter() - t1, len(kept)
+            out["lc_gate_pairs_walked"], out["lc_gate_max_score"] = len(pairs), float(lc_max_score)
+            if linear_solver == "device":
+                its, batches = pg.covariance_stats["iterations"], pg.covariance_stats["batches"]
+                out["lc_gate_pcg"] = {"systems": pg.covariance_stats["systems"], "batches": len(batches),
+                                      "iterations_min_median_max": [int(np.min(its)), float(np.median(its)), int(np.max(its))] if its else None,
+                                      "not_converged": int(sum(f != 0 for f in pg.covariance_stats["flags"])),
+                                      "solve_s": float(sum(b[2] for b in batches)),
+                                      "us_per_iteration_per_batch": [1e6 * b[2] / max(b[1], 1) for b in batches]}
+            pcg_phase("lc_gate")
         out["lc_candidate_scans"] = len(cand)
     else:
         idx = np.arange(n_scans)
@@ -273,6 +305,11 @@ if __name__ == "__main__":
     ap.add_argument("--linear-solver", choices=["host", "device"], default="host",
                     help="the linear step of every solve: scipy on the host, or block-Jacobi PCG on the GPU (with HITL: "
                          "needs --hitl-device)")
+    ap.add_argument("--lc-gate", choices=["geometric", "chi-square"], default="geometric",
+                    help="the loop-closure pair gate: distance and separation, or LCMatcher's chi-square test on the cross-covariance "
+                         "blocks of the pose graph (PoseGraph.cross_covariances with --linear-solver's solver), intersected with "
+                         "the separation rule")
+    ap.add_argument("--lc-max-score", type=float, default=5000.0, help="the chi-square gate's threshold (lc_matcher.cc:66: 5000)")
     ap.add_argument("-v", action="store_true")
     a = ap.parse_args()
     if not 0 <= a.lc_submap < LC_MIN_SEPARATION:
@@ -293,7 +330,7 @@ if __name__ == "__main__":
         os.dup2(saved, 1)
     res = run(a.scans, a.window, verbose=a.v and rank == 0, residual=a.residual, rank=rank, world=world,
               device="cuda:%d" % local, hitl_device=a.hitl_device, normals=a.normals, lc_submap=a.lc_submap,
-              linear_solver=a.linear_solver)
+              linear_solver=a.linear_solver, lc_gate=a.lc_gate, lc_max_score=a.lc_max_score)
     res["world_size"] = world
     if rank == 0:
         print(json.dumps(res))

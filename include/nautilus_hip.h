@@ -65,7 +65,8 @@ const char *nhip_version(void);
  * 16 pose index of a block, 32 scan id of a correspondence-search block, 64 feature index and 128 feature count of
  * nhip_features_pack_dev, 256 scan offset of nhip_normals_estimate_dev, 512 member scan id and 1024 merged point count beyond
  * the capacity of nhip_submaps_gather_dev, 2048 contributor id of nhip_bsr_assemble_dev, 4096 block column of
- * nhip_bsr_assemble_dev / nhip_bsr_pcg_dev.  Clears the record (in the order of `stream`).
+ * nhip_bsr_assemble_dev / nhip_bsr_pcg_dev / nhip_bsr_pcg_columns_dev, 8192 gauge or right-hand-side index of
+ * nhip_bsr_pcg_columns_dev.  Clears the record (in the order of `stream`).
  * ONE record per DEVICE, shared by every stream and host thread that uses the library on it: a host with several streams
  * on one device learns THAT an id was bad and which, not on which stream; a call that finds a record consumes it -- reports
  * of kernels still running on OTHER streams at that moment can be reported by this call or wiped by its clear.  Clients
@@ -473,6 +474,32 @@ int nhip_bsr_pcg_dev(const int32_t *d_row_ptr, const int32_t *d_col, const doubl
                      const uint8_t *d_fixed, int32_t n_blocks, int32_t nnzb, double lambda, double diag_floor, double tol,
                      int32_t max_iters, int32_t check_every, double *d_x, void *d_workspace, int64_t workspace_bytes,
                      nhip_pcg_stats_t *stats, void *stream);
+
+/* K12: columns of the inverse -- n_systems systems on ONE matrix.  System s solves (H + ridge * I) x = e_j, j = d_rhs_index[s]
+ * a scalar index in [0, 3 * n_blocks), over the FREE blocks of s: every block with d_fixed[b] == 0 except block d_gauge[s]
+ * (-1: none).  ridge >= 0 is added to every diagonal entry; there is no lambda term.  Each system runs nhip_bsr_pcg_dev's
+ * algorithm on its own -- x = 0 at the start, the preconditioner the inverse of every ridged diagonal block (zero for a block
+ * that is not free), the same end tests and flags, a breakdown before x is touched -- with its own scalars, end words, count
+ * and residual; systems end at different iterations and a system that has ended is never written again.  j in a block that
+ * is not free: x = 0, 0 iterations, flag 0, residual 0.
+ * d_x: 3 * n_blocks * n_systems doubles, SYSTEM-MINOR -- element e of system s at d_x[e * n_systems + s]; exactly 0 on the
+ * blocks that are not free.  stats: n_systems entries in host memory.
+ * Two launches per iteration serve every system (a stored block is read once per 64 systems).  No floating-point atomics;
+ * every dot product is summed in an order that depends on n_blocks alone: the bits of a system's x, its count, flag and
+ * residual are the same in every run and do NOT depend on n_systems, on the system's place in the batch or on the other
+ * systems of the batch -- a caller may split a list into chunks freely.  Like nhip_bsr_pcg_dev the call reads device memory
+ * between its launches (one word per `check_every` iterations: the number of systems still running; x and stats do not depend
+ * on check_every), returns with the stream drained and cannot be captured into a graph.
+ * A d_gauge[s] outside [-1, n_blocks) or a d_rhs_index[s] outside [0, 3 * n_blocks) is never used as an index: that system is
+ * x = 0, 0 iterations, flag 2, and nhip_dev_status() reports it (kind 8192, index = s).  A block column outside [0, n_blocks)
+ * is skipped and reported (kind 4096).  Rows of any length are taken by one lane per system: a free block row of L stored
+ * blocks costs its wave L dependent steps.  d_workspace: nhip_bsr_pcg_columns_workspace_bytes(...) bytes, 16-byte aligned.
+ * 3 * n_blocks * n_systems must not exceed 2^31 - 1.  n_systems == 0 or n_blocks == 0: NHIP_OK, nothing launched. */
+int64_t nhip_bsr_pcg_columns_workspace_bytes(int32_t n_blocks, int32_t nnzb, int32_t n_systems);
+int nhip_bsr_pcg_columns_dev(const int32_t *d_row_ptr, const int32_t *d_col, const double *d_values, const uint8_t *d_fixed,
+                             int32_t n_blocks, int32_t nnzb, const int32_t *d_gauge, const int32_t *d_rhs_index,
+                             int32_t n_systems, double ridge, double tol, int32_t max_iters, int32_t check_every, double *d_x,
+                             void *d_workspace, int64_t workspace_bytes, nhip_pcg_stats_t *stats, void *stream);
 
 /* K5: correspondence search, the step that feeds K4 (Solver::GetPointToPointMatching,
  * src/optimization/solver.cc:132-172; KDTree::FindNearestPoint, src/util/kdtree.cc:253-305).

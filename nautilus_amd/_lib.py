@@ -140,6 +140,9 @@ PROTOTYPES = {
     "nhip_bsr_pcg_workspace_bytes": (_i64, [_i32, _i32]),
     "nhip_bsr_pcg_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64, _f64, _i32, _i32, _vp, _vp, _i64,
                                    _P(PcgStats), _vp]),
+    "nhip_bsr_pcg_columns_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "nhip_bsr_pcg_columns_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _f64, _f64, _i32, _i32, _vp, _vp, _i64,
+                                           _P(PcgStats), _vp]),
     "nhip_scans_upload": (C.c_int, [_vp, _vp, _i32, _P(_vp)]),
     "nhip_scans_free": (C.c_int, [_vp]),
     "nhip_grids_build": (C.c_int, [_vp, _vp, _i32, _P(GridSpec), _P(_vp)]),

@@ -53,7 +53,8 @@ struct IdBounds {          // (plain data: it travels inside the kernels' parame
 };
 constexpr uint32_t BAD_TARGET_ID = 1u, BAD_PAIR_SRC = 2u, BAD_PAIR_SLOT = 4u, BAD_BLOCK_ID = 8u, BAD_POSE_ID = 16u,
                    BAD_SCAN_ID = 32u, BAD_FEATURE_IDX = 64u, BAD_FEATURE_COUNT = 128u, BAD_SCAN_OFFSETS = 256u,
-                   BAD_MEMBER_ID = 512u, BAD_SUBMAP_CAPACITY = 1024u, BAD_CONTRIB_ID = 2048u, BAD_BLOCK_COLUMN = 4096u;
+                   BAD_MEMBER_ID = 512u, BAD_SUBMAP_CAPACITY = 1024u, BAD_CONTRIB_ID = 2048u, BAD_BLOCK_COLUMN = 4096u,
+                   BAD_SYSTEM_ID = 8192u;
 constexpr int DEV_STATUS_WORDS = 4;  // {OR of the kinds seen, kind / value / index of the first report}
 uint32_t *dev_status();              // of the current device (allocated on the device's first use; null if that failed)
 #ifdef __HIPCC__
@@ -388,5 +389,15 @@ int64_t bsr_pcg_workspace_bytes(int32_t nb, int32_t nnzb);
 int launch_bsr_pcg(const int32_t *d_row_ptr, const int32_t *d_col, const double *d_values, const double *d_grad,
                    const uint8_t *d_fixed, int32_t nb, int32_t nnzb, double lambda, double diag_floor, double tol,
                    int32_t first, int32_t last, bool final, double *d_x, void *d_ws, hipStream_t s);
+// columns of the inverse: S systems (H + ridge I) x = e_j on one matrix, each with a block of its own held constant
+// (nhip_linsolve_columns.hip, K12); launch_bsr_pcg_columns enqueues like launch_bsr_pcg; bsr_pcg_columns_read waits for the
+// stream and brings down the number of systems still running and, where `iters` is given, every system's end words
+int64_t bsr_pcg_columns_workspace_bytes(int32_t nb, int32_t nnzb, int32_t n_systems);
+int launch_bsr_pcg_columns(const int32_t *d_row_ptr, const int32_t *d_col, const double *d_values, const uint8_t *d_fixed,
+                           int32_t nb, int32_t nnzb, const int32_t *d_gauge, const int32_t *d_rhs_index, int32_t n_systems,
+                           double ridge, double tol, int32_t first, int32_t last, bool final, double *d_x, void *d_ws,
+                           hipStream_t s);
+int bsr_pcg_columns_read(const void *d_ws, int32_t nb, int32_t n_systems, int32_t *n_active, int32_t *iters, int32_t *flag,
+                         double *relres, hipStream_t s);
 
 }  // namespace nhip

@@ -2,14 +2,16 @@
 
   BlockStructure   the block-sparse pattern of a graph, built ONCE per graph on the host in numpy from the (u, v) unknown
                    blocks of its 28-double rows: what nhip_bsr_assemble_dev and nhip_bsr_pcg_dev take
-  DeviceSystem     the device arrays of one structure -- values, gradient, x, the PCG workspace -- and the two calls
-                   (HipBackend.device_system makes one)
+  DeviceSystem     the device arrays of one structure -- values, gradient, x, the PCG workspace -- and the calls: assemble,
+                   solve, and inverse_columns (many unit right-hand sides on the assembled matrix, each system with a gauge
+                   block of its own: nhip_bsr_pcg_columns_dev)  (HipBackend.device_system makes one)
 
 Unknown blocks are 3 wide.  Row r couples blocks u[r] != v[r]; its 6 x 6 is ordered [u | v] and lands in four stored
 blocks: quadrant 0 in (u, u), 1 in (u, v), 2 (= 1 transposed) in (v, u), 3 in (v, v).  The full symmetric pattern is stored,
 so the matrix-vector product needs no transposed pass.
 """
 import ctypes as C
+import time
 
 import numpy as np
 
@@ -83,9 +85,20 @@ class DeviceSystem:
         self.set_fixed(fixed)
 
     def set_fixed(self, blocks):
+        """The blocks held constant by solve and inverse_columns from now on (ValueError for a block outside the structure)."""
+        blocks = np.asarray(list(blocks), dtype=np.int64).reshape(-1)
+        if len(blocks) and (blocks.min() < 0 or blocks.max() >= self.st.n_blocks):
+            raise ValueError("set_fixed: block %d outside [0, %d)" % (
+                blocks[(blocks < 0) | (blocks >= self.st.n_blocks)][0], self.st.n_blocks))
         mask = np.zeros(max(self.st.n_blocks, 1), dtype=np.uint8)
-        mask[np.asarray(list(blocks), dtype=np.int64)] = 1
+        mask[blocks] = 1
+        self._fixed = tuple(int(b) for b in np.nonzero(mask[:self.st.n_blocks])[0])
         self.d_fixed = self.torch.from_numpy(mask).to(self.dev)
+
+    @property
+    def fixed(self):
+        """The blocks of the current mask, ascending (what set_fixed takes back)."""
+        return self._fixed
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
@@ -121,6 +134,52 @@ class DeviceSystem:
         x = self.d_x[:3 * st.n_blocks].cpu().numpy()
         check(self.lib.nhip_dev_status(sp, None))
         return x, PcgResult(stats.iterations, stats.flag, stats.relative_residual)
+
+    def inverse_columns(self, gauge, rhs_index, ridge=1e-12, tol=1e-10, max_iters=None, check_every=32, max_bytes=1 << 30):
+        """Columns of inverses of the matrix the last assemble left on the device (nhip_bsr_pcg_columns_dev): system s solves
+        (H + ridge I) x = e_j, j = rhs_index[s], over the blocks that are neither in the fixed mask nor block gauge[s] (-1:
+        none), by the block-Jacobi PCG of solve.  Returns (x, [PcgResult]): x a (3 n_blocks, S) float64 DEVICE tensor, column
+        s the solution of system s (zero on the blocks that are not free).  The systems are solved in chunks so that one
+        call's x and workspace stay within max_bytes (at least one system per call); a system's bits do not depend on the
+        chunking.  .column_batches lists the calls: (systems, the iterations of the slowest, seconds)."""
+        st, torch = self.st, self.torch
+        gauge = np.ascontiguousarray(gauge, dtype=np.int32).reshape(-1)
+        rhs_index = np.ascontiguousarray(rhs_index, dtype=np.int32).reshape(-1)
+        if len(gauge) != len(rhs_index):
+            raise ValueError("inverse_columns: %d gauges for %d right-hand sides" % (len(gauge), len(rhs_index)))
+        if max_iters is None:
+            max_iters = max(200, 3 * st.n_blocks)
+        S, n3 = len(gauge), 3 * st.n_blocks
+        x = torch.zeros((n3, S), dtype=torch.float64, device=self.dev)
+        results, self.column_batches = [], []
+        if S == 0 or n3 == 0:
+            return x, results
+        need = lambda n: int(self.lib.nhip_bsr_pcg_columns_workspace_bytes(st.n_blocks, st.nnzb, n))
+        chunk = S
+        while chunk > 1 and need(chunk) + 8 * n3 * chunk > max_bytes:
+            chunk = (chunk + 1) // 2
+        chunk = min(chunk, max((2 ** 31 - 1) // n3, 1))
+        sp = self._stream()
+        for s0 in range(0, S, chunk):
+            n = min(chunk, S - s0)
+            d_gauge = torch.from_numpy(gauge[s0:s0 + n]).to(self.dev)
+            d_rhs = torch.from_numpy(rhs_index[s0:s0 + n]).to(self.dev)
+            whole = n == S
+            d_x = x if whole else torch.empty((n3, n), dtype=torch.float64, device=self.dev)
+            ws_bytes = need(n)
+            d_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.dev)
+            stats = (_lib.PcgStats * n)()
+            t0 = time.perf_counter()
+            check(self.lib.nhip_bsr_pcg_columns_dev(self.d_row_ptr.data_ptr(), self.d_col.data_ptr(), self.d_values.data_ptr(),
+                                                    self.d_fixed.data_ptr(), st.n_blocks, st.nnzb, d_gauge.data_ptr(),
+                                                    d_rhs.data_ptr(), n, float(ridge), float(tol), int(max_iters),
+                                                    int(check_every), d_x.data_ptr(), d_ws.data_ptr(), ws_bytes, stats, sp))
+            self.column_batches.append((n, max(r.iterations for r in stats), time.perf_counter() - t0))  # (returns drained)
+            if not whole:
+                x[:, s0:s0 + n] = d_x
+            results += [PcgResult(r.iterations, r.flag, r.relative_residual) for r in stats]
+        check(self.lib.nhip_dev_status(sp, None))
+        return x, results
 
     def download(self):
         """(values (nnzb, 3, 3), grad (3 n_blocks,), cost) on the host."""

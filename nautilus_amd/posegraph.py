@@ -440,6 +440,7 @@ class PoseGraph:
         self.lc = None
         self.hitl = []
         self.linear_stats = {k: 0 for k in LINEAR_STATS}  # of this graph's solve(linear_solver="device") calls
+        self.covariance_stats = {"systems": 0, "iterations": [], "flags": [], "batches": []}  # of the last cross_covariances("device")
         self._device = None  # (what the system was built from, DeviceSystem): the structure is fixed once the graph is
         # odometry factors always come from `odom`; the estimate may start elsewhere (previous window pass)
         self.poses = np.array(odom if initial is None else initial, dtype=np.float64)
@@ -532,17 +533,30 @@ class PoseGraph:
     def _lines(self):
         return np.array([c.chosen_line_pose for c in self.hitl], dtype=np.float64).reshape(-1, 3)
 
-    def cross_covariances(self, pairs):
+    def cross_covariances(self, pairs, linear_solver="host", dtype=np.float32, cg_tol=1e-10):
         """Covariance blocks the way LCMatcher asks Ceres for them (GetCovarianceMatrix,
         lc_matcher.cc:28-46): the (source pose, target pose) cross block of (J^T J)^-1 of the current
         problem with the pose just before the earlier of the two held constant instead of pose 0;
-        returns the top-left 2 x 2 (translation) of each 3 x 3 block, float32 like the reference.
-        J^T J comes from the backend's per-block normal equations; the sparse solves are host work."""
+        returns the top-left 2 x 2 (translation) of each 3 x 3 block, float32 like the reference
+        (dtype=np.float64: the blocks before that cast).
+        linear_solver "host": J^T J comes from the backend's per-block normal equations; the sparse solves are host
+        work, one factorisation per gauge.  "device": the system is evaluated and assembled on the GPU as for
+        solve(linear_solver="device") (the same backend and constraints are needed: TypeError otherwise) and the wanted
+        columns of all the gauged inverses come from ONE batched block-Jacobi PCG to ||r|| <= cg_tol ||b||
+        (linsolve.DeviceSystem.inverse_columns); four doubles per pair come down.  .linear_stats counts its systems,
+        .covariance_stats describes the last such call."""
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("cross_covariances: dtype %r (np.float32 or np.float64)" % (dtype,))
+        if linear_solver == "device":
+            return self._cross_covariances_device(pairs, cg_tol).astype(dtype)
+        if linear_solver != "host":
+            raise ValueError("cross_covariances: linear_solver %r (\"host\" or \"device\")" % (linear_solver,))
         import scipy.sparse as sp
         from scipy.sparse.linalg import splu
         H, _, _ = self._assemble(self.poses, self._lines(), research=False)
         H = H.tocsc()[:3 * self.n][:, :3 * self.n]
-        out = np.zeros((len(pairs), 2, 2), dtype=np.float32)
+        out = np.zeros((len(pairs), 2, 2), dtype=np.float64)
         by_gauge = {}
         for k, (s_, t_) in enumerate(pairs):
             by_gauge.setdefault(max(min(int(s_), int(t_)) - 1, 0), []).append(k)
@@ -559,7 +573,52 @@ class PoseGraph:
                 rhs[pos[3 * t_], 0] = 1.0
                 rhs[pos[3 * t_ + 1], 1] = 1.0
                 x = lu.solve(rhs)
-                out[k] = x[[pos[3 * s_], pos[3 * s_ + 1]], :].astype(np.float32)
+                out[k] = x[[pos[3 * s_], pos[3 * s_ + 1]], :]
+        return out.astype(dtype)
+
+    def _cross_covariances_device(self, pairs, cg_tol):
+        """cross_covariances' blocks in float64 from the device: two systems per distinct (gauge, target) -- the columns
+        3 t and 3 t + 1 of the inverse gauged there -- solved in one batch; pose 0 is free for this call, the HITL line
+        blocks are held constant (the host path's cut to the first 3 N unknowns); the mask is put back afterwards."""
+        system = self._device_system()
+        N, torch = self.n, self.backend.torch
+        index, gauge, rhs, take = {}, [], [], []  # (gauge, target) -> its first system; per pair with a block: (k, s, system)
+        for k, (s_, t_) in enumerate(pairs):
+            s_, t_ = int(s_), int(t_)
+            if not (0 <= s_ < N and 0 <= t_ < N):
+                raise ValueError("cross_covariances: pair (%d, %d) outside the %d poses" % (s_, t_, N))
+            g = max(min(s_, t_) - 1, 0)
+            if s_ == g or t_ == g:
+                continue  # a constant block has no covariance
+            if (g, t_) not in index:
+                index[(g, t_)] = len(gauge)
+                gauge += [g, g]
+                rhs += [3 * t_, 3 * t_ + 1]
+            take.append((k, s_, index[(g, t_)]))
+        out = np.zeros((len(pairs), 2, 2), dtype=np.float64)
+        self.covariance_stats = {"systems": len(gauge), "iterations": [], "flags": [], "batches": []}
+        if not take:
+            return out
+        held = system.fixed
+        system.set_fixed(range(N, N + len(self.hitl)))
+        try:
+            self._evaluate_device(system, self.poses, self._lines(), research=False)
+            with clocked("path"), clocked("path_linear"):
+                x, results = system.inverse_columns(gauge, rhs, tol=cg_tol)
+                rows = torch.tensor([[3 * s_, 3 * s_, 3 * s_ + 1, 3 * s_ + 1] for _, s_, _ in take], device=x.device)
+                cols = torch.tensor([[c, c + 1, c, c + 1] for _, _, c in take], device=x.device)
+                blocks = x[rows, cols].cpu().numpy()
+        finally:
+            system.set_fixed(held)
+        out[[k for k, _, _ in take]] = blocks.reshape(-1, 2, 2)
+        self.covariance_stats["iterations"] = [r.iterations for r in results]
+        self.covariance_stats["flags"] = [r.flag for r in results]
+        self.covariance_stats["batches"] = list(system.column_batches)  # (systems, iterations of the slowest, seconds) per call
+        for stats in (self.linear_stats, LINEAR_STATS):
+            stats["solves"] += len(results)
+            stats["iterations"] += sum(r.iterations for r in results)
+            stats["not_converged"] += sum(r.flag == 1 for r in results)
+            stats["breakdowns"] += sum(r.flag == 2 for r in results)
         return out
 
     def _device_system(self):
