@@ -375,7 +375,7 @@ int launch_resid_odometry_normal_eq(const float *d_t_odom, const float *d_r_odom
 
 // the block-sparse linear system of the pose graph (nhip_linsolve.hip, K11): assembly from 28-double rows, and the
 // block-Jacobi preconditioned CG; the arguments have passed the checks of nhip_host_linsolve.hip
-struct PcgStats {  // what pcg_state_kernel leaves in the workspace's first bytes for the host
+struct PcgStats {  // what the PCG kernels keep in the workspace's first bytes; the host reads it between batches and at the end
   int32_t done_a, done_b;  // set by the direction kernel / the update kernel once the solve has ended
   int32_t iterations, flag;
   double relres, bb;

@@ -11,7 +11,8 @@
 // partial per workgroup, written at a fixed index, and the NEXT kernel's prologue sums them in a fixed order, redundantly in
 // every workgroup.  No floating-point atomics anywhere: the same input gives the same bits.  alpha, beta and the end-of-solve
 // words live in the workspace; kernels enqueued after the end read the words and return.
-#include "nhip_common.h"
+// The method's step (the preconditioner, the scalars, the flags) is nhip_pcg.h's, shared with nhip_linsolve_columns.hip.
+#include "nhip_pcg.h"
 
 namespace nhip {
 
@@ -166,26 +167,21 @@ PcgWs pcg_ws(void *ws, int32_t nb) {
   W.st = reinterpret_cast<PcgStats *>(base);
   W.sc = reinterpret_cast<PcgScalars *>(base + 64);
   W.n_long = reinterpret_cast<int32_t *>(base + 128);
-  size_t o = 256;
   const size_t n3 = 3 * (size_t)nb;
   W.ga = (int32_t)((n3 + LT - 1) / LT);
   W.gb = (nb + LT - 1) / LT;
-  auto take = [&](size_t doubles) {
-    double *p = reinterpret_cast<double *>(base + o);
-    o += 8 * doubles;
-    return p;
-  };
-  W.minv = take(3 * n3);
-  W.r = take(n3);
-  W.z = take(n3);
-  W.q = take(n3);
-  W.p[0] = take(n3);
-  W.p[1] = take(n3);
-  W.longs = reinterpret_cast<int32_t *>(take(((size_t)nb + 1) / 2));
-  W.pq = take((size_t)W.ga + LONG_WGS);
-  W.rr = take((size_t)W.gb);
-  W.rz = take((size_t)W.gb);
-  W.bytes = o;
+  WsCarver c{base, 256, 8};
+  W.minv = c.take<double>(3 * n3);
+  W.r = c.take<double>(n3);
+  W.z = c.take<double>(n3);
+  W.q = c.take<double>(n3);
+  W.p[0] = c.take<double>(n3);
+  W.p[1] = c.take<double>(n3);
+  W.longs = c.take<int32_t>((size_t)nb);
+  W.pq = c.take<double>((size_t)W.ga + LONG_WGS);
+  W.rr = c.take<double>((size_t)W.gb);
+  W.rz = c.take<double>((size_t)W.gb);
+  W.bytes = c.o;
   return W;
 }
 
@@ -209,8 +205,15 @@ __device__ __forceinline__ double sum_partials(const double *__restrict__ part, 
   for (int32_t i = threadIdx.x; i < n; i += LT) v += part[i];
   return block_sum(v, s);
 }
-__device__ __forceinline__ bool finite(double v) { return fabs(v) <= 1.79769313486231570815e308; }  // (false for NaN)
-__device__ __forceinline__ int32_t clamp_end(int32_t v, int32_t nnzb) { return v < 0 ? 0 : v > nnzb ? nnzb : v; }
+
+// the end of the solve, written by its one owner thread: `done` is the end word of the kernel that saw it
+__device__ __forceinline__ void end_solve(PcgStats *st, int32_t k, int32_t flag, double relres, int32_t *done) {
+  st->iterations = k;
+  st->flag = flag;
+  st->relres = relres;
+  __threadfence();
+  *done = 1;
+}
 
 // Workgroups 0 .. gb - 1: one lane per block.  Workgroup gb: the list of long rows, ascending.
 __global__ __launch_bounds__(LT) void pcg_setup_kernel(const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
@@ -245,30 +248,14 @@ __global__ __launch_bounds__(LT) void pcg_setup_kernel(const int32_t *__restrict
     const bool fx = fixed[b] != 0;
     double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, r[3] = {0, 0, 0}, z[3] = {0, 0, 0};
     if (!fx) {
-      // the diagonal block: columns ascend within a row (a row without one has a zero diagonal block)
-      double d[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-      int32_t lo = clamp_end(row_ptr[b], nnzb), hi = clamp_end(row_ptr[b + 1], nnzb) - 1;
-      while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (col[mid] < b) lo = mid + 1; else hi = mid;
-      }
-      if (lo == hi && col[lo] == b) {
-#pragma unroll
-        for (int e = 0; e < 9; e++) d[e] = values[9 * (size_t)lo + e];
-      }
+      double d[9];
+      diag_block(row_ptr, col, values, b, nnzb, d);
 #pragma unroll
       for (int i = 0; i < 3; i++) d[4 * i] += lambda * (d[4 * i] + diag_floor);
-      const double c00 = d[4] * d[8] - d[5] * d[7], c01 = d[5] * d[6] - d[3] * d[8], c02 = d[3] * d[7] - d[4] * d[6];
-      const double inv = 1.0 / (d[0] * c00 + d[1] * c01 + d[2] * c02);
-      m[0] = c00 * inv; m[1] = (d[2] * d[7] - d[1] * d[8]) * inv; m[2] = (d[1] * d[5] - d[2] * d[4]) * inv;
-      m[3] = c01 * inv; m[4] = (d[0] * d[8] - d[2] * d[6]) * inv; m[5] = (d[2] * d[3] - d[0] * d[5]) * inv;
-      m[6] = c02 * inv; m[7] = (d[1] * d[6] - d[0] * d[7]) * inv; m[8] = (d[0] * d[4] - d[1] * d[3]) * inv;
+      invert3(d, m);
 #pragma unroll
       for (int i = 0; i < 3; i++) r[i] = -grad[3 * (size_t)b + i];
-#pragma unroll
-      for (int i = 0; i < 3; i++) z[i] = m[3 * i] * r[0] + m[3 * i + 1] * r[1] + m[3 * i + 2] * r[2];
-      vrr = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-      vrz = r[0] * z[0] + r[1] * z[1] + r[2] * z[2];
+      precondition(m, r, z, 1, &vrr, &vrz);
     }
 #pragma unroll
     for (int e = 0; e < 9; e++) W.minv[9 * (size_t)b + e] = m[e];
@@ -300,9 +287,8 @@ __global__ __launch_bounds__(LT) void pcg_setup_kernel(const int32_t *__restrict
 }
 
 // Iteration k's first kernel; `k` iterations are complete when it starts.  Every workgroup forms the same scalars from the
-// update kernel's partials: the end of the solve (non-finite scalar: flag 2; ||r|| <= tol ||b||: flag 0; `final`, the
-// closing launch behind max_iters iterations: flag 1) or beta.  Then q = A p with p = z + beta p_old formed where it is
-// loaded.  Workgroups 0 .. ga - 1: one lane per scalar row (a lane of a long row only writes its p); workgroups ga ..:
+// update kernel's partials (direction_step): the end of the solve or beta.  Then q = A p with p = z + beta p_old formed where
+// it is loaded.  Workgroups 0 .. ga - 1: one lane per scalar row (a lane of a long row only writes its p); workgroups ga ..:
 // the long rows in turn, a row's blocks dealt over the lanes, summed in a fixed order.
 // (The end words: done_a is written here by workgroup 0 alone and only when every workgroup of this launch has decided to
 //  return anyway -- they all evaluate the same partials -- so a workgroup that already reads it as set does what it would do.)
@@ -318,27 +304,19 @@ __global__ __launch_bounds__(LT) void pcg_direction_kernel(const int32_t *__rest
     if (st->done_a | st->done_b) return;
   }
   const double rr = sum_partials(W.rr, W.gb, s_sum), rz = sum_partials(W.rz, W.gb, s_sum);
-  const double bb = k == 0 ? rr : W.st->bb;
-  const double relres = bb > 0.0 ? sqrt(rr) / sqrt(bb) : (rr == 0.0 ? 0.0 : rr);
-  double beta = 0.0;
-  if (k > 0) beta = rz / W.sc[(k - 1) & 1].rz;
-  const bool broke = !finite(rr) || !finite(rz) || !finite(beta);
-  const bool converged = !broke && sqrt(rr) <= tol * sqrt(bb);
-  if (broke || converged || final) {
-    if (blockIdx.x == 0 && tid == 0) {
-      W.st->iterations = k;
-      W.st->flag = broke ? 2 : converged ? 0 : 1;
-      W.st->relres = relres;
-      __threadfence();
-      W.st->done_a = 1;
-    }
+  // (the first iteration has none before it: nothing is loaded, and the step ignores both)
+  const double bb_prev = k == 0 ? 0.0 : W.st->bb, rz_prev = k > 0 ? W.sc[(k - 1) & 1].rz : 0.0;
+  const DirectionStep d = direction_step(rr, rz, bb_prev, rz_prev, k, tol, final != 0);
+  if (d.ended) {
+    if (blockIdx.x == 0 && tid == 0) end_solve(W.st, k, d.flag, d.relres, &W.st->done_a);
     return;
   }
   if (blockIdx.x == 0 && tid == 0) {
     W.sc[k & 1].rz = rz;
-    W.sc[k & 1].relres = relres;
-    if (k == 0) W.st->bb = rr;
+    W.sc[k & 1].relres = d.relres;
+    if (k == 0) W.st->bb = d.bb;
   }
+  const double beta = d.beta;
   const double *__restrict__ z = W.z;
   const double *__restrict__ pold = W.p[(k + 1) & 1];
   double *__restrict__ pnew = W.p[k & 1];
@@ -420,8 +398,8 @@ __global__ __launch_bounds__(LT) void pcg_direction_kernel(const int32_t *__rest
   if (tid == 0) W.pq[blockIdx.x] = dot;
 }
 
-// Iteration k's second kernel, one lane per block: alpha = r . z / p . q (p . q <= 0 or a non-finite scalar: breakdown, flag 2,
-// before x is touched -- x stays the last iterate); x += alpha p, r -= alpha q, z = M^-1 r; the partials of r . r and r . z.
+// Iteration k's second kernel, one lane per block: alpha or a breakdown (update_step; x stays the last iterate); x += alpha p,
+// r -= alpha q, z = M^-1 r; the partials of r . r and r . z.
 // (done_b: written by workgroup 0 alone, under the same rule as the direction kernel's done_a.)
 __global__ __launch_bounds__(LT) void pcg_update_kernel(const uint8_t *__restrict__ fixed, int32_t nb, int32_t k,
                                                         double *__restrict__ x, PcgWs W) {
@@ -432,23 +410,17 @@ __global__ __launch_bounds__(LT) void pcg_update_kernel(const uint8_t *__restric
     if (st->done_a | st->done_b) return;
   }
   const double pq = sum_partials(W.pq, W.ga + LONG_WGS, s_sum);
-  const double rz = W.sc[k & 1].rz;
-  const double alpha = rz / pq;
-  if (!(pq > 0.0) || !finite(pq) || !finite(alpha)) {
-    if (blockIdx.x == 0 && tid == 0) {
-      W.st->iterations = k;
-      W.st->flag = 2;
-      W.st->relres = W.sc[k & 1].relres;
-      __threadfence();
-      W.st->done_b = 1;
-    }
+  const UpdateStep u = update_step(W.sc[k & 1].rz, pq);
+  const double alpha = u.alpha;
+  if (u.broke) {
+    if (blockIdx.x == 0 && tid == 0) end_solve(W.st, k, PCG_BREAKDOWN, W.sc[k & 1].relres, &W.st->done_b);
     return;
   }
   const int32_t b = blockIdx.x * LT + tid;
   double vrr = 0.0, vrz = 0.0;
   if (b < nb && !fixed[b]) {  // (a fixed block's x, r and z stay the zeros of the set-up)
     const double *p = W.p[k & 1] + 3 * (size_t)b, *q = W.q + 3 * (size_t)b, *m = W.minv + 9 * (size_t)b;
-    double r[3], z[3];
+    double r[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
       const size_t e = 3 * (size_t)b + i;
@@ -456,13 +428,7 @@ __global__ __launch_bounds__(LT) void pcg_update_kernel(const uint8_t *__restric
       r[i] = W.r[e] - alpha * q[i];
       W.r[e] = r[i];
     }
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-      z[i] = m[3 * i] * r[0] + m[3 * i + 1] * r[1] + m[3 * i + 2] * r[2];
-      W.z[3 * (size_t)b + i] = z[i];
-    }
-    vrr = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-    vrz = r[0] * z[0] + r[1] * z[1] + r[2] * z[2];
+    precondition(m, r, W.z + 3 * (size_t)b, 1, &vrr, &vrz);
   }
   vrr = block_sum(vrr, s_sum);
   vrz = block_sum(vrz, s_sum);

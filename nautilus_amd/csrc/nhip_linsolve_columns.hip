@@ -22,7 +22,8 @@
 // A system that has ended is never written again; its lanes idle through the barriers.  A workgroup returns early only when
 // all its systems had ended before the launch -- decided from ONE read of the end words, shared through LDS, so that the
 // four waves decide alike.
-#include "nhip_common.h"
+// The method's step (the preconditioner, the scalars, the flags) is nhip_pcg.h's, shared with nhip_linsolve.hip.
+#include "nhip_pcg.h"
 
 namespace nhip {
 
@@ -47,38 +48,30 @@ struct ColWs {
 };
 ColWs col_ws(void *ws, int32_t nb, int32_t S) {
   ColWs W;
-  char *base = static_cast<char *>(ws);
-  W.n_active = reinterpret_cast<int32_t *>(base);
-  size_t o = 256;
+  W.n_active = static_cast<int32_t *>(ws);
   const size_t s = (size_t)S, v = 3 * (size_t)nb * s;
   W.g = (nb + CB - 1) / CB;
-  auto take = [&](size_t bytes) {
-    char *p = base + o;
-    o += (bytes + 15) & ~(size_t)15;
-    return p;
-  };
-  W.ended = reinterpret_cast<int32_t *>(take(4 * s));
-  W.iters = reinterpret_cast<int32_t *>(take(4 * s));
-  W.flag = reinterpret_cast<int32_t *>(take(4 * s));
-  W.relres = reinterpret_cast<double *>(take(8 * s));
-  W.bb = reinterpret_cast<double *>(take(8 * s));
-  W.rz_at = reinterpret_cast<double *>(take(16 * s));
-  W.rel_at = reinterpret_cast<double *>(take(16 * s));
-  W.minv = reinterpret_cast<double *>(take(72 * (size_t)nb));
-  W.r = reinterpret_cast<double *>(take(8 * v));
-  W.z = reinterpret_cast<double *>(take(8 * v));
-  W.q = reinterpret_cast<double *>(take(8 * v));
-  W.p[0] = reinterpret_cast<double *>(take(8 * v));
-  W.p[1] = reinterpret_cast<double *>(take(8 * v));
-  W.pq = reinterpret_cast<double *>(take(8 * (size_t)W.g * s));
-  W.rr = reinterpret_cast<double *>(take(8 * (size_t)W.g * s));
-  W.rz = reinterpret_cast<double *>(take(8 * (size_t)W.g * s));
-  W.bytes = o;
+  WsCarver c{static_cast<char *>(ws), 256, 16};
+  W.ended = c.take<int32_t>(s);
+  W.iters = c.take<int32_t>(s);
+  W.flag = c.take<int32_t>(s);
+  W.relres = c.take<double>(s);
+  W.bb = c.take<double>(s);
+  W.rz_at = c.take<double>(2 * s);
+  W.rel_at = c.take<double>(2 * s);
+  W.minv = c.take<double>(9 * (size_t)nb);
+  W.r = c.take<double>(v);
+  W.z = c.take<double>(v);
+  W.q = c.take<double>(v);
+  W.p[0] = c.take<double>(v);
+  W.p[1] = c.take<double>(v);
+  W.pq = c.take<double>((size_t)W.g * s);
+  W.rr = c.take<double>((size_t)W.g * s);
+  W.rz = c.take<double>((size_t)W.g * s);
+  W.bytes = c.o;
   return W;
 }
 
-__device__ __forceinline__ bool finite(double v) { return fabs(v) <= 1.79769313486231570815e308; }  // (false for NaN)
-__device__ __forceinline__ int32_t clamp_end(int32_t v, int32_t nnzb) { return v < 0 ? 0 : v > nnzb ? nnzb : v; }
 // the wave's index as a value the compiler knows to be the same in every lane (what is loaded by it is loaded once per wave)
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
@@ -114,29 +107,6 @@ __device__ __forceinline__ void end_system(const ColWs &W, int32_t s, int32_t k,
   atomicSub(W.n_active, 1);
 }
 
-// the ridged diagonal block of row b (columns ascend within a row; a row without one has a zero diagonal block), inverted
-__device__ __forceinline__ void ridged_inverse(const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
-                                               const double *__restrict__ values, int32_t b, int32_t nnzb, double ridge,
-                                               double (&m)[9]) {
-  double d[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  int32_t lo = clamp_end(row_ptr[b], nnzb), hi = clamp_end(row_ptr[b + 1], nnzb) - 1;
-  while (lo < hi) {
-    const int32_t mid = (lo + hi) >> 1;
-    if (col[mid] < b) lo = mid + 1; else hi = mid;
-  }
-  if (lo == hi && col[lo] == b) {
-#pragma unroll
-    for (int e = 0; e < 9; e++) d[e] = values[9 * (size_t)lo + e];
-  }
-#pragma unroll
-  for (int i = 0; i < 3; i++) d[4 * i] += ridge;
-  const double c00 = d[4] * d[8] - d[5] * d[7], c01 = d[5] * d[6] - d[3] * d[8], c02 = d[3] * d[7] - d[4] * d[6];
-  const double inv = 1.0 / (d[0] * c00 + d[1] * c01 + d[2] * c02);
-  m[0] = c00 * inv; m[1] = (d[2] * d[7] - d[1] * d[8]) * inv; m[2] = (d[1] * d[5] - d[2] * d[4]) * inv;
-  m[3] = c01 * inv; m[4] = (d[0] * d[8] - d[2] * d[6]) * inv; m[5] = (d[2] * d[3] - d[0] * d[5]) * inv;
-  m[6] = c02 * inv; m[7] = (d[1] * d[6] - d[0] * d[7]) * inv; m[8] = (d[0] * d[4] - d[1] * d[3]) * inv;
-}
-
 // grid (g, ceil(S / CT)).  A gauge or a right-hand side outside its range is compared, never used as an index: the system is
 // zero, ended with flag 2, and reported.  Workgroup row 0 owns the systems' state and the count of running systems (zeroed by
 // the launcher in front of this kernel); system tile 0 writes the shared preconditioner.
@@ -156,7 +126,13 @@ __global__ __launch_bounds__(CLT) void columns_setup_kernel(const int32_t *__res
   for (int32_t b = blockIdx.x * CB + w; b < nb && b < (int32_t)(blockIdx.x + 1) * CB; b += CW) {
     const bool fx = fixed[b] != 0;
     double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (!fx) ridged_inverse(row_ptr, col, values, b, nnzb, ridge, m);
+    if (!fx) {
+      double d[9];
+      diag_block(row_ptr, col, values, b, nnzb, d);
+#pragma unroll
+      for (int i = 0; i < 3; i++) d[4 * i] += ridge;
+      invert3(d, m);
+    }
     if (blockIdx.y == 0 && lane == 0) {
 #pragma unroll
       for (int e = 0; e < 9; e++) W.minv[9 * (size_t)b + e] = m[e];
@@ -166,10 +142,10 @@ __global__ __launch_bounds__(CLT) void columns_setup_kernel(const int32_t *__res
     if (good && !fx && b != gs && b == jb) {
 #pragma unroll
       for (int i = 0; i < 3; i++) r[i] = i == ji ? 1.0 : 0.0;
-#pragma unroll
-      for (int i = 0; i < 3; i++) z[i] = m[3 * i] * r[0] + m[3 * i + 1] * r[1] + m[3 * i + 2] * r[2];
-      vrr += r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-      vrz += r[0] * z[0] + r[1] * z[1] + r[2] * z[2];
+      double trr, trz;
+      precondition(m, r, z, 1, &trr, &trz);
+      vrr += trr;
+      vrz += trz;
     }
 #pragma unroll
     for (int i = 0; i < 3; i++) {
@@ -190,7 +166,7 @@ __global__ __launch_bounds__(CLT) void columns_setup_kernel(const int32_t *__res
     if (blockIdx.x == 0) {
       W.ended[s] = good ? 0 : 1;
       W.iters[s] = 0;
-      W.flag[s] = good ? 0 : 2;
+      W.flag[s] = good ? PCG_CONVERGED : PCG_BREAKDOWN;
       W.relres[s] = 0.0;
       W.bb[s] = 0.0;
       if (good) atomicAdd(W.n_active, 1);
@@ -200,11 +176,10 @@ __global__ __launch_bounds__(CLT) void columns_setup_kernel(const int32_t *__res
 }
 
 // Iteration k's first kernel; `k` iterations are complete when it starts.  Every workgroup of a system tile forms the same
-// scalars per system from the update kernel's partials: the end of the solve (non-finite scalar: flag 2; ||r|| <= tol ||b||:
-// flag 0; `final`, the closing launch behind max_iters iterations: flag 1) or beta.  Then q = A p with p = z + beta p_old
-// formed where it is loaded.  (The end words of a system are written by workgroup row 0 alone, and only where every
-// workgroup of this launch decides alike -- they all evaluate the same partials -- so a workgroup that already reads a
-// system as ended does what it would do.)
+// scalars per system from the update kernel's partials (direction_step): the end of the solve or beta.  Then q = A p with
+// p = z + beta p_old formed where it is loaded.  (The end words of a system are written by workgroup row 0 alone, and only
+// where every workgroup of this launch decides alike -- they all evaluate the same partials -- so a workgroup that already
+// reads a system as ended does what it would do.)
 __global__ __launch_bounds__(CLT) void columns_direction_kernel(const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ col,
                                                                 const double *__restrict__ values,
                                                                 const uint8_t *__restrict__ fixed, int32_t nb, int32_t nnzb,
@@ -222,19 +197,18 @@ __global__ __launch_bounds__(CLT) void columns_direction_kernel(const int32_t *_
   const double rz = sum_partials(W.rz, W.g, Ss, s, live, s_part, w, lane);
   double beta = 0.0;
   if (live) {
-    const double bb = k == 0 ? rr : W.bb[s];
-    const double relres = bb > 0.0 ? sqrt(rr) / sqrt(bb) : (rr == 0.0 ? 0.0 : rr);
-    if (k > 0) beta = rz / W.rz_at[(size_t)((k - 1) & 1) * Ss + s];
-    const bool broke = !finite(rr) || !finite(rz) || !finite(beta);
-    const bool converged = !broke && sqrt(rr) <= tol * sqrt(bb);
+    // (the first iteration has none before it: nothing is loaded, and the step ignores both)
+    const double bb_prev = k == 0 ? 0.0 : W.bb[s], rz_prev = k > 0 ? W.rz_at[(size_t)((k - 1) & 1) * Ss + s] : 0.0;
+    const DirectionStep d = direction_step(rr, rz, bb_prev, rz_prev, k, tol, final != 0);
     const bool owner = blockIdx.x == 0 && w == 0;
-    if (broke || converged || final) {
-      if (owner) end_system(W, s, k, broke ? 2 : converged ? 0 : 1, relres);
+    beta = d.beta;
+    if (d.ended) {
+      if (owner) end_system(W, s, k, d.flag, d.relres);
       live = false;
     } else if (owner) {
       W.rz_at[(size_t)(k & 1) * Ss + s] = rz;
-      W.rel_at[(size_t)(k & 1) * Ss + s] = relres;
-      if (k == 0) W.bb[s] = rr;
+      W.rel_at[(size_t)(k & 1) * Ss + s] = d.relres;
+      if (k == 0) W.bb[s] = d.bb;
     }
   }
   const int32_t gs = live ? gauge[s] : -1;  // (a running system's gauge is in [-1, nb): the set-up ended the others)
@@ -280,8 +254,8 @@ __global__ __launch_bounds__(CLT) void columns_direction_kernel(const int32_t *_
   if (w == 0 && live) W.pq[(size_t)blockIdx.x * Ss + s] = dot;
 }
 
-// Iteration k's second kernel: alpha = r . z / p . q per system (p . q <= 0 or a non-finite scalar: breakdown, flag 2, before x
-// is touched -- x stays the last iterate); x += alpha p, r -= alpha q, z = M^-1 r; the partials of r . r and r . z.
+// Iteration k's second kernel: alpha or a breakdown per system (update_step; x stays the last iterate); x += alpha p,
+// r -= alpha q, z = M^-1 r; the partials of r . r and r . z.
 __global__ __launch_bounds__(CLT) void columns_update_kernel(const uint8_t *__restrict__ fixed, int32_t nb,
                                                              const int32_t *__restrict__ gauge, int32_t S, int32_t k,
                                                              double *__restrict__ x, ColWs W) {
@@ -295,10 +269,10 @@ __global__ __launch_bounds__(CLT) void columns_update_kernel(const uint8_t *__re
   const double pq = sum_partials(W.pq, W.g, Ss, s, live, s_part, w, lane);
   double alpha = 0.0;
   if (live) {
-    const double rz = W.rz_at[(size_t)(k & 1) * Ss + s];
-    alpha = rz / pq;
-    if (!(pq > 0.0) || !finite(pq) || !finite(alpha)) {
-      if (blockIdx.x == 0 && w == 0) end_system(W, s, k, 2, W.rel_at[(size_t)(k & 1) * Ss + s]);
+    const UpdateStep u = update_step(W.rz_at[(size_t)(k & 1) * Ss + s], pq);
+    alpha = u.alpha;
+    if (u.broke) {
+      if (blockIdx.x == 0 && w == 0) end_system(W, s, k, PCG_BREAKDOWN, W.rel_at[(size_t)(k & 1) * Ss + s]);
       live = false;
     }
   }
@@ -309,7 +283,7 @@ __global__ __launch_bounds__(CLT) void columns_update_kernel(const uint8_t *__re
     if (fixed[b]) continue;
     if (!live || b == gs) continue;
     const double *m = W.minv + 9 * (size_t)b;
-    double r[3], z[3];
+    double r[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
       const size_t e = (3 * (size_t)b + i) * Ss + s;
@@ -317,13 +291,10 @@ __global__ __launch_bounds__(CLT) void columns_update_kernel(const uint8_t *__re
       r[i] = W.r[e] - alpha * W.q[e];
       W.r[e] = r[i];
     }
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-      z[i] = m[3 * i] * r[0] + m[3 * i + 1] * r[1] + m[3 * i + 2] * r[2];
-      W.z[(3 * (size_t)b + i) * Ss + s] = z[i];
-    }
-    vrr += r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-    vrz += r[0] * z[0] + r[1] * z[1] + r[2] * z[2];
+    double trr, trz;
+    precondition(m, r, W.z + 3 * (size_t)b * Ss + s, Ss, &trr, &trz);
+    vrr += trr;
+    vrz += trz;
   }
   vrr = waves_sum(vrr, s_part, w, lane);
   vrz = waves_sum(vrz, s_part, w, lane);

@@ -100,6 +100,9 @@ class DeviceSystem:
         """The blocks of the current mask, ascending (what set_fixed takes back)."""
         return self._fixed
 
+    def _max_iters(self, max_iters):  # solve's and inverse_columns' cap on the PCG's iterations
+        return max(200, 3 * self.st.n_blocks) if max_iters is None else int(max_iters)
+
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
 
@@ -123,9 +126,7 @@ class DeviceSystem:
     def solve(self, lam, diag_floor=1e-9, tol=1e-10, max_iters=None, check_every=32):
         """(H + lam diag(diag(H) + diag_floor)) x = -g over the free blocks by block-Jacobi PCG (nhip_bsr_pcg_dev):
         (x (3 n_blocks,) float64 on the host, PcgResult)."""
-        st = self.st
-        if max_iters is None:
-            max_iters = max(200, 3 * st.n_blocks)
+        st, max_iters = self.st, self._max_iters(max_iters)
         stats, sp = _lib.PcgStats(), self._stream()
         check(self.lib.nhip_bsr_pcg_dev(self.d_row_ptr.data_ptr(), self.d_col.data_ptr(), self.d_values.data_ptr(),
                                         self.d_grad.data_ptr(), self.d_fixed.data_ptr(), st.n_blocks, st.nnzb, float(lam),
@@ -147,8 +148,7 @@ class DeviceSystem:
         rhs_index = np.ascontiguousarray(rhs_index, dtype=np.int32).reshape(-1)
         if len(gauge) != len(rhs_index):
             raise ValueError("inverse_columns: %d gauges for %d right-hand sides" % (len(gauge), len(rhs_index)))
-        if max_iters is None:
-            max_iters = max(200, 3 * st.n_blocks)
+        max_iters = self._max_iters(max_iters)
         S, n3 = len(gauge), 3 * st.n_blocks
         x = torch.zeros((n3, S), dtype=torch.float64, device=self.dev)
         results, self.column_batches = [], []

@@ -410,6 +410,11 @@ class HitlConstraint:
         return self._arrays[1]
 
 
+def _coo_blocks(idx, H6):
+    """The (n, 6) unknowns of n blocks and their (n, 6, 6) matrices -> COO rows, columns and values, block after block."""
+    return np.repeat(idx, 6, axis=1).ravel(), np.tile(idx, (1, 6)).ravel(), H6.ravel()
+
+
 def _blocks_from_normal_equations(neq, idx):
     """(n, 28) rows -- upper triangle of a 6 x 6 J^T J, J^T r, r^T r -- and the (n, 6) unknowns of every block -> the COO
     rows, columns and values of the full symmetric blocks."""
@@ -417,7 +422,45 @@ def _blocks_from_normal_equations(neq, idx):
     H6 = np.zeros((len(neq), 6, 6))
     H6[:, iu[0], iu[1]] = neq[:, :21]
     H6 = H6 + np.transpose(H6, (0, 2, 1)) - np.einsum("bij,ij->bij", H6, np.eye(6))
-    return np.repeat(idx, 6, axis=1).ravel(), np.tile(idx, (1, 6)).ravel(), H6.ravel()
+    return _coo_blocks(idx, H6)
+
+
+class _HostLinearStep:
+    """PoseGraph.solve's linear step on the host: H and g from _assemble, scipy's spsolve over the unknowns behind pose 0."""
+
+    def __init__(self, graph):
+        self.graph, self.free = graph, np.arange(3, graph.n_unknowns)
+
+    def evaluate(self, poses, lines, research):
+        self.H, self.g, cost = self.graph._assemble(poses, lines, research)
+        return cost
+
+    def step(self, lam):
+        import scipy.sparse as sp
+        from scipy.sparse.linalg import spsolve
+        Hf = self.H[self.free][:, self.free]
+        step = np.zeros(self.graph.n_unknowns)
+        with clocked("host_solver"):
+            step[self.free] = spsolve(Hf + lam * sp.diags(Hf.diagonal() + 1e-9), -self.g[self.free])
+        return step, None
+
+
+class _DeviceLinearStep:
+    """PoseGraph.solve's linear step on the device: the system assembled on the GPU, block-Jacobi PCG.  A solve that reached
+    max_iters (flag 1) gives a step like any other -- the cost test accepts or rejects it; a breakdown (flag 2) is a rejected
+    step, and the system on the device is still the one at the poses it was evaluated at."""
+
+    def __init__(self, graph, cg_tol, cg_max_iters):
+        self.graph, self.system, self.cg_tol, self.cg_max_iters = graph, graph._device_system(), cg_tol, cg_max_iters
+
+    def evaluate(self, poses, lines, research):
+        return self.graph._evaluate_device(self.system, poses, lines, research)
+
+    def step(self, lam):
+        with clocked("path"), clocked("path_linear"):
+            step, res = self.system.solve(lam, 1e-9, self.cg_tol, self.cg_max_iters)
+        self.graph._count_linear([res])
+        return step, res
 
 
 class PoseGraph:
@@ -477,13 +520,12 @@ class PoseGraph:
             if research:
                 self.icp.search()  # correspondences are rebuilt per solve, like each window pass of the reference
             neq = self.icp.normal_equations(self.kind)
-        rows, cols, vals = [], [], []
+        coo = []  # (rows, columns, values) per group of blocks, in the order coo_matrix(...).tocsc() sums duplicates
         g = np.zeros(NU)
         cost = 0.5 * float(neq[:, 27].sum()) if len(neq) else 0.0
         bs, bt = self.icp.block_src, self.icp.block_tgt
         idx = np.concatenate([3 * bs[:, None] + np.arange(3), 3 * bt[:, None] + np.arange(3)], axis=1)  # (B, 6)
-        for out, v in zip((rows, cols, vals), _blocks_from_normal_equations(neq, idx)):
-            out.append(v)
+        coo.append(_blocks_from_normal_equations(neq, idx))
         np.add.at(g, idx.ravel(), neq[:, 21:27].ravel())
         for fac in (self.odo, self.lc):
             if fac is None or fac.n == 0:
@@ -494,9 +536,7 @@ class PoseGraph:
             Hf = np.einsum("fki,fkj->fij", J, J)
             gf = np.einsum("fki,fk->fi", J, r)
             idf = np.concatenate([3 * fac.pose_i[:, None] + np.arange(3), 3 * fac.pose_j[:, None] + np.arange(3)], axis=1)
-            rows.append(np.repeat(idf, 6, axis=1).ravel())
-            cols.append(np.tile(idf, (1, 6)).ravel())
-            vals.append(Hf.ravel())
+            coo.append(_coo_blocks(idf, Hf))
             np.add.at(g, idf.ravel(), gf.ravel())
             cost += 0.5 * float((r * r).sum())
         for c, con in enumerate(self.hitl):
@@ -508,8 +548,7 @@ class PoseGraph:
                     neq = self.backend.point_to_line_normal_eq(con, poses, lines, c)
                 idh = np.concatenate([3 * con.block_pose.astype(np.int64)[:, None] + np.arange(3),
                                       np.full((con.n_blocks, 1), 3 * N + 3 * c) + np.arange(3)], axis=1)
-                for out, v in zip((rows, cols, vals), _blocks_from_normal_equations(neq, idh)):
-                    out.append(v)
+                coo.append(_blocks_from_normal_equations(neq, idh))
                 np.add.at(g, idh.ravel(), neq[:, 21:27].ravel())
                 cost += 0.5 * float(neq[:, 27].sum())
                 continue
@@ -521,13 +560,11 @@ class PoseGraph:
                 r, j0, j1 = self.backend.point_to_line(seg, pts, pb, bp, bl, poses, lines)
             J = np.concatenate([j0, j1], axis=1)  # (n, 6): d/d pose of the point's node, d/d chosen_line_pose
             ids = np.concatenate([3 * bp[pb][:, None] + np.arange(3), np.full((len(pts), 1), 3 * N + 3 * c) + np.arange(3)], axis=1)
-            Hp = np.einsum("ni,nj->nij", J, J)
-            rows.append(np.repeat(ids, 6, axis=1).ravel())
-            cols.append(np.tile(ids, (1, 6)).ravel())
-            vals.append(Hp.ravel())
+            coo.append(_coo_blocks(ids, np.einsum("ni,nj->nij", J, J)))
             np.add.at(g, ids.ravel(), (J * r[:, None]).ravel())
             cost += 0.5 * float((r * r).sum())
-        H = sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(NU, NU)).tocsc()
+        rows, cols, vals = (np.concatenate(part) for part in zip(*coo))
+        H = sp.coo_matrix((vals, (rows, cols)), shape=(NU, NU)).tocsc()
         return H, g, cost
 
     def _lines(self):
@@ -614,12 +651,15 @@ class PoseGraph:
         self.covariance_stats["iterations"] = [r.iterations for r in results]
         self.covariance_stats["flags"] = [r.flag for r in results]
         self.covariance_stats["batches"] = list(system.column_batches)  # (systems, iterations of the slowest, seconds) per call
+        self._count_linear(results)
+        return out
+
+    def _count_linear(self, results):  # the PcgResults of device solves into .linear_stats and LINEAR_STATS
         for stats in (self.linear_stats, LINEAR_STATS):
             stats["solves"] += len(results)
             stats["iterations"] += sum(r.iterations for r in results)
             stats["not_converged"] += sum(r.flag == 1 for r in results)
             stats["breakdowns"] += sum(r.flag == 2 for r in results)
-        return out
 
     def _device_system(self):
         """The block-sparse system of this graph on the device, built on the first solve(linear_solver="device") and again
@@ -665,74 +705,35 @@ class PoseGraph:
             with clocked("path_linear"):
                 return system.assemble(rows)
 
-    def _solve_device(self, iterations, damping, verbose, cg_tol, cg_max_iters):
-        """solve() with the linear step on the device: the same Levenberg loop; a PCG solve that reached max_iters (flag 1)
-        gives a step like any other -- the cost test accepts or rejects it; a breakdown (flag 2) counts as a rejected step."""
-        system = self._device_system()
-        poses, lines = self.poses.copy(), self._lines()
-        cost = self._evaluate_device(system, poses, lines, research=True)
-        history, lam, N = [cost], damping, self.n
-        for it in range(iterations):
-            with clocked("path"), clocked("path_linear"):
-                step, res = system.solve(lam, 1e-9, cg_tol, cg_max_iters)
-            for stats in (self.linear_stats, LINEAR_STATS):
-                stats["solves"] += 1
-                stats["iterations"] += res.iterations
-                stats["not_converged"] += res.flag == 1
-                stats["breakdowns"] += res.flag == 2
-            accepted = False
-            if res.flag != 2:
-                trial, trial_lines = poses + step[:3 * N].reshape(-1, 3), lines + step[3 * N:].reshape(-1, 3)
-                cost2 = self._evaluate_device(system, trial, trial_lines, research=False)
-                accepted = cost2 < cost
-            if accepted:
-                poses, lines, cost, lam = trial, trial_lines, cost2, max(lam * 0.3, 1e-9)
-            else:
-                lam *= 10.0
-                if res.flag != 2:  # (the system on the device is the trial's: back to the one at `poses`)
-                    cost = self._evaluate_device(system, poses, lines, research=False)
-            history.append(cost)
-            if verbose:
-                print("iter %d cost %.6g lambda %.2g pcg %r" % (it, cost, lam, res))
-        self.poses = poses
-        for c, con in enumerate(self.hitl):
-            con.chosen_line_pose = lines[c].copy()
-        return poses, history
-
     def solve(self, iterations=8, damping=1e-3, verbose=False, linear_solver="host", cg_tol=1e-10, cg_max_iters=None):
         """Gauss-Newton with Levenberg damping; pose 0 constant (SetParameterBlockConstant, solver.cc:384-386).
         linear_solver "host": the system assembled in numpy from downloaded rows, scipy's spsolve.  "device": assembled on
         the GPU and solved there by block-Jacobi PCG to ||r|| <= cg_tol ||b|| in at most cg_max_iters iterations (None:
         max(200, 3 x the unknown blocks)); needs a backend with device_system and device HITL constraints (TypeError
         otherwise); .linear_stats counts the solves."""
-        if linear_solver == "device":
-            return self._solve_device(iterations, damping, verbose, cg_tol, cg_max_iters)
-        if linear_solver != "host":
+        if linear_solver not in ("host", "device"):
             raise ValueError("solve: linear_solver %r (\"host\" or \"device\")" % (linear_solver,))
-        import scipy.sparse as sp
-        from scipy.sparse.linalg import spsolve
+        linear = _DeviceLinearStep(self, cg_tol, cg_max_iters) if linear_solver == "device" else _HostLinearStep(self)
         poses, lines = self.poses.copy(), self._lines()
-        H, g, cost = self._assemble(poses, lines, research=True)
-        history = [cost]
-        NU = self.n_unknowns
-        free = np.arange(3, NU)
-        lam = damping
+        cost = linear.evaluate(poses, lines, research=True)
+        history, lam, N = [cost], damping, self.n
         for it in range(iterations):
-            Hf = H[free][:, free]
-            step = np.zeros(NU)
-            with clocked("host_solver"):
-                step[free] = spsolve(Hf + lam * sp.diags(Hf.diagonal() + 1e-9), -g[free])
-            trial = poses + step[:3 * self.n].reshape(-1, 3)
-            trial_lines = lines + step[3 * self.n:].reshape(-1, 3)
-            H2, g2, cost2 = self._assemble(trial, trial_lines, research=False)
-            if cost2 < cost:
-                poses, lines, H, g, cost, lam = trial, trial_lines, H2, g2, cost2, max(lam * 0.3, 1e-9)
+            step, res = linear.step(lam)  # (res: the device's PcgResult, None on the host)
+            broke = res is not None and res.flag == 2
+            accepted = False
+            if not broke:
+                trial, trial_lines = poses + step[:3 * N].reshape(-1, 3), lines + step[3 * N:].reshape(-1, 3)
+                cost2 = linear.evaluate(trial, trial_lines, research=False)
+                accepted = cost2 < cost
+            if accepted:
+                poses, lines, cost, lam = trial, trial_lines, cost2, max(lam * 0.3, 1e-9)
             else:
                 lam *= 10.0
-                H, g, cost = self._assemble(poses, lines, research=False)
+                if not broke:  # (the system is the trial's: back to the one at `poses`)
+                    cost = linear.evaluate(poses, lines, research=False)
             history.append(cost)
             if verbose:
-                print("iter %d cost %.6g lambda %.2g" % (it, cost, lam))
+                print("iter %d cost %.6g lambda %.2g" % (it, cost, lam) + ("" if res is None else " pcg %r" % (res,)))
         self.poses = poses
         for c, con in enumerate(self.hitl):
             con.chosen_line_pose = lines[c].copy()
