@@ -25,7 +25,8 @@ int nhip_host_phases(double out[8]);
  * out[0] = 0 one kernel per pair from start to end (+ the hand-over kernel when out[5]), 1 split form in one round,
  * 2 split form in several rounds on the caller's stream, 3 split form in rounds with the candidates on the library's
  * helper stream of the current device; out[1] pairs per round; out[2] rounds' state the workspace holds; out[3] rounds;
- * out[4] 1 when NHIP_SEARCH_SHORT_SCANS was honoured; out[5] hand-over kernel launched; out[6] instrumented build;
+ * out[4] 1 when NHIP_SEARCH_SHORT_SCANS was honoured; out[5] hand-over kernel launched; out[6] bit 0: instrumented build,
+ * bit 1: the kernels that keep a list of level-2 runs take their strip bounds from it (clear: NHIP_BNB_L2_RUNS=0);
  * out[7] n_pairs. */
 int nhip_csm_last_launch(int32_t out[8]);
 /* What the calling thread's last nhip_csm_get_transformation did: {the coarse optimum's score, the form the fine level ran in
@@ -43,8 +44,12 @@ int nhip_bnb_stats(uint64_t *evaluated, uint64_t *total);
  * wave time in the candidate phase, of which window origins / sub-block bounds / exact sums, the slowest wave of
  * each pair, seed phase and bound phase (per workgroup); out[11..13] further clocks, out[14] = poses of 16-bit grids whose exact
  * sums were read from the 16-bit image (the rest was settled on the plane of high bytes); out[15] = pairs a score gate
- * settled right after their bounds (nhip_csm_match_gated); (synchronises; resets) */
-int nhip_bnb_stats_levels(uint64_t out[16]);
+ * settled right after their bounds (nhip_csm_match_gated); out[16..18] = rotation passes of the kernels that keep a list
+ * of level-2 runs (the split form's candidates, the hand-over kernel; not the seeds) that took their strip bounds from
+ * it, that took them per stored cell because some group of 8 lanes would have held more than 257 points, and that did
+ * because the rotation had more runs than the list holds -- all three stay 0 under NHIP_BNB_L2_RUNS=0; out[19..23]
+ * unused, 0; (synchronises; resets) */
+int nhip_bnb_stats_levels(uint64_t out[24]);
 /* ... and per pair of the last launch (4 x 4 sub-blocks evaluated exactly, a whole block counting four), before
  * nhip_bnb_stats resets the totals */
 int nhip_bnb_stats_per_pair(uint64_t *evaluated, int32_t n_pairs);

@@ -266,13 +266,14 @@ def bnb_stats():
 
 def bnb_stats_levels():
     """{whole blocks evaluated, blocks in all, candidates refined, 4 x 4 sub-blocks evaluated} since the last call."""
-    v = (C.c_uint64 * 16)()
+    v = (C.c_uint64 * 24)()
     check(_lib.load().nhip_bnb_stats_levels(v))
     return {"blocks_whole": v[0], "blocks_total": v[1], "candidates_refined": v[2], "sub_blocks": v[3],
             "clk_wave_phase3": v[4], "clk_origins": v[5], "clk_sub_bounds": v[6], "clk_exact": v[7],
             "clk_slowest_wave": v[8], "clk_seeds": v[9], "clk_bounds": v[10], "clk_wave_phase3_100MHz": v[11],
             "pairs_handed_over": v[12], "clk_wave_second_kernel": v[13], "pose_evals16": v[14],
-            "pairs_settled_by_gate": v[15]}
+            "pairs_settled_by_gate": v[15], "passes_l2_runs": v[16], "passes_per_cell_field": v[17],
+            "passes_per_cell_capacity": v[18]}
 
 
 def score_volume(scans, grids, src, slot, theta0, search, origin=(0, 0)):
@@ -317,8 +318,8 @@ def last_launch():
     check(_lib.load().nhip_csm_last_launch(out))
     form = {0: "fused", 1: "split, one round", 2: "split, rounds on one stream", 3: "split, rounds overlapped on the helper stream"}
     return {"form": form.get(out[0], "?"), "form_id": out[0], "pairs_per_round": out[1], "rounds_of_state": out[2],
-            "rounds": out[3], "short_scans": bool(out[4]), "hand_over_kernel": bool(out[5]), "instrumented": bool(out[6]),
-            "n_pairs": out[7]}
+            "rounds": out[3], "short_scans": bool(out[4]), "hand_over_kernel": bool(out[5]), "instrumented": bool(out[6] & 1),
+            "l2_runs": bool(out[6] & 2), "n_pairs": out[7]}
 
 
 def drop_in_cache_stats():

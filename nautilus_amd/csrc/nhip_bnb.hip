@@ -176,9 +176,11 @@ __device__ __forceinline__ void process_candidate_c(const BnbParams &P, __amdgpu
   }
 }
 
-// ---- shader-clock sums of a wave's rotation passes by part (instrumented build)
+// ---- shader-clock sums of a wave's rotation passes by part, and how many of the passes that asked for a run list took
+// their strip bounds from it, or per cell because of the field check / the list's capacity (instrumented build)
 struct PhaseClocks {
   long long org, strip, eval;
+  uint32_t run_passes, cell_passes_field, cell_passes_full;
 };
 
 // The instrumented build's flush into stats[] (indices: include/nautilus_hip_debug.h): work counts n[0..3] as
@@ -196,23 +198,34 @@ __device__ __forceinline__ void flush_stats(unsigned long long *stats, const uin
     atomicAdd(&stats[5], (unsigned long long)clk->org);
     atomicAdd(&stats[6], (unsigned long long)clk->strip);
     atomicAdd(&stats[7], (unsigned long long)clk->eval);
+    if (clk->run_passes) atomicAdd(&stats[16], (unsigned long long)clk->run_passes);
+    if (clk->cell_passes_field) atomicAdd(&stats[17], (unsigned long long)clk->cell_passes_field);
+    if (clk->cell_passes_full) atomicAdd(&stats[18], (unsigned long long)clk->cell_passes_full);
   }
 }
 
 // ---- one rotation of one pair: its candidate blocks (masks m0 | m1 over block index b = NB * Y + X, bounds u0 / u1
 // lane-wise) through sub-block bounds and exact sums, origins held in registers.  `done`: the workgroup's bound row
-// of this rotation, where finished blocks are zeroed (seeds), or null.
-template <int CB, bool GLOBAL>
+// of this rotation, where finished blocks are zeroed (seeds), or null.  RUNS: the wave has RUN_WAVE words at `runs` for
+// the rotation's runs by level-2 entry, and the strip bounds walk those (unless P.l2_runs is off, or cache_origins
+// reports that this rotation's runs do not fit the list or its 16-bit fields: then, as without RUNS, per cell).
+template <int CB, bool GLOBAL, bool RUNS = false>
 __device__ __forceinline__ void rotation_pass(const BnbParams &P, const PairCtx &C, int32_t k, uint32_t u0, uint32_t u1,
                                               unsigned long long m0, unsigned long long m1, int lane,
                                               unsigned long long *best, uint32_t *done, uint32_t *org,
-                                              uint32_t (&n_work)[4], PhaseClocks &clk) {
+                                              uint32_t (&n_work)[4], PhaseClocks &clk, uint32_t *runs = nullptr) {
   long long t_mark = 0;
   float cf, sf;
   rotation_k(P, C.pair, k, &cf, &sf);
   if (BNB_STATS(P)) t_mark = clock64();
-  const int32_t nch = cache_origins(P, C.pts, C.n_pts, cf, sf, C.cx, C.cy, lane, org, true);
+  int32_t nrc = RUNS_NONE;
+  const int32_t nch = cache_origins<RUNS>(P, C.pts, C.n_pts, cf, sf, C.cx, C.cy, lane, org, true, runs, RUNS && P.l2_runs != 0, &nrc);
   if (BNB_STATS(P)) clk.org += clock64() - t_mark;
+  if (RUNS && BNB_STATS(P)) {
+    clk.run_passes += nrc > 0 ? 1u : 0u;
+    clk.cell_passes_field += nrc == RUNS_FIELD ? 1u : 0u;
+    clk.cell_passes_full += nrc == RUNS_FULL ? 1u : 0u;
+  }
   // (stored image + skip map: every offset an evaluation can form lies inside; see nhip_layout.hip make_layout)
   // (8-bit grids: the image, on which the exact sums run; 16-bit grids: the tiled copy of the image, for pose_sum16)
   const __amdgpu_buffer_rsrc_t rsrc16 = CB == 1 ? uniform_rsrc(C.grid, P.grid_bytes + P.skip_bytes)
@@ -236,7 +249,8 @@ __device__ __forceinline__ void rotation_pass(const BnbParams &P, const PairCtx 
     uint32_t bcopy = GLOBAL ? best_sum<true>(best) : 0u;  // (one look per strip at a best in global memory)
     if (P.levels >= 2) {
       if (BNB_STATS(P)) t_mark = clock64();
-      strip_bounds_c(P, p4, org, nch, Y, X0, len, CB == 1 ? 1u : 257u, sb);
+      if (RUNS && nrc > 0) strip_bounds_c<RunList<RUN_CHUNKS>>(P, p4, runs + lane, nrc, Y, X0, len, CB == 1 ? 1u : 257u, sb);
+      else strip_bounds_c<CellList>(P, p4, org, nch, Y, X0, len, CB == 1 ? 1u : 257u, sb);
       if (BNB_STATS(P)) clk.strip += clock64() - t_mark;
       n_work[1] += (uint32_t)len;
     } else {
@@ -433,7 +447,7 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : BNB_THREADS, SPLIT ? SPL
     __syncthreads();
     uint32_t *org = s_org + wave * ORG_WAVE + lane;
     // (NHIP_BNB_STATS=1: shader-clock sums -- wave time in phase 3 by part, and the workgroup's wall time)
-    PhaseClocks clk = {0, 0, 0};
+    PhaseClocks clk = {0, 0, 0, 0u, 0u, 0u};
     long long t_busy = 0, t_wall = 0;
     const long long t_phase1 = BNB_STATS(P) ? clock64() : 0;
     if (BNB_TIMELINE(P) && threadIdx.x == 0 && pair < BNB_STATS_PAIRS) BNB_TIMELINE(P)[4 * pair + 1] = wall_clock64();
@@ -656,8 +670,10 @@ __global__ __launch_bounds__(256, 4) void csm_bnb_rot_kernel(BnbParams P) {
   const uint32_t count = filled < P.rot_cap ? filled : P.rot_cap;
   const RotEntry *list = P.rot_list + (size_t)xcd * P.rot_cap;
   __shared__ uint32_t s_org2[4 * ORG_WAVE];
+  __shared__ uint32_t s_run2[4 * RUN_WAVE];
   uint32_t *org = s_org2 + (threadIdx.x >> 6) * ORG_WAVE + lane;
-  PhaseClocks clk = {0, 0, 0};
+  uint32_t *runs = s_run2 + (threadIdx.x >> 6) * RUN_WAVE;
+  PhaseClocks clk = {0, 0, 0, 0u, 0u, 0u};
   const long long t0 = BNB_STATS(P) ? clock64() : 0;
   for (;;) {
     const uint32_t i = wave_fetch_add(P.rot_count + 8 * xcd + 1, 1u, lane);
@@ -670,7 +686,7 @@ __global__ __launch_bounds__(256, 4) void csm_bnb_rot_kernel(BnbParams P) {
     uint32_t n[4] = {0u, 0u, 0u, 0u};
     // (no block bounds here: 0xffffffff lets every candidate through to its sub-block bounds, which are checked
     //  against the best as it stands in keys[pair])
-    rotation_pass<CB, true>(P, C, k, 0xffffffffu, 0xffffffffu, m0, m1, lane, &P.keys[pair], nullptr, org, n, clk);
+    rotation_pass<CB, true, true>(P, C, k, 0xffffffffu, 0xffffffffu, m0, m1, lane, &P.keys[pair], nullptr, org, n, clk, runs);
     if (BNB_STATS(P) && lane == 0) flush_stats(BNB_STATS(P), n, pair, nullptr);
   }
   if (BNB_STATS(P) && lane == 0) {
@@ -804,6 +820,7 @@ constexpr int CAND_THREADS = 64 * CAND_WAVES;
 template <int CB>
 __global__ __launch_bounds__(CAND_THREADS, CB == 2 ? 5 : 4) void csm_bnb_cand_kernel(BnbParams P) {
   __shared__ uint32_t s_org2[CAND_WAVES * ORG_WAVE];
+  __shared__ uint32_t s_run2[CAND_WAVES * RUN_WAVE];  // (25.6 KB with the origins: five workgroups per CU have 32 KB each)
   __shared__ unsigned long long s_best2;
   __shared__ uint32_t s_next2;
   const int lane = threadIdx.x & 63;
@@ -827,10 +844,11 @@ __global__ __launch_bounds__(CAND_THREADS, CB == 2 ? 5 : 4) void csm_bnb_cand_ke
   uint32_t *next = shared ? &P.ps_next[pair] : &s_next2;
   const uint32_t *rows = P.ps_rows + (size_t)pair * (size_t)P.n_theta * 128u;
   uint32_t *org = s_org2 + (threadIdx.x >> 6) * ORG_WAVE + lane;
+  uint32_t *runs = s_run2 + (threadIdx.x >> 6) * RUN_WAVE;
   PairCtx C;
   pair_context(P, pair, &C);
   uint32_t n_work[4] = {0u, 0u, 0u, 0u};
-  PhaseClocks clk = {0, 0, 0};
+  PhaseClocks clk = {0, 0, 0, 0u, 0u, 0u};
   const long long t0 = BNB_STATS(P) ? clock64() : 0;
   for (;;) {
     const uint32_t rank = wave_fetch_add(next, 1u, lane);
@@ -843,7 +861,7 @@ __global__ __launch_bounds__(CAND_THREADS, CB == 2 ? 5 : 4) void csm_bnb_cand_ke
     const unsigned long long m0 = __ballot(u0 != 0u && u0 >= bsum);
     const unsigned long long m1 = __ballot(u1 != 0u && u1 >= bsum && lane + 64 < NB * NB);
     if ((m0 | m1) == 0ull) continue;
-    rotation_pass<CB, true>(P, C, k, u0, u1, m0, m1, lane, best, nullptr, org, n_work, clk);
+    rotation_pass<CB, true, true>(P, C, k, u0, u1, m0, m1, lane, best, nullptr, org, n_work, clk, runs);
   }
   if (BNB_STATS(P) && lane == 0) {
     atomicAdd(&BNB_STATS(P)[13], (unsigned long long)(clock64() - t0));

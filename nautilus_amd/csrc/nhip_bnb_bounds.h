@@ -3,12 +3,14 @@
 // Owns: coarse_rotation -- the bounds of all 11 x 11 blocks of one rotation from the pooled table, gathered per RUN of
 // points that share a pooled entry (the run lists: LIST_ENTRIES words of LDS per wave) -- with slot_block, the layout its
 // totals come out in; sub_bounds -- the four 4 x 4 sub-block bounds of one block, from the points; strip_bounds_c -- the
-// same for a strip of up to three blocks, from the origins a wave holds.
+// same for a strip of up to three blocks, from the origins a wave holds (CellList) or their runs by level-2 entry (RunList).
 // Assumes: the pooled tables behind the stored image as the table build leaves them (nhip_grid_blur.hip,
 // nhip_grid_tables.hip: zero rows below the pooled image, a pitch that is a multiple of 16, offsets below
 // 1 << RUN_SHIFT), 16-bit packed fields (LANE_WEIGHT, 18 chunks of 64 points).  Every bound is at least the largest sum of the poses it covers; nothing here reads the stored cells.
 // Included by nhip_bnb.hip only.
 #pragma once
+#include <type_traits>
+
 #include "nhip_bnb_origin.h"
 
 namespace nhip {
@@ -272,17 +274,36 @@ __device__ __forceinline__ void sub_bounds(const BnbParams &P, __amdgpu_buffer_r
 }
 
 // Sub-block bounds of a strip of up to three blocks (Y, X0), (Y, X0 + 1), (Y, X0 + 2): their twelve table bytes are
-// consecutive, ONE 16-byte load per point.  out[4 t + q]: block X0 + t, sub-block q = 2 sy + sx.
+// consecutive, ONE 16-byte load per list entry.  out[4 t + q]: block X0 + t, sub-block q = 2 sy + sx.
 // `len` blocks are wanted (wave-uniform): their 4 len bytes start at a 2-byte-aligned offset, so 8 / 12 / 16 bytes are
 // loaded -- the vector-memory address unit's time goes with the dwords a lane loads, and the candidates are bound by it.
-__device__ __forceinline__ void strip_bounds_c(const BnbParams &P, __amdgpu_buffer_rsrc_t p4, const uint32_t *org,
-                                               int32_t nch, int32_t Y, int32_t X0, int len, uint32_t scale,
-                                               uint32_t (&out)[12]) {
+// The list is the wave's origins merged by stored cell (CellList) or, where the wave keeps one, their runs by level-2
+// entry (RunList): the address is a function of that entry alone, every member of a run reads the same bytes, and the
+// sums are integers -- the twelve bounds come out the same from either list, from ~5 chunks of loads instead of ~12.
+struct CellList {
+  static constexpr int ROUNDS = 2, H = OC / ROUNDS;  // H: chunks whose loads are in flight together; a round past the list is skipped
+  static __device__ __forceinline__ uint32_t entry(const uint32_t *list, int c) { return origin_of(list, c); }
+  static __device__ __forceinline__ uint32_t offset(uint32_t o, uint32_t DP) { return (org_row(o) >> 2) * DP + 2u * (org_col(o) >> 2); }
+  static __device__ __forceinline__ uint32_t count(uint32_t o) { return org_cnt(o); }
+};
+// (one round of H = 4, 5, 6 or 8 chunks, chosen by the list's length -- what the kernel pays for is load instructions, and 95 %
+//  of a 1081-beam scan's rotations have 4 to 6 chunks of runs.  Past its end the run list reads as entries of no points in
+//  the zero border.)
+template <int CHUNKS>
+struct RunList {
+  static constexpr int ROUNDS = 1, H = CHUNKS;
+  static __device__ __forceinline__ uint32_t entry(const uint32_t *list, int c) { return list[64 * c]; }
+  static __device__ __forceinline__ uint32_t offset(uint32_t e, uint32_t DP) { return run_row2(e) * DP + 2u * run_col2(e); }
+  static __device__ __forceinline__ uint32_t count(uint32_t e) { return run_cnt(e); }
+};
+
+// The packed sums of a strip over the list (`list`: the lane's word of chunk 0; nch: the list's chunks, wave-uniform) ...
+template <class LIST>
+__device__ __forceinline__ void strip_sums(const BnbParams &P, __amdgpu_buffer_rsrc_t p4, const uint32_t *list, int32_t nch,
+                                           int32_t Y, int32_t X0, int len, uint32_t (&E)[3], uint32_t (&O)[3]) {
   const uint32_t DP = (uint32_t)P.pool4_pitch;
   const uint32_t off = (uint32_t)(2 * Y) * DP + (uint32_t)(4 * X0);
-  uint32_t E[3] = {0u, 0u, 0u}, O[3] = {0u, 0u, 0u};  // 16-bit fields: 18 chunks * 255 * 8 lanes < 65536
-  constexpr int ROUNDS = 2;
-  constexpr int H = OC / ROUNDS;  // chunks whose loads are in flight together
+  constexpr int ROUNDS = LIST::ROUNDS, H = LIST::H;
 #pragma unroll
   for (int h = 0; h < ROUNDS; h++) {
     if (H * h >= nch) continue;
@@ -291,12 +312,12 @@ __device__ __forceinline__ void strip_bounds_c(const BnbParams &P, __amdgpu_buff
     uint32_t aa[H];
 #pragma unroll
     for (int j = 0; j < H; j++) {
-      const uint32_t o = origin_of(org, H * h + j);
+      const uint32_t o = LIST::entry(list, H * h + j);
       // (lanes without a point: origin (0, 0), whose entries lie in the zero border)
-      const uint32_t a = (org_row(o) >> 2) * DP + 2u * (org_col(o) >> 2) + off;
+      const uint32_t a = LIST::offset(o, DP) + off;
       sh[j] = (a & 2u) * 8u;
       aa[j] = a & ~3u;
-      cn[j] = org_cnt(o);
+      cn[j] = LIST::count(o);
     }
     if (len == 1) {
 #pragma unroll
@@ -324,6 +345,23 @@ __device__ __forceinline__ void strip_bounds_c(const BnbParams &P, __amdgpu_buff
       E[1] += __umul24(n1 & M8, cn[j]); O[1] += __umul24((n1 >> 8) & M8, cn[j]);
       E[2] += __umul24(n2 & M8, cn[j]); O[2] += __umul24((n2 >> 8) & M8, cn[j]);
     }
+  }
+}
+
+// ... and the twelve bounds from them
+template <class LIST>
+__device__ __forceinline__ void strip_bounds_c(const BnbParams &P, __amdgpu_buffer_rsrc_t p4, const uint32_t *list,
+                                               int32_t nch, int32_t Y, int32_t X0, int len, uint32_t scale,
+                                               uint32_t (&out)[12]) {
+  uint32_t E[3] = {0u, 0u, 0u}, O[3] = {0u, 0u, 0u};  // 16-bit fields: at most 257 points per group of 8 lanes (cache_origins)
+  if (std::is_same<LIST, CellList>::value) {
+    strip_sums<CellList>(P, p4, list, nch, Y, X0, len, E, O);
+  } else {
+    static_assert(RUN_CHUNKS == 8, "the rounds below cover the run list");
+    if (nch <= 4) strip_sums<RunList<4>>(P, p4, list, nch, Y, X0, len, E, O);
+    else if (nch == 5) strip_sums<RunList<5>>(P, p4, list, nch, Y, X0, len, E, O);
+    else if (nch == 6) strip_sums<RunList<6>>(P, p4, list, nch, Y, X0, len, E, O);
+    else strip_sums<RunList<8>>(P, p4, list, nch, Y, X0, len, E, O);
   }
   // sums over the wave without LDS: the packed fields over groups of 8 lanes (quad permutations, then the mirror image
   // of the half row holds the other quad's sum), unpacked, over the row of 16 (its mirror image), then down the rows

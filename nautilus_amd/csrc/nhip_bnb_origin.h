@@ -3,10 +3,12 @@
 //
 // Owns: window_origin (the spec's cell from single-precision arithmetic, with its double-precision rare path; LEAN: the
 // form of the bounds phase, exact to the pooled entry), the rotation's (cos, sin) (rotation_k), patch_origin, the packed
-// per-wave list of a rotation's origins in LDS (cache_origins, origin_of, org_row / org_col / org_cnt), and the
-// wave-uniform buffer descriptor every gather here reads through (uniform_rsrc, the u32xN load types, idx_guard).
+// per-wave list of a rotation's origins in LDS (cache_origins, origin_of, org_row / org_col / org_cnt), the shorter list
+// of their runs by level-2 entry (run_row2 / run_col2 / run_cnt), and the wave-uniform buffer descriptor every gather
+// here reads through (uniform_rsrc, the u32xN load types, idx_guard).
 // Assumes: BnbParams as launch_csm_bnb fills it (nhip_bnb_host.hip); a wave's list has ORG_WAVE words of LDS of its
-// own; rows and columns of a stored grid below ORG_LIMIT for the packed form.  Included by nhip_bnb.hip only.
+// own, its run list RUN_WAVE; rows and columns of a stored grid below ORG_LIMIT for the packed form.  Included by
+// nhip_bnb.hip only.
 #pragma once
 #include "nhip_bnb_params.h"
 #include "nhip_bnb_wave.h"
@@ -179,6 +181,23 @@ __device__ __forceinline__ uint32_t org_cnt(uint32_t o) { return (o & 63u) + 1u;
 //  cells lie in the zero border)
 __device__ __forceinline__ uint32_t origin_of(const uint32_t *org, int c) { return c < OCL ? org[64 * c] : 0u; }
 
+// ---- the second list: runs of origins by level-2 entry
+// The strip bounds (nhip_bnb_bounds.h) read the level-2 table at an address that depends only on the origin's 4 x 4 entry
+// (row >> 2, column >> 2), and consecutive beams run along walls: of a 1081-beam scan's ~750 cells ~300 start a new
+// entry.  A wave that has LDS for it (`runs`: RUN_WAVE words) writes, beside the list above, one word per RUN -- a live
+// lane whose entry differs from its predecessor's, or that starts a 64-point chunk (so a run has at most 64 points;
+// A, B, A stays three runs) -- as the origin's word with the bits below the entry cleared and the run's points in the
+// cleared count field: (row >> 2) << 21 | (column >> 2) << 8 | points (1 .. 64; 0: no entry, adds nothing).
+constexpr uint32_t RUN_KEY_MASK = (~0u << (ORG_ROW_SHIFT + 2)) | (((ORG_LIMIT >> 2) - 1u) << (ORG_COL_SHIFT + 2));
+__device__ __forceinline__ uint32_t run_row2(uint32_t e) { return e >> (ORG_ROW_SHIFT + 2); }
+__device__ __forceinline__ uint32_t run_col2(uint32_t e) { return (e >> (ORG_COL_SHIFT + 2)) & ((ORG_LIMIT >> 2) - 1u); }
+__device__ __forceinline__ uint32_t run_cnt(uint32_t e) { return e & 127u; }
+// What cache_origins says of the run list: the number of its 64-entry chunks (>= 1: the strip bounds may walk it), or why
+// there is none -- not asked for; some aligned group of 8 lanes would hold more than 257 points (the same limit of the
+// 16-bit fields as the cell list's, checked on its own: runs concentrate the counts), which includes every rotation whose
+// cell list had to be rebuilt unmerged; more than RUN_WAVE runs.  Such a rotation takes the strip bounds per cell.
+enum : int32_t { RUNS_NONE = 0, RUNS_FIELD = -1, RUNS_FULL = -2 };
+
 // Returns the number of 64-entry chunks of the list (wave-uniform).  The packed sums of the bounds and exact sums hold
 // 16-bit fields that are added over 8 lanes before they are unpacked: the points of every aligned group of 8 lanes,
 // over all chunks, must not exceed 257 (257 * 255 = 65,535).  One point per entry keeps that by construction (<= 18
@@ -187,9 +206,16 @@ __device__ __forceinline__ uint32_t origin_of(const uint32_t *org, int c) { retu
 // `merged`: measured on 10,000 pairs with row-major planes 7.45 -> 7.38 ms for 16-bit grids and 6.81 -> 6.93 ms for
 // 8-bit ones (the multiply-adds that replace the adds cost what the loads saved); with the tiled planes both widths
 // merge (8-bit: 6.31 -> 6.25 ms).
+// RUNS (with `runs`, the wave's RUN_WAVE words, and want_runs, wave-uniform): the run list is written in the same sweep
+// and *run_chunks says what became of it (above).
+template <bool RUNS = false>
 __device__ __forceinline__ int32_t cache_origins(const BnbParams &P, const float2 *pts, int32_t n_pts, float cf, float sf,
-                                                 int32_t cx, int32_t cy, int lane, uint32_t *org, bool merged) {
+                                                 int32_t cx, int32_t cy, int lane, uint32_t *org, bool merged,
+                                                 uint32_t *runs = nullptr, bool want_runs = false,
+                                                 int32_t *run_chunks = nullptr) {
   uint32_t *base = org - lane;  // the wave's list
+  const bool with_runs = RUNS && want_runs;
+  if (RUNS) *run_chunks = RUNS_NONE;
   for (int merge = merged ? 1 : 0; merge >= 0; merge--) {
     // (rolled: the origin arithmetic holds a division on its rare path.  The points of the next D chunks are in flight
     //  while one chunk's origins are computed; that array rotates so that its indices stay static.)
@@ -202,6 +228,7 @@ __device__ __forceinline__ int32_t cache_origins(const BnbParams &P, const float
       py[d] = q.y;
     }
     uint32_t tail = 0u;  // entries written (wave-uniform)
+    uint32_t rtail = 0u;  // runs found (wave-uniform; those past RUN_WAVE are not written)
 #pragma unroll 1
     for (int c = 0; c < OCL; c++) {
       const int32_t idx = 64 * c + lane;
@@ -234,14 +261,30 @@ __device__ __forceinline__ int32_t cache_origins(const BnbParams &P, const float
         base[tail + before] = o | (cnt - 1u);
       }
       tail += (uint32_t)__builtin_popcountll(H);
+      if (RUNS && with_runs && merge) {
+        // (a run's head is a cell's head too: the same predecessor, compared above the entry's low bits)
+        const bool head2 = live && (lane == 0 || ((o ^ prev) & RUN_KEY_MASK) != 0u);
+        const unsigned long long H2 = __ballot(head2);
+        const unsigned long long rest2 = ((H2 | ~L) >> lane) >> 1;
+        const uint32_t cnt2 = rest2 ? (uint32_t)__builtin_ctzll(rest2) + 1u : (uint32_t)(64 - lane);
+        const uint32_t at = rtail + __builtin_amdgcn_mbcnt_hi((uint32_t)(H2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)H2, 0u));
+        if (head2 && at < (uint32_t)RUN_WAVE) runs[at] = (o & RUN_KEY_MASK) | cnt2;
+        rtail += (uint32_t)__builtin_popcountll(H2);
+      }
     }
     const int32_t nch = (int32_t)((tail + 63u) >> 6);
     // (the rest of the list reads as row 0, column 0: the sums below unroll over groups of chunks and may read past nch)
     for (uint32_t e = tail + (uint32_t)lane; e < (uint32_t)ORG_WAVE; e += 64u) base[e] = 0u;
+    // (... and the rest of the run list as entries of no points)
+    if (RUNS && with_runs && merge)
+      for (uint32_t e = rtail + (uint32_t)lane; e < (uint32_t)RUN_WAVE; e += 64u) runs[e] = 0u;
     // (the wave reads only its own words back: LDS operations of one wave are performed in order)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if (merge == 0) return nch;
+    if (merge == 0) {
+      if (RUNS && with_runs) *run_chunks = RUNS_FIELD;
+      return nch;
+    }
     // the points of this lane's entries, summed over the aligned group of 8 lanes
     uint32_t w = 0u;
     for (int c = 0; c < nch; c++) {
@@ -249,7 +292,18 @@ __device__ __forceinline__ int32_t cache_origins(const BnbParams &P, const float
       w += 64u * (uint32_t)c + (uint32_t)lane < tail ? org_cnt(e) : 0u;
     }
     w = sum8(w);
-    if (__ballot(w > 257u) == 0ull) return nch;
+    if (__ballot(w > 257u) == 0ull) {
+      if (RUNS && with_runs) {
+        // the same check of the run list, whose fields hold whole runs
+        const int32_t nrc = (int32_t)((rtail + 63u) >> 6);
+        uint32_t w2 = 0u;
+        if (rtail <= (uint32_t)RUN_WAVE)
+          for (int c = 0; c < nrc; c++) w2 += run_cnt(runs[64 * c + lane]);
+        w2 = sum8(w2);
+        *run_chunks = rtail > (uint32_t)RUN_WAVE ? RUNS_FULL : (__ballot(w2 > 257u) != 0ull ? RUNS_FIELD : nrc);
+      }
+      return nch;
+    }
     __builtin_amdgcn_wave_barrier();
   }
   return 0;  // (not reached)

@@ -26,6 +26,10 @@ constexpr int OCL = 17;               // chunks of window origins a wave holds: 
 constexpr int ORG_WAVE = OCL * 64;    // words of LDS per wave
 constexpr int ORG_LDS = BNB_WAVES * ORG_WAVE * 4;  // bytes per workgroup (34,816: the 1200 x 1200 grid's pooled table is 35,712)
 constexpr uint32_t ORG_LIMIT = 1u << 13;           // rows / columns of a stored grid the packed origins hold
+// The second list of the kernels that work candidates rotation by rotation (csm_bnb_cand_kernel, csm_bnb_rot_kernel): runs of
+// consecutive origins inside one 4 x 4 level-2 entry, which is all the strip bounds read (nhip_bnb_origin.h has the format).
+constexpr int RUN_CHUNKS = 8;                      // 64-entry chunks of runs a wave holds: 512 runs (a 1081-beam scan: ~300)
+constexpr int RUN_WAVE = RUN_CHUNKS * 64;          // words of LDS per wave
 
 // ---- the dynamic LDS of csm_bnb_kernel, in this order (the kernel carves it, bnb_plan and launch_main size it):
 //   first region   the pooled table while the bounds are computed (if staged), then the waves' window origins
@@ -53,7 +57,7 @@ constexpr size_t lds_bytes(size_t first, int32_t n_theta, bool split) {
 }
 
 constexpr int BNB_STATS_PAIRS = 1 << 20;           // per-pair counters kept by NHIP_BNB_STATS=1
-constexpr int BNB_STATS_HEAD = 16;    // totals: 4 counts, then shader-clock sums of the by-rotation kernel (see nhip_bnb_stats_levels)
+constexpr int BNB_STATS_HEAD = 24;    // totals: 4 counts, shader-clock sums of the by-rotation kernel, the strip paths (see nhip_bnb_stats_levels)
 
 // One rotation of a pair with many candidates, handed to the second kernel: (pair, rotation) and the mask of its
 // 121 candidate blocks.
@@ -115,6 +119,7 @@ struct BnbParams {
   double res, inv_res;
   float inv_res_f;  // RN_f32(1 / res): the single-precision path of the window origins
   ScoreGate gate;   // the caller's min_score (nhip_csm_match_gated): a pair's best starts at its floor key (nhip_csm_shared.h)
+  int32_t l2_runs;  // strip bounds from the list of level-2 runs where a kernel keeps one (0: NHIP_BNB_L2_RUNS=0, per cell everywhere)
 };
 
 // The kernel launches of one batch in each build: launchers_product() (nhip_bnb.hip), launchers_instr()

@@ -233,6 +233,7 @@ struct BnbPlan {
   BnbForm form;
   int32_t n_pairs, cb, levels;
   bool second, general_all, short_scans, pool_lds, instrumented, stats, timeline;
+  bool l2_runs;      // strip bounds over runs of level-2 entries in the kernels that keep that list (NHIP_BNB_L2_RUNS=0: per cell)
   bool sized_split;  // the size rule (bnb_workspace_bytes) gives this list room for the split form
   uint32_t rot_cap, heavy_min, keep_ranks, split_min, split_max;  // split_max 0: by the round's length
   int64_t batch, slots, slot_bytes, rounds;  // pairs per round (0: fused), rounds' state the workspace holds, bytes of one
@@ -274,7 +275,7 @@ int64_t bnb_workspace_bytes(int32_t n_pairs);
 int64_t bnb_workspace_bytes_lists(int32_t n_pairs);
 void bnb_last_launch(int32_t out[8]);
 bool bnb_fits(const GridLayout &L, const nhip_search_t *search);
-int bnb_stats_read(unsigned long long out[16]);
+int bnb_stats_read(unsigned long long out[24]);
 int bnb_timeline_read(unsigned long long *out, int32_t n);
 int bnb_timeline_cand_read(unsigned long long *out, int32_t n);
 int bnb_stats_per_pair(unsigned long long *out, int32_t n);

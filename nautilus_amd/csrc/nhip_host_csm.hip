@@ -618,7 +618,7 @@ int nhip_bnb_timeline_candidates(uint64_t *ticks, int32_t n_pairs) {
 }
 
 int nhip_bnb_stats(uint64_t *evaluated, uint64_t *total) {
-  unsigned long long v[16];
+  unsigned long long v[24];
   int rc = bnb_stats_read(v);
   if (rc) return rc;
   if (evaluated) *evaluated = v[0] + (v[3] + 3) / 4;  // in blocks: four sub-blocks = one block
@@ -626,12 +626,12 @@ int nhip_bnb_stats(uint64_t *evaluated, uint64_t *total) {
   return NHIP_OK;
 }
 
-int nhip_bnb_stats_levels(uint64_t out[16]) {
+int nhip_bnb_stats_levels(uint64_t out[24]) {
   NHIP_REQUIRE(out != nullptr, "bnb_stats_levels: null out");
-  unsigned long long v[16];
+  unsigned long long v[24];
   int rc = bnb_stats_read(v);
   if (rc) return rc;
-  for (int i = 0; i < 16; i++) out[i] = v[i];
+  for (int i = 0; i < 24; i++) out[i] = v[i];
   return NHIP_OK;
 }
 
