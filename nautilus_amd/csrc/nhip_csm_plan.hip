@@ -91,6 +91,9 @@ int launch_csm_match(const MatchJob &job, const MatchPlan &plan) {
   NHIP_REQUIRE(!job.pair_kbase || plan.form == MATCH_BNB, "csm_match: rotation offsets per pair with a lattice the matcher does not take");
   int rc = check_search(job.spec, L, job.search);
   if (rc) return rc;
+  // (what the exact-score pass requires of the grids, before the search it follows is launched: a refused call writes nothing)
+  NHIP_REQUIRE(!(job.search->flags & NHIP_SEARCH_EXACT_SCORE) || L.R <= 15, "csm_match: NHIP_SEARCH_EXACT_SCORE reads row "
+               "windows of at most 31 bits; the grids' blur radius %d > 15 (sigma > 5 cells)", L.R);
   NHIP_REQUIRE(L.has_image || plan.form == MATCH_BNB, "csm_match: this search takes the kernel that performs every add "
                "(NHIP_SEARCH_EXHAUSTIVE, or a lattice beyond the branch-and-bound matcher's envelope), which reads the row-major "
                "image the grids were built without (NHIP_GRID_NO_IMAGE)");
