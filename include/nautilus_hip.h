@@ -66,7 +66,7 @@ const char *nhip_version(void);
  * nhip_features_pack_dev, 256 scan offset of nhip_normals_estimate_dev, 512 member scan id and 1024 merged point count beyond
  * the capacity of nhip_submaps_gather_dev, 2048 contributor id of nhip_bsr_assemble_dev, 4096 block column of
  * nhip_bsr_assemble_dev / nhip_bsr_pcg_dev / nhip_bsr_pcg_columns_dev, 8192 gauge or right-hand-side index of
- * nhip_bsr_pcg_columns_dev.  Clears the record (in the order of `stream`).
+ * nhip_bsr_pcg_columns_dev, 16384 scan offset of nhip_vectorize_dev.  Clears the record (in the order of `stream`).
  * ONE record per DEVICE, shared by every stream and host thread that uses the library on it: a host with several streams
  * on one device learns THAT an id was bad and which, not on which stream; a call that finds a record consumes it -- reports
  * of kernels still running on OTHER streams at that moment can be reported by this call or wiped by its clear.  Clients
@@ -639,6 +639,88 @@ int nhip_normals_spec_default(nhip_normals_spec_t *out);
 int nhip_normals_estimate_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const nhip_normals_spec_t *spec,
                               float *d_normals, int32_t *d_info, void *stream);
 
+/* K13: MAP VECTORISATION -- Solver::Vectorize (solver.cc:581-624): every scan at its pose, merged, reduced to wall segments
+ * x1 y1 x2 y2 ("Map vectorisation"; tests/vectorize_reference.py restates it in numpy).  Build-defined:
+ * an exhaustive, deterministic Hough transform over the occupied cells of a world raster with greedy peak extraction; all
+ * integer after the point transform.
+ *   points   scan i's affine (c, s, tx, ty) = ((float)cos, (float)sin, (float)x, (float)y) of its pose (nhip_map_pose_affines);
+ *            x' = ((c x) + ((-s) y)) + tx, y' = ((s x) + (c y)) + ty in float, every operation rounded on its own.
+ *   raster   cell (floor((double)x' / res) - cell_x0, floor((double)y' / res) - cell_y0); a point that is not finite, whose
+ *            floor is not below 2^63 in magnitude or whose cell is outside width x height is dropped; counts[height][width].
+ *   cells    those with counts >= min_hits, row-major (cy, then cx), as (cx, cy) int32 pairs: M cells, all live.
+ *   tables   C[t] = lrint(2^14 cos(pi t / n_theta)), S[t] = lrint(2^14 sin(pi t / n_theta)) (nhip_vectorize_tables);
+ *            rho_q = cx C[t] + cy S[t] + (width << 14), bin b = rho_q >> 14, n_rho = 2 width + height + 1 bins;
+ *            a_q = cy C[t] - cx S[t] + (width << 14), along-line bin a = a_q >> 14 (the floor: a_q is negative for some
+ *            cells where C[t] < 0), -height <= a < width + height.
+ *   votes    votes[t][b]: the live cells in that bin.
+ *   a round  1. the peak: the largest votes, ties to the smallest t n_rho + b.  Below min_votes: the call ends, flag 0.
+ *               Otherwise, if max_rounds rounds were made already: the call ends, flag 1.
+ *            2. the band: live cells with |rho_q - ((b << 14) + (1 << 13))| <= lrint(band 2^14); the set of their bins a.
+ *            3. runs: maximal ascending sequences of set bins whose neighbours differ by at most max_gap + 1; KEPT iff
+ *               a_hi - a_lo + 1 >= min_length; taken in ascending a.
+ *            4. no run kept: every band cell is retired (dies, its n_theta votes are subtracted, no record).  Kept runs that
+ *               do not fit into what is left of max_segments: nothing is committed, the call ends, flag 2.  Otherwise every
+ *               band cell inside a kept run dies, its votes are subtracted and it adds 1, cx, cy, cx^2, cx cy, cy^2 to its
+ *               run's record; band cells outside the kept runs stay live.  `rounds` counts the rounds that retired or committed.
+ *   record   10 int64: {t, b, a_lo, a_hi, n, sum x, sum y, sum xx, sum xy, sum yy}.
+ *   stats    8 int32: {M, segments, rounds, flag, cells emitted, cells retired, n_rho, 0}.  More than max_cells cells: flag 3,
+ *            M is the count needed, nothing is vectorised and nothing is written past the buffers.
+ *   lines    nhip_vectorize_endpoints (pure host, double): m = (sum x / n, sum y / n); cxx = sum xx - sum x mx, cxy = sum xy -
+ *            sum x my, cyy = sum yy - sum y my; phi = 0.5 atan2(2 cxy, cxx - cyy), d = (cos phi, sin phi).  The ends are the
+ *            points (rho c - alpha s, rho s + alpha c) of the Hough line, c = C[t] / 2^14, s = S[t] / 2^14, rho = ((b << 14)
+ *            + 2^13 - (width << 14)) / 2^14, alpha = a - width for a = a_lo and a = a_hi + 1, each projected onto the line
+ *            through m along d: q = m + ((p - m) . d) d; metres ((cell_x0 + q.x) + 0.5) res, ((cell_y0 + q.y) + 0.5) res, rounded to
+ *            float.  Every operation rounded on its own.
+ * Accepted ranges (anything else is NHIP_ERR_ARG before anything is launched, with or without a device): res finite and > 0;
+ * width, height 1..16384; min_hits 1..2^30; n_theta 2..1024; min_votes >= 1; band finite, 0.5..65536 (cells); max_gap >= 0;
+ * min_length >= 1; max_segments >= 0; max_cells >= 0; max_rounds >= 0; check_every >= 1. */
+typedef struct nhip_vectorize_spec {
+  double res;           /* metres per cell (0.05) */
+  double band;          /* half width of a line's band, in cells (1.5) */
+  int32_t cell_x0;      /* the window's first cell, in world cells (the caller's: hostside.map_window) */
+  int32_t cell_y0;
+  int32_t width;        /* cells */
+  int32_t height;
+  int32_t min_hits;     /* points that make a cell occupied (2) */
+  int32_t n_theta;      /* rows of the accumulator: directions over half a turn (360) */
+  int32_t min_votes;    /* the smallest peak that still makes a round (20) */
+  int32_t max_gap;      /* empty along-line bins a run may bridge (4) */
+  int32_t min_length;   /* along-line bins a kept run spans (10) */
+  int32_t max_segments; /* capacity of the records (4096) */
+  int32_t flags;        /* 0 */
+  int32_t reserved;     /* 0 */
+} nhip_vectorize_spec_t;
+/* byte offsets of the planes a caller may read out of a workspace it owns (all 256-byte aligned, in this order), and its size */
+typedef struct nhip_vectorize_layout {
+  int64_t counts_offset; /* int32 [height][width] */
+  int64_t cells_offset;  /* int32 (cx, cy) pairs, max_cells of them */
+  int64_t votes_offset;  /* int32 [n_theta][n_rho]: after the call, the votes of the cells still live */
+  int64_t live_offset;   /* one byte per cell: 1 live, 0 dead */
+  int64_t bytes;         /* = nhip_vectorize_workspace_bytes */
+  int32_t n_rho;         /* 2 width + height + 1 */
+  int32_t n_along;       /* width + 2 height + 1: along-line bins, bin a at index a + height */
+} nhip_vectorize_layout_t;
+/* the defaults of the table above; the window (cell_x0, cell_y0, width, height) is 0 and is the caller's to set; pure host */
+int nhip_vectorize_spec_default(nhip_vectorize_spec_t *out);
+/* C[n_theta], S[n_theta]; pure host */
+int nhip_vectorize_tables(const nhip_vectorize_spec_t *spec, int32_t *c_table, int32_t *s_table);
+/* 4 floats per pose (x, y, theta: 3 doubles): ((float)cos theta, (float)sin theta, (float)x, (float)y), the cast of
+ * TransformPointcloud (slam_util.h:55-63); pure host */
+int nhip_map_pose_affines(const double *poses, int32_t n_poses, float *out);
+/* bytes of the workspace for up to max_cells cells (-1: a bad spec, message in nhip_last_error); pure host */
+int64_t nhip_vectorize_workspace_bytes(const nhip_vectorize_spec_t *spec, int32_t max_cells);
+int nhip_vectorize_workspace_layout(const nhip_vectorize_spec_t *spec, int32_t max_cells, nhip_vectorize_layout_t *out);
+/* The whole step on the caller's buffers and stream; never allocates.  d_affines: 4 floats per scan.  d_records: room for
+ * max_segments records (may be NULL if that is 0); d_stats: 8 int32.  The host looks at the device once per check_every
+ * rounds (one word) and once at the end: the call returns with the stream drained, and records, stats and planes do not
+ * depend on check_every.  The offsets are read by the kernels: a scan whose first offset is negative or whose end lies
+ * before its start is treated as empty and nhip_dev_status() reports it (kind 16384). */
+int nhip_vectorize_dev(const float *d_xy, const int32_t *d_offsets, const float *d_affines, int32_t n_scans,
+                       const nhip_vectorize_spec_t *spec, int32_t max_cells, int32_t max_rounds, int32_t check_every,
+                       int64_t *d_records, int32_t *d_stats, void *d_workspace, int64_t workspace_bytes, void *stream);
+/* records (n x 10 int64) -> lines (n x 4 floats: x1 y1 x2 y2, what WriteMapLines takes); pure host */
+int nhip_vectorize_endpoints(const nhip_vectorize_spec_t *spec, const int64_t *records, int32_t n, float *lines);
+
 /* HITL point selection: GetRelevantPosesForHITL (solver.cc:479-513) for every scan at once.  A point p of scan s goes to
  * the world as w = (c px - s py + tx, s px + c py + ty) with (c, s, tx, ty) = d_pose_f32[4s ..], the entries of
  * PoseArrayToAffine(pose).cast<float>() (nhip_pose_affines forms them), every operation a float operation rounded on its
@@ -728,6 +810,11 @@ int nhip_features_extract(const nhip_scans_t *scans, const nhip_feature_spec_t *
 /* nhip_normals_estimate_dev on uploaded scans; host outputs (normals: 2 floats per point; info: 4 int32 per point, may be
  * NULL). */
 int nhip_normals_estimate(const nhip_scans_t *scans, const nhip_normals_spec_t *spec, float *normals, int32_t *info);
+
+/* nhip_vectorize_dev on uploaded scans, with host poses (3 doubles per scan) and host outputs (records: room for
+ * max_segments x 10 int64; stats: 8 int32); allocates and frees its workspace. */
+int nhip_vectorize(const nhip_scans_t *scans, const double *poses, const nhip_vectorize_spec_t *spec, int32_t max_cells,
+                   int32_t max_rounds, int32_t check_every, int64_t *records, int32_t *stats);
 
 /* The reference-shaped single-pair call: CorrelativeScanMatcher(scanner_range, trans_range, low_res, high_res)
  * .GetTransformation(pc_a, pc_b, rot_a, rot_b, rot_restriction) -> (score, ((tx, ty), theta))

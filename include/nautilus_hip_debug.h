@@ -106,7 +106,10 @@ int nhip_round_norm_dev(const float *d_dx, const float *d_dy, int64_t n, int32_t
 #define NHIP_TIMER_CSM_BOUNDS 6 /* split form of the matcher: bounds + seeds (csm_bnb_kernel<., ., true, true>) ... */
 #define NHIP_TIMER_CSM_CAND 7   /* ... and the candidates (csm_bnb_cand_kernel); both inside NHIP_TIMER_CSM */
 #define NHIP_TIMER_EXACT_SCORE 8 /* the pass of NHIP_SEARCH_EXACT_SCORE (after, not inside, NHIP_TIMER_CSM) */
-#define NHIP_TIMER_COUNT 9
+#define NHIP_TIMER_VEC_RASTER 9  /* map vectorisation: clears, raster, cell list ... */
+#define NHIP_TIMER_VEC_VOTES 10  /* ... the votes of every cell ... */
+#define NHIP_TIMER_VEC_ROUNDS 11 /* ... and the rounds, one interval per batch of check_every rounds */
+#define NHIP_TIMER_COUNT 12
 int nhip_timing_enable(int on);
 int nhip_timing_reset(void);
 /* synchronises the recorded events; total_ms / launches since the last reset */

@@ -20,6 +20,7 @@ NHIP_NORMALS_MAX_BINS, NHIP_NORMALS_MAX_SAMPLES = 64, 128
 NHIP_GRID_SKIP_MAP, NHIP_GRID_NO_IMAGE = 1, 2
 NHIP_TIMER_CSM, NHIP_TIMER_GRID, NHIP_TIMER_RESID, NHIP_TIMER_CORR, NHIP_TIMER_NORMEQ, NHIP_TIMER_GRID_CLEAR = 0, 1, 2, 3, 4, 5
 NHIP_TIMER_CSM_BOUNDS, NHIP_TIMER_CSM_CAND, NHIP_TIMER_EXACT_SCORE = 6, 7, 8
+NHIP_TIMER_VEC_RASTER, NHIP_TIMER_VEC_VOTES, NHIP_TIMER_VEC_ROUNDS = 9, 10, 11
 
 
 class NhipError(RuntimeError):
@@ -64,6 +65,18 @@ class FeatureSpec(C.Structure):
 class NormalsSpec(C.Structure):
     _fields_ = [("neighborhood_size", C.c_double), ("neighborhood_step_size", C.c_double), ("mean_distance", C.c_double),
                 ("bin_number", C.c_int32), ("max_growth_steps", C.c_int32), ("seed", C.c_uint32), ("flags", C.c_int32)]
+
+
+class VectorizeSpec(C.Structure):
+    _fields_ = [("res", C.c_double), ("band", C.c_double), ("cell_x0", C.c_int32), ("cell_y0", C.c_int32),
+                ("width", C.c_int32), ("height", C.c_int32), ("min_hits", C.c_int32), ("n_theta", C.c_int32),
+                ("min_votes", C.c_int32), ("max_gap", C.c_int32), ("min_length", C.c_int32), ("max_segments", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class VectorizeLayout(C.Structure):
+    _fields_ = [("counts_offset", C.c_int64), ("cells_offset", C.c_int64), ("votes_offset", C.c_int64),
+                ("live_offset", C.c_int64), ("bytes", C.c_int64), ("n_rho", C.c_int32), ("n_along", C.c_int32)]
 
 
 class HitlSpec(C.Structure):
@@ -168,6 +181,14 @@ PROTOTYPES = {
     "nhip_normals_spec_default": (C.c_int, [_P(NormalsSpec)]),
     "nhip_normals_estimate_dev": (C.c_int, [_vp, _vp, _i32, _P(NormalsSpec), _vp, _vp, _vp]),
     "nhip_normals_estimate": (C.c_int, [_vp, _P(NormalsSpec), _vp, _vp]),
+    "nhip_vectorize_spec_default": (C.c_int, [_P(VectorizeSpec)]),
+    "nhip_vectorize_tables": (C.c_int, [_P(VectorizeSpec), _vp, _vp]),
+    "nhip_map_pose_affines": (C.c_int, [_vp, _i32, _vp]),
+    "nhip_vectorize_workspace_bytes": (_i64, [_P(VectorizeSpec), _i32]),
+    "nhip_vectorize_workspace_layout": (C.c_int, [_P(VectorizeSpec), _i32, _P(VectorizeLayout)]),
+    "nhip_vectorize_dev": (C.c_int, [_vp, _vp, _vp, _i32, _P(VectorizeSpec), _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "nhip_vectorize": (C.c_int, [_vp, _vp, _P(VectorizeSpec), _i32, _i32, _i32, _vp, _vp]),
+    "nhip_vectorize_endpoints": (C.c_int, [_P(VectorizeSpec), _vp, _i32, _vp]),
     "nhip_hitl_spec_default": (C.c_int, [_P(HitlSpec)]),
     "nhip_hitl_select_dev": (C.c_int, [_vp, _vp, _i32, _vp, _P(HitlSpec), _vp, _vp, _vp, _vp, _vp, _vp]),
     "nhip_hitl_pack_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -54,7 +54,7 @@ struct IdBounds {          // (plain data: it travels inside the kernels' parame
 constexpr uint32_t BAD_TARGET_ID = 1u, BAD_PAIR_SRC = 2u, BAD_PAIR_SLOT = 4u, BAD_BLOCK_ID = 8u, BAD_POSE_ID = 16u,
                    BAD_SCAN_ID = 32u, BAD_FEATURE_IDX = 64u, BAD_FEATURE_COUNT = 128u, BAD_SCAN_OFFSETS = 256u,
                    BAD_MEMBER_ID = 512u, BAD_SUBMAP_CAPACITY = 1024u, BAD_CONTRIB_ID = 2048u, BAD_BLOCK_COLUMN = 4096u,
-                   BAD_SYSTEM_ID = 8192u;
+                   BAD_SYSTEM_ID = 8192u, BAD_MAP_SCAN_OFFSETS = 16384u;
 constexpr int DEV_STATUS_WORDS = 4;  // {OR of the kinds seen, kind / value / index of the first report}
 uint32_t *dev_status();              // of the current device (allocated on the device's first use; null if that failed)
 #ifdef __HIPCC__
@@ -343,6 +343,38 @@ int launch_submap_gather(const float *d_xy, const int32_t *d_offsets, int32_t n_
 // sample limit's second term
 int launch_normals_estimate(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const nhip_normals_spec_t &spec,
                             int32_t sample_limit, float *d_normals, int32_t *d_info, hipStream_t s);
+
+// map vectorisation (nhip_vectorize.hip, K13); the spec has passed vectorize_spec_check (nhip_host_vectorize.hip)
+struct VecState {     // the first bytes of the workspace: what the round kernels keep between launches
+  int32_t stats[8];   // {M, segments, rounds, flag, cells emitted, cells retired, n_rho, 0}: the caller's stats, as they grow
+  int32_t end;        // set once the call has ended: every kernel of a round returns at once; the ONE word the host reads between batches
+  int32_t peak_t, peak_b, peak_votes;
+  int32_t action;     // of the round's runs kernel: VEC_RETIRE / VEC_COMMIT
+  int32_t n_band;     // entries of the band list
+};
+enum { VEC_RETIRE = 1, VEC_COMMIT = 2 };
+struct VecLayout {    // byte offsets inside the workspace (256-byte aligned); the first four planes are the caller's to read
+  int64_t state, counts, cells, votes, live, row_off, tables, partial, bits, run_of_bin, run_lo, run_hi, run_slot, band_list, bytes;
+  int32_t n_rho, n_along, bit_words, max_runs;
+};
+void vec_layout(const nhip_vectorize_spec_t &spec, int32_t max_cells, VecLayout *L);
+struct VecParams {    // plain data: travels in the kernels' parameter blocks
+  int32_t width, height, cell_x0, cell_y0, n_theta, n_rho, n_along, min_hits, min_votes, band_q, gap1, min_length, max_segments,
+      max_cells, max_rounds, n_scans;
+  double res, inv_res;
+  VecState *st;
+  int32_t *counts, *cells, *votes, *row_off, *run_of_bin, *run_lo, *run_hi, *run_slot, *band_list;
+  const int32_t *C, *S;
+  uint8_t *live;
+  unsigned long long *partial;
+  uint32_t *bits;
+  long long *records;
+  uint32_t *status;
+};
+// clears the state and the counts, then raster, cell list and the votes of every cell
+int launch_vec_front(const VecParams &P, const float *d_xy, const int32_t *d_offsets, const float *d_affines, hipStream_t s);
+// enqueues `n` rounds; each returns at once when the call has ended
+int launch_vec_rounds(const VecParams &P, int32_t n, hipStream_t s);
 
 int launch_resid_point_to_line(const float *d_segments, const float *d_points,
                                const int32_t *d_point_block, int64_t n_points,

@@ -266,6 +266,18 @@ def read_map_lines(path):
     return np.array([[float(v) for v in line.split(",")] for line in open(path) if line.strip()], dtype=np.float64).reshape(-1, 4)
 
 
+def map_window(poses, range_m, res):
+    """The smallest raster window that holds every pose +- range_m on both axes, in world cells of `res` metres (cell of x:
+    floor(x / res), cimg_debug.h:31-37): (cell_x0, cell_y0, width, height), what the map vectorisation's spec takes
+    ("Map vectorisation").  No poses: the one cell at the origin."""
+    P = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+    if len(P) == 0:
+        return 0, 0, 1, 1
+    lo = np.floor((P[:, :2].min(axis=0) - float(range_m)) / float(res)).astype(np.int64)
+    hi = np.floor((P[:, :2].max(axis=0) + float(range_m)) / float(res)).astype(np.int64)
+    return int(lo[0]), int(lo[1]), int(hi[0] - lo[0] + 1), int(hi[1] - lo[1] + 1)
+
+
 def hitl_segments(msg):
     """LineSegmentsFromHitlMsg (solver.cc:467-478): msg = dict with line_a_start, line_a_end, line_b_start,
     line_b_end, each (x, y[, z]) -> two LineSegment<float> as (x0, y0, x1, y1) float32 rows."""

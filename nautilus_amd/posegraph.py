@@ -105,6 +105,20 @@ class HipBackend:
         from . import normals
         return normals.estimate(xy, offsets, spec, device=str(self.dev))
 
+    def vectorize(self, poses, spec=None, xy=None, offsets=None):
+        """The vector map at `poses`, made on the GPU (vectorize.py: Solver::Vectorize): (lines float32 (n, 4), records,
+        stats).  Runs on the clouds the arena already holds (the last ICP problem's upload); with xy and offsets given, on
+        those -- uploaded only if they are not the arena's (a FEATURE-mode solve keeps feature clouds there).  spec=None: the
+        defaults on the window of every pose +- 30 m."""
+        from . import vectorize
+        spec = vectorize.window_spec(poses) if spec is None else spec
+        held = self.arena.clouds
+        if xy is not None and (held is None or held[4][0] is not xy):
+            return vectorize.vectorize(xy, offsets, poses, spec, device=str(self.dev))
+        if held is None:
+            raise RuntimeError("HipBackend.vectorize: no clouds on the device yet (the first icp() batch uploads them): pass xy, offsets")
+        return vectorize.vectorize_on_device(held[1], held[3], int(held[3].numel()) - 1, poses, spec)
+
     def reserve_icp(self, offsets, window):
         """Work buffers for the largest problem of a growing-window solve (all (i, j), j in [i - window, i)): allocated once."""
         off = np.asarray(offsets, dtype=np.int64)
