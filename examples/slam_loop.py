@@ -56,7 +56,7 @@ LC_MIN_SEPARATION = 20  # nodes between the two scans of a loop-closure pair (th
 def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, verbose=False, residual="normal",
         rank=0, world=1, device="cuda:0", backend=None, iterations=4, hitl=True, cell_bits=16, gate="scatter",
         min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False, normals="bag", lc_submap=0,
-        linear_solver="host", lc_gate="geometric", lc_max_score=5000.0, map_output=None):
+        linear_solver="host", lc_gate="geometric", lc_max_score=5000.0, map_output=None, grid_output=None):
     """min_scatter_score: LCCandidateFilter's threshold is 0.70 (lc_candidate_filter.cc:76); scans of the synthetic
     24 m x 16 m room score ~0.4, so callers on that world pass a lower one.
     hitl_device: the HITL constraint's points are selected and packed on the GPU (hitl.select, under the "path" clock) and
@@ -80,6 +80,9 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     map_output: a path -- the final poses' vector map (Solver::Vectorize, solver.cc:581-624: backend.vectorize, on the GPU)
     is written there as 'x1,y1,x2,y2' lines (hostside.write_map_lines); the result reports map_segments and vectorize_s, and
     keeps the poses the map was made at in "map_poses".
+    grid_output: a path stem -- the final poses' occupancy grid (backend.occupancy_grid: every scan ray-traced on the GPU) is
+    written as STEM.pgm and STEM.yaml, map_server's pair (hostside.write_occupancy_map); the result reports occupancy_s and
+    grid_occupied / grid_free / grid_unknown, and keeps the poses in "grid_poses".
     With world > 1 (one process per GPU under torch.distributed): the window ICP solve is replicated -- its
     consumer, the solver, is host-side -- and the loop-closure pairs are sharded by target across the ranks,
     matched, and all-gathered (nautilus_amd/sharding.py); every rank ends with the same trajectory."""
@@ -271,6 +274,20 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
             hostside.write_map_lines(map_output, map_lines)
         out["map_segments"], out["map_cells"], out["map_rounds"], out["map_flag"] = (int(map_stats[k]) for k in (1, 0, 2, 3))
         out["map_poses"] = [[float(v) for v in p] for p in poses]
+    if grid_output is not None:
+        # ---- the occupancy grid of the solved trajectory (build-defined: DESIGN.md section 3, "Occupancy grid")
+        if not hasattr(backend, "occupancy_grid"):
+            raise RuntimeError("run: grid_output needs a backend with occupancy_grid(); backend %r has none" % (backend.name,))
+        from nautilus_amd import occupancy
+        grid_spec = occupancy.window_spec(poses)
+        t0 = time.perf_counter()
+        grid, _, _, grid_stats = backend.occupancy_grid(poses, spec=grid_spec, xy=xy, offsets=off)  # (outside the stage clocks)
+        out["occupancy_s"] = time.perf_counter() - t0
+        if rank == 0:
+            hostside.write_occupancy_map(grid_output, grid, grid_spec)
+        out["grid_occupied"], out["grid_free"], out["grid_unknown"] = (int(grid_stats[k]) for k in (5, 6, 7))
+        out["grid_window"] = [grid_spec.cell_x0, grid_spec.cell_y0, grid_spec.width, grid_spec.height]
+        out["grid_poses"] = [[float(v) for v in p] for p in poses]
     out["t_total_s"] = sum(v for k, v in out.items() if k.startswith("t_") and k.endswith("_s"))
     # By owner: the hot path of this repo (every call into the backend: correspondence search, normal equations,
     # gating, scan matching -- "gpu_path_s" with the product's backend, "cpu_path_s" with the oracle's), the sparse
@@ -326,6 +343,8 @@ if __name__ == "__main__":
     ap.add_argument("--lc-max-score", type=float, default=5000.0, help="the chi-square gate's threshold (lc_matcher.cc:66: 5000)")
     ap.add_argument("--map-output", metavar="PATH", default=None,
                     help="vectorise the final poses' map on the GPU and write it there, one 'x1,y1,x2,y2' line per wall segment")
+    ap.add_argument("--grid-output", metavar="STEM", default=None,
+                    help="ray-trace the final poses' occupancy grid on the GPU and write STEM.pgm and STEM.yaml (map_server's pair)")
     ap.add_argument("-v", action="store_true")
     a = ap.parse_args()
     if not 0 <= a.lc_submap < LC_MIN_SEPARATION:
@@ -346,7 +365,8 @@ if __name__ == "__main__":
         os.dup2(saved, 1)
     res = run(a.scans, a.window, verbose=a.v and rank == 0, residual=a.residual, rank=rank, world=world,
               device="cuda:%d" % local, hitl_device=a.hitl_device, normals=a.normals, lc_submap=a.lc_submap,
-              linear_solver=a.linear_solver, lc_gate=a.lc_gate, lc_max_score=a.lc_max_score, map_output=a.map_output)
+              linear_solver=a.linear_solver, lc_gate=a.lc_gate, lc_max_score=a.lc_max_score, map_output=a.map_output,
+              grid_output=a.grid_output)
     res["world_size"] = world
     if rank == 0:
         print(json.dumps(res))

@@ -66,7 +66,8 @@ const char *nhip_version(void);
  * nhip_features_pack_dev, 256 scan offset of nhip_normals_estimate_dev, 512 member scan id and 1024 merged point count beyond
  * the capacity of nhip_submaps_gather_dev, 2048 contributor id of nhip_bsr_assemble_dev, 4096 block column of
  * nhip_bsr_assemble_dev / nhip_bsr_pcg_dev / nhip_bsr_pcg_columns_dev, 8192 gauge or right-hand-side index of
- * nhip_bsr_pcg_columns_dev, 16384 scan offset of nhip_vectorize_dev.  Clears the record (in the order of `stream`).
+ * nhip_bsr_pcg_columns_dev, 16384 scan offset of nhip_vectorize_dev /
+ * nhip_occupancy_dev.  Clears the record (in the order of `stream`).
  * ONE record per DEVICE, shared by every stream and host thread that uses the library on it: a host with several streams
  * on one device learns THAT an id was bad and which, not on which stream; a call that finds a record consumes it -- reports
  * of kernels still running on OTHER streams at that moment can be reported by this call or wiped by its clear.  Clients
@@ -721,6 +722,53 @@ int nhip_vectorize_dev(const float *d_xy, const int32_t *d_offsets, const float 
 /* records (n x 10 int64) -> lines (n x 4 floats: x1 y1 x2 y2, what WriteMapLines takes); pure host */
 int nhip_vectorize_endpoints(const nhip_vectorize_spec_t *spec, const int64_t *records, int32_t n, float *lines);
 
+/* K14: OCCUPANCY GRID -- the occupied / free / unknown raster of every scan at its pose, free space ray-traced from the
+ * sensor to every return ("Occupancy grid"; tests/occupancy_reference.py restates it in numpy).
+ * Build-defined and deterministic; all integer after the cells.
+ *   points   as K13's: scan i's affine (nhip_map_pose_affines), x' = ((c x) + ((-s) y)) + tx, y' likewise, in float.  The
+ *            ray origin of scan i is (tx, ty).
+ *   cells    floor((double)v / res) of the origin and of every end point.  A scan whose origin is not finite or has a floor
+ *            of magnitude >= 2^62 is DROPPED; a point that is not finite or has such a floor is DROPPED.  d = end - origin
+ *            per axis (in double, from the two floors); |dx| or |dy| > max_ray_cells: the beam is LONG and adds nothing.
+ *   ray      n = max(|dx|, |dy|); the free cells of a beam are origin + (rdiv(k dx, n), rdiv(k dy, n)) for k = 0 .. n - 1,
+ *            rdiv(a, n) = floor((2 a + n) / (2 n)) (a floor division: nearest, halves up, on both signs).  n = 0: none.
+ *   a scan   H = the end cells of its kept beams; F = the free cells of its kept beams minus H.  hits[cy][cx] counts the
+ *            scans with the cell in H, misses[cy][cx] those with it in F: one observation per scan and cell, inside the
+ *            window (cell_x0, cell_y0, width, height) -- rays that start or end outside it still mark what they cross.
+ *   grid     int8 [height][width], ROS OccupancyGrid values; obs = hits + misses (int64): obs < min_obs: -1; else
+ *            1000 hits >= occ_permille obs: 100; else 1000 hits <= free_permille obs: 0; else -1.
+ *   planes   without NHIP_OCC_ACCUMULATE the call clears hits and misses first (in-stream); with it the call adds onto what
+ *            they hold.  The grid is classified from the planes as they stand after the call.
+ *   stats    8 int64: {scans traced, scans dropped (or offsets that are not a scan), beams traced, beams long, points dropped}
+ *            of this call (the points of a dropped scan are counted nowhere), {cells occupied, free, unknown} of the grid.
+ * Accepted ranges (anything else is NHIP_ERR_ARG before anything is launched, with or without a device): res finite and > 0;
+ * width, height 1..16384; max_ray_cells 1..4096; min_obs 1..2^30; occ_permille 1..1000; free_permille 0..occ_permille - 1;
+ * flags 0 or NHIP_OCC_ACCUMULATE; reserved 0; n_scans >= 0. */
+#define NHIP_OCC_ACCUMULATE 1
+typedef struct nhip_occupancy_spec {
+  double res;            /* metres per cell (0.05) */
+  int32_t cell_x0;       /* the window's first cell, in world cells (the caller's: hostside.map_window) */
+  int32_t cell_y0;
+  int32_t width;         /* cells */
+  int32_t height;
+  int32_t max_ray_cells; /* the longest beam traced, in cells per axis (640: 30 m and the discretisation) */
+  int32_t min_obs;       /* observations that make a cell known (1) */
+  int32_t occ_permille;  /* hits per 1000 observations from which a cell is occupied (650: map_server's 0.65) */
+  int32_t free_permille; /* ... up to which it is free (196: map_server's 0.196) */
+  int32_t flags;         /* 0, or NHIP_OCC_ACCUMULATE */
+  int32_t reserved;      /* 0 */
+} nhip_occupancy_spec_t;
+/* the defaults of the table above; the window is 0 and is the caller's to set; pure host */
+int nhip_occupancy_spec_default(nhip_occupancy_spec_t *out);
+/* The whole step on the caller's buffers and stream; never allocates, needs no workspace, enqueues and returns without
+ * waiting.  d_affines: 4 floats per scan.  d_hits, d_misses: int32 [height][width], 16-byte aligned; d_grid: int8
+ * [height][width], 4-byte aligned; d_stats: 8 int64.  n_scans = 0 is a call: the planes cleared (without the flag), the grid
+ * classified.  The offsets are read by the kernels: a scan whose first offset is negative or whose end lies before its start
+ * is treated as empty, counted as dropped, and nhip_dev_status() reports it (kind 16384). */
+int nhip_occupancy_dev(const float *d_xy, const int32_t *d_offsets, const float *d_affines, int32_t n_scans,
+                       const nhip_occupancy_spec_t *spec, int32_t *d_hits, int32_t *d_misses, int8_t *d_grid, int64_t *d_stats,
+                       void *stream);
+
 /* HITL point selection: GetRelevantPosesForHITL (solver.cc:479-513) for every scan at once.  A point p of scan s goes to
  * the world as w = (c px - s py + tx, s px + c py + ty) with (c, s, tx, ty) = d_pose_f32[4s ..], the entries of
  * PoseArrayToAffine(pose).cast<float>() (nhip_pose_affines forms them), every operation a float operation rounded on its
@@ -815,6 +863,12 @@ int nhip_normals_estimate(const nhip_scans_t *scans, const nhip_normals_spec_t *
  * max_segments x 10 int64; stats: 8 int32); allocates and frees its workspace. */
 int nhip_vectorize(const nhip_scans_t *scans, const double *poses, const nhip_vectorize_spec_t *spec, int32_t max_cells,
                    int32_t max_rounds, int32_t check_every, int64_t *records, int32_t *stats);
+
+/* nhip_occupancy_dev on uploaded scans, with host poses (3 doubles per scan) and host outputs (hits, misses: width x height
+ * int32; grid: width x height int8; stats: 8 int64); allocates and frees its device buffers.  With NHIP_OCC_ACCUMULATE hits
+ * and misses are also inputs: they are uploaded first. */
+int nhip_occupancy(const nhip_scans_t *scans, const double *poses, const nhip_occupancy_spec_t *spec, int32_t *hits,
+                   int32_t *misses, int8_t *grid, int64_t *stats);
 
 /* The reference-shaped single-pair call: CorrelativeScanMatcher(scanner_range, trans_range, low_res, high_res)
  * .GetTransformation(pc_a, pc_b, rot_a, rot_b, rot_restriction) -> (score, ((tx, ty), theta))

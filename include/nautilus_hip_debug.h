@@ -109,7 +109,9 @@ int nhip_round_norm_dev(const float *d_dx, const float *d_dy, int64_t n, int32_t
 #define NHIP_TIMER_VEC_RASTER 9  /* map vectorisation: clears, raster, cell list ... */
 #define NHIP_TIMER_VEC_VOTES 10  /* ... the votes of every cell ... */
 #define NHIP_TIMER_VEC_ROUNDS 11 /* ... and the rounds, one interval per batch of check_every rounds */
-#define NHIP_TIMER_COUNT 12
+#define NHIP_TIMER_OCC_TRACE 12    /* occupancy grid: the clears and the ray trace of every scan ... */
+#define NHIP_TIMER_OCC_CLASSIFY 13 /* ... and the classification of the window */
+#define NHIP_TIMER_COUNT 14
 int nhip_timing_enable(int on);
 int nhip_timing_reset(void);
 /* synchronises the recorded events; total_ms / launches since the last reset */

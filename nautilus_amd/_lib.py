@@ -21,6 +21,8 @@ NHIP_GRID_SKIP_MAP, NHIP_GRID_NO_IMAGE = 1, 2
 NHIP_TIMER_CSM, NHIP_TIMER_GRID, NHIP_TIMER_RESID, NHIP_TIMER_CORR, NHIP_TIMER_NORMEQ, NHIP_TIMER_GRID_CLEAR = 0, 1, 2, 3, 4, 5
 NHIP_TIMER_CSM_BOUNDS, NHIP_TIMER_CSM_CAND, NHIP_TIMER_EXACT_SCORE = 6, 7, 8
 NHIP_TIMER_VEC_RASTER, NHIP_TIMER_VEC_VOTES, NHIP_TIMER_VEC_ROUNDS = 9, 10, 11
+NHIP_TIMER_OCC_TRACE, NHIP_TIMER_OCC_CLASSIFY = 12, 13
+NHIP_OCC_ACCUMULATE = 1
 
 
 class NhipError(RuntimeError):
@@ -77,6 +79,12 @@ class VectorizeSpec(C.Structure):
 class VectorizeLayout(C.Structure):
     _fields_ = [("counts_offset", C.c_int64), ("cells_offset", C.c_int64), ("votes_offset", C.c_int64),
                 ("live_offset", C.c_int64), ("bytes", C.c_int64), ("n_rho", C.c_int32), ("n_along", C.c_int32)]
+
+
+class OccupancySpec(C.Structure):
+    _fields_ = [("res", C.c_double), ("cell_x0", C.c_int32), ("cell_y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("max_ray_cells", C.c_int32), ("min_obs", C.c_int32), ("occ_permille", C.c_int32), ("free_permille", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
 class HitlSpec(C.Structure):
@@ -189,6 +197,9 @@ PROTOTYPES = {
     "nhip_vectorize_dev": (C.c_int, [_vp, _vp, _vp, _i32, _P(VectorizeSpec), _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     "nhip_vectorize": (C.c_int, [_vp, _vp, _P(VectorizeSpec), _i32, _i32, _i32, _vp, _vp]),
     "nhip_vectorize_endpoints": (C.c_int, [_P(VectorizeSpec), _vp, _i32, _vp]),
+    "nhip_occupancy_spec_default": (C.c_int, [_P(OccupancySpec)]),
+    "nhip_occupancy_dev": (C.c_int, [_vp, _vp, _vp, _i32, _P(OccupancySpec), _vp, _vp, _vp, _vp, _vp]),
+    "nhip_occupancy": (C.c_int, [_vp, _vp, _P(OccupancySpec), _vp, _vp, _vp, _vp]),
     "nhip_hitl_spec_default": (C.c_int, [_P(HitlSpec)]),
     "nhip_hitl_select_dev": (C.c_int, [_vp, _vp, _i32, _vp, _P(HitlSpec), _vp, _vp, _vp, _vp, _vp, _vp]),
     "nhip_hitl_pack_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -376,6 +376,19 @@ int launch_vec_front(const VecParams &P, const float *d_xy, const int32_t *d_off
 // enqueues `n` rounds; each returns at once when the call has ended
 int launch_vec_rounds(const VecParams &P, int32_t n, hipStream_t s);
 
+// occupancy grid (nhip_occupancy.hip, K14); the spec has passed occupancy_spec_check (nhip_host_occupancy.hip)
+struct OccParams {    // plain data: travels in the kernels' parameter blocks
+  int32_t width, height, cell_x0, cell_y0, max_ray_cells, min_obs, occ_permille, free_permille, n_scans;
+  double res, inv_res;
+  int32_t *hits, *misses;
+  int8_t *grid;
+  long long *stats;   // 8 words: {scans traced, scans dropped, beams traced, beams long, points dropped, occupied, free, unknown}
+  uint32_t *status;
+};
+// clears the stats (and, with `clear`, both planes), then the trace of every scan and the classification of the window
+int launch_occupancy(const OccParams &P, bool clear, const float *d_xy, const int32_t *d_offsets, const float *d_affines,
+                     hipStream_t s);
+
 int launch_resid_point_to_line(const float *d_segments, const float *d_points,
                                const int32_t *d_point_block, int64_t n_points,
                                const int32_t *d_block_pose, const int32_t *d_block_line,

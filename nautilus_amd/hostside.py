@@ -9,6 +9,7 @@ end-to-end test can be driven the way nautilus drives them.  Nothing here is on 
   HitlSlamInputMsg (two line segments)    msg/HitlSlamInputMsg.msg:1-4, solver.cc:467-478
 """
 import math
+import os
 
 import numpy as np
 
@@ -276,6 +277,52 @@ def map_window(poses, range_m, res):
     lo = np.floor((P[:, :2].min(axis=0) - float(range_m)) / float(res)).astype(np.int64)
     hi = np.floor((P[:, :2].max(axis=0) + float(range_m)) / float(res)).astype(np.int64)
     return int(lo[0]), int(lo[1]), int(hi[0] - lo[0] + 1), int(hi[1] - lo[1] + 1)
+
+
+OCCUPANCY_PIXELS = ((100, 0), (0, 254), (-1, 205))  # (grid value, pixel): map_server's convention with negate 0
+
+
+def write_occupancy_map(path_stem, grid, spec):
+    """An occupancy grid (int8 (H, W): 100 occupied, 0 free, -1 unknown; occupancy.occupancy_grid) as the pair of files
+    map_server loads: path_stem + '.pgm', a binary PGM (occupied 0, free 254, unknown 205; image row 0 = the highest y), and
+    path_stem + '.yaml' beside it (plain text: image, resolution, origin = the window's corner in metres, negate,
+    occupied_thresh, free_thresh).  Returns the two paths."""
+    g = np.asarray(grid, dtype=np.int8)
+    if g.shape != (spec.height, spec.width):
+        raise ValueError("write_occupancy_map: grid of shape %s for a window of %d x %d" % (g.shape, spec.height, spec.width))
+    img = np.full(g.shape, 205, np.uint8)
+    for value, pixel in OCCUPANCY_PIXELS:
+        img[g == value] = pixel
+    pgm, yaml = path_stem + ".pgm", path_stem + ".yaml"
+    with open(pgm, "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (spec.width, spec.height))
+        f.write(img[::-1].tobytes())
+    with open(yaml, "w") as f:
+        f.write("image: %s\nresolution: %r\norigin: [%r, %r, 0.0]\nnegate: 0\noccupied_thresh: %r\nfree_thresh: %r\n"
+                % (os.path.basename(pgm), float(spec.res), spec.cell_x0 * float(spec.res), spec.cell_y0 * float(spec.res),
+                   spec.occ_permille / 1000.0, spec.free_permille / 1000.0))
+    return pgm, yaml
+
+
+def read_occupancy_map(path_stem):
+    """What write_occupancy_map wrote: (grid int8 (H, W), dict of the YAML's entries: image (str), resolution, origin (list),
+    negate, occupied_thresh, free_thresh)."""
+    info = {}
+    for line in open(path_stem + ".yaml"):
+        if ":" in line:
+            k, v = (t.strip() for t in line.split(":", 1))
+            info[k] = ([float(t) for t in v.strip("[]").split(",")] if v.startswith("[") else
+                       v if k == "image" else int(v) if k == "negate" else float(v))
+    raw = open(os.path.join(os.path.dirname(path_stem), info["image"]), "rb").read()
+    head = raw.split(b"\n", 3)
+    if head[0] != b"P5" or head[2] != b"255":
+        raise ValueError("read_occupancy_map: %s is not a binary PGM with 255 levels" % info["image"])
+    w, h = (int(t) for t in head[1].split())
+    img = np.frombuffer(head[3], dtype=np.uint8, count=w * h).reshape(h, w)[::-1]
+    grid = np.full((h, w), -1, np.int8)
+    for value, pixel in OCCUPANCY_PIXELS:
+        grid[img == pixel] = value
+    return grid, info
 
 
 def hitl_segments(msg):

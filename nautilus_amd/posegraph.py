@@ -119,6 +119,19 @@ class HipBackend:
             raise RuntimeError("HipBackend.vectorize: no clouds on the device yet (the first icp() batch uploads them): pass xy, offsets")
         return vectorize.vectorize_on_device(held[1], held[3], int(held[3].numel()) - 1, poses, spec)
 
+    def occupancy_grid(self, poses, spec=None, xy=None, offsets=None):
+        """The occupancy grid at `poses`, ray-traced on the GPU (occupancy.py): (grid int8 (H, W), hits, misses, stats).  Runs
+        on the clouds the arena already holds, or on xy and offsets, exactly as vectorize() chooses.  spec=None: the defaults
+        on the window of every pose +- 30 m."""
+        from . import occupancy
+        spec = occupancy.window_spec(poses) if spec is None else spec
+        held = self.arena.clouds
+        if xy is not None and (held is None or held[4][0] is not xy):
+            return occupancy.occupancy_grid(xy, offsets, poses, spec, device=str(self.dev))
+        if held is None:
+            raise RuntimeError("HipBackend.occupancy_grid: no clouds on the device yet (the first icp() batch uploads them): pass xy, offsets")
+        return occupancy.occupancy_grid_on_device(held[1], held[3], int(held[3].numel()) - 1, poses, spec)
+
     def reserve_icp(self, offsets, window):
         """Work buffers for the largest problem of a growing-window solve (all (i, j), j in [i - window, i)): allocated once."""
         off = np.asarray(offsets, dtype=np.int64)
