@@ -177,31 +177,52 @@ __device__ __forceinline__ void coarse_rotation(const BnbParams &P, const uint8_
 
   // (Tried: the window origins of TWO chunks per turn in one basic block, so that the scheduler interleaves the two
   //  chains -- bounds + seeds 3.18 -> 3.23 ms, profiles/r04_bounds_variants.txt: the chains' latency is hidden already.)
-  // (the points of the next PD chunks are in flight while one chunk is worked: with two workgroups per CU gathering
-  //  from their grids, a point load takes ~1,300 clocks, more than a chunk's work)
-  constexpr int PD = 2;
-  float2 qn[PD];
-#pragma unroll
-  for (int d = 0; d < PD; d++) qn[d] = 64 * d + lane < n_pts ? pts[64 * d + lane] : make_float2(0.f, 0.f);
-  for (int32_t c = 0;; c += 64) {
-    const bool more = c < n_pts;  // (one more turn after the last chunk drains the list)
+  // The points of the next PD = 2 chunks are in flight while one chunk is worked: with two workgroups per CU gathering
+  // from their grids, a point load takes ~1,300 clocks, more than a chunk's work.  Each slot is a register pair of its
+  // own (q0, q1) and a turn of the loop works both, so that the wait before a slot's points are used is vmcnt(1): it
+  // admits the other slot's load, issued one chunk later.  What keeps that depth in the compiled loop
+  // (profiles/r14_point_prefetch_isa.txt; each of these, left out, brings back a full wait):
+  //  - the chunk's points leave the slot through an opaque copy, and the slot's next chunk is loaded straight into it
+  //    (a ring qn[d] = qn[d + 1] is loaded into a temporary and copied at the back-edge, behind vmcnt(0));
+  //  - the load is unconditional, its index clamped to the scan's last point (a guarded load is a select on the loaded
+  //    registers); lanes past the scan's end are dropped by `live` as before;
+  //  - both slots load on every turn and only the second BODY is predicated (a break between the bodies leaves a path
+  //    into the header on which the first slot's load is the youngest);
+  //  - the priming loads are issued first slot first.
+  // Nothing else of the loop uses the vector-memory counter out of order: the gather's loads (global form) are awaited
+  // inside their pass, and the run list is LDS.
+  auto offsets = [&](float2 pt, int32_t c) {  // pooled offsets of chunk c from its points
     uint32_t a = zero_a;
-    if (more) {
-      const float2 pt = qn[0];
-#pragma unroll
-      for (int d = 0; d < PD - 1; d++) qn[d] = qn[d + 1];
-      if (c + 64 * PD + lane < n_pts) qn[PD - 1] = pts[c + 64 * PD + lane];
-      const bool live = c + lane < n_pts;
-      if (live) {
-        int32_t prow, pcol;
-        window_origin<true>(pt, cf, sf, P, cx, cy, &prow, &pcol);
-        // (both factors are below 2^12: rows and pitch of the pooled image; the padding keeps prow positive)
-        a = __umul24((uint32_t)prow >> 3, (uint32_t)DP) + ((uint32_t)pcol >> 3);
+    if (c + lane < n_pts) {
+      int32_t prow, pcol;
+      window_origin<true>(pt, cf, sf, P, cx, cy, &prow, &pcol);
+      // (both factors are below 2^12: rows and pitch of the pooled image; the padding keeps prow positive)
+      a = __umul24((uint32_t)prow >> 3, (uint32_t)DP) + ((uint32_t)pcol >> 3);
+    }
+    return a;
+  };
+  constexpr int PD = 2;
+  if (n_pts > 0) {  // (an empty scan loads nothing)
+    const int32_t last = n_pts - 1;
+    float2 q0 = pts[min(lane, last)];
+    __builtin_amdgcn_sched_barrier(0);
+    float2 q1 = pts[min(64 + lane, last)];
+    for (int32_t c = 0; c < n_pts; c += 64 * PD) {
+      {
+        float2 pt = q0;
+        asm volatile("" : "+v"(pt.x), "+v"(pt.y));
+        q0 = pts[min(c + 64 * PD + lane, last)];
+        feed(offsets(pt, c), c, true);
+      }
+      {
+        float2 pt = q1;
+        asm volatile("" : "+v"(pt.x), "+v"(pt.y));
+        q1 = pts[min(c + 64 * PD + 64 + lane, last)];
+        if (c + 64 < n_pts) feed(offsets(pt, c + 64), c + 64, true);
       }
     }
-    feed(a, c, more);
-    if (!more) break;
   }
+  feed(zero_a, 0, false);  // (one more turn after the last chunk drains the list)
 }
 
 // (Tried, commit 9e18995: LANES = (list entry, block row) -- a lane holds 12 byte sums instead of 11 x 12, no transposing

@@ -208,7 +208,9 @@ enum : int32_t { RUNS_NONE = 0, RUNS_FIELD = -1, RUNS_FULL = -2 };
 // merge (8-bit: 6.31 -> 6.25 ms).
 // RUNS (with `runs`, the wave's RUN_WAVE words, and want_runs, wave-uniform): the run list is written in the same sweep
 // and *run_chunks says what became of it (above).
-template <bool RUNS = false>
+// RING: the form of the loop over the scan's chunks, see there -- the ring of the candidates' kernels (the callers with
+// RUNS) or the slots of the seeds.
+template <bool RUNS = false, bool RING = RUNS>
 __device__ __forceinline__ int32_t cache_origins(const BnbParams &P, const float2 *pts, int32_t n_pts, float cf, float sf,
                                                  int32_t cx, int32_t cy, int lane, uint32_t *org, bool merged,
                                                  uint32_t *runs = nullptr, bool want_runs = false,
@@ -217,31 +219,20 @@ __device__ __forceinline__ int32_t cache_origins(const BnbParams &P, const float
   const bool with_runs = RUNS && want_runs;
   if (RUNS) *run_chunks = RUNS_NONE;
   for (int merge = merged ? 1 : 0; merge >= 0; merge--) {
-    // (rolled: the origin arithmetic holds a division on its rare path.  The points of the next D chunks are in flight
-    //  while one chunk's origins are computed; that array rotates so that its indices stay static.)
-    constexpr int D = 6;
-    float px[D], py[D];
-#pragma unroll
-    for (int d = 0; d < D; d++) {
-      const float2 q = 64 * d + lane < n_pts ? pts[64 * d + lane] : make_float2(0.f, 0.f);
-      px[d] = q.x;
-      py[d] = q.y;
-    }
+    // (the seeds, !RING.)  The points of the next D chunks are in flight while one chunk's origins are computed.  Each of
+    // the D slots is a register pair of its own and a turn of the loop works all D (the turn is rolled: the origin
+    // arithmetic holds a division on its rare path), so that the wait before a slot's points are used is vmcnt(D - 1): it
+    // admits the D - 1 loads issued after it.  The form is coarse_rotation's (nhip_bnb_bounds.h, which says what loses the
+    // depth again): the points leave the slot through an opaque copy and the slot's next chunk is loaded straight into
+    // it, unconditionally, from an offset clamped to the scan's last point; every slot loads on every turn and only the
+    // bodies after the first are predicated; the priming loads are issued in slot order.  D = 3, 4 and 6 measured the
+    // same (bounds + seeds 2.71 -> 2.66 ms, profiles/r14_point_prefetch.txt); three take the fewest registers.
+    constexpr int D = 3;
     uint32_t tail = 0u;  // entries written (wave-uniform)
     uint32_t rtail = 0u;  // runs found (wave-uniform; those past RUN_WAVE are not written)
-#pragma unroll 1
-    for (int c = 0; c < OCL; c++) {
+    // the entries of chunk c (64 * c < n_pts) from its points
+    auto chunk = [&](float2 pt, int c) {
       const int32_t idx = 64 * c + lane;
-      if (64 * c >= n_pts) break;
-      const float2 pt = make_float2(px[0], py[0]);
-      const float2 qn = idx + 64 * D < n_pts ? pts[idx + 64 * D] : make_float2(0.f, 0.f);
-#pragma unroll
-      for (int d = 0; d < D - 1; d++) {
-        px[d] = px[d + 1];
-        py[d] = py[d + 1];
-      }
-      px[D - 1] = qn.x;
-      py[D - 1] = qn.y;
       const bool live = idx < n_pts;
       uint32_t o = 0u;
       if (live) {
@@ -270,6 +261,62 @@ __device__ __forceinline__ int32_t cache_origins(const BnbParams &P, const float
         const uint32_t at = rtail + __builtin_amdgcn_mbcnt_hi((uint32_t)(H2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)H2, 0u));
         if (head2 && at < (uint32_t)RUN_WAVE) runs[at] = (o & RUN_KEY_MASK) | cnt2;
         rtail += (uint32_t)__builtin_popcountll(H2);
+      }
+    };
+    const int32_t n_in = min(n_pts, 64 * OCL);  // (the list holds OCL chunks; the callers send no longer scan here)
+    if (RING) {
+      // The candidates' kernels: a ring of R chunks that rotates so that its indices stay static.  Its compiled loop
+      // awaits, at the back-edge, the load the turn has just issued -- and the slots below, which do not, were worth
+      // 0.03 ms of these kernels' 2.48, inside the spread of their runs (profiles/r14_point_prefetch.txt: the waits
+      // move into the exact sums, whose loads the address unit serialises anyway).  So they keep the parent's code.
+      constexpr int R = 6;
+      float px[R], py[R];
+#pragma unroll
+      for (int d = 0; d < R; d++) {
+        const float2 q = 64 * d + lane < n_pts ? pts[64 * d + lane] : make_float2(0.f, 0.f);
+        px[d] = q.x;
+        py[d] = q.y;
+      }
+#pragma unroll 1
+      for (int c = 0; c < OCL; c++) {
+        const int32_t idx = 64 * c + lane;
+        if (64 * c >= n_pts) break;
+        const float2 pt = make_float2(px[0], py[0]);
+        const float2 qn = idx + 64 * R < n_pts ? pts[idx + 64 * R] : make_float2(0.f, 0.f);
+#pragma unroll
+        for (int d = 0; d < R - 1; d++) {
+          px[d] = px[d + 1];
+          py[d] = py[d + 1];
+        }
+        px[R - 1] = qn.x;
+        py[R - 1] = qn.y;
+        chunk(pt, c);
+      }
+    } else if (n_in > 0) {  // (an empty scan loads nothing)
+      // (a 32-bit byte offset from the wave-uniform pointer, at most 8 * 64 * OCL: one address register per load)
+      const uint32_t last = 8u * (uint32_t)(n_in - 1);
+      auto point_at = [&](int32_t i) {
+        return *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(pts) + min(8u * (uint32_t)i, last));
+      };
+      float2 q[D];
+#pragma unroll
+      for (int d = 0; d < D; d++) {
+        // (the offset opaque: these addresses are the same for every rotation, and kept across the caller's loop over
+        //  its rotations they cost the kernel of 16-bit grids, at its 96 registers, spilled dwords)
+        int32_t i = 64 * d + lane;
+        asm volatile("" : "+v"(i));
+        q[d] = point_at(i);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+#pragma unroll 1
+      for (int c = 0; 64 * c < n_in; c += D) {
+#pragma unroll
+        for (int d = 0; d < D; d++) {
+          float2 pt = q[d];
+          asm volatile("" : "+v"(pt.x), "+v"(pt.y));
+          q[d] = point_at(64 * (c + d + D) + lane);
+          if (d == 0 || 64 * (c + d) < n_in) chunk(pt, c + d);
+        }
       }
     }
     const int32_t nch = (int32_t)((tail + 63u) >> 6);
