@@ -56,7 +56,8 @@ LC_MIN_SEPARATION = 20  # nodes between the two scans of a loop-closure pair (th
 def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, verbose=False, residual="normal",
         rank=0, world=1, device="cuda:0", backend=None, iterations=4, hitl=True, cell_bits=16, gate="scatter",
         min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False, normals="bag", lc_submap=0,
-        linear_solver="host", lc_gate="geometric", lc_max_score=5000.0, map_output=None, grid_output=None):
+        linear_solver="host", lc_gate="geometric", lc_max_score=5000.0, map_output=None, grid_output=None, lc_verify=None,
+        lc_max_violation=None):
     """min_scatter_score: LCCandidateFilter's threshold is 0.70 (lc_candidate_filter.cc:76); scans of the synthetic
     24 m x 16 m room score ~0.4, so callers on that world pass a lower one.
     hitl_device: the HITL constraint's points are selected and packed on the GPU (hitl.select, under the "path" clock) and
@@ -83,6 +84,12 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     grid_output: a path stem -- the final poses' occupancy grid (backend.occupancy_grid: every scan ray-traced on the GPU) is
     written as STEM.pgm and STEM.yaml, map_server's pair (hostside.write_occupancy_map); the result reports occupancy_s and
     grid_occupied / grid_free / grid_unknown, and keeps the poses in "grid_poses".
+    lc_verify: "free-space" -- every match record is checked against the target's free space ("Free-space
+    check"): a record is kept only if the source returns that land in space the target's beams crossed, plus the source beams
+    that run through a target hit, are at most lc_max_violation permille (None: freespace.DEFAULT_MAX_PERMILLE) of the returns
+    inside the grid.  A backend whose match() takes `freespace` checks on the device inside the call; any other is checked by
+    hostside.freespace_counts.  The result reports lc_verified, lc_verify_rejected (they sum to the unverified run's
+    lc_accepted) and the rms relative error of either set.  Not with world > 1 or lc_submap.
     With world > 1 (one process per GPU under torch.distributed): the window ICP solve is replicated -- its
     consumer, the solver, is host-side -- and the loop-closure pairs are sharded by target across the ranks,
     matched, and all-gathered (nautilus_amd/sharding.py); every rank ends with the same trajectory."""
@@ -107,6 +114,12 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
                          % (lc_submap, LC_MIN_SEPARATION))
     if lc_submap and world > 1:
         raise ValueError("run: lc_submap with world > 1 (sharded matching has no submaps)")
+    if lc_verify not in (None, "free-space"):
+        raise ValueError("run: lc_verify %r (None or \"free-space\")" % (lc_verify,))
+    if lc_verify and (world > 1 or lc_submap):
+        raise ValueError("run: lc_verify with world > 1 or lc_submap (the free-space check has no sharded path and no submap targets)")
+    if lc_max_violation is not None and not 0 <= int(lc_max_violation) <= 1000:
+        raise ValueError("run: lc_max_violation %r: permille, 0..1000" % (lc_max_violation,))
     out = {"backend": backend.name, "n_scans": n_scans, "window": window, "residual": residual,
            "err_odometry_m": posegraph.trajectory_error(odom, bag.truth)}
     posegraph.clock_reset()
@@ -211,9 +224,16 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
                 xy_m, off_m, tgt_m = hostside.submap_extra_scans(xy, off, poses, tgt, lc_submap)
             with posegraph.clocked("path"):
                 m, spec, search = backend.match(xy_m, off_m, src, tgt_m, theta0, cell_bits)
+        elif lc_verify and "freespace" in inspect.signature(backend.match).parameters:
+            from nautilus_amd import freespace
+            with posegraph.clocked("path"):
+                m, spec, search, fs_counts = backend.match(xy, off, src, tgt, theta0, cell_bits, freespace=freespace.default_spec())
         else:
             with posegraph.clocked("path"):
                 m, spec, search = backend.match(xy, off, src, tgt, theta0, cell_bits)
+            if lc_verify:  # (a backend without the parameter: the plain numpy host path, as submap_extra_scans is for submaps)
+                with posegraph.clocked("marshal"):
+                    fs_counts = hostside.freespace_counts(xy, off, src, tgt, theta0, m, spec, search)
         out["t_csm_s"] = time.perf_counter() - t0
         with posegraph.clocked("marshal"):  # (records -> (tx, ty, theta) as consumed at solver.cc:640-644, vectorised)
             rel = np.stack([(m["ix"].astype(np.float64) - (search.nx - 1) // 2) * spec.res,
@@ -224,9 +244,18 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         # "Anything above this threshold for CSM is deemed a successful local loop closure"
         # (csm_score_threshold = -5.0, config/default_config.lua:84-85); optima on the lattice border are open-ended
         good = inside & (m["score"] > csm_score_threshold)
-        out["lc_accepted"] = int(good.sum())
         truth_rel = np.array([bag.true_relative(s, t) for s, t in zip(src, tgt)])
-        out["lc_rel_err_m"] = float(np.sqrt(np.mean(np.sum((rel[good, :2] - truth_rel[good, :2]) ** 2, axis=1)))) if good.any() else None
+        rms = lambda sel: float(np.sqrt(np.mean(np.sum((rel[sel, :2] - truth_rel[sel, :2]) ** 2, axis=1)))) if sel.any() else None
+        if lc_verify:
+            from nautilus_amd import freespace
+            permille = freespace.DEFAULT_MAX_PERMILLE if lc_max_violation is None else int(lc_max_violation)
+            verified = freespace.keep(fs_counts, permille)
+            out["lc_verify"], out["lc_max_violation"] = lc_verify, permille
+            out["lc_verified"], out["lc_verify_rejected"] = int((good & verified).sum()), int((good & ~verified).sum())
+            out["lc_verify_rejected_rel_err_m"] = rms(good & ~verified)
+            good &= verified
+        out["lc_accepted"] = int(good.sum())
+        out["lc_rel_err_m"] = rms(good)
         lc = (src[good], tgt[good], rel[good])
         t0 = time.perf_counter()
         with posegraph.clocked("marshal"):
@@ -341,6 +370,12 @@ if __name__ == "__main__":
                          "blocks of the pose graph (PoseGraph.cross_covariances with --linear-solver's solver), intersected with "
                          "the separation rule")
     ap.add_argument("--lc-max-score", type=float, default=5000.0, help="the chi-square gate's threshold (lc_matcher.cc:66: 5000)")
+    ap.add_argument("--lc-verify", choices=["free-space"], default=None,
+                    help="check every match record against the target's free space and drop the contradicted ones "
+                         "(not with several ranks or --lc-submap)")
+    ap.add_argument("--lc-max-violation", type=int, default=None, metavar="PERMILLE",
+                    help="with --lc-verify: the largest share of a source's returns in the target's free space, plus its beams "
+                         "through target hits, that is kept (default: freespace.DEFAULT_MAX_PERMILLE)")
     ap.add_argument("--map-output", metavar="PATH", default=None,
                     help="vectorise the final poses' map on the GPU and write it there, one 'x1,y1,x2,y2' line per wall segment")
     ap.add_argument("--grid-output", metavar="STEM", default=None,
@@ -366,7 +401,7 @@ if __name__ == "__main__":
     res = run(a.scans, a.window, verbose=a.v and rank == 0, residual=a.residual, rank=rank, world=world,
               device="cuda:%d" % local, hitl_device=a.hitl_device, normals=a.normals, lc_submap=a.lc_submap,
               linear_solver=a.linear_solver, lc_gate=a.lc_gate, lc_max_score=a.lc_max_score, map_output=a.map_output,
-              grid_output=a.grid_output)
+              grid_output=a.grid_output, lc_verify=a.lc_verify, lc_max_violation=a.lc_max_violation)
     res["world_size"] = world
     if rank == 0:
         print(json.dumps(res))

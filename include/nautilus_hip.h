@@ -67,7 +67,8 @@ const char *nhip_version(void);
  * the capacity of nhip_submaps_gather_dev, 2048 contributor id of nhip_bsr_assemble_dev, 4096 block column of
  * nhip_bsr_assemble_dev / nhip_bsr_pcg_dev / nhip_bsr_pcg_columns_dev, 8192 gauge or right-hand-side index of
  * nhip_bsr_pcg_columns_dev, 16384 scan offset of nhip_vectorize_dev /
- * nhip_occupancy_dev.  Clears the record (in the order of `stream`).
+ * nhip_occupancy_dev, 32768 source scan, grid slot or record index of a pair of nhip_freespace_check_dev.  Clears the record
+ * (in the order of `stream`).
  * ONE record per DEVICE, shared by every stream and host thread that uses the library on it: a host with several streams
  * on one device learns THAT an id was bad and which, not on which stream; a call that finds a record consumes it -- reports
  * of kernels still running on OTHER streams at that moment can be reported by this call or wiped by its clear.  Clients
@@ -769,6 +770,55 @@ int nhip_occupancy_dev(const float *d_xy, const int32_t *d_offsets, const float 
                        const nhip_occupancy_spec_t *spec, int32_t *d_hits, int32_t *d_misses, int8_t *d_grid, int64_t *d_stats,
                        void *stream);
 
+/* K15: FREE-SPACE CHECK of match records ("Free-space check"; tests/freespace_reference.py restates it
+ * in numpy).  A record's score says how much of the source landed on the target's blurred hits; the check says where the rest
+ * landed.  Build-defined and deterministic; all integer after the cells; no matcher kernel is involved.
+ *   free plane  one per slot, in the layout of the slot's hit raster (hits_pitch, side + 64 rows, zero border of 32 cells,
+ *               hits_bytes per slot), in a buffer of its own.  The sensor's cell is (S/2, S/2); a target point's end cell is
+ *               S/2 + floor((double)v / res) per axis; a non-finite or out-of-grid point gives no ray.  For an end cell d away,
+ *               n = max(|dx|, |dy|), the free cells are (S/2, S/2) + (rdiv(k dx, n), rdiv(k dy, n)), k = 0 .. n - 1, rdiv the
+ *               occupancy grid's.  F = the union over all beams minus the slot's hit raster.
+ *   source cell the matcher's: R(theta_k) = R(theta0) R(delta_k) from the nhip_csm_rot0 / nhip_csm_delta_table values, the point
+ *               rotated in float with individually rounded products; cell = S/2 + floor((double)v' / res) + shift, shift =
+ *               pair_origin + (ix - (nx - 1) / 2, iy - (ny - 1) / 2).
+ *   class       of each source point, the first that applies: DROPPED (non-finite after rotation), OUTSIDE (the shifted cell is
+ *               out of the grid, or |dx| or |dy| of the unshifted cell offset exceeds 4096), HIT (a target hit within Chebyshev
+ *               distance hit_radius of the cell), FREE (the cell's bit in F), UNKNOWN.
+ *   through     of every point of class HIT, FREE or UNKNOWN: its beam runs from the source sensor's cell o = (S/2, S/2) + shift
+ *               to the point's cell, d the unshifted offset; it counts if for some k = 0 .. n - 1 - end_margin the cell
+ *               o + (rdiv(k dx, n), rdiv(k dy, n)) lies inside the grid and is a target hit (undilated).
+ *   record      int32[8] per pair: {n_points, dropped, outside, hit, free, unknown, through, 0}; a rejected match record
+ *               (itheta < 0) gives eight -1.
+ * Accepted ranges (anything else is NHIP_ERR_ARG before anything is launched, with or without a device): hit_radius 0..16,
+ * end_margin 0..64, flags 0, reserved 0; a grid spec whose side / 2 exceeds 4096 is refused. */
+typedef struct nhip_freespace_spec {
+  int32_t hit_radius; /* Chebyshev radius of the dilated hit test, in cells (2) */
+  int32_t end_margin; /* steps before a beam's end that `through` does not look at (3) */
+  int32_t flags;      /* 0 */
+  int32_t reserved;   /* 0 */
+} nhip_freespace_spec_t;
+/* the defaults; pure host */
+int nhip_freespace_spec_default(nhip_freespace_spec_t *out);
+/* bytes of the free planes of n_slots slots of these grids (hits_bytes each), or -1 for a spec the check refuses; pure host */
+int64_t nhip_freespace_planes_bytes(const nhip_grid_spec_t *grid_spec, int64_t n_slots);
+/* The free planes of the n_targets slots of d_grids (built from the same scans and target ids by nhip_grid_build_dev), into
+ * d_free (16-byte aligned; every byte of it is written: it needs no clearing).  Never allocates, enqueues and returns without
+ * waiting.  A target id outside [0, n_scans) is an empty scan and nhip_dev_status() reports it (kind 1). */
+int nhip_freespace_trace_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const int32_t *d_target_ids,
+                             int32_t n_targets, const nhip_grid_spec_t *grid_spec, const uint8_t *d_grids, uint8_t *d_free,
+                             void *stream);
+/* The records of n_pairs pairs: the pair arguments of nhip_csm_match_dev, the planes nhip_freespace_trace_dev made of the
+ * same d_grids, the match records (device memory, as the matcher left them) and d_counts (8 int32 per pair).  pair_origin is
+ * any int32 pair (not held to max_shift: a shift beyond the grid puts every point OUTSIDE).  A pair whose source, slot or
+ * record indices are out of range is never dereferenced: its record is eight zeros and nhip_dev_status() reports it (kind
+ * 32768, index = the pair); the other pairs are unaffected. */
+int nhip_freespace_check_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const uint8_t *d_grids,
+                             int32_t n_grids, const nhip_grid_spec_t *grid_spec, const int32_t *d_pair_src,
+                             const int32_t *d_pair_slot, const double *d_rot0_cs, const double *d_delta_cs,
+                             const int32_t *d_pair_origin, int32_t n_pairs, const nhip_search_t *search, const uint8_t *d_free,
+                             const nhip_match_t *d_matches, const nhip_freespace_spec_t *fs_spec, int32_t *d_counts,
+                             void *stream);
+
 /* HITL point selection: GetRelevantPosesForHITL (solver.cc:479-513) for every scan at once.  A point p of scan s goes to
  * the world as w = (c px - s py + tx, s px + c py + ty) with (c, s, tx, ty) = d_pose_f32[4s ..], the entries of
  * PoseArrayToAffine(pose).cast<float>() (nhip_pose_affines forms them), every operation a float operation rounded on its
@@ -869,6 +919,15 @@ int nhip_vectorize(const nhip_scans_t *scans, const double *poses, const nhip_ve
  * and misses are also inputs: they are uploaded first. */
 int nhip_occupancy(const nhip_scans_t *scans, const double *poses, const nhip_occupancy_spec_t *spec, int32_t *hits,
                    int32_t *misses, int8_t *grid, int64_t *stats);
+
+/* nhip_freespace_check_dev on handles: the pair arguments of nhip_csm_match, the records it returned (host memory) and
+ * counts (8 int32 per pair, host memory).  `scans` must be the scans `grids` was built from: the first call on a grids handle
+ * traces its free planes from them (nhip_freespace_trace_dev) and keeps the planes with the handle; later calls only check.
+ * Ids out of range are NHIP_ERR_ARG before anything is launched.  A handle built by nhip_grids_build_submaps is refused with
+ * NHIP_ERR_STATE: a submap's free space needs one ray origin per member. */
+int nhip_csm_freespace(const nhip_scans_t *scans, const nhip_grids_t *grids, const int32_t *pair_src, const int32_t *pair_slot,
+                       const double *theta0, const int32_t *pair_origin, int32_t n_pairs, const nhip_search_t *search,
+                       const nhip_match_t *matches, const nhip_freespace_spec_t *fs_spec, int32_t *counts);
 
 /* The reference-shaped single-pair call: CorrelativeScanMatcher(scanner_range, trans_range, low_res, high_res)
  * .GetTransformation(pc_a, pc_b, rot_a, rot_b, rot_restriction) -> (score, ((tx, ty), theta))

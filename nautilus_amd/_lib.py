@@ -87,6 +87,10 @@ class OccupancySpec(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FreespaceSpec(C.Structure):
+    _fields_ = [("hit_radius", C.c_int32), ("end_margin", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class HitlSpec(C.Structure):
     _fields_ = [("line_a", C.c_float * 4), ("line_b", C.c_float * 4), ("line_width", C.c_double),
                 ("point_threshold", C.c_int32), ("reserved", C.c_int32)]
@@ -200,6 +204,12 @@ PROTOTYPES = {
     "nhip_occupancy_spec_default": (C.c_int, [_P(OccupancySpec)]),
     "nhip_occupancy_dev": (C.c_int, [_vp, _vp, _vp, _i32, _P(OccupancySpec), _vp, _vp, _vp, _vp, _vp]),
     "nhip_occupancy": (C.c_int, [_vp, _vp, _P(OccupancySpec), _vp, _vp, _vp, _vp]),
+    "nhip_freespace_spec_default": (C.c_int, [_P(FreespaceSpec)]),
+    "nhip_freespace_planes_bytes": (_i64, [_P(GridSpec), _i64]),
+    "nhip_freespace_trace_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(GridSpec), _vp, _vp, _vp]),
+    "nhip_freespace_check_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(GridSpec), _vp, _vp, _vp, _vp, _vp, _i32, _P(Search),
+                                           _vp, _vp, _P(FreespaceSpec), _vp, _vp]),
+    "nhip_csm_freespace": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _P(Search), _vp, _P(FreespaceSpec), _vp]),
     "nhip_hitl_spec_default": (C.c_int, [_P(HitlSpec)]),
     "nhip_hitl_select_dev": (C.c_int, [_vp, _vp, _i32, _vp, _P(HitlSpec), _vp, _vp, _vp, _vp, _vp, _vp]),
     "nhip_hitl_pack_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),

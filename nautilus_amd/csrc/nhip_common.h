@@ -54,7 +54,7 @@ struct IdBounds {          // (plain data: it travels inside the kernels' parame
 constexpr uint32_t BAD_TARGET_ID = 1u, BAD_PAIR_SRC = 2u, BAD_PAIR_SLOT = 4u, BAD_BLOCK_ID = 8u, BAD_POSE_ID = 16u,
                    BAD_SCAN_ID = 32u, BAD_FEATURE_IDX = 64u, BAD_FEATURE_COUNT = 128u, BAD_SCAN_OFFSETS = 256u,
                    BAD_MEMBER_ID = 512u, BAD_SUBMAP_CAPACITY = 1024u, BAD_CONTRIB_ID = 2048u, BAD_BLOCK_COLUMN = 4096u,
-                   BAD_SYSTEM_ID = 8192u, BAD_MAP_SCAN_OFFSETS = 16384u;
+                   BAD_SYSTEM_ID = 8192u, BAD_MAP_SCAN_OFFSETS = 16384u, BAD_FREESPACE_PAIR = 32768u;
 constexpr int DEV_STATUS_WORDS = 4;  // {OR of the kinds seen, kind / value / index of the first report}
 uint32_t *dev_status();              // of the current device (allocated on the device's first use; null if that failed)
 #ifdef __HIPCC__
@@ -388,6 +388,27 @@ struct OccParams {    // plain data: travels in the kernels' parameter blocks
 // clears the stats (and, with `clear`, both planes), then the trace of every scan and the classification of the window
 int launch_occupancy(const OccParams &P, bool clear, const float *d_xy, const int32_t *d_offsets, const float *d_affines,
                      hipStream_t s);
+
+// free-space check of match records (nhip_freespace.hip, K15); the specs have passed the checks of nhip_host_freespace.hip
+struct FsParams {     // plain data: travels in the kernels' parameter blocks (the trace reads the first group, the check both)
+  const float2 *xy;
+  const int32_t *offsets;
+  const uint8_t *grids;      // the slots: a slot's hit raster is at hits_offset
+  uint8_t *free_planes;      // hits_bytes per slot, the raster's layout
+  int32_t S, hits_pitch;
+  int64_t slot_bytes, hits_offset, hits_bytes;
+  double res, inv_res;
+  IdBounds ids;
+  const int32_t *target_ids;  // trace: the scan behind each slot
+  int32_t n_targets;
+  const int32_t *pair_src, *pair_slot, *pair_origin;  // check: as the matcher's (pair_origin may be null)
+  const double *rot0_cs, *delta_cs;
+  const nhip_match_t *matches;
+  int32_t *counts;            // 8 per pair
+  int32_t n_pairs, pairs_per_xcd, n_theta, nx, ny, hx, hy, hit_radius, end_margin;
+};
+int launch_fs_trace(const FsParams &P, hipStream_t s);
+int launch_fs_check(const FsParams &P, hipStream_t s);
 
 int launch_resid_point_to_line(const float *d_segments, const float *d_points,
                                const int32_t *d_point_block, int64_t n_points,

@@ -59,7 +59,12 @@ struct nhip_grids {
   nhip_grid_spec_t spec;
   nhip::GridLayout L;
   int32_t n = 0;
-  std::mutex mu;  // (the late skip-map build)
+  std::mutex mu;  // (the late skip-map build, the late free-space trace)
+  // the free-space check (nhip_csm_freespace): the scan behind every slot, whether the slots are submaps, and the free
+  // planes, traced by the first check on the handle and kept with it
+  std::vector<int32_t> target_ids;
+  bool submaps = false, free_traced = false;
+  nhip::DevBuf free_planes;
 };
 
 namespace nhip {

@@ -242,6 +242,7 @@ static int grids_build_on(const float *d_xy, const int32_t *d_offsets, int32_t n
   g->spec = *spec;
   g->L = L;
   g->n = n_targets;
+  g->target_ids.assign(target_ids, target_ids + n_targets);
   g->shape = grids_shape(spec, n_targets);
   DevBuf ids;
   DevBuf &ws = g->ws;
@@ -364,6 +365,7 @@ int nhip_grids_build_submaps(const nhip_scans_t *scans, const int32_t *member_sc
   if (rc) return rc;
   rc = grids_build_on(d_xy.as<const float>(), d_off.as<const int32_t>(), n_targets, ids.data(), n_targets, spec, out);
   if (rc) return rc;
+  (*out)->submaps = true;
   if (n_targets == 0) {
     NHIP_TRY_HIP(hipStreamSynchronize(nullptr));  // (nothing was built: the offsets kernel alone ran)
     InFlight::done();

@@ -15,6 +15,7 @@
 //   occ_classify_kernel  one pass over the window: 16-byte loads of both planes, four cells of `grid` per store, the three
 //                        cell counts reduced per workgroup, one atomic each.
 #include "nhip_common.h"
+#include "nhip_ray.h"  // (rdiv: the ray's step, shared with K15)
 
 #pragma clang fp contract(off)
 
@@ -41,23 +42,6 @@ constexpr bool STEP_ATOMICS = false;
 __host__ __device__ constexpr int32_t occ_words_per_row(int32_t max_ray_cells) { return (2 * max_ray_cells + 1 + 31) >> 5; }
 __host__ __device__ constexpr int32_t occ_band_rows(int32_t max_ray_cells) { return OCC_BITMAP_WORDS / occ_words_per_row(max_ray_cells); }
 static_assert(occ_band_rows(4096) >= 1 && occ_words_per_row(4096) * occ_band_rows(4096) <= OCC_BITMAP_WORDS, "a row of the largest box fits");
-
-// floor((2 a + n) / (2 n)), n >= 1, |a| < 2^24: the estimate by the reciprocal is off by at most a step or two, the remainder
-// says by how many (C's / would truncate)
-__device__ __forceinline__ int32_t rdiv(int32_t a, int32_t n, float inv_den) {
-  const int32_t num = 2 * a + n, den = 2 * n;
-  int32_t q = (int32_t)floorf(__fmul_rn((float)num, inv_den));
-  int32_t r = num - q * den;
-  while (r < 0) {
-    q--;
-    r += den;
-  }
-  while (r >= den) {
-    q++;
-    r -= den;
-  }
-  return q;
-}
 
 struct ScanFrame {  // of one scan: its affine and its origin's floors
   float c, sn, tx, ty;

@@ -181,6 +181,103 @@ def submap_extra_scans(xy, offsets, poses, pair_tgt, radius):
     return xy2, off2, (n_scans + np.searchsorted(targets, pair_tgt)).astype(np.int32)
 
 
+def _freespace_planes(points, side, res):
+    """One target scan's (hits, free) planes, (side, side) bool, row = y: "Free-space check" item 1."""
+    half = side // 2
+    p = np.asarray(points, dtype=np.float32).reshape(-1, 2)
+    hits, free = np.zeros((side, side), bool), np.zeros((side, side), bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        fl = np.floor(p.astype(np.float64) / res)
+    ok = np.isfinite(p).all(axis=1) & (fl >= -half).all(axis=1) & (fl < side - half).all(axis=1)
+    ends = np.unique(fl[ok].astype(np.int64), axis=0)
+    for dx, dy in ends:
+        hits[half + dy, half + dx] = True
+        n = max(abs(dx), abs(dy))
+        k = np.arange(n, dtype=np.int64)
+        free[half + (2 * k * dy + n) // (2 * n), half + (2 * k * dx + n) // (2 * n)] = True
+    return hits, free & ~hits
+
+
+def _dilated(hits, r):
+    """hits OR-ed over every Chebyshev neighbourhood of radius r (separable, by shifted copies)."""
+    out = hits.copy()
+    for axis in (0, 1):
+        acc = out.copy()
+        for s in range(1, r + 1):
+            lo, hi = [slice(None)] * 2, [slice(None)] * 2
+            lo[axis], hi[axis] = slice(0, -s), slice(s, None)
+            acc[tuple(hi)] |= out[tuple(lo)]
+            acc[tuple(lo)] |= out[tuple(hi)]
+        out = acc
+    return out
+
+
+def freespace_counts(xy, offsets, pair_src, pair_tgt, theta0, matches, grid_spec, search, fs_spec=None, pair_origin=None):
+    """The free-space check of match records in plain numpy on the host ("Free-space check"; the device
+    form is nhip_freespace_check_dev): int32 (n, 8) per pair {n_points, dropped, outside, hit, free, unknown, through, 0},
+    eight -1 for a rejected record.  pair_tgt are SCAN ids (a target's planes are made from its scan here, not read from a
+    slot).  Product code: a backend whose match() has no `freespace` parameter verifies its records with this
+    (examples/slam_loop.py --lc-verify free-space).  fs_spec: anything with hit_radius and end_margin (None: 2 and 3)."""
+    from . import csm
+    f = np.float32
+    xy = np.asarray(xy, dtype=f).reshape(-1, 2)
+    off = np.asarray(offsets, dtype=np.int64)
+    pair_src, pair_tgt = np.asarray(pair_src, dtype=np.int64), np.asarray(pair_tgt, dtype=np.int64)
+    n_pairs = len(pair_src)
+    radius, margin = (2, 3) if fs_spec is None else (int(fs_spec.hit_radius), int(fs_spec.end_margin))
+    if not (0 <= radius <= 16 and 0 <= margin <= 64):
+        raise ValueError("freespace_counts: hit_radius %d outside 0..16 or end_margin %d outside 0..64" % (radius, margin))
+    side, res = csm.grid_layout(grid_spec).side, float(grid_spec.res)
+    if side // 2 > 4096:
+        raise ValueError("freespace_counts: a grid of side %d: side / 2 exceeds 4096" % side)
+    half = side // 2
+    org = np.zeros((n_pairs, 2), np.int64) if pair_origin is None else np.asarray(pair_origin, dtype=np.int64).reshape(n_pairs, 2)
+    rot0 = csm.rot0_table(np.asarray(theta0, dtype=np.float64)) if n_pairs else np.zeros((0, 2))
+    delta = csm.delta_table(search)
+    counts, planes = np.zeros((n_pairs, 8), np.int32), {}
+    for i in range(n_pairs):
+        m = matches[i]
+        if m["itheta"] < 0:
+            counts[i] = -1
+            continue
+        t = int(pair_tgt[i])
+        if t not in planes:
+            hits, free = _freespace_planes(xy[off[t]:off[t + 1]], side, res)
+            planes[t] = (hits, free, _dilated(hits, radius))
+        hits, free, near = planes[t]
+        c0, s0 = rot0[i]
+        cd, sd = delta[int(m["itheta"])]
+        cf, sf = f(c0 * cd - s0 * sd), f(s0 * cd + c0 * sd)  # (double products and sums, each rounded, then to float)
+        q = xy[off[pair_src[i]]:off[pair_src[i] + 1]]
+        shift = org[i] + (int(m["ix"]) - (search.nx - 1) // 2, int(m["iy"]) - (search.ny - 1) // 2)
+        with np.errstate(invalid="ignore", over="ignore"):
+            v = np.stack([(cf * q[:, 0]).astype(f) - (sf * q[:, 1]).astype(f), (sf * q[:, 0]).astype(f) + (cf * q[:, 1]).astype(f)], axis=1).astype(f)
+            fin = np.isfinite(v).all(axis=1)
+            fl = np.floor(v.astype(np.float64) / res)
+            short = fin & (np.abs(fl) <= 4096).all(axis=1)
+        d = np.where(short[:, None], fl, 0).astype(np.int64)
+        cell = half + d + shift
+        inside = short & (cell >= 0).all(axis=1) & (cell < side).all(axis=1)
+        cx, cy = cell[inside, 0], cell[inside, 1]
+        is_hit = near[cy, cx]
+        is_free = ~is_hit & free[cy, cx]
+        through = 0
+        o = half + shift
+        beams, copies = np.unique(d[inside], axis=0, return_counts=True)  # (equal offsets, equal rays)
+        for (dx, dy), mult in zip(beams, copies):
+            n = max(abs(dx), abs(dy))
+            k = np.arange(max(n - margin, 0), dtype=np.int64)
+            if not len(k):
+                continue
+            rx, ry = o[0] + (2 * k * dx + n) // (2 * n), o[1] + (2 * k * dy + n) // (2 * n)
+            ok = (rx >= 0) & (rx < side) & (ry >= 0) & (ry < side)
+            if hits[ry[ok], rx[ok]].any():
+                through += int(mult)
+        counts[i] = (len(q), int((~fin).sum()), int((fin & ~inside).sum()), int(is_hit.sum()), int(is_free.sum()),
+                     int((~is_hit & ~is_free).sum()), through, 0)
+    return counts
+
+
 def distance_to_line_segment_f32(points, seg):
     """DistanceToLineSegment<float> (slam_util.h:92-110) for an (n, 2) float32 array: Hyperplane::Through normal,
     projection inside the endpoints' closed x and y intervals -> |signed distance|, else nearest endpoint."""

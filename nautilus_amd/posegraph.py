@@ -242,14 +242,20 @@ class HipBackend:
                                                float(max_score), _lib.ptr(scores), _lib.ptr(flags)))
         return scores, flags
 
-    def match(self, xy, offsets, pair_src, pair_tgt, theta0, cell_bits=16, submap_radius=0, poses=None):
+    def match(self, xy, offsets, pair_src, pair_tgt, theta0, cell_bits=16, submap_radius=0, poses=None, freespace=None):
         """Batched loop-closure scan matching (BASELINE config #2 lattice): (records, spec, search).
         Only the scans the list names go to the device (the candidate scans of a 10,000-scan bag are ~150: 1.3 MB instead
         of the bag's 86 MB, whose upload cost more than matching the 3,275 pairs).
         submap_radius K > 0: every target's table is built from its SUBMAP -- the scans t - K .. t + K placed in t's frame
         by `poses` (n_scans, 3), merged on the device (nhip_submaps_gather_dev) from the same sub-bag, which then holds the
-        members too.  0: the tables of the target scans alone; no gather is launched."""
+        members too.  0: the tables of the target scans alone; no gather is launched.
+        freespace: a freespace.spec() -- the free-space check of every record ("Free-space check") is made
+        inside the call, while the tables are on the device: the targets' free planes traced, the records classified where
+        the matcher left them; returns (records, spec, search, counts int32 (n, 8)).  None: the three-tuple, no extra launch.
+        Not with submap_radius > 0 (a submap's free space needs one ray origin per member)."""
         from . import csm, hostside
+        if freespace is not None and int(submap_radius) > 0:
+            raise ValueError("match: freespace with submap_radius %d: the free-space check has no submap targets" % int(submap_radius))
         spec = csm.grid_spec(30.0, 0.05, 2.0, 1e-10, 40, cell_bits)
         search = csm.search_spec(61, 81, 81, math.radians(1.0))
         pair_src, pair_tgt = np.asarray(pair_src), np.asarray(pair_tgt)
@@ -272,7 +278,8 @@ class HipBackend:
         slot = np.searchsorted(ids, tgt).astype(np.int32)
         n, lib, torch, dev = len(src), self.lib, self.torch, self.dev
         if n == 0:
-            return np.zeros(0, dtype=csm.MATCH_DTYPE), spec, search
+            none = (np.zeros(0, dtype=csm.MATCH_DTYPE), spec, search)
+            return none if freespace is None else none + (np.zeros((0, 8), dtype=np.int32),)
         if len(sub_off) > 1 and int(np.diff(sub_off).max()) <= _lib.NHIP_SHORT_SCAN_POINTS:
             search.flags |= _lib.NHIP_SEARCH_SHORT_SCANS
         # Device buffers from torch's caching allocator (the tables of 150 targets are 1.8 GB: a hipMalloc / hipFree pair of
@@ -312,8 +319,17 @@ class HipBackend:
         check(lib.nhip_csm_match_dev(d_xy.data_ptr(), d_off.data_ptr(), n_sub, d_grids.data_ptr(), len(ids), C.byref(spec), d_src.data_ptr(),
                                      d_slot.data_ptr(), d_rot0.data_ptr(), d_delta.data_ptr(), None, n, C.byref(search),
                                      d_keys.data_ptr(), d_out.data_ptr(), None, d_ws_m.data_ptr(), ws_m, sp))
+        if freespace is not None:
+            from . import freespace as fs
+            d_free = fs.trace_on_device(d_xy, d_off, n_sub, d_ids, len(ids), spec, d_grids)
+            d_counts = fs.check_on_device(d_xy, d_off, n_sub, d_grids, len(ids), spec, d_src, d_slot, d_rot0, d_delta, None, n,
+                                          search, d_free, d_out, freespace)
         m = d_out.cpu().numpy().view(csm.MATCH_DTYPE).reshape(-1).copy()
-        return m, spec, search
+        if freespace is None:
+            return m, spec, search
+        counts = d_counts.cpu().numpy()
+        check(lib.nhip_dev_status(sp, None))
+        return m, spec, search, counts
 
 
 class _HipIcp:
