@@ -57,7 +57,7 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         rank=0, world=1, device="cuda:0", backend=None, iterations=4, hitl=True, cell_bits=16, gate="scatter",
         min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False, normals="bag", lc_submap=0,
         linear_solver="host", lc_gate="geometric", lc_max_score=5000.0, map_output=None, grid_output=None, lc_verify=None,
-        lc_max_violation=None):
+        lc_max_violation=None, lc_top_k=5):
     """min_scatter_score: LCCandidateFilter's threshold is 0.70 (lc_candidate_filter.cc:76); scans of the synthetic
     24 m x 16 m room score ~0.4, so callers on that world pass a lower one.
     hitl_device: the HITL constraint's points are selected and packed on the GPU (hitl.select, under the "path" clock) and
@@ -78,6 +78,11 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     backend's chi_square_gate; what it keeps is intersected with the geometric gate's separation rule (the later scan is the
     source, more than 20 nodes apart).  Needs gate "scatter".  lc_max_score: the test's threshold (LCMatcher's 5000: on the
     synthetic room, whose dense scans pin every pose to a fraction of a millimetre, that keeps nothing).
+    lc_gate "appearance": no pose enters -- every scan of the candidate list (gate "scatter": LCCandidateFilter's; otherwise every
+    scan) is compared with the earlier ones by ring descriptor ("Place descriptors"), its lc_top_k nearest more
+    than 20 nodes apart become the pairs (src = the query), and the matcher's theta0 is the heading the aligning rotation gives,
+    not the estimate's heading difference.  A backend with place_candidates() does it on the device; any other is served by
+    hostside.place_candidates.  Everything after that is the same; the result reports lc_gate, lc_top_k, place_s and lc_pairs.
     map_output: a path -- the final poses' vector map (Solver::Vectorize, solver.cc:581-624: backend.vectorize, on the GPU)
     is written there as 'x1,y1,x2,y2' lines (hostside.write_map_lines); the result reports map_segments and vectorize_s, and
     keeps the poses the map was made at in "map_poses".
@@ -107,8 +112,10 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     if normals not in ("bag", "device"):
         raise ValueError("run: normals %r" % (normals,))
     lc_submap = int(lc_submap)
-    if lc_gate not in ("geometric", "chi-square") or (lc_gate == "chi-square" and gate != "scatter"):
-        raise ValueError("run: lc_gate %r (\"geometric\", or \"chi-square\" with gate \"scatter\")" % (lc_gate,))
+    if lc_gate not in ("geometric", "chi-square", "appearance") or (lc_gate == "chi-square" and gate != "scatter"):
+        raise ValueError("run: lc_gate %r (\"geometric\", \"appearance\", or \"chi-square\" with gate \"scatter\")" % (lc_gate,))
+    if not 1 <= int(lc_top_k) <= 32:
+        raise ValueError("run: lc_top_k %r: 1..32" % (lc_top_k,))
     if not 0 <= lc_submap < LC_MIN_SEPARATION:
         raise ValueError("run: lc_submap %d: a submap radius is >= 0 and below the pair gate's minimum separation (%d)"
                          % (lc_submap, LC_MIN_SEPARATION))
@@ -157,8 +164,27 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     out["err_icp_m"] = posegraph.trajectory_error(poses, bag.truth)
     out["icp_correspondences"] = pg.icp.n_corr
 
+    def appearance_pairs(ids):
+        """lc_gate "appearance": the K nearest earlier scans of every scan of `ids` by ring descriptor (place.py), more than 20
+        nodes apart, and the heading each aligning rotation gives.  No pose enters."""
+        from nautilus_amd import place
+        t1 = time.perf_counter()
+        ids = np.asarray(ids, dtype=np.int32)
+        pspec = place.spec(top_k=int(lc_top_k), min_separation=LC_MIN_SEPARATION, flags=place.NHIP_PLACE_PAST_ONLY)
+        if hasattr(backend, "place_candidates"):
+            with posegraph.clocked("path"):
+                rec, _ = backend.place_candidates(xy, off, ids, pspec)
+        else:  # (a backend without the method: the plain numpy host path, as freespace_counts is for the free-space check)
+            with posegraph.clocked("marshal"):
+                rec, _ = hostside.place_candidates(xy, off, ids, pspec)
+        out["lc_gate"], out["lc_top_k"], out["place_s"] = lc_gate, int(lc_top_k), time.perf_counter() - t1
+        s_, t_, th = place.pairs(ids, rec)
+        out["lc_pairs"] = np.stack([s_, t_], axis=1).tolist()
+        return s_, t_, th
+
     # ---- loop-closure candidates
     t0 = time.perf_counter()
+    place_theta0 = None
     if gate == "scatter":
         # LCCandidateFilter::GetLCCandidates: scatter-matrix score of every scan (one GPU pass), nodes >= 5 m apart ...
         with posegraph.clocked("path"):
@@ -169,6 +195,8 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         if lc_gate == "geometric":
             with posegraph.clocked("path"):
                 src, tgt = hostside.geometric_pair_gate(poses, cand, max_range=3.5, min_separation=LC_MIN_SEPARATION, backend=backend)
+        elif lc_gate == "appearance":  # the LCCandidateFilter list is the list of scans that are compared
+            src, tgt, place_theta0 = appearance_pairs(cand)
         else:
             t1 = time.perf_counter()
             pairs = [(int(s_), int(c)) for s_ in cand for c in cand if c != s_]
@@ -192,6 +220,8 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
                                       "us_per_iteration_per_batch": [1e6 * b[2] / max(b[1], 1) for b in batches]}
             pcg_phase("lc_gate")
         out["lc_candidate_scans"] = len(cand)
+    elif lc_gate == "appearance":
+        src, tgt, place_theta0 = appearance_pairs(np.arange(n_scans))
     else:
         idx = np.arange(n_scans)
         d = np.linalg.norm(poses[:, None, :2] - poses[None, :, :2], axis=2)
@@ -205,6 +235,8 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         t0 = time.perf_counter()
         a = poses[src, 2] - poses[tgt, 2]
         theta0 = a - 2 * math.pi * np.rint(a / (2 * math.pi))
+        if place_theta0 is not None:  # (the heading difference the descriptors' aligning rotation gives, not the estimate's)
+            theta0 = place_theta0
         if world > 1:
             spec_search = {}
 
@@ -365,10 +397,12 @@ if __name__ == "__main__":
     ap.add_argument("--linear-solver", choices=["host", "device"], default="host",
                     help="the linear step of every solve: scipy on the host, or block-Jacobi PCG on the GPU (with HITL: "
                          "needs --hitl-device)")
-    ap.add_argument("--lc-gate", choices=["geometric", "chi-square"], default="geometric",
+    ap.add_argument("--lc-gate", choices=["geometric", "chi-square", "appearance"], default="geometric",
                     help="the loop-closure pair gate: distance and separation, or LCMatcher's chi-square test on the cross-covariance "
                          "blocks of the pose graph (PoseGraph.cross_covariances with --linear-solver's solver), intersected with "
-                         "the separation rule")
+                         "the separation rule, or the nearest earlier scans by ring descriptor (no pose enters; the matcher's "
+                         "theta0 comes from the descriptors' aligning rotation)")
+    ap.add_argument("--lc-top-k", type=int, default=5, metavar="K", help="with --lc-gate appearance: candidates kept per scan (1..32)")
     ap.add_argument("--lc-max-score", type=float, default=5000.0, help="the chi-square gate's threshold (lc_matcher.cc:66: 5000)")
     ap.add_argument("--lc-verify", choices=["free-space"], default=None,
                     help="check every match record against the target's free space and drop the contradicted ones "
@@ -401,7 +435,7 @@ if __name__ == "__main__":
     res = run(a.scans, a.window, verbose=a.v and rank == 0, residual=a.residual, rank=rank, world=world,
               device="cuda:%d" % local, hitl_device=a.hitl_device, normals=a.normals, lc_submap=a.lc_submap,
               linear_solver=a.linear_solver, lc_gate=a.lc_gate, lc_max_score=a.lc_max_score, map_output=a.map_output,
-              grid_output=a.grid_output, lc_verify=a.lc_verify, lc_max_violation=a.lc_max_violation)
+              grid_output=a.grid_output, lc_verify=a.lc_verify, lc_max_violation=a.lc_max_violation, lc_top_k=a.lc_top_k)
     res["world_size"] = world
     if rank == 0:
         print(json.dumps(res))

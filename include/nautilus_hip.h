@@ -67,7 +67,8 @@ const char *nhip_version(void);
  * the capacity of nhip_submaps_gather_dev, 2048 contributor id of nhip_bsr_assemble_dev, 4096 block column of
  * nhip_bsr_assemble_dev / nhip_bsr_pcg_dev / nhip_bsr_pcg_columns_dev, 8192 gauge or right-hand-side index of
  * nhip_bsr_pcg_columns_dev, 16384 scan offset of nhip_vectorize_dev /
- * nhip_occupancy_dev, 32768 source scan, grid slot or record index of a pair of nhip_freespace_check_dev.  Clears the record
+ * nhip_occupancy_dev / nhip_place_describe_dev, 32768 source scan, grid slot or record index of a pair of
+ * nhip_freespace_check_dev, 65536 scan id of the list of nhip_place_match_dev.  Clears the record
  * (in the order of `stream`).
  * ONE record per DEVICE, shared by every stream and host thread that uses the library on it: a host with several streams
  * on one device learns THAT an id was bad and which, not on which stream; a call that finds a record consumes it -- reports
@@ -819,6 +820,62 @@ int nhip_freespace_check_dev(const float *d_xy, const int32_t *d_offsets, int32_
                              const nhip_match_t *d_matches, const nhip_freespace_spec_t *fs_spec, int32_t *d_counts,
                              void *stream);
 
+/* K16: PLACE DESCRIPTORS -- loop-closure candidates by appearance, from no pose at all ("Place
+ * descriptors"; tests/place_reference.py restates it in numpy).  The reference asks a learned embedding behind a service
+ * (lc_match_threshold, solver.cc:58-60); the network is not in its tree, so the descriptor is build-defined: R rings x 64
+ * sectors of the scan frame, one bit per bin that holds a return.  Two float comparisons per point, integers after them.
+ *   tables      e_k = (float)((double)range_max k / R), edge2[k] = e_k e_k (one float multiply), k = 0 .. R;
+ *               dir[j] = ((float)cos(2 pi j / 64), (float)sin(2 pi j / 64)), j = 0 .. 31, cos and sin in double.
+ *   bit         of a point (x, y), every operation a float operation rounded on its own: r2 = (x x) + (y y); the point is
+ *               dropped unless r2 is finite and r2 < edge2[R]; ring = #{k in 1 .. R-1: r2 >= edge2[k]}; neg = y < 0 or (y == 0
+ *               and x < 0); (u, v) = neg ? (-x, -y) : (x, y); sector = #{j in 1 .. 31: (dir[j].x v) - (dir[j].y u) >= 0} +
+ *               (neg ? 32 : 0); bit `sector` of word `ring` is set.
+ *   descriptor  uint64 D[R] per scan, bits = the sum of the words' popcounts.
+ *   distance    dist(i, j, s) = sum_r popcount(D_i[r] XOR rotl64(D_j[r], s)); dist(i, j) = min_s, shift = the smallest
+ *               minimising s.  The heading of scan i relative to scan j is theta0 = AngleMod(-shift 2 pi / 64).
+ *   list        ids: n_ids scan ids, strictly ascending.  Entry b (scan j) is admissible for query a (scan i) iff |i - j| >
+ *               min_separation, j < i under NHIP_PLACE_PAST_ONLY, bits_i > 0 and bits_j > 0, and
+ *               1000 dist <= max_permille (bits_i + bits_j).
+ *   records     per query top_k x int32[4] = {j, shift, dist, bits_j}: the admissible candidates in ascending (dist, j)
+ *               order; unfilled records are four -1.
+ *   stats       8 int64: {n_ids, admissible pairs before the permille gate, after it, records written, queries without a
+ *               record, scans of the list with bits == 0, 0, 0}.
+ * Accepted ranges (anything else is NHIP_ERR_ARG before anything is launched, with or without a device): n_rings 1..32 to
+ * describe and 1..15 to match (a pair's result is a 16-bit key dist * 64 + shift, 0xFFFF for none: dist <= 64 R must stay
+ * below 1023); range_max finite and > 0; top_k 1..32; min_separation >= 0; max_permille 0..1000; flags 0 or
+ * NHIP_PLACE_PAST_ONLY; n_ids 0..2^20. */
+#define NHIP_PLACE_PAST_ONLY 1
+#define NHIP_PLACE_WORKSPACE_MAX (64ll << 20) /* what nhip_place_workspace_bytes asks for at most: longer lists go in chunks */
+typedef struct nhip_place_spec {
+  int32_t n_rings;        /* R (10) */
+  float range_max;        /* the outer edge of the last ring, metres (30) */
+  int32_t top_k;          /* K records per query (5) */
+  int32_t min_separation; /* scans between the two of a pair (20) */
+  int32_t max_permille;   /* the gate: dist per 1000 of bits_i + bits_j (1000: no gate) */
+  int32_t flags;          /* 0, or NHIP_PLACE_PAST_ONLY */
+} nhip_place_spec_t;
+/* the defaults of the table above; pure host */
+int nhip_place_spec_default(nhip_place_spec_t *out);
+/* edge2: n_rings + 1 floats; dir: 32 x 2 floats; pure host */
+int nhip_place_tables(const nhip_place_spec_t *spec, float *edge2, float *dir);
+/* bytes of the key workspace of a list of n_ids: 2 bytes per (query row, candidate), rows of n_ids rounded up to 64
+ * candidates, all rows if that stays within NHIP_PLACE_WORKSPACE_MAX, else as many multiples of 16 rows as do (at least 16);
+ * -1: a bad spec or n_ids, message in nhip_last_error; pure host */
+int64_t nhip_place_workspace_bytes(const nhip_place_spec_t *spec, int32_t n_ids);
+/* The descriptors of all scans: d_desc n_scans x n_rings uint64, d_bits n_scans int32.  Never allocates, enqueues and
+ * returns without waiting.  A scan whose first offset is negative or whose end lies before its start is treated as empty and
+ * nhip_dev_status() reports it (kind 16384). */
+int nhip_place_describe_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const nhip_place_spec_t *spec,
+                            uint64_t *d_desc, int32_t *d_bits, void *stream);
+/* The records of the list d_ids (ascending: the caller's promise) among the descriptors nhip_place_describe_dev made with
+ * the same n_rings: d_records n_ids x top_k x 4 int32, d_stats 8 int64.  The workspace (2-byte aligned) may be smaller than
+ * nhip_place_workspace_bytes says, down to 16 rows: the query rows are then taken in more chunks, with the same result.  An id
+ * outside [0, n_scans) is never dereferenced: it is a scan without bits, in no record and with none of its own, and
+ * nhip_dev_status() reports it (kind 65536, index = its position in the list). */
+int nhip_place_match_dev(const uint64_t *d_desc, const int32_t *d_bits, int32_t n_scans, const int32_t *d_ids, int32_t n_ids,
+                         const nhip_place_spec_t *spec, int32_t *d_records, int64_t *d_stats, void *d_workspace,
+                         int64_t workspace_bytes, void *stream);
+
 /* HITL point selection: GetRelevantPosesForHITL (solver.cc:479-513) for every scan at once.  A point p of scan s goes to
  * the world as w = (c px - s py + tx, s px + c py + ty) with (c, s, tx, ty) = d_pose_f32[4s ..], the entries of
  * PoseArrayToAffine(pose).cast<float>() (nhip_pose_affines forms them), every operation a float operation rounded on its
@@ -928,6 +985,13 @@ int nhip_occupancy(const nhip_scans_t *scans, const double *poses, const nhip_oc
 int nhip_csm_freespace(const nhip_scans_t *scans, const nhip_grids_t *grids, const int32_t *pair_src, const int32_t *pair_slot,
                        const double *theta0, const int32_t *pair_origin, int32_t n_pairs, const nhip_search_t *search,
                        const nhip_match_t *matches, const nhip_freespace_spec_t *fs_spec, int32_t *counts);
+
+/* nhip_place_describe_dev + nhip_place_match_dev on uploaded scans: ids (host, n_ids, strictly ascending and inside the
+ * scans: anything else is NHIP_ERR_ARG before anything is launched), records (n_ids x top_k x 4 int32) and stats (8 int64)
+ * in host memory; desc (n_scans x n_rings uint64) and bits (n_scans int32) may be NULL.  Allocates and frees its device
+ * buffers; the key workspace is nhip_place_workspace_bytes. */
+int nhip_place_candidates(const nhip_scans_t *scans, const int32_t *ids, int32_t n_ids, const nhip_place_spec_t *spec,
+                          int32_t *records, int64_t *stats, uint64_t *desc, int32_t *bits);
 
 /* The reference-shaped single-pair call: CorrelativeScanMatcher(scanner_range, trans_range, low_res, high_res)
  * .GetTransformation(pc_a, pc_b, rot_a, rot_b, rot_restriction) -> (score, ((tx, ty), theta))

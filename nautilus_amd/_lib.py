@@ -23,6 +23,8 @@ NHIP_TIMER_CSM_BOUNDS, NHIP_TIMER_CSM_CAND, NHIP_TIMER_EXACT_SCORE = 6, 7, 8
 NHIP_TIMER_VEC_RASTER, NHIP_TIMER_VEC_VOTES, NHIP_TIMER_VEC_ROUNDS = 9, 10, 11
 NHIP_TIMER_OCC_TRACE, NHIP_TIMER_OCC_CLASSIFY = 12, 13
 NHIP_OCC_ACCUMULATE = 1
+NHIP_PLACE_PAST_ONLY = 1
+NHIP_PLACE_WORKSPACE_MAX = 64 << 20
 
 
 class NhipError(RuntimeError):
@@ -89,6 +91,11 @@ class OccupancySpec(C.Structure):
 
 class FreespaceSpec(C.Structure):
     _fields_ = [("hit_radius", C.c_int32), ("end_margin", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PlaceSpec(C.Structure):
+    _fields_ = [("n_rings", C.c_int32), ("range_max", C.c_float), ("top_k", C.c_int32), ("min_separation", C.c_int32),
+                ("max_permille", C.c_int32), ("flags", C.c_int32)]
 
 
 class HitlSpec(C.Structure):
@@ -210,6 +217,12 @@ PROTOTYPES = {
     "nhip_freespace_check_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(GridSpec), _vp, _vp, _vp, _vp, _vp, _i32, _P(Search),
                                            _vp, _vp, _P(FreespaceSpec), _vp, _vp]),
     "nhip_csm_freespace": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _P(Search), _vp, _P(FreespaceSpec), _vp]),
+    "nhip_place_spec_default": (C.c_int, [_P(PlaceSpec)]),
+    "nhip_place_tables": (C.c_int, [_P(PlaceSpec), _vp, _vp]),
+    "nhip_place_workspace_bytes": (_i64, [_P(PlaceSpec), _i32]),
+    "nhip_place_describe_dev": (C.c_int, [_vp, _vp, _i32, _P(PlaceSpec), _vp, _vp, _vp]),
+    "nhip_place_match_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(PlaceSpec), _vp, _vp, _vp, _i64, _vp]),
+    "nhip_place_candidates": (C.c_int, [_vp, _vp, _i32, _P(PlaceSpec), _vp, _vp, _vp, _vp]),
     "nhip_hitl_spec_default": (C.c_int, [_P(HitlSpec)]),
     "nhip_hitl_select_dev": (C.c_int, [_vp, _vp, _i32, _vp, _P(HitlSpec), _vp, _vp, _vp, _vp, _vp, _vp]),
     "nhip_hitl_pack_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -54,7 +54,7 @@ struct IdBounds {          // (plain data: it travels inside the kernels' parame
 constexpr uint32_t BAD_TARGET_ID = 1u, BAD_PAIR_SRC = 2u, BAD_PAIR_SLOT = 4u, BAD_BLOCK_ID = 8u, BAD_POSE_ID = 16u,
                    BAD_SCAN_ID = 32u, BAD_FEATURE_IDX = 64u, BAD_FEATURE_COUNT = 128u, BAD_SCAN_OFFSETS = 256u,
                    BAD_MEMBER_ID = 512u, BAD_SUBMAP_CAPACITY = 1024u, BAD_CONTRIB_ID = 2048u, BAD_BLOCK_COLUMN = 4096u,
-                   BAD_SYSTEM_ID = 8192u, BAD_MAP_SCAN_OFFSETS = 16384u, BAD_FREESPACE_PAIR = 32768u;
+                   BAD_SYSTEM_ID = 8192u, BAD_MAP_SCAN_OFFSETS = 16384u, BAD_FREESPACE_PAIR = 32768u, BAD_PLACE_ID = 65536u;
 constexpr int DEV_STATUS_WORDS = 4;  // {OR of the kinds seen, kind / value / index of the first report}
 uint32_t *dev_status();              // of the current device (allocated on the device's first use; null if that failed)
 #ifdef __HIPCC__
@@ -409,6 +409,30 @@ struct FsParams {     // plain data: travels in the kernels' parameter blocks (t
 };
 int launch_fs_trace(const FsParams &P, hipStream_t s);
 int launch_fs_check(const FsParams &P, hipStream_t s);
+
+// place descriptors (nhip_place.hip, K16); the spec has passed place_spec_check (nhip_host_place.hip)
+constexpr int PLACE_MAX_RINGS = 32;        // of a descriptor
+constexpr int PLACE_MATCH_MAX_RINGS = 15;  // of a match: dist <= 64 R must stay below 1023 for the 16-bit key
+constexpr int PLACE_QT = 16;               // query rows a workgroup of the distance kernel takes with one load of its candidates
+struct PlaceTables {  // plain data: travels in the describe kernel's parameter block (nhip_place_tables fills the same values)
+  int32_t n_rings;
+  float edge2[PLACE_MAX_RINGS + 1];
+  float dir[64];      // 32 x {cos, sin}
+};
+struct PlaceMatch {   // plain data: travels in the kernels' parameter blocks
+  const unsigned long long *desc;  // n_scans x n_rings
+  const int32_t *bits;             // n_scans
+  const int32_t *ids;              // n_ids, ascending
+  uint16_t *keys;                  // the workspace: chunk rows x pitch
+  int32_t *records;                // n_ids x top_k x 4
+  long long *stats;                // 8 words
+  uint32_t *status;
+  int32_t n_scans, n_ids, pitch, n_rings, top_k, min_separation, max_permille, flags;
+};
+int launch_place_describe(const PlaceTables &T, const float *d_xy, const int32_t *d_offsets, int32_t n_scans, uint64_t *d_desc,
+                          int32_t *d_bits, hipStream_t s);
+// clears the stats, then distance and top-K kernels per chunk of `chunk_rows` query rows (the workspace holds that many)
+int launch_place_match(const PlaceMatch &P, int32_t chunk_rows, hipStream_t s);
 
 int launch_resid_point_to_line(const float *d_segments, const float *d_points,
                                const int32_t *d_point_block, int64_t n_points,

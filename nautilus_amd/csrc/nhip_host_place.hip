@@ -1,0 +1,156 @@
+// nhip_host_place.hip -- the place-descriptor entry points of the C ABI (kernels: nhip_place.hip, K16): the spec's defaults and
+// its check, the tables, the workspace rule, the forms on the caller's buffers and stream, and the handle form with a host list
+// and host outputs.
+#include "nhip_common.h"
+#include "nhip_host.h"
+
+using namespace nhip;
+
+namespace {
+
+constexpr int32_t PLACE_MAX_IDS = 1 << 20;
+constexpr int32_t PLACE_MAX_CHUNK_ROWS = 1 << 19;  // (a launch's grid: chunk rows / PLACE_QT workgroups along y)
+
+// the accepted ranges of include/nautilus_hip.h; `match`: the call compares descriptors
+int place_spec_check(const nhip_place_spec_t *s, bool match, const char *who) {
+  NHIP_REQUIRE(s, "%s: null spec", who);
+  const int max_rings = match ? PLACE_MATCH_MAX_RINGS : PLACE_MAX_RINGS;
+  NHIP_REQUIRE(s->n_rings >= 1 && s->n_rings <= max_rings, "%s: n_rings %d outside 1..%d%s", who, s->n_rings, max_rings,
+               match ? " (the 16-bit key of a pair holds dist <= 1022)" : "");
+  NHIP_REQUIRE(std::isfinite(s->range_max) && s->range_max > 0, "%s: range_max must be finite and > 0", who);
+  NHIP_REQUIRE(s->top_k >= 1 && s->top_k <= 32, "%s: top_k %d outside 1..32", who, s->top_k);
+  NHIP_REQUIRE(s->min_separation >= 0, "%s: min_separation %d must be >= 0", who, s->min_separation);
+  NHIP_REQUIRE(s->max_permille >= 0 && s->max_permille <= 1000, "%s: max_permille %d outside 0..1000", who, s->max_permille);
+  NHIP_REQUIRE(s->flags == 0 || s->flags == NHIP_PLACE_PAST_ONLY, "%s: flags %d: 0 or NHIP_PLACE_PAST_ONLY", who, s->flags);
+  return NHIP_OK;
+}
+
+void place_tables(const nhip_place_spec_t &s, float *edge2, float *dir) {
+  for (int k = 0; k <= s.n_rings; k++) {
+    const float e = (float)((double)s.range_max * k / s.n_rings);
+    edge2[k] = e * e;
+  }
+  const double two_pi = 6.283185307179586476925286766559;
+  for (int j = 0; j < 32; j++) dir[2 * j] = (float)std::cos(two_pi * j / 64), dir[2 * j + 1] = (float)std::sin(two_pi * j / 64);
+}
+
+int64_t place_row_bytes(int32_t n_ids) { return 2 * (((int64_t)n_ids + 63) & ~63ll); }
+
+// the arguments have been checked
+int place_match_run(const uint64_t *d_desc, const int32_t *d_bits, int32_t n_scans, const int32_t *d_ids, int32_t n_ids,
+                    const nhip_place_spec_t &spec, int32_t *d_records, int64_t *d_stats, void *d_ws, int64_t ws_bytes, hipStream_t s) {
+  PlaceMatch P;
+  P.desc = reinterpret_cast<const unsigned long long *>(d_desc), P.bits = d_bits, P.ids = d_ids;
+  P.keys = static_cast<uint16_t *>(d_ws), P.records = d_records, P.stats = reinterpret_cast<long long *>(d_stats);
+  P.status = dev_status();
+  P.n_scans = n_scans, P.n_ids = n_ids, P.pitch = (int32_t)(place_row_bytes(n_ids) / 2);
+  P.n_rings = spec.n_rings, P.top_k = spec.top_k, P.min_separation = spec.min_separation, P.max_permille = spec.max_permille;
+  P.flags = spec.flags;
+  int64_t rows = n_ids > 0 ? ws_bytes / place_row_bytes(n_ids) / PLACE_QT * PLACE_QT : PLACE_QT;
+  NHIP_REQUIRE(rows >= PLACE_QT, "place_match: a workspace of %lld bytes holds fewer than %d rows of %lld bytes", (long long)ws_bytes,
+               PLACE_QT, (long long)place_row_bytes(n_ids));
+  if (rows > PLACE_MAX_CHUNK_ROWS) rows = PLACE_MAX_CHUNK_ROWS;
+  return launch_place_match(P, (int32_t)rows, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int nhip_place_spec_default(nhip_place_spec_t *out) {
+  NHIP_REQUIRE(out, "place_spec_default: null pointer");
+  *out = nhip_place_spec_t{};
+  out->n_rings = 10;
+  out->range_max = 30.0f;
+  out->top_k = 5;
+  out->min_separation = 20;
+  out->max_permille = 1000;
+  return NHIP_OK;
+}
+
+int nhip_place_tables(const nhip_place_spec_t *spec, float *edge2, float *dir) {
+  int rc = place_spec_check(spec, false, "place_tables");
+  if (rc) return rc;
+  NHIP_REQUIRE(edge2 && dir, "place_tables: null pointer");
+  place_tables(*spec, edge2, dir);
+  return NHIP_OK;
+}
+
+int64_t nhip_place_workspace_bytes(const nhip_place_spec_t *spec, int32_t n_ids) {
+  if (place_spec_check(spec, true, "place_workspace_bytes")) return -1;
+  if (n_ids < 0 || n_ids > PLACE_MAX_IDS) {
+    set_error("place_workspace_bytes: n_ids %d outside 0..%d", n_ids, PLACE_MAX_IDS);
+    return -1;
+  }
+  const int64_t tile = PLACE_QT * place_row_bytes(n_ids > 0 ? n_ids : 1), tiles = ((int64_t)n_ids + PLACE_QT - 1) / PLACE_QT;
+  const int64_t fit = NHIP_PLACE_WORKSPACE_MAX / tile;
+  return tile * (tiles < 1 ? 1 : tiles <= fit ? tiles : fit < 1 ? 1 : fit);
+}
+
+int nhip_place_describe_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const nhip_place_spec_t *spec,
+                            uint64_t *d_desc, int32_t *d_bits, void *stream) {
+  int rc = place_spec_check(spec, false, "place_describe_dev");  // (a bad spec is an argument error with or without a device)
+  if (rc) return rc;
+  NHIP_REQUIRE(n_scans >= 0, "place_describe_dev: n_scans %d must be >= 0", n_scans);
+  if ((rc = require_device())) return rc;
+  NHIP_REQUIRE(n_scans == 0 || (d_xy && d_offsets && d_desc && d_bits), "place_describe_dev: null pointer");
+  NHIP_REQUIRE((reinterpret_cast<uintptr_t>(d_desc) & 7) == 0, "place_describe_dev: d_desc must be 8-byte aligned");
+  PlaceTables T;
+  T.n_rings = spec->n_rings;
+  place_tables(*spec, T.edge2, T.dir);
+  return launch_place_describe(T, d_xy, d_offsets, n_scans, d_desc, d_bits, static_cast<hipStream_t>(stream));
+}
+
+int nhip_place_match_dev(const uint64_t *d_desc, const int32_t *d_bits, int32_t n_scans, const int32_t *d_ids, int32_t n_ids,
+                         const nhip_place_spec_t *spec, int32_t *d_records, int64_t *d_stats, void *d_workspace,
+                         int64_t workspace_bytes, void *stream) {
+  int rc = place_spec_check(spec, true, "place_match_dev");
+  if (rc) return rc;
+  NHIP_REQUIRE(n_scans >= 0 && n_ids >= 0 && n_ids <= PLACE_MAX_IDS, "place_match_dev: n_scans %d must be >= 0, n_ids %d in 0..%d", n_scans,
+               n_ids, PLACE_MAX_IDS);
+  if ((rc = require_device())) return rc;
+  NHIP_REQUIRE(d_stats && (n_ids == 0 || (d_desc && d_bits && d_ids && d_records && d_workspace)), "place_match_dev: null pointer");
+  NHIP_REQUIRE((reinterpret_cast<uintptr_t>(d_desc) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_stats) & 7) == 0 &&
+                   (reinterpret_cast<uintptr_t>(d_workspace) & 1) == 0,
+               "place_match_dev: d_desc and d_stats must be 8-byte aligned, d_workspace 2-byte");
+  return place_match_run(d_desc, d_bits, n_scans, d_ids, n_ids, *spec, d_records, d_stats, d_workspace, workspace_bytes,
+                         static_cast<hipStream_t>(stream));
+}
+
+int nhip_place_candidates(const nhip_scans_t *scans, const int32_t *ids, int32_t n_ids, const nhip_place_spec_t *spec,
+                          int32_t *records, int64_t *stats, uint64_t *desc, int32_t *bits) {
+  int rc = place_spec_check(spec, true, "place_candidates");
+  if (rc || (rc = require_device())) return rc;
+  NHIP_REQUIRE(scans && stats && n_ids >= 0 && n_ids <= PLACE_MAX_IDS && (n_ids == 0 || (ids && records)), "place_candidates: bad arguments");
+  const int32_t n = scans->n_scans;
+  for (int32_t b = 0; b < n_ids; b++) {
+    NHIP_REQUIRE(ids[b] >= 0 && ids[b] < n, "place_candidates: ids[%d] = %d outside the %d scans", b, ids[b], n);
+    NHIP_REQUIRE(b == 0 || ids[b] > ids[b - 1], "place_candidates: ids[%d] = %d after %d: the list must ascend strictly", b, ids[b], ids[b - 1]);
+  }
+  const size_t R = (size_t)spec->n_rings, K = (size_t)spec->top_k;
+  const int64_t ws_bytes = nhip_place_workspace_bytes(spec, n_ids);
+  DevBuf dd, db, di, dr, ds, dw;
+  if ((rc = dd.alloc(8 * R * (size_t)(n > 0 ? n : 1))) || (rc = db.alloc(4 * (size_t)(n > 0 ? n : 1))) ||
+      (rc = di.alloc(4 * (size_t)(n_ids > 0 ? n_ids : 1))) || (rc = dr.alloc(16 * K * (size_t)(n_ids > 0 ? n_ids : 1))) ||
+      (rc = ds.alloc(64)) || (rc = dw.alloc((size_t)ws_bytes)))
+    return rc;
+  InFlight inflight;
+  if (n_ids) NHIP_TRY_HIP(hipMemcpy(di.p, ids, 4 * (size_t)n_ids, hipMemcpyHostToDevice));
+  PlaceTables T;
+  T.n_rings = spec->n_rings;
+  place_tables(*spec, T.edge2, T.dir);
+  if ((rc = launch_place_describe(T, scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), n, dd.as<uint64_t>(),
+                                  db.as<int32_t>(), nullptr)))
+    return rc;
+  if ((rc = place_match_run(dd.as<const uint64_t>(), db.as<const int32_t>(), n, di.as<const int32_t>(), n_ids, *spec, dr.as<int32_t>(),
+                            ds.as<int64_t>(), dw.p, ws_bytes, nullptr)))
+    return rc;
+  if (n_ids) NHIP_TRY_HIP(hipMemcpy(records, dr.p, 16 * K * (size_t)n_ids, hipMemcpyDeviceToHost));
+  NHIP_TRY_HIP(hipMemcpy(stats, ds.p, 64, hipMemcpyDeviceToHost));
+  if (desc && n) NHIP_TRY_HIP(hipMemcpy(desc, dd.p, 8 * R * (size_t)n, hipMemcpyDeviceToHost));
+  if (bits && n) NHIP_TRY_HIP(hipMemcpy(bits, db.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
+  InFlight::done();  // (the downloads above synchronised the null stream)
+  return NHIP_OK;
+}
+
+}  // extern "C"

@@ -278,6 +278,75 @@ def freespace_counts(xy, offsets, pair_src, pair_tgt, theta0, matches, grid_spec
     return counts
 
 
+def place_descriptors(xy, offsets, spec):
+    """The ring descriptors of the packed scans in plain numpy ("Place descriptors"; the device form is
+    nhip_place_describe_dev): (D uint64 (n_scans, R), bits int32 (n_scans,)).  The tables are the library's
+    (nhip_place_tables: pure host)."""
+    from . import place
+    f = np.float32
+    edge2, dirs = place.tables(spec)
+    R = int(spec.n_rings)
+    p = np.asarray(xy, dtype=f).reshape(-1, 2)
+    off = np.asarray(offsets, dtype=np.int64)
+    x, y = p[:, 0], p[:, 1]
+    with np.errstate(invalid="ignore", over="ignore"):
+        r2 = ((x * x).astype(f) + (y * y).astype(f)).astype(f)
+        kept = np.isfinite(r2) & (r2 < edge2[R])
+        ring = np.searchsorted(edge2[1:R], r2, side="right")  # (#{k: r2 >= edge2[k]}: the edges ascend)
+        neg = (y < 0) | ((y == 0) & (x < 0))
+        u, v = np.where(neg, -x, x).astype(f), np.where(neg, -y, y).astype(f)
+        sector = np.where(neg, 32, 0)
+        for j in range(1, 32):
+            sector = sector + (((dirs[j, 0] * v).astype(f) - (dirs[j, 1] * u).astype(f)).astype(f) >= 0)
+    scan = np.repeat(np.arange(len(off) - 1), np.diff(off))
+    D = np.zeros((len(off) - 1, R), dtype=np.uint64)
+    np.bitwise_or.at(D, (scan[kept], ring[kept]), np.uint64(1) << sector[kept].astype(np.uint64))
+    return D, np.bitwise_count(D).sum(axis=1).astype(np.int32)
+
+
+def place_candidates(xy, offsets, ids, spec=None):
+    """Loop-closure candidates by appearance in plain numpy on the host (the device form is nhip_place_candidates): (records
+    int32 (n_ids, K, 4) = {j, shift, dist, bits_j}, four -1 where unfilled; stats int64 (8,)).  Product code: a backend
+    without place_candidates() proposes its pairs with this (examples/slam_loop.py --lc-gate appearance)."""
+    from . import place
+    spec = place.default_spec() if spec is None else spec
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    n_scans = len(offsets) - 1
+    if len(ids) and (ids[0] < 0 or ids[-1] >= n_scans or (np.diff(ids) <= 0).any()):
+        raise ValueError("place_candidates: ids must ascend strictly inside the %d scans" % n_scans)
+    R, K = int(spec.n_rings), int(spec.top_k)
+    if not (1 <= R <= 15 and 1 <= K <= 32 and spec.min_separation >= 0 and 0 <= spec.max_permille <= 1000):
+        raise ValueError("place_candidates: n_rings 1..15, top_k 1..32, min_separation >= 0, max_permille 0..1000")
+    D, bits = place_descriptors(xy, offsets, spec)
+    D, bits = D[ids], bits[ids].astype(np.int64)
+    M = len(ids)
+    rec, stats = np.full((M, K, 4), -1, dtype=np.int32), np.zeros(8, dtype=np.int64)
+    stats[0], stats[5] = M, int((bits == 0).sum())
+    if M == 0:
+        return rec, stats
+    # rotl64(D_j, s) for every candidate and shift, once: (M, 64, R)
+    s = np.arange(1, 64, dtype=np.uint64)[None, :, None]
+    rot = np.concatenate([D[:, None, :], (D[:, None, :] << s) | (D[:, None, :] >> (np.uint64(64) - s))], axis=1)
+    for a in range(M):
+        adm = (np.abs(ids - ids[a]) > spec.min_separation) & (bits > 0) & (bits[a] > 0)
+        if spec.flags & place.NHIP_PLACE_PAST_ONLY:
+            adm &= ids < ids[a]
+        b = np.nonzero(adm)[0]
+        stats[1] += len(b)
+        if len(b):
+            d = np.bitwise_count(D[a][None, None, :] ^ rot[b]).sum(axis=2).astype(np.int64)  # (len(b), 64)
+            shift = d.argmin(axis=1)  # (the first minimum: the smallest shift)
+            dist = d[np.arange(len(b)), shift]
+            gate = 1000 * dist <= int(spec.max_permille) * (bits[a] + bits[b])
+            b, shift, dist = b[gate], shift[gate], dist[gate]
+            stats[2] += len(b)
+            order = np.lexsort((b, dist))[:K]
+            rec[a, :len(order)] = np.stack([ids[b[order]], shift[order], dist[order], bits[b[order]]], axis=1)
+            stats[3] += len(order)
+        stats[4] += not (rec[a, 0, 0] >= 0)
+    return rec, stats
+
+
 def distance_to_line_segment_f32(points, seg):
     """DistanceToLineSegment<float> (slam_util.h:92-110) for an (n, 2) float32 array: Hyperplane::Through normal,
     projection inside the endpoints' closed x and y intervals -> |signed distance|, else nearest endpoint."""

@@ -220,6 +220,25 @@ class HipBackend:
         st.close()
         return out
 
+    def place_candidates(self, xy, offsets, ids, spec=None):
+        """Loop-closure candidates by appearance among the scans `ids` (ascending), from no pose at all (place.py:
+        nhip_place_candidates): (records int32 (n_ids, K, 4) = {j, shift, dist, bits_j}, stats int64 (8,))."""
+        from . import csm, place
+        # Only the scans the list names go to the device, as in match(): the others keep their ids as empty scans.
+        off = np.asarray(offsets, dtype=np.int64)
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        if len(ids) and (ids.min() < 0 or ids.max() >= len(off) - 1):
+            raise ValueError("place_candidates: an id outside the %d scans" % (len(off) - 1))
+        lengths = np.zeros(len(off) - 1, dtype=np.int64)
+        lengths[ids] = np.diff(off)[ids]
+        xy = np.asarray(xy, dtype=np.float32).reshape(-1, 2)
+        xy = np.concatenate([xy[off[i]:off[i + 1]] for i in ids]) if len(ids) else xy[:0]
+        st = csm.ScanTable(xy, np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32))
+        try:
+            return place.candidates(st, ids, spec)
+        finally:
+            st.close()
+
     def pair_gate(self, poses, candidates, max_range, min_separation):
         P = np.ascontiguousarray(poses, dtype=np.float64)
         cand = np.ascontiguousarray(candidates, dtype=np.int32)
