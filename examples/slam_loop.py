@@ -57,7 +57,7 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         rank=0, world=1, device="cuda:0", backend=None, iterations=4, hitl=True, cell_bits=16, gate="scatter",
         min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False, normals="bag", lc_submap=0,
         linear_solver="host", lc_gate="geometric", lc_max_score=5000.0, map_output=None, grid_output=None, lc_verify=None,
-        lc_max_violation=None, lc_top_k=5):
+        lc_max_violation=None, lc_top_k=5, lc_consistency=False, lc_min_set=3, _lc_corrupt=None):
     """min_scatter_score: LCCandidateFilter's threshold is 0.70 (lc_candidate_filter.cc:76); scans of the synthetic
     24 m x 16 m room score ~0.4, so callers on that world pass a lower one.
     hitl_device: the HITL constraint's points are selected and packed on the GPU (hitl.select, under the "path" clock) and
@@ -95,6 +95,14 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     inside the grid.  A backend whose match() takes `freespace` checks on the device inside the call; any other is checked by
     hostside.freespace_counts.  The result reports lc_verified, lc_verify_rejected (they sum to the unverified run's
     lc_accepted) and the rms relative error of either set.  Not with world > 1 or lc_submap.
+    lc_consistency: the accepted records -- after the score gate and, with lc_verify, the free-space check -- are judged against
+    each other ("Loop-closure consistency"): the cycle two records form with the estimate between their ends
+    must close up to the drift the estimate can have gathered, and only the records of a greedily grown set of mutually consistent
+    ones become constraints -- none if the set has fewer than lc_min_set members.  A backend with consistent_set() does it on the
+    device; any other is served by hostside.consistent_set.  The result reports lc_consistency, lc_consistent, lc_inconsistent
+    (they sum to the unfiltered run's lc_accepted), lc_inconsistent_rel_err_m and consistency_s.  Not with world > 1.
+    _lc_corrupt: TEST ONLY -- a callable (src, tgt, rel, good) -> rel that replaces the records' transforms before the consistency
+    filter and the constraints (tests/test_consistency_loop_gpu.py displaces accepted records with it).
     With world > 1 (one process per GPU under torch.distributed): the window ICP solve is replicated -- its
     consumer, the solver, is host-side -- and the loop-closure pairs are sharded by target across the ranks,
     matched, and all-gathered (nautilus_amd/sharding.py); every rank ends with the same trajectory."""
@@ -125,6 +133,10 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         raise ValueError("run: lc_verify %r (None or \"free-space\")" % (lc_verify,))
     if lc_verify and (world > 1 or lc_submap):
         raise ValueError("run: lc_verify with world > 1 or lc_submap (the free-space check has no sharded path and no submap targets)")
+    if lc_consistency and world > 1:
+        raise ValueError("run: lc_consistency with world > 1 (the consistent set has no sharded path)")
+    if lc_consistency and int(lc_min_set) < 0:
+        raise ValueError("run: lc_min_set %r must be >= 0" % (lc_min_set,))
     if lc_max_violation is not None and not 0 <= int(lc_max_violation) <= 1000:
         raise ValueError("run: lc_max_violation %r: permille, 0..1000" % (lc_max_violation,))
     out = {"backend": backend.name, "n_scans": n_scans, "window": window, "residual": residual,
@@ -286,6 +298,26 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
             out["lc_verified"], out["lc_verify_rejected"] = int((good & verified).sum()), int((good & ~verified).sum())
             out["lc_verify_rejected_rel_err_m"] = rms(good & ~verified)
             good &= verified
+        if _lc_corrupt is not None:
+            rel = np.ascontiguousarray(_lc_corrupt(src, tgt, rel.copy(), good.copy()), dtype=np.float64)
+        if lc_consistency:
+            from nautilus_amd import consistency
+            t1 = time.perf_counter()
+            idx = np.nonzero(good)[0]
+            if hasattr(backend, "consistent_set"):
+                with posegraph.clocked("path"):
+                    members, n_members, _ = backend.consistent_set(poses, src[idx], tgt[idx], rel[idx])
+            else:  # (a backend without the method: the plain numpy host path, as place_candidates is for the appearance gate)
+                with posegraph.clocked("marshal"):
+                    members, n_members, _ = hostside.consistent_set(consistency.prepare(poses, src[idx], tgt[idx], rel[idx]))
+            consistent = np.zeros(len(good), dtype=bool)
+            consistent[idx[consistency.keep(members, n_members, len(idx), int(lc_min_set))]] = True
+            out["lc_consistency"], out["lc_min_set"], out["consistency_s"] = True, int(lc_min_set), time.perf_counter() - t1
+            out["lc_consistent"], out["lc_inconsistent"] = int((good & consistent).sum()), int((good & ~consistent).sum())
+            out["lc_inconsistent_rel_err_m"] = rms(good & ~consistent)
+            out["lc_consistent_pairs"] = np.stack([src[good & consistent], tgt[good & consistent]], axis=1).tolist()
+            out["lc_inconsistent_pairs"] = np.stack([src[good & ~consistent], tgt[good & ~consistent]], axis=1).tolist()
+            good &= consistent
         out["lc_accepted"] = int(good.sum())
         out["lc_rel_err_m"] = rms(good)
         lc = (src[good], tgt[good], rel[good])
@@ -410,6 +442,11 @@ if __name__ == "__main__":
     ap.add_argument("--lc-max-violation", type=int, default=None, metavar="PERMILLE",
                     help="with --lc-verify: the largest share of a source's returns in the target's free space, plus its beams "
                          "through target hits, that is kept (default: freespace.DEFAULT_MAX_PERMILLE)")
+    ap.add_argument("--lc-consistency", action="store_true",
+                    help="keep only the accepted loop closures of a mutually consistent set (pairwise consistency of the cycles "
+                         "they form with the estimate; not with several ranks)")
+    ap.add_argument("--lc-min-set", type=int, default=3, metavar="N",
+                    help="with --lc-consistency: a consistent set of fewer members is not trusted and no loop closure is kept")
     ap.add_argument("--map-output", metavar="PATH", default=None,
                     help="vectorise the final poses' map on the GPU and write it there, one 'x1,y1,x2,y2' line per wall segment")
     ap.add_argument("--grid-output", metavar="STEM", default=None,
@@ -435,7 +472,8 @@ if __name__ == "__main__":
     res = run(a.scans, a.window, verbose=a.v and rank == 0, residual=a.residual, rank=rank, world=world,
               device="cuda:%d" % local, hitl_device=a.hitl_device, normals=a.normals, lc_submap=a.lc_submap,
               linear_solver=a.linear_solver, lc_gate=a.lc_gate, lc_max_score=a.lc_max_score, map_output=a.map_output,
-              grid_output=a.grid_output, lc_verify=a.lc_verify, lc_max_violation=a.lc_max_violation, lc_top_k=a.lc_top_k)
+              grid_output=a.grid_output, lc_verify=a.lc_verify, lc_max_violation=a.lc_max_violation, lc_top_k=a.lc_top_k,
+              lc_consistency=a.lc_consistency, lc_min_set=a.lc_min_set)
     res["world_size"] = world
     if rank == 0:
         print(json.dumps(res))

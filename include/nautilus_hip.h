@@ -68,7 +68,8 @@ const char *nhip_version(void);
  * nhip_bsr_assemble_dev / nhip_bsr_pcg_dev / nhip_bsr_pcg_columns_dev, 8192 gauge or right-hand-side index of
  * nhip_bsr_pcg_columns_dev, 16384 scan offset of nhip_vectorize_dev /
  * nhip_occupancy_dev / nhip_place_describe_dev, 32768 source scan, grid slot or record index of a pair of
- * nhip_freespace_check_dev, 65536 scan id of the list of nhip_place_match_dev.  Clears the record
+ * nhip_freespace_check_dev, 65536 scan id of the list of nhip_place_match_dev, 131072 degree and 262144
+ * member index of nhip_consistency_set_dev.  Clears the record
  * (in the order of `stream`).
  * ONE record per DEVICE, shared by every stream and host thread that uses the library on it: a host with several streams
  * on one device learns THAT an id was bad and which, not on which stream; a call that finds a record consumes it -- reports
@@ -876,6 +877,67 @@ int nhip_place_match_dev(const uint64_t *d_desc, const int32_t *d_bits, int32_t 
                          const nhip_place_spec_t *spec, int32_t *d_records, int64_t *d_stats, void *d_workspace,
                          int64_t workspace_bytes, void *stream);
 
+/* K17: LOOP-CLOSURE CONSISTENCY -- the records of loop closure judged against each other ("Loop-closure
+ * consistency"; tests/consistency_reference.py restates it in numpy).  The reference leaves wrong closures to a human (HITL
+ * curation); this is pairwise consistency maximisation (Mangelson et al., ICRA 2018), build-defined: two records are consistent
+ * if the cycle they form with the odometry between their ends closes up to the drift that odometry can have gathered, and a
+ * large set of mutually consistent records is grown greedily.
+ *   records     M x 8 doubles {cw, sw, xw, yw, px, py, la, lb}, prepared on the host (nautilus_amd/consistency.py, prepare):
+ *               W_m = X_tgt o Z_m o X_src^-1 as cosine, sine and translation, the position of tgt, the arc lengths of src and
+ *               tgt along the trajectory.  No kernel calls a transcendental.
+ *   pair test   for m != n, lo = min(m, n), hi = max(m, n) (symmetric by construction); every operation an fp64 operation
+ *               rounded on its own, in this order (a b: product; negation and the factor 2 are exact):
+ *                 ihx = -((c_hi x_hi) + (s_hi y_hi))        ihy = (s_hi x_hi) - (c_hi y_hi)
+ *                 cq  = (c_lo c_hi) + (s_lo s_hi)           sq  = (s_lo c_hi) - (c_lo s_hi)
+ *                 qx  = ((c_lo ihx) - (s_lo ihy)) + x_lo    qy  = ((s_lo ihx) + (c_lo ihy)) + y_lo
+ *                 ex  = (((cq px_lo) - (sq py_lo)) + qx) - px_lo
+ *                 ey  = (((sq px_lo) + (cq py_lo)) + qy) - py_lo
+ *                 e2  = (ex ex) + (ey ey)                   chord = 2 - (2 cq)
+ *                 len = |la_lo - la_hi| + |lb_lo - lb_hi|
+ *                 tt  = min(t0 + (t_rate len), t_max)       tr  = min(r0 + (r_rate len), r_max)
+ *               with min(a, b) = b < a ? b : a (a NaN sum stays); consistent iff e2 <= (tt tt) and chord <= (tr tr): a NaN
+ *               anywhere fails a comparison.  The diagonal is 0.
+ *   matrix      M rows of W = ceil(M / 64) uint64 words, bit n of row m in bit n % 64 of word n / 64, zero beyond M;
+ *               deg[m] = popcount(row m).
+ *   set         C = all records; each step: u = the member of C with the largest score, the smaller index among equals --
+ *               the score is deg[u] in the first step and popcount(A[u] & C) after it --, u is appended, C &= A[u]; until C is
+ *               empty or max_steps members are appended.  M = 0: the empty set; a matrix without edges: record 0 alone.
+ *   stats       8 int64: {M, edges, the largest degree, steps taken (= members), 1 if the step cap ended the set with C not
+ *               empty, 0, 0, 0}; nhip_consistency_adjacency_dev writes the first three and zeros.
+ * Accepted ranges (anything else is NHIP_ERR_ARG before anything is launched, with or without a device): every tolerance finite
+ * and >= 0, t_max >= t0, r_max >= r0, max_steps >= 1, flags 0, M 0..65536. */
+#define NHIP_CONSISTENCY_STATE_BYTES 8448 /* the set's own part of the workspace: 256 bytes of state, then 1024 words of C */
+typedef struct nhip_consistency_spec {
+  double t0;         /* translation tolerance of a cycle without odometry, metres (0.8) */
+  double t_rate;     /* ... gained per metre of odometry the cycle spans (0.1) */
+  double t_max;      /* ... and its cap (16) */
+  double r0;         /* rotation tolerance, as a chord ~ radians (0.1) */
+  double r_rate;     /* ... per metre (0.005) */
+  double r_max;      /* ... cap (0.5) */
+  int32_t max_steps; /* members appended at most (65536: no cap) */
+  int32_t flags;     /* 0 */
+} nhip_consistency_spec_t;
+/* the defaults of the table above; pure host */
+int nhip_consistency_spec_default(nhip_consistency_spec_t *out);
+/* bytes of the ONE buffer a caller needs for M records: the set's state and live set in the first
+ * NHIP_CONSISTENCY_STATE_BYTES, then room for the matrix (8 M W bytes, from that offset) and the degrees (4 M bytes, behind the
+ * matrix), rounded up to 256.  -1: M outside 0..65536, message in nhip_last_error; pure host */
+int64_t nhip_consistency_workspace_bytes(int32_t M);
+/* The matrix and the degrees of M prepared records (d_records: M x 8 doubles): d_adj M x W uint64, d_deg M int32, d_stats 8
+ * int64.  Never allocates, enqueues and returns without waiting. */
+int nhip_consistency_adjacency_dev(const double *d_records, int32_t M, const nhip_consistency_spec_t *spec, uint64_t *d_adj,
+                                   int32_t *d_deg, int64_t *d_stats, void *stream);
+/* The consistent set of a matrix: d_members M int32 in pick order (-1 behind them), d_n_members one int32, d_stats 8 int64.
+ * d_workspace (256-byte aligned) is the buffer of nhip_consistency_workspace_bytes(M) -- a smaller one is NHIP_ERR_ARG; d_adj
+ * and d_deg normally lie inside it, at the offsets given there.  Steps are enqueued check_every at a time (0: the default,
+ * 8) and the call reads one word between two batches: it WAITS for the stream, and check_every changes no result.  A degree
+ * outside [0, M) counts as 0 and nhip_dev_status() reports it (kind 131072, index = the record); a member index outside
+ * [0, M) -- only a workspace overwritten during the call can produce one -- ends the set and is reported (kind 262144).  Bits
+ * of the matrix beyond M and on the diagonal are never followed. */
+int nhip_consistency_set_dev(const uint64_t *d_adj, const int32_t *d_deg, int32_t M, const nhip_consistency_spec_t *spec,
+                             int32_t check_every, int32_t *d_members, int32_t *d_n_members, int64_t *d_stats, void *d_workspace,
+                             int64_t workspace_bytes, void *stream);
+
 /* HITL point selection: GetRelevantPosesForHITL (solver.cc:479-513) for every scan at once.  A point p of scan s goes to
  * the world as w = (c px - s py + tx, s px + c py + ty) with (c, s, tx, ty) = d_pose_f32[4s ..], the entries of
  * PoseArrayToAffine(pose).cast<float>() (nhip_pose_affines forms them), every operation a float operation rounded on its
@@ -992,6 +1054,11 @@ int nhip_csm_freespace(const nhip_scans_t *scans, const nhip_grids_t *grids, con
  * buffers; the key workspace is nhip_place_workspace_bytes. */
 int nhip_place_candidates(const nhip_scans_t *scans, const int32_t *ids, int32_t n_ids, const nhip_place_spec_t *spec,
                           int32_t *records, int64_t *stats, uint64_t *desc, int32_t *bits);
+
+/* nhip_consistency_adjacency_dev + nhip_consistency_set_dev on host memory: records (M x 8 doubles), members (M int32, -1 behind
+ * the set), n_members (one int32) and stats (8 int64).  Allocates and frees its device buffers; steps in batches of 8. */
+int nhip_consistency(const double *records, int32_t M, const nhip_consistency_spec_t *spec, int32_t *members, int32_t *n_members,
+                     int64_t *stats);
 
 /* The reference-shaped single-pair call: CorrelativeScanMatcher(scanner_range, trans_range, low_res, high_res)
  * .GetTransformation(pc_a, pc_b, rot_a, rot_b, rot_restriction) -> (score, ((tx, ty), theta))

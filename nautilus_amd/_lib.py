@@ -25,6 +25,7 @@ NHIP_TIMER_OCC_TRACE, NHIP_TIMER_OCC_CLASSIFY = 12, 13
 NHIP_OCC_ACCUMULATE = 1
 NHIP_PLACE_PAST_ONLY = 1
 NHIP_PLACE_WORKSPACE_MAX = 64 << 20
+NHIP_CONSISTENCY_STATE_BYTES = 8448
 
 
 class NhipError(RuntimeError):
@@ -96,6 +97,11 @@ class FreespaceSpec(C.Structure):
 class PlaceSpec(C.Structure):
     _fields_ = [("n_rings", C.c_int32), ("range_max", C.c_float), ("top_k", C.c_int32), ("min_separation", C.c_int32),
                 ("max_permille", C.c_int32), ("flags", C.c_int32)]
+
+
+class ConsistencySpec(C.Structure):
+    _fields_ = [("t0", C.c_double), ("t_rate", C.c_double), ("t_max", C.c_double), ("r0", C.c_double), ("r_rate", C.c_double),
+                ("r_max", C.c_double), ("max_steps", C.c_int32), ("flags", C.c_int32)]
 
 
 class HitlSpec(C.Structure):
@@ -223,6 +229,11 @@ PROTOTYPES = {
     "nhip_place_describe_dev": (C.c_int, [_vp, _vp, _i32, _P(PlaceSpec), _vp, _vp, _vp]),
     "nhip_place_match_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(PlaceSpec), _vp, _vp, _vp, _i64, _vp]),
     "nhip_place_candidates": (C.c_int, [_vp, _vp, _i32, _P(PlaceSpec), _vp, _vp, _vp, _vp]),
+    "nhip_consistency_spec_default": (C.c_int, [_P(ConsistencySpec)]),
+    "nhip_consistency_workspace_bytes": (_i64, [_i32]),
+    "nhip_consistency_adjacency_dev": (C.c_int, [_vp, _i32, _P(ConsistencySpec), _vp, _vp, _vp, _vp]),
+    "nhip_consistency_set_dev": (C.c_int, [_vp, _vp, _i32, _P(ConsistencySpec), _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "nhip_consistency": (C.c_int, [_vp, _i32, _P(ConsistencySpec), _vp, _vp, _vp]),
     "nhip_hitl_spec_default": (C.c_int, [_P(HitlSpec)]),
     "nhip_hitl_select_dev": (C.c_int, [_vp, _vp, _i32, _vp, _P(HitlSpec), _vp, _vp, _vp, _vp, _vp, _vp]),
     "nhip_hitl_pack_dev": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),

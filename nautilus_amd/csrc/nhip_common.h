@@ -54,7 +54,8 @@ struct IdBounds {          // (plain data: it travels inside the kernels' parame
 constexpr uint32_t BAD_TARGET_ID = 1u, BAD_PAIR_SRC = 2u, BAD_PAIR_SLOT = 4u, BAD_BLOCK_ID = 8u, BAD_POSE_ID = 16u,
                    BAD_SCAN_ID = 32u, BAD_FEATURE_IDX = 64u, BAD_FEATURE_COUNT = 128u, BAD_SCAN_OFFSETS = 256u,
                    BAD_MEMBER_ID = 512u, BAD_SUBMAP_CAPACITY = 1024u, BAD_CONTRIB_ID = 2048u, BAD_BLOCK_COLUMN = 4096u,
-                   BAD_SYSTEM_ID = 8192u, BAD_MAP_SCAN_OFFSETS = 16384u, BAD_FREESPACE_PAIR = 32768u, BAD_PLACE_ID = 65536u;
+                   BAD_SYSTEM_ID = 8192u, BAD_MAP_SCAN_OFFSETS = 16384u, BAD_FREESPACE_PAIR = 32768u, BAD_PLACE_ID = 65536u,
+                   BAD_CONSISTENCY_DEGREE = 131072u, BAD_CONSISTENCY_MEMBER = 262144u;
 constexpr int DEV_STATUS_WORDS = 4;  // {OR of the kinds seen, kind / value / index of the first report}
 uint32_t *dev_status();              // of the current device (allocated on the device's first use; null if that failed)
 #ifdef __HIPCC__
@@ -433,6 +434,34 @@ int launch_place_describe(const PlaceTables &T, const float *d_xy, const int32_t
                           int32_t *d_bits, hipStream_t s);
 // clears the stats, then distance and top-K kernels per chunk of `chunk_rows` query rows (the workspace holds that many)
 int launch_place_match(const PlaceMatch &P, int32_t chunk_rows, hipStream_t s);
+
+// loop-closure consistency (nhip_consistency.hip, K17); the spec has passed consistency_spec_check (nhip_host_consistency.hip)
+constexpr int32_t CONSISTENCY_MAX_RECORDS = 65536;  // W = ceil(M / 64) <= 1024 words: the live set fits the score kernel's LDS
+struct ConsistencyState {  // the first bytes of the workspace: what the step kernels keep between launches
+  unsigned long long key;  // the step's best (score << 32 | ~u), by 64-bit atomicMax; 0 between steps
+  int32_t steps;           // members appended so far
+  int32_t done;            // set once the set has ended: every kernel returns at once; the ONE word the host reads between batches
+};
+struct ConsistencyTol {    // the spec's tolerances: plain data in the adjacency kernel's parameter block
+  double t0, t_rate, t_max, r0, r_rate, r_max;
+};
+struct ConsistencySet {    // plain data: travels in the set kernels' parameter blocks
+  const unsigned long long *adj;  // M rows of W words
+  const int32_t *deg;             // M
+  unsigned long long *C;          // W words of the workspace: the live set
+  ConsistencyState *st;
+  int32_t *members, *n_members;
+  long long *stats;               // 8 words
+  uint32_t *status;
+  int32_t M, W, max_steps;        // (max_steps: already min(spec.max_steps, M))
+};
+// clears the degrees, then the whole matrix and the degrees, then stats = {M, edges, largest degree, 0 ...}
+int launch_consistency_adjacency(const double *d_records, int32_t M, const ConsistencyTol &T, unsigned long long *d_adj, int32_t *d_deg,
+                                 long long *d_stats, hipStream_t s);
+// the members cleared to -1, the live set to all M records, the stats' first three words from the degrees
+int launch_consistency_begin(const ConsistencySet &P, hipStream_t s);
+// enqueues `n` steps (score + commit); each returns at once when the set has ended
+int launch_consistency_steps(const ConsistencySet &P, int32_t n, hipStream_t s);
 
 int launch_resid_point_to_line(const float *d_segments, const float *d_points,
                                const int32_t *d_point_block, int64_t n_points,

@@ -347,6 +347,74 @@ def place_candidates(xy, offsets, ids, spec=None):
     return rec, stats
 
 
+def _consistency_rows(rec, rows, tol):
+    """Rows `rows` of the consistency matrix of the prepared records, as booleans (len(rows), M): the pair test of DESIGN.md
+    section 3, "Loop-closure consistency", every operation a float64 operation of numpy, rounded on its own."""
+    M = len(rec)
+    m, n = np.asarray(rows)[:, None], np.arange(M)[None, :]
+    row_is_lo = m < n
+    a = [np.where(row_is_lo, rec[m, k], rec[n, k]) for k in range(8)]  # lo
+    b = [np.where(row_is_lo, rec[n, k], rec[m, k]) for k in range(8)]  # hi
+    t0, t_rate, t_max, r0, r_rate, r_max = tol
+    with np.errstate(invalid="ignore", over="ignore"):
+        ihx, ihy = -((b[0] * b[2]) + (b[1] * b[3])), (b[1] * b[2]) - (b[0] * b[3])
+        cq, sq = (a[0] * b[0]) + (a[1] * b[1]), (a[1] * b[0]) - (a[0] * b[1])
+        qx, qy = ((a[0] * ihx) - (a[1] * ihy)) + a[2], ((a[1] * ihx) + (a[0] * ihy)) + a[3]
+        ex = (((cq * a[4]) - (sq * a[5])) + qx) - a[4]
+        ey = (((sq * a[4]) + (cq * a[5])) + qy) - a[5]
+        e2, chord = (ex * ex) + (ey * ey), 2.0 - (2.0 * cq)
+        length = np.abs(a[6] - b[6]) + np.abs(a[7] - b[7])
+        tt, tr = t0 + (t_rate * length), r0 + (r_rate * length)
+        tt, tr = np.where(t_max < tt, t_max, tt), np.where(r_max < tr, r_max, tr)
+        return (e2 <= tt * tt) & (chord <= tr * tr) & (m != n)
+
+
+def consistent_set(records, spec=None, adjacency=False):
+    """The consistent set of prepared loop-closure records (consistency.prepare) in plain numpy on the host (the device form is
+    nhip_consistency): (members int32 (M,) in pick order, -1 behind them; n_members; stats int64 (8,)), with adjacency=True also
+    (matrix uint64 (M, W), degrees int32 (M,)).  Product code: a backend without consistent_set() filters its records with this
+    (examples/slam_loop.py --lc-consistency)."""
+    from . import consistency
+    spec = consistency.default_spec() if spec is None else spec
+    rec = np.ascontiguousarray(records, dtype=np.float64)
+    if rec.ndim != 2 or rec.shape[1] != 8 or len(rec) > consistency.MAX_RECORDS:
+        raise ValueError("consistent_set: records of shape %s; (M, 8) with M <= %d wanted" % (rec.shape, consistency.MAX_RECORDS))
+    tol = [float(getattr(spec, k)) for k in ("t0", "t_rate", "t_max", "r0", "r_rate", "r_max")]
+    if not (all(np.isfinite(v) and v >= 0 for v in tol) and tol[2] >= tol[0] and tol[5] >= tol[3] and spec.max_steps >= 1 and spec.flags == 0):
+        raise ValueError("consistent_set: tolerances finite and >= 0, t_max >= t0, r_max >= r0, max_steps >= 1, flags 0")
+    M, W = len(rec), (len(rec) + 63) // 64
+    bits = np.zeros((M, W * 64), dtype=bool)
+    for r0_ in range(0, M, 256):  # (rows in chunks: a chunk's temporaries are 256 x M doubles)
+        rows = np.arange(r0_, min(r0_ + 256, M))
+        bits[rows, :M] = _consistency_rows(rec, rows, tol)
+    A = np.packbits(bits, axis=1, bitorder="little").view(np.uint64).reshape(M, W) if M else np.zeros((0, 0), dtype=np.uint64)
+    deg = np.bitwise_count(A).sum(axis=1).astype(np.int32)
+    members, stats = np.full(M, -1, dtype=np.int32), np.zeros(8, dtype=np.int64)
+    stats[0] = M
+    n = 0
+    if M:
+        stats[1], stats[2] = int(deg.sum()) // 2, int(deg.max())
+        live = np.ones(M, dtype=bool)  # (C as booleans, and as words for the popcounts)
+        C_words = np.packbits(np.concatenate([live, np.zeros(W * 64 - M, dtype=bool)]), bitorder="little").view(np.uint64)
+        score = deg.astype(np.int64)
+        cap = min(int(spec.max_steps), M)
+        while True:
+            idx = np.nonzero(live)[0]
+            u = int(idx[np.argmax(score[idx])])  # (the first maximum: the smallest index)
+            members[n] = u
+            n += 1
+            C_words = C_words & A[u]
+            C_words[u >> 6] &= ~(np.uint64(1) << np.uint64(u & 63))
+            live = np.unpackbits(C_words.view(np.uint8), bitorder="little")[:M].astype(bool)
+            if not live.any() or n >= cap:
+                break
+            score = np.zeros(M, dtype=np.int64)
+            rows = np.nonzero(live)[0]
+            score[rows] = np.bitwise_count(A[rows] & C_words[None, :]).sum(axis=1)
+        stats[3], stats[4] = n, int(live.any())
+    return (members, n, stats, A, deg) if adjacency else (members, n, stats)
+
+
 def distance_to_line_segment_f32(points, seg):
     """DistanceToLineSegment<float> (slam_util.h:92-110) for an (n, 2) float32 array: Hyperplane::Through normal,
     projection inside the endpoints' closed x and y intervals -> |signed distance|, else nearest endpoint."""

@@ -239,6 +239,12 @@ class HipBackend:
         finally:
             st.close()
 
+    def consistent_set(self, poses, src, tgt, rel, spec=None):
+        """The mutually consistent set of the loop closures (src, tgt, rel) under the trajectory `poses` (consistency.py:
+        nhip_consistency): (members int32 (M,) in pick order, -1 behind them; n_members; stats int64 (8,))."""
+        from . import consistency
+        return consistency.consistent_set(consistency.prepare(poses, src, tgt, rel), spec)
+
     def pair_gate(self, poses, candidates, max_range, min_separation):
         P = np.ascontiguousarray(poses, dtype=np.float64)
         cand = np.ascontiguousarray(candidates, dtype=np.int32)
