@@ -57,7 +57,7 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         rank=0, world=1, device="cuda:0", backend=None, iterations=4, hitl=True, cell_bits=16, gate="scatter",
         min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False, normals="bag", lc_submap=0,
         linear_solver="host", lc_gate="geometric", lc_max_score=5000.0, map_output=None, grid_output=None, lc_verify=None,
-        lc_max_violation=None, lc_top_k=5, lc_consistency=False, lc_min_set=3, _lc_corrupt=None):
+        lc_max_violation=None, lc_top_k=5, lc_consistency=False, lc_min_set=3, _lc_corrupt=None, lc_sequence=0, lc_sequence_step=1):
     """min_scatter_score: LCCandidateFilter's threshold is 0.70 (lc_candidate_filter.cc:76); scans of the synthetic
     24 m x 16 m room score ~0.4, so callers on that world pass a lower one.
     hitl_device: the HITL constraint's points are selected and packed on the GPU (hitl.select, under the "path" clock) and
@@ -83,6 +83,11 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     than 20 nodes apart become the pairs (src = the query), and the matcher's theta0 is the heading the aligning rotation gives,
     not the estimate's heading difference.  A backend with place_candidates() does it on the device; any other is served by
     hostside.place_candidates.  Everything after that is the same; the result reports lc_gate, lc_top_k, place_s and lc_pairs.
+    lc_sequence W > 0 (only with lc_gate "appearance"): the descriptors are compared over a window of 2W + 1 frames, lc_sequence_step
+    scans apart, around both scans of a pair and in both directions of travel ("Place sequences"): a backend
+    with place_sequence_candidates() does it on the device, any other is served by hostside.place_sequence_candidates.  2 W step
+    must stay within the minimum separation (20).  The result also reports lc_sequence, lc_sequence_step, lc_sequence_reverse
+    (records of direction 1) and lc_sequence_short (records whose window was cut short).  0: a single scan's descriptor, as before.
     map_output: a path -- the final poses' vector map (Solver::Vectorize, solver.cc:581-624: backend.vectorize, on the GPU)
     is written there as 'x1,y1,x2,y2' lines (hostside.write_map_lines); the result reports map_segments and vectorize_s, and
     keeps the poses the map was made at in "map_poses".
@@ -124,6 +129,12 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         raise ValueError("run: lc_gate %r (\"geometric\", \"appearance\", or \"chi-square\" with gate \"scatter\")" % (lc_gate,))
     if not 1 <= int(lc_top_k) <= 32:
         raise ValueError("run: lc_top_k %r: 1..32" % (lc_top_k,))
+    lc_sequence, lc_sequence_step = int(lc_sequence), int(lc_sequence_step)
+    if lc_sequence and lc_gate != "appearance":
+        raise ValueError("run: lc_sequence %d needs lc_gate \"appearance\", not %r" % (lc_sequence, lc_gate))
+    if not (0 <= lc_sequence <= 8 and 1 <= lc_sequence_step <= 16 and 2 * lc_sequence * lc_sequence_step <= LC_MIN_SEPARATION):
+        raise ValueError("run: lc_sequence %d in 0..8, lc_sequence_step %d in 1..16, twice their product at most the minimum "
+                         "separation (%d)" % (lc_sequence, lc_sequence_step, LC_MIN_SEPARATION))
     if not 0 <= lc_submap < LC_MIN_SEPARATION:
         raise ValueError("run: lc_submap %d: a submap radius is >= 0 and below the pair gate's minimum separation (%d)"
                          % (lc_submap, LC_MIN_SEPARATION))
@@ -183,7 +194,19 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         t1 = time.perf_counter()
         ids = np.asarray(ids, dtype=np.int32)
         pspec = place.spec(top_k=int(lc_top_k), min_separation=LC_MIN_SEPARATION, flags=place.NHIP_PLACE_PAST_ONLY)
-        if hasattr(backend, "place_candidates"):
+        if lc_sequence:  # (the window of frames around both scans, DESIGN.md section 3, "Place sequences")
+            qspec = place.seq_spec(half_window=lc_sequence, step=lc_sequence_step)
+            if hasattr(backend, "place_sequence_candidates"):
+                with posegraph.clocked("path"):
+                    rec, _ = backend.place_sequence_candidates(xy, off, ids, pspec, qspec)
+            else:
+                with posegraph.clocked("marshal"):
+                    rec, _ = hostside.place_sequence_candidates(xy, off, ids, pspec, qspec)
+            filled = rec[:, :, 0] >= 0
+            out["lc_sequence"], out["lc_sequence_step"] = lc_sequence, lc_sequence_step
+            out["lc_sequence_reverse"] = int((filled & (rec[:, :, 7] == 1)).sum())
+            out["lc_sequence_short"] = int((filled & (rec[:, :, 6] < 2 * lc_sequence + 1)).sum())
+        elif hasattr(backend, "place_candidates"):
             with posegraph.clocked("path"):
                 rec, _ = backend.place_candidates(xy, off, ids, pspec)
         else:  # (a backend without the method: the plain numpy host path, as freespace_counts is for the free-space check)
@@ -435,6 +458,11 @@ if __name__ == "__main__":
                          "the separation rule, or the nearest earlier scans by ring descriptor (no pose enters; the matcher's "
                          "theta0 comes from the descriptors' aligning rotation)")
     ap.add_argument("--lc-top-k", type=int, default=5, metavar="K", help="with --lc-gate appearance: candidates kept per scan (1..32)")
+    ap.add_argument("--lc-sequence", type=int, default=None, metavar="W",
+                    help="with --lc-gate appearance: compare the descriptors over a window of 2W + 1 frames around both scans of a "
+                         "pair, in both directions of travel (0..8; 0: a single scan's descriptor)")
+    ap.add_argument("--lc-sequence-step", type=int, default=None, metavar="S",
+                    help="with --lc-sequence: scans between two frames of a window (1..16; 2 W S at most %d)" % LC_MIN_SEPARATION)
     ap.add_argument("--lc-max-score", type=float, default=5000.0, help="the chi-square gate's threshold (lc_matcher.cc:66: 5000)")
     ap.add_argument("--lc-verify", choices=["free-space"], default=None,
                     help="check every match record against the target's free space and drop the contradicted ones "
@@ -456,6 +484,14 @@ if __name__ == "__main__":
     if not 0 <= a.lc_submap < LC_MIN_SEPARATION:
         ap.error("--lc-submap %d: the radius must be in [0, %d): a source must never be in its target's submap"
                  % (a.lc_submap, LC_MIN_SEPARATION))
+    if (a.lc_sequence is not None or a.lc_sequence_step is not None) and a.lc_gate != "appearance":
+        ap.error("--lc-sequence and --lc-sequence-step need --lc-gate appearance")
+    if a.lc_sequence_step is not None and a.lc_sequence is None:
+        ap.error("--lc-sequence-step needs --lc-sequence")
+    seq_w, seq_step = a.lc_sequence or 0, 1 if a.lc_sequence_step is None else a.lc_sequence_step
+    if not (0 <= seq_w <= 8 and 1 <= seq_step <= 16 and 2 * seq_w * seq_step <= LC_MIN_SEPARATION):
+        ap.error("--lc-sequence %d in 0..8, --lc-sequence-step %d in 1..16, twice their product at most %d"
+                 % (seq_w, seq_step, LC_MIN_SEPARATION))
     rank, world, local = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), \
         int(os.environ.get("LOCAL_RANK", "0"))
     if "RANK" in os.environ:  # python -m torch.distributed.run --nproc-per-node N examples/slam_loop.py ...
@@ -473,7 +509,7 @@ if __name__ == "__main__":
               device="cuda:%d" % local, hitl_device=a.hitl_device, normals=a.normals, lc_submap=a.lc_submap,
               linear_solver=a.linear_solver, lc_gate=a.lc_gate, lc_max_score=a.lc_max_score, map_output=a.map_output,
               grid_output=a.grid_output, lc_verify=a.lc_verify, lc_max_violation=a.lc_max_violation, lc_top_k=a.lc_top_k,
-              lc_consistency=a.lc_consistency, lc_min_set=a.lc_min_set)
+              lc_consistency=a.lc_consistency, lc_min_set=a.lc_min_set, lc_sequence=seq_w, lc_sequence_step=seq_step)
     res["world_size"] = world
     if rank == 0:
         print(json.dumps(res))

@@ -68,7 +68,7 @@ const char *nhip_version(void);
  * nhip_bsr_assemble_dev / nhip_bsr_pcg_dev / nhip_bsr_pcg_columns_dev, 8192 gauge or right-hand-side index of
  * nhip_bsr_pcg_columns_dev, 16384 scan offset of nhip_vectorize_dev /
  * nhip_occupancy_dev / nhip_place_describe_dev, 32768 source scan, grid slot or record index of a pair of
- * nhip_freespace_check_dev, 65536 scan id of the list of nhip_place_match_dev, 131072 degree and 262144
+ * nhip_freespace_check_dev, 65536 scan id of the list of nhip_place_match_dev / nhip_place_seq_match_dev, 131072 degree and 262144
  * member index of nhip_consistency_set_dev.  Clears the record
  * (in the order of `stream`).
  * ONE record per DEVICE, shared by every stream and host thread that uses the library on it: a host with several streams
@@ -877,6 +877,50 @@ int nhip_place_match_dev(const uint64_t *d_desc, const int32_t *d_bits, int32_t 
                          const nhip_place_spec_t *spec, int32_t *d_records, int64_t *d_stats, void *d_workspace,
                          int64_t workspace_bytes, void *stream);
 
+/* K16b: PLACE SEQUENCES -- the appearance match of K16 taken over a window of frames around both scans of a pair (DESIGN.md
+ * section 3, "Place sequences"; tests/place_seq_reference.py restates it in numpy).  The reference votes over a window of frames
+ * around a keyframe (lc_match_window_size = 5, default_config.lua:138-139); the code that used it is not in its tree, so the
+ * window is build-defined: the diagonal sum of SeqSLAM over the single-scan distances.  Descriptors, bits, dist, shift and
+ * theta0 are K16's.  A frame is a SCAN ID in [0, n_scans), not a position in the list.
+ *   pair        entry b (scan j) is admissible for query a (scan i) iff |i - j| > min_separation, j < i under
+ *               NHIP_PLACE_PAST_ONLY, bits_i > 0 and bits_j > 0 (K16's rule without the permille gate).
+ *   frames      for direction sigma in {+1, -1} and offset d in -W .. W: a = i + d step, b = j + sigma d step.  Offset d counts
+ *               for sigma iff 0 <= a < n_scans, 0 <= b < n_scans, bits_a > 0 and bits_b > 0 (d = 0 always counts).
+ *   sums        sum_sigma = the sum of dist(a, b), norm_sigma = the sum of bits_a + bits_b, frames_sigma = the count, over the
+ *               offsets that count.
+ *   score       score_sigma = (sum_sigma (2W + 1)) div frames_sigma: a window cut short is scaled to a full one (<= 16,320).
+ *   direction   0 (sigma = +1, the same way round) if score_+ <= score_-, else 1 (sigma = -1, the place revisited the other
+ *               way round); seq, sum, norm and frames are those of the chosen direction.
+ *   gate        1000 sum <= max_permille norm: K16's permille gate, taken on the window.
+ *   records     per query top_k x int32[8] = {j, shift, dist, bits_j, seq, sum, frames, direction}: shift and dist of the centre
+ *               frames (i, j); the admissible, gated candidates in ascending (seq, j); unfilled records are eight -1.
+ *   stats       8 int64, laid out as K16's, with slot 6 = gated pairs whose direction is 1 and slot 7 = gated pairs with
+ *               frames < 2W + 1.
+ * At W = 0, fields 0..3 of every record and stats 0..5 are nhip_place_match_dev's, seq = sum = dist, frames = 1, direction = 0.
+ * Accepted ranges (anything else is NHIP_ERR_ARG before anything is launched, with or without a device): those of a K16 match
+ * (n_rings 1..15), half_window 0..8, step 1..16, min_separation >= 2 half_window step (the two windows of a pair then never
+ * touch); n_scans >= 0; n_ids 0..2^20. */
+typedef struct nhip_place_seq_spec {
+  int32_t half_window; /* W: the window is 2W + 1 frames (2: the reference's window of 5) */
+  int32_t step;        /* scans between two frames of a window (1) */
+} nhip_place_seq_spec_t;
+/* the defaults of the table above; pure host */
+int nhip_place_seq_spec_default(nhip_place_seq_spec_t *out);
+/* bytes of the workspace: per query scan a row of the plane of single distances (2 bytes per scan, n_scans rounded up to 64) and
+ * a row of window keys (2 bytes per entry, n_ids rounded up to 64).  All scans at once if that stays within
+ * NHIP_PLACE_WORKSPACE_MAX; else as many query scans per chunk as fit beside the chunk's halo of 2 half_window step plane rows,
+ * at least 16.  -1: a bad spec, n_scans or n_ids, message in nhip_last_error; pure host */
+int64_t nhip_place_seq_workspace_bytes(const nhip_place_spec_t *spec, const nhip_place_seq_spec_t *seq, int32_t n_scans, int32_t n_ids);
+/* The records of the list d_ids (ascending: the caller's promise) among the descriptors of ALL n_scans scans -- the window
+ * frames need not be entries of the list: d_records n_ids x top_k x 8 int32, d_stats 8 int64.  The workspace (2-byte aligned)
+ * may be smaller than nhip_place_seq_workspace_bytes says, down to 16 query scans and their halo: the query scans are then
+ * taken in more chunks, with the same result.  Never allocates, enqueues and returns without waiting.  An id outside
+ * [0, n_scans) is never dereferenced and is reported as by nhip_place_match_dev (kind 65536); a window frame outside the scans
+ * is absent and no error. */
+int nhip_place_seq_match_dev(const uint64_t *d_desc, const int32_t *d_bits, int32_t n_scans, const int32_t *d_ids, int32_t n_ids,
+                             const nhip_place_spec_t *spec, const nhip_place_seq_spec_t *seq, int32_t *d_records, int64_t *d_stats,
+                             void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* K17: LOOP-CLOSURE CONSISTENCY -- the records of loop closure judged against each other ("Loop-closure
  * consistency"; tests/consistency_reference.py restates it in numpy).  The reference leaves wrong closures to a human (HITL
  * curation); this is pairwise consistency maximisation (Mangelson et al., ICRA 2018), build-defined: two records are consistent
@@ -1054,6 +1098,13 @@ int nhip_csm_freespace(const nhip_scans_t *scans, const nhip_grids_t *grids, con
  * buffers; the key workspace is nhip_place_workspace_bytes. */
 int nhip_place_candidates(const nhip_scans_t *scans, const int32_t *ids, int32_t n_ids, const nhip_place_spec_t *spec,
                           int32_t *records, int64_t *stats, uint64_t *desc, int32_t *bits);
+
+/* nhip_place_describe_dev + nhip_place_seq_match_dev on uploaded scans: ids as for nhip_place_candidates, records (n_ids x
+ * top_k x 8 int32) and stats (8 int64) in host memory.  Every scan a window reaches must be among the uploaded ones with its
+ * points, or it is a frame without bits.  Allocates and frees its device buffers; the workspace is
+ * nhip_place_seq_workspace_bytes. */
+int nhip_place_seq_candidates(const nhip_scans_t *scans, const int32_t *ids, int32_t n_ids, const nhip_place_spec_t *spec,
+                              const nhip_place_seq_spec_t *seq, int32_t *records, int64_t *stats);
 
 /* nhip_consistency_adjacency_dev + nhip_consistency_set_dev on host memory: records (M x 8 doubles), members (M int32, -1 behind
  * the set), n_members (one int32) and stats (8 int64).  Allocates and frees its device buffers; steps in batches of 8. */

@@ -99,6 +99,10 @@ class PlaceSpec(C.Structure):
                 ("max_permille", C.c_int32), ("flags", C.c_int32)]
 
 
+class PlaceSeqSpec(C.Structure):
+    _fields_ = [("half_window", C.c_int32), ("step", C.c_int32)]
+
+
 class ConsistencySpec(C.Structure):
     _fields_ = [("t0", C.c_double), ("t_rate", C.c_double), ("t_max", C.c_double), ("r0", C.c_double), ("r_rate", C.c_double),
                 ("r_max", C.c_double), ("max_steps", C.c_int32), ("flags", C.c_int32)]
@@ -229,6 +233,10 @@ PROTOTYPES = {
     "nhip_place_describe_dev": (C.c_int, [_vp, _vp, _i32, _P(PlaceSpec), _vp, _vp, _vp]),
     "nhip_place_match_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(PlaceSpec), _vp, _vp, _vp, _i64, _vp]),
     "nhip_place_candidates": (C.c_int, [_vp, _vp, _i32, _P(PlaceSpec), _vp, _vp, _vp, _vp]),
+    "nhip_place_seq_spec_default": (C.c_int, [_P(PlaceSeqSpec)]),
+    "nhip_place_seq_workspace_bytes": (_i64, [_P(PlaceSpec), _P(PlaceSeqSpec), _i32, _i32]),
+    "nhip_place_seq_match_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(PlaceSpec), _P(PlaceSeqSpec), _vp, _vp, _vp, _i64, _vp]),
+    "nhip_place_seq_candidates": (C.c_int, [_vp, _vp, _i32, _P(PlaceSpec), _P(PlaceSeqSpec), _vp, _vp]),
     "nhip_consistency_spec_default": (C.c_int, [_P(ConsistencySpec)]),
     "nhip_consistency_workspace_bytes": (_i64, [_i32]),
     "nhip_consistency_adjacency_dev": (C.c_int, [_vp, _i32, _P(ConsistencySpec), _vp, _vp, _vp, _vp]),

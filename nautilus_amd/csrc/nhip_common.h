@@ -435,6 +435,22 @@ int launch_place_describe(const PlaceTables &T, const float *d_xy, const int32_t
 // clears the stats, then distance and top-K kernels per chunk of `chunk_rows` query rows (the workspace holds that many)
 int launch_place_match(const PlaceMatch &P, int32_t chunk_rows, hipStream_t s);
 
+// place sequences (nhip_place_seq.hip, K16b); the specs have passed place_seq_spec_check (nhip_host_place.hip)
+struct PlaceSeq {     // plain data: travels in the kernels' parameter blocks
+  const unsigned long long *desc;  // n_scans x n_rings
+  const int32_t *bits;             // n_scans
+  const int32_t *ids;              // n_ids, ascending
+  uint16_t *plane;                 // the workspace's first part: single distances by scan id, (chunk scans + halo) x pitch_s
+  uint16_t *keys;                  // its second part: seq per (query scan of the chunk, candidate entry), chunk scans x pitch
+  int32_t *records;                // n_ids x top_k x 8
+  long long *stats;                // 8 words
+  uint32_t *status;
+  int32_t n_scans, n_ids, pitch_s, pitch, n_rings, top_k, min_separation, max_permille, flags, half_window, step;
+};
+// clears the stats, then plane, window and top-K kernels per chunk of `chunk_scans` >= 1 query scans (the workspace holds
+// that many rows of keys and that many plus 2 half_window step rows of the plane, or all scans' rows of both)
+int launch_place_seq_match(const PlaceSeq &P, int32_t chunk_scans, hipStream_t s);
+
 // loop-closure consistency (nhip_consistency.hip, K17); the spec has passed consistency_spec_check (nhip_host_consistency.hip)
 constexpr int32_t CONSISTENCY_MAX_RECORDS = 65536;  // W = ceil(M / 64) <= 1024 words: the live set fits the score kernel's LDS
 struct ConsistencyState {  // the first bytes of the workspace: what the step kernels keep between launches

@@ -1,6 +1,6 @@
-// nhip_host_place.hip -- the place-descriptor entry points of the C ABI (kernels: nhip_place.hip, K16): the spec's defaults and
-// its check, the tables, the workspace rule, the forms on the caller's buffers and stream, and the handle form with a host list
-// and host outputs.
+// nhip_host_place.hip -- the place-descriptor entry points of the C ABI (kernels: nhip_place.hip, K16, and nhip_place_seq.hip,
+// K16b): the specs' defaults and their checks, the tables, the workspace rules, the forms on the caller's buffers and stream,
+// and the handle forms with a host list and host outputs.
 #include "nhip_common.h"
 #include "nhip_host.h"
 
@@ -51,6 +51,59 @@ int place_match_run(const uint64_t *d_desc, const int32_t *d_bits, int32_t n_sca
                PLACE_QT, (long long)place_row_bytes(n_ids));
   if (rows > PLACE_MAX_CHUNK_ROWS) rows = PLACE_MAX_CHUNK_ROWS;
   return launch_place_match(P, (int32_t)rows, s);
+}
+
+// ---- place sequences (K16b) ----
+constexpr int32_t SEQ_MIN_CHUNK = 16;  // query scans a chunk holds at least (beside its halo)
+
+int place_seq_spec_check(const nhip_place_spec_t *s, const nhip_place_seq_spec_t *q, const char *who) {
+  int rc = place_spec_check(s, true, who);
+  if (rc) return rc;
+  NHIP_REQUIRE(q, "%s: null sequence spec", who);
+  NHIP_REQUIRE(q->half_window >= 0 && q->half_window <= 8, "%s: half_window %d outside 0..8", who, q->half_window);
+  NHIP_REQUIRE(q->step >= 1 && q->step <= 16, "%s: step %d outside 1..16", who, q->step);
+  NHIP_REQUIRE(s->min_separation >= 2 * q->half_window * q->step,
+               "%s: min_separation %d below 2 half_window step = %d: the two windows of a pair would touch", who, s->min_separation,
+               2 * q->half_window * q->step);
+  return NHIP_OK;
+}
+
+// the workspace of a chunk of S query scans: S + halo rows of the plane (all scans' rows without a halo when S covers them),
+// then S rows of keys
+struct SeqLayout {
+  int64_t row_s, row_i, halo_bytes, per_scan, full;
+  int32_t all;  // query scans when nothing is chunked: n_scans, at least 1
+};
+SeqLayout seq_layout(const nhip_place_seq_spec_t &q, int32_t n_scans, int32_t n_ids) {
+  SeqLayout L;
+  L.row_s = place_row_bytes(n_scans > 0 ? n_scans : 1), L.row_i = place_row_bytes(n_ids > 0 ? n_ids : 1);
+  L.halo_bytes = 2ll * q.half_window * q.step * L.row_s, L.per_scan = L.row_s + L.row_i;
+  L.all = n_scans > 0 ? n_scans : 1;
+  L.full = L.all * L.per_scan;
+  return L;
+}
+
+// the arguments have been checked
+int place_seq_run(const uint64_t *d_desc, const int32_t *d_bits, int32_t n_scans, const int32_t *d_ids, int32_t n_ids,
+                  const nhip_place_spec_t &spec, const nhip_place_seq_spec_t &seq, int32_t *d_records, int64_t *d_stats, void *d_ws,
+                  int64_t ws_bytes, hipStream_t s) {
+  const SeqLayout L = seq_layout(seq, n_scans, n_ids);
+  int64_t S = L.all, plane_rows = L.all;
+  if (ws_bytes < L.full) {
+    S = ws_bytes >= L.halo_bytes ? (ws_bytes - L.halo_bytes) / L.per_scan : 0;
+    NHIP_REQUIRE(S >= SEQ_MIN_CHUNK, "place_seq_match: a workspace of %lld bytes holds fewer than %d query scans (%lld bytes each) beside a halo of %lld bytes",
+                 (long long)ws_bytes, SEQ_MIN_CHUNK, (long long)L.per_scan, (long long)L.halo_bytes);
+    if (S > PLACE_MAX_CHUNK_ROWS / 2) S = PLACE_MAX_CHUNK_ROWS / 2;  // (a launch's grid: plane rows / PLACE_QT workgroups along y)
+    plane_rows = S + 2ll * seq.half_window * seq.step;
+  }
+  PlaceSeq P;
+  P.desc = reinterpret_cast<const unsigned long long *>(d_desc), P.bits = d_bits, P.ids = d_ids;
+  P.plane = static_cast<uint16_t *>(d_ws), P.keys = P.plane + plane_rows * (L.row_s / 2);
+  P.records = d_records, P.stats = reinterpret_cast<long long *>(d_stats), P.status = dev_status();
+  P.n_scans = n_scans, P.n_ids = n_ids, P.pitch_s = (int32_t)(L.row_s / 2), P.pitch = (int32_t)(L.row_i / 2);
+  P.n_rings = spec.n_rings, P.top_k = spec.top_k, P.min_separation = spec.min_separation, P.max_permille = spec.max_permille;
+  P.flags = spec.flags, P.half_window = seq.half_window, P.step = seq.step;
+  return launch_place_seq_match(P, (int32_t)S, s);
 }
 
 }  // namespace
@@ -149,6 +202,79 @@ int nhip_place_candidates(const nhip_scans_t *scans, const int32_t *ids, int32_t
   NHIP_TRY_HIP(hipMemcpy(stats, ds.p, 64, hipMemcpyDeviceToHost));
   if (desc && n) NHIP_TRY_HIP(hipMemcpy(desc, dd.p, 8 * R * (size_t)n, hipMemcpyDeviceToHost));
   if (bits && n) NHIP_TRY_HIP(hipMemcpy(bits, db.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
+  InFlight::done();  // (the downloads above synchronised the null stream)
+  return NHIP_OK;
+}
+
+int nhip_place_seq_spec_default(nhip_place_seq_spec_t *out) {
+  NHIP_REQUIRE(out, "place_seq_spec_default: null pointer");
+  *out = nhip_place_seq_spec_t{};
+  out->half_window = 2;
+  out->step = 1;
+  return NHIP_OK;
+}
+
+int64_t nhip_place_seq_workspace_bytes(const nhip_place_spec_t *spec, const nhip_place_seq_spec_t *seq, int32_t n_scans, int32_t n_ids) {
+  if (place_seq_spec_check(spec, seq, "place_seq_workspace_bytes")) return -1;
+  if (n_scans < 0 || n_ids < 0 || n_ids > PLACE_MAX_IDS) {
+    set_error("place_seq_workspace_bytes: n_scans %d must be >= 0, n_ids %d in 0..%d", n_scans, n_ids, PLACE_MAX_IDS);
+    return -1;
+  }
+  const SeqLayout L = seq_layout(*seq, n_scans, n_ids);
+  if (L.full <= NHIP_PLACE_WORKSPACE_MAX) return L.full;
+  int64_t S = NHIP_PLACE_WORKSPACE_MAX >= L.halo_bytes ? (NHIP_PLACE_WORKSPACE_MAX - L.halo_bytes) / L.per_scan : 0;
+  if (S < SEQ_MIN_CHUNK) S = SEQ_MIN_CHUNK;
+  const int64_t bytes = S * L.per_scan + L.halo_bytes;
+  return bytes < L.full ? bytes : L.full;
+}
+
+int nhip_place_seq_match_dev(const uint64_t *d_desc, const int32_t *d_bits, int32_t n_scans, const int32_t *d_ids, int32_t n_ids,
+                             const nhip_place_spec_t *spec, const nhip_place_seq_spec_t *seq, int32_t *d_records, int64_t *d_stats,
+                             void *d_workspace, int64_t workspace_bytes, void *stream) {
+  int rc = place_seq_spec_check(spec, seq, "place_seq_match_dev");
+  if (rc) return rc;
+  NHIP_REQUIRE(n_scans >= 0 && n_ids >= 0 && n_ids <= PLACE_MAX_IDS, "place_seq_match_dev: n_scans %d must be >= 0, n_ids %d in 0..%d",
+               n_scans, n_ids, PLACE_MAX_IDS);
+  if ((rc = require_device())) return rc;
+  NHIP_REQUIRE(d_stats && (n_ids == 0 || (d_ids && d_records && d_workspace && (n_scans == 0 || (d_desc && d_bits)))),
+               "place_seq_match_dev: null pointer");
+  NHIP_REQUIRE((reinterpret_cast<uintptr_t>(d_desc) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_stats) & 7) == 0 &&
+                   (reinterpret_cast<uintptr_t>(d_workspace) & 1) == 0,
+               "place_seq_match_dev: d_desc and d_stats must be 8-byte aligned, d_workspace 2-byte");
+  return place_seq_run(d_desc, d_bits, n_scans, d_ids, n_ids, *spec, *seq, d_records, d_stats, d_workspace, workspace_bytes,
+                       static_cast<hipStream_t>(stream));
+}
+
+int nhip_place_seq_candidates(const nhip_scans_t *scans, const int32_t *ids, int32_t n_ids, const nhip_place_spec_t *spec,
+                              const nhip_place_seq_spec_t *seq, int32_t *records, int64_t *stats) {
+  int rc = place_seq_spec_check(spec, seq, "place_seq_candidates");
+  if (rc || (rc = require_device())) return rc;
+  NHIP_REQUIRE(scans && stats && n_ids >= 0 && n_ids <= PLACE_MAX_IDS && (n_ids == 0 || (ids && records)), "place_seq_candidates: bad arguments");
+  const int32_t n = scans->n_scans;
+  for (int32_t b = 0; b < n_ids; b++) {
+    NHIP_REQUIRE(ids[b] >= 0 && ids[b] < n, "place_seq_candidates: ids[%d] = %d outside the %d scans", b, ids[b], n);
+    NHIP_REQUIRE(b == 0 || ids[b] > ids[b - 1], "place_seq_candidates: ids[%d] = %d after %d: the list must ascend strictly", b, ids[b], ids[b - 1]);
+  }
+  const size_t R = (size_t)spec->n_rings, K = (size_t)spec->top_k;
+  const int64_t ws_bytes = nhip_place_seq_workspace_bytes(spec, seq, n, n_ids);
+  DevBuf dd, db, di, dr, ds, dw;
+  if ((rc = dd.alloc(8 * R * (size_t)(n > 0 ? n : 1))) || (rc = db.alloc(4 * (size_t)(n > 0 ? n : 1))) ||
+      (rc = di.alloc(4 * (size_t)(n_ids > 0 ? n_ids : 1))) || (rc = dr.alloc(32 * K * (size_t)(n_ids > 0 ? n_ids : 1))) ||
+      (rc = ds.alloc(64)) || (rc = dw.alloc((size_t)ws_bytes)))
+    return rc;
+  InFlight inflight;
+  if (n_ids) NHIP_TRY_HIP(hipMemcpy(di.p, ids, 4 * (size_t)n_ids, hipMemcpyHostToDevice));
+  PlaceTables T;
+  T.n_rings = spec->n_rings;
+  place_tables(*spec, T.edge2, T.dir);
+  if ((rc = launch_place_describe(T, scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), n, dd.as<uint64_t>(),
+                                  db.as<int32_t>(), nullptr)))
+    return rc;
+  if ((rc = place_seq_run(dd.as<const uint64_t>(), db.as<const int32_t>(), n, di.as<const int32_t>(), n_ids, *spec, *seq,
+                          dr.as<int32_t>(), ds.as<int64_t>(), dw.p, ws_bytes, nullptr)))
+    return rc;
+  if (n_ids) NHIP_TRY_HIP(hipMemcpy(records, dr.p, 32 * K * (size_t)n_ids, hipMemcpyDeviceToHost));
+  NHIP_TRY_HIP(hipMemcpy(stats, ds.p, 64, hipMemcpyDeviceToHost));
   InFlight::done();  // (the downloads above synchronised the null stream)
   return NHIP_OK;
 }

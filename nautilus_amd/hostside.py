@@ -347,6 +347,85 @@ def place_candidates(xy, offsets, ids, spec=None):
     return rec, stats
 
 
+def place_sequence_candidates(xy, offsets, ids, spec=None, seq=None, descriptors=None):
+    """Loop-closure candidates by sequence in plain numpy on the host ("Place sequences"; the device form
+    is nhip_place_seq_candidates): (records int32 (n_ids, K, 8) = {j, shift, dist, bits_j, seq, sum, frames, direction}, eight
+    -1 where unfilled; stats int64 (8,)).  The window frames are scan ids: every scan is described, not only the list's.
+    descriptors: (D uint64 (n_scans, R), bits (n_scans,)) to use instead of describing xy.  Product code: a backend without
+    place_sequence_candidates() proposes its pairs with this (examples/slam_loop.py --lc-gate appearance --lc-sequence W)."""
+    from . import place
+    spec = place.default_spec() if spec is None else spec
+    seq = place.default_seq_spec() if seq is None else seq
+    R, K, W, step = int(spec.n_rings), int(spec.top_k), int(seq.half_window), int(seq.step)
+    if not (1 <= R <= 15 and 1 <= K <= 32 and 0 <= spec.max_permille <= 1000 and 0 <= W <= 8 and 1 <= step <= 16 and
+            spec.min_separation >= 2 * W * step):
+        raise ValueError("place_sequence_candidates: n_rings 1..15, top_k 1..32, max_permille 0..1000, half_window 0..8, "
+                         "step 1..16, min_separation >= 2 half_window step")
+    D, bits = place_descriptors(xy, offsets, spec) if descriptors is None else descriptors
+    D, bits = np.asarray(D, dtype=np.uint64).reshape(-1, R), np.asarray(bits, dtype=np.int64).reshape(-1)
+    n = len(bits)
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    if len(ids) and (ids[0] < 0 or ids[-1] >= n or (np.diff(ids) <= 0).any()):
+        raise ValueError("place_sequence_candidates: ids must ascend strictly inside the %d scans" % n)
+    M = len(ids)
+    rec, stats = np.full((M, K, 8), -1, dtype=np.int32), np.zeros(8, dtype=np.int64)
+    stats[0], stats[5] = M, int((bits[ids] == 0).sum())
+    if M == 0:
+        return rec, stats
+    # rotl64(D_b, s) for every scan and shift, once: (n, 64, R); a row of single distances when a window first asks for it
+    s = np.arange(1, 64, dtype=np.uint64)[None, :, None]
+    rot = np.concatenate([D[:, None, :], (D[:, None, :] << s) | (D[:, None, :] >> (np.uint64(64) - s))], axis=1)
+    rows = {}
+
+    def row(a):
+        if a not in rows:
+            d = np.bitwise_count(D[a][None, None, :] ^ rot).sum(axis=2).astype(np.int64)  # (n, 64)
+            shift = d.argmin(axis=1)  # (the first minimum: the smallest shift)
+            rows[a] = (d[np.arange(n), shift], shift)
+        return rows[a]
+
+    for a in range(M):
+        i = int(ids[a])
+        adm = (np.abs(ids - i) > spec.min_separation) & (bits[ids] > 0) & (bits[i] > 0)
+        if spec.flags & place.NHIP_PLACE_PAST_ONLY:
+            adm &= ids < i
+        b = np.nonzero(adm)[0]
+        stats[1] += len(b)
+        if len(b):
+            j = ids[b]
+            total, norm, frames = (np.zeros((2, len(b)), dtype=np.int64) for _ in range(3))
+            for d in range(-W, W + 1):
+                fa = i + d * step
+                if not (0 <= fa < n and bits[fa] > 0):
+                    continue
+                dist_a = row(fa)[0]
+                for g, sigma in enumerate((1, -1)):
+                    fb = j + sigma * d * step
+                    ok = (fb >= 0) & (fb < n)
+                    fb = np.where(ok, fb, 0)
+                    ok &= bits[fb] > 0
+                    total[g] += np.where(ok, dist_a[fb], 0)
+                    norm[g] += np.where(ok, bits[fa] + bits[fb], 0)
+                    frames[g] += ok
+            score = (total * (2 * W + 1)) // frames  # (frames >= 1: d = 0 always counts)
+            direction = (score[0] > score[1]).astype(np.int64)
+            at = np.arange(len(b))
+            score, total, norm, frames = score[direction, at], total[direction, at], norm[direction, at], frames[direction, at]
+            gate = 1000 * total <= int(spec.max_permille) * norm
+            stats[2] += int(gate.sum())
+            stats[6] += int((gate & (direction == 1)).sum())
+            stats[7] += int((gate & (frames < 2 * W + 1)).sum())
+            order = np.nonzero(gate)[0]
+            order = order[np.lexsort((j[order], score[order]))][:K]
+            dist_i, shift_i = row(i)
+            jo = j[order]
+            rec[a, :len(order)] = np.stack([jo, shift_i[jo], dist_i[jo], bits[jo], score[order], total[order], frames[order],
+                                            direction[order]], axis=1)
+            stats[3] += len(order)
+        stats[4] += not (rec[a, 0, 0] >= 0)
+    return rec, stats
+
+
 def _consistency_rows(rec, rows, tol):
     """Rows `rows` of the consistency matrix of the prepared records, as booleans (len(rows), M): the pair test of DESIGN.md
     section 3, "Loop-closure consistency", every operation a float64 operation of numpy, rounded on its own."""

@@ -239,6 +239,33 @@ class HipBackend:
         finally:
             st.close()
 
+    def place_sequence_candidates(self, xy, offsets, ids, spec=None, seq=None):
+        """Loop-closure candidates by sequence among the scans `ids` (ascending): the appearance match over a window of frames
+        around both scans of a pair (place.py: nhip_place_seq_candidates): (records int32 (n_ids, K, 8) = {j, shift, dist,
+        bits_j, seq, sum, frames, direction}, stats int64 (8,))."""
+        from . import csm, place
+        spec = place.default_spec() if spec is None else spec
+        seq = place.default_seq_spec() if seq is None else seq
+        # The scans the list names AND every window frame ids +- d step inside the scans go to the device: a frame that stayed
+        # behind would be a scan without bits.  The others keep their ids as empty scans.
+        off = np.asarray(offsets, dtype=np.int64)
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        n = len(off) - 1
+        if len(ids) and (ids.min() < 0 or ids.max() >= n):
+            raise ValueError("place_sequence_candidates: an id outside the %d scans" % n)
+        reach = np.arange(-int(seq.half_window), int(seq.half_window) + 1, dtype=np.int64) * int(seq.step)
+        frames = np.unique(ids.astype(np.int64)[:, None] + reach[None, :])
+        frames = frames[(frames >= 0) & (frames < n)]
+        lengths = np.zeros(n, dtype=np.int64)
+        lengths[frames] = np.diff(off)[frames]
+        xy = np.asarray(xy, dtype=np.float32).reshape(-1, 2)
+        xy = np.concatenate([xy[off[i]:off[i + 1]] for i in frames]) if len(frames) else xy[:0]
+        st = csm.ScanTable(xy, np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32))
+        try:
+            return place.sequence_candidates(st, ids, spec, seq)
+        finally:
+            st.close()
+
     def consistent_set(self, poses, src, tgt, rel, spec=None):
         """The mutually consistent set of the loop closures (src, tgt, rel) under the trajectory `poses` (consistency.py:
         nhip_consistency): (members int32 (M,) in pick order, -1 behind them; n_members; stats int64 (8,))."""
