@@ -57,7 +57,8 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         rank=0, world=1, device="cuda:0", backend=None, iterations=4, hitl=True, cell_bits=16, gate="scatter",
         min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False, normals="bag", lc_submap=0,
         linear_solver="host", lc_gate="geometric", lc_max_score=5000.0, map_output=None, grid_output=None, lc_verify=None,
-        lc_max_violation=None, lc_top_k=5, lc_consistency=False, lc_min_set=3, _lc_corrupt=None, lc_sequence=0, lc_sequence_step=1):
+        lc_max_violation=None, lc_top_k=5, lc_consistency=False, lc_min_set=3, _lc_corrupt=None, lc_sequence=0, lc_sequence_step=1,
+        lc_loss=None, lc_loss_scale=1.0):
     """min_scatter_score: LCCandidateFilter's threshold is 0.70 (lc_candidate_filter.cc:76); scans of the synthetic
     24 m x 16 m room score ~0.4, so callers on that world pass a lower one.
     hitl_device: the HITL constraint's points are selected and packed on the GPU (hitl.select, under the "path" clock) and
@@ -106,6 +107,13 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     ones become constraints -- none if the set has fewer than lc_min_set members.  A backend with consistent_set() does it on the
     device; any other is served by hostside.consistent_set.  The result reports lc_consistency, lc_consistent, lc_inconsistent
     (they sum to the unfiltered run's lc_accepted), lc_inconsistent_rel_err_m and consistency_s.  Not with world > 1.
+    lc_loss: None (or "none"), "huber", "soft-l1" or "cauchy" -- the robust loss of the loop-closure factors (DESIGN.md section 3,
+    "Robust loss"; PoseGraph.add_loop_closures(loss=...)) in the closure solve and in the HITL phase's growing-window solve, with
+    scale lc_loss_scale in units of the weighted residual: at the closures' weight 10, 1.0 is 0.1 m or 0.1 rad, two cells of the
+    matcher's lattice.  The filters in front of the solve are all-or-nothing; the loss weighs what they let through by its own
+    residual.  The result then also reports lc_loss, lc_loss_scale and, after the closure solve, lc_weights ([src, tgt, rho'] per
+    accepted record), lc_weight_min, lc_downweighted (records with rho' < 0.5), lc_downweighted_pairs and
+    lc_downweighted_rel_err_m.  Works with world > 1 (the solve is replicated).
     _lc_corrupt: TEST ONLY -- a callable (src, tgt, rel, good) -> rel that replaces the records' transforms before the consistency
     filter and the constraints (tests/test_consistency_loop_gpu.py displaces accepted records with it).
     With world > 1 (one process per GPU under torch.distributed): the window ICP solve is replicated -- its
@@ -150,6 +158,12 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         raise ValueError("run: lc_min_set %r must be >= 0" % (lc_min_set,))
     if lc_max_violation is not None and not 0 <= int(lc_max_violation) <= 1000:
         raise ValueError("run: lc_max_violation %r: permille, 0..1000" % (lc_max_violation,))
+    loss = None
+    if lc_loss not in (None, "none"):
+        from nautilus_amd.loss import Loss
+        if lc_loss not in ("huber", "soft-l1", "cauchy"):
+            raise ValueError("run: lc_loss %r (None, \"none\", \"huber\", \"soft-l1\" or \"cauchy\")" % (lc_loss,))
+        loss = Loss(lc_loss.replace("-", "_"), lc_loss_scale)  # (ValueError: a scale that is not finite or is <= 0)
     out = {"backend": backend.name, "n_scans": n_scans, "window": window, "residual": residual,
            "err_odometry_m": posegraph.trajectory_error(odom, bag.truth)}
     posegraph.clock_reset()
@@ -346,11 +360,22 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         lc = (src[good], tgt[good], rel[good])
         t0 = time.perf_counter()
         with posegraph.clocked("marshal"):
-            pg.add_loop_closures(*lc)
+            pg.add_loop_closures(*lc, loss=loss)
         poses, _ = pg.solve(iterations=2 * iterations, verbose=verbose, linear_solver=linear_solver)
         out["t_lc_solve_s"] = time.perf_counter() - t0
         pcg_phase("lc")
         out["err_lc_m"] = posegraph.trajectory_error(poses, bag.truth)
+        if loss is not None:
+            # what the loss made of every record at the solved poses (outside the stage clocks' t_*: a report, not a solve stage)
+            rho1 = pg.closure_weights()[:, 2]
+            down = np.zeros(len(good), dtype=bool)
+            down[np.nonzero(good)[0][rho1 < 0.5]] = True
+            out["lc_loss"], out["lc_loss_scale"] = lc_loss, float(lc_loss_scale)
+            out["lc_weights"] = [[int(s), int(t), float(w)] for s, t, w in zip(lc[0], lc[1], rho1)]
+            out["lc_weight_min"] = float(rho1.min()) if len(rho1) else None
+            out["lc_downweighted"] = int(down.sum())
+            out["lc_downweighted_pairs"] = np.stack([src[down], tgt[down]], axis=1).tolist()
+            out["lc_downweighted_rel_err_m"] = rms(down)
 
     # ---- HITL: the user marks the same wall twice; HitlCallback re-solves with the point-to-line blocks
     if hitl:
@@ -374,7 +399,7 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         pg, poses = posegraph.solve_growing_window(xy, nrm, off, poses.copy(), max(1, window - 1), window, iterations=iterations, kind=kind,
                                                    device=device, verbose=verbose, backend=backend, initial=poses,
                                                    hitl=[con] if con.n_a + con.n_b else [], loop_closures=lc, features=feats,
-                                                   linear_solver=linear_solver)
+                                                   linear_solver=linear_solver, lc_loss=loss)
         out["t_hitl_solve_s"] = time.perf_counter() - t0
         pcg_phase("hitl")
         out["err_hitl_m"] = posegraph.trajectory_error(poses, bag.truth)
@@ -475,6 +500,12 @@ if __name__ == "__main__":
                          "they form with the estimate; not with several ranks)")
     ap.add_argument("--lc-min-set", type=int, default=3, metavar="N",
                     help="with --lc-consistency: a consistent set of fewer members is not trusted and no loop closure is kept")
+    ap.add_argument("--lc-loss", choices=["none", "huber", "soft-l1", "cauchy"], default="none",
+                    help="robust loss of the loop-closure factors in the closure solve and the HITL phase's solve: every record is "
+                         "weighed by its own residual instead of entering at full weight")
+    ap.add_argument("--lc-loss-scale", type=float, default=1.0, metavar="A",
+                    help="with --lc-loss: the loss' scale in units of the weighted residual (at the closures' weight 10, 1.0 is "
+                         "0.1 m or 0.1 rad, two cells of the matcher's lattice)")
     ap.add_argument("--map-output", metavar="PATH", default=None,
                     help="vectorise the final poses' map on the GPU and write it there, one 'x1,y1,x2,y2' line per wall segment")
     ap.add_argument("--grid-output", metavar="STEM", default=None,
@@ -492,6 +523,8 @@ if __name__ == "__main__":
     if not (0 <= seq_w <= 8 and 1 <= seq_step <= 16 and 2 * seq_w * seq_step <= LC_MIN_SEPARATION):
         ap.error("--lc-sequence %d in 0..8, --lc-sequence-step %d in 1..16, twice their product at most %d"
                  % (seq_w, seq_step, LC_MIN_SEPARATION))
+    if a.lc_loss != "none" and not (math.isfinite(a.lc_loss_scale) and a.lc_loss_scale > 0):
+        ap.error("--lc-loss-scale %r: finite and > 0" % (a.lc_loss_scale,))
     rank, world, local = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), \
         int(os.environ.get("LOCAL_RANK", "0"))
     if "RANK" in os.environ:  # python -m torch.distributed.run --nproc-per-node N examples/slam_loop.py ...
@@ -509,7 +542,8 @@ if __name__ == "__main__":
               device="cuda:%d" % local, hitl_device=a.hitl_device, normals=a.normals, lc_submap=a.lc_submap,
               linear_solver=a.linear_solver, lc_gate=a.lc_gate, lc_max_score=a.lc_max_score, map_output=a.map_output,
               grid_output=a.grid_output, lc_verify=a.lc_verify, lc_max_violation=a.lc_max_violation, lc_top_k=a.lc_top_k,
-              lc_consistency=a.lc_consistency, lc_min_set=a.lc_min_set, lc_sequence=seq_w, lc_sequence_step=seq_step)
+              lc_consistency=a.lc_consistency, lc_min_set=a.lc_min_set, lc_sequence=seq_w, lc_sequence_step=seq_step,
+              lc_loss=None if a.lc_loss == "none" else a.lc_loss, lc_loss_scale=a.lc_loss_scale)
     res["world_size"] = world
     if rank == 0:
         print(json.dumps(res))

@@ -434,6 +434,37 @@ int nhip_resid_odometry_normal_eq_dev(const float *d_t_odom, const float *d_r_od
                                       double rotation_weight, const double *d_poses, int32_t n_poses, double *d_out,
                                       void *stream);
 
+/* The same factors under a ROBUST LOSS ("Robust loss"; kernel nhip_loss.hip).  With r and J as above,
+ * s = r0 r0 + r1 r1 + r2 r2 (products rounded, added in that order; the plain call's slot 27), a the scale in units of the
+ * weighted residual and b = a a (one rounded product):
+ *   kind          rho(s)                                   rho'(s)
+ *   NONE    (0)   s                                        1
+ *   HUBER   (1)   s <= b: s;  else 2 a sqrt(s) - b         s <= b: 1;  else a / sqrt(s)
+ *   SOFT_L1 (2)   2 b (sqrt(1 + s/b) - 1)                  1 / sqrt(1 + s/b)
+ *   CAUCHY  (3)   b log1p(s/b)                             1 / (1 + s/b)
+ * (Ceres' HuberLoss, SoftLOneLoss, CauchyLoss; the operation order is nhip_loss.hip's header and nautilus_amd/loss.py).
+ * All have rho'' <= 0, for which Ceres' Corrector scales by w = sqrt(rho') and nothing else: r~ = w r, J~ = w J, every entry
+ * one rounded product.  The row:
+ *   d_out[28*f + 0..20] = upper triangle of J~^T J~     d_out[28*f + 21..26] = J~^T r~     d_out[28*f + 27] = rho(s)
+ * with the sums in the plain call's order, so that half the sum of the slots 27 is Ceres' robust cost.  d_weights, unless
+ * NULL, receives {s, rho, rho', sqrt(rho')} per factor.  NONE gives the plain call's row bit for bit.  A factor whose pose
+ * index is out of range gives 28 + 4 zeros and is reported (kind 16); n_factors == 0 launches nothing.
+ * NHIP_ERR_ARG before anything is launched, with or without a device: a kind outside 0..3, flags != 0, with a kind other
+ * than NONE a scale that is not finite or is <= 0, a negative size, a null pointer other than d_weights. */
+#define NHIP_LOSS_NONE 0
+#define NHIP_LOSS_HUBER 1
+#define NHIP_LOSS_SOFT_L1 2
+#define NHIP_LOSS_CAUCHY 3
+typedef struct nhip_loss_spec {
+  int32_t kind;  /* NHIP_LOSS_* */
+  int32_t flags; /* 0 */
+  double scale;  /* a; unused by NONE */
+} nhip_loss_spec_t;
+int nhip_resid_odometry_robust_normal_eq_dev(const float *d_t_odom, const float *d_r_odom, const int32_t *d_pose_i,
+                                             const int32_t *d_pose_j, int32_t n_factors, double translation_weight,
+                                             double rotation_weight, const nhip_loss_spec_t *loss, const double *d_poses,
+                                             int32_t n_poses, double *d_out, double *d_weights, void *stream);
+
 /* ------------------------------------------------------------------ K11: the pose graph's linear system on the device
  * The Gauss-Newton system of a pose graph as a block-sparse matrix of 3 x 3 blocks in fp64 (DESIGN.md section 3,
  * "Block-sparse system").  n_blocks unknown blocks of 3; the sources are 28-double rows (every *_normal_eq_dev call writes

@@ -26,6 +26,7 @@ NHIP_OCC_ACCUMULATE = 1
 NHIP_PLACE_PAST_ONLY = 1
 NHIP_PLACE_WORKSPACE_MAX = 64 << 20
 NHIP_CONSISTENCY_STATE_BYTES = 8448
+NHIP_LOSS_NONE, NHIP_LOSS_HUBER, NHIP_LOSS_SOFT_L1, NHIP_LOSS_CAUCHY = 0, 1, 2, 3
 
 
 class NhipError(RuntimeError):
@@ -108,6 +109,10 @@ class ConsistencySpec(C.Structure):
                 ("r_max", C.c_double), ("max_steps", C.c_int32), ("flags", C.c_int32)]
 
 
+class LossSpec(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("scale", C.c_double)]
+
+
 class HitlSpec(C.Structure):
     _fields_ = [("line_a", C.c_float * 4), ("line_b", C.c_float * 4), ("line_width", C.c_double),
                 ("point_threshold", C.c_int32), ("reserved", C.c_int32)]
@@ -178,6 +183,8 @@ PROTOTYPES = {
     "nhip_resid_odometry_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f64, _f64, _vp, _i32, _vp, _vp,
                                           _vp, _vp]),
     "nhip_resid_odometry_normal_eq_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f64, _f64, _vp, _i32, _vp, _vp]),
+    "nhip_resid_odometry_robust_normal_eq_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f64, _f64, _P(LossSpec), _vp, _i32, _vp, _vp,
+                                                           _vp]),
     "nhip_bsr_assemble_dev": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "nhip_bsr_pcg_workspace_bytes": (_i64, [_i32, _i32]),
     "nhip_bsr_pcg_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64, _f64, _i32, _i32, _vp, _vp, _i64,

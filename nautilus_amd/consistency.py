@@ -2,7 +2,8 @@
 cycle they form with the odometry between their ends closes up to the drift that odometry can have gathered (pairwise
 consistency maximisation: Mangelson et al., ICRA 2018); all M^2 / 2 cycle checks make a bit matrix, and a large set of mutually
 consistent records is grown greedily on it.  One wrong record -- two corridors that look alike, score well and contradict no
-free space -- bends a whole trajectory: PoseGraph.add_loop_closures has no robust loss.
+free space -- bends a whole trajectory when it enters PoseGraph.add_loop_closures at full weight (a robust loss, loss.py, is
+that call's option and the last line of defence behind this filter).
 
 Build-defined (nhip_consistency_adjacency_dev / nhip_consistency_set_dev / nhip_consistency, kernel unit K17), in the place of the
 reference's human curation.  The spec -- fp64 + - x and comparisons in a fixed order, integers after them, so a numpy restatement

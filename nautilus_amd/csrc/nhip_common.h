@@ -509,6 +509,14 @@ int launch_resid_odometry_normal_eq(const float *d_t_odom, const float *d_r_odom
                                     const int32_t *d_pose_j, int32_t n_factors, double tw, double rw,
                                     const double *d_poses, int32_t n_poses, double *d_out, hipStream_t s);
 
+// the same under a robust loss (nhip_loss.hip): rows of the reweighted factors with rho(s) in slot 27, and unless d_weights
+// is null {s, rho, rho', sqrt(rho')} per factor; the spec has passed loss_spec_check (nhip_layout.hip), which needs no HIP
+int loss_spec_check(const nhip_loss_spec_t *loss, const char *who);
+int launch_resid_odometry_robust_normal_eq(const float *d_t_odom, const float *d_r_odom, const int32_t *d_pose_i,
+                                           const int32_t *d_pose_j, int32_t n_factors, double tw, double rw, int32_t kind,
+                                           double scale, const double *d_poses, int32_t n_poses, double *d_out,
+                                           double *d_weights, hipStream_t s);
+
 // the block-sparse linear system of the pose graph (nhip_linsolve.hip, K11): assembly from 28-double rows, and the
 // block-Jacobi preconditioned CG; the arguments have passed the checks of nhip_host_linsolve.hip
 struct PcgStats {  // what the PCG kernels keep in the workspace's first bytes; the host reads it between batches and at the end

@@ -163,6 +163,23 @@ int nhip_resid_odometry_normal_eq_dev(const float *d_t_odom, const float *d_r_od
                                          d_poses, n_poses, d_out, static_cast<hipStream_t>(stream));
 }
 
+int nhip_resid_odometry_robust_normal_eq_dev(const float *d_t_odom, const float *d_r_odom, const int32_t *d_pose_i,
+                                             const int32_t *d_pose_j, int32_t n_factors, double translation_weight,
+                                             double rotation_weight, const nhip_loss_spec_t *loss, const double *d_poses,
+                                             int32_t n_poses, double *d_out, double *d_weights, void *stream) {
+  // (the spec, the sizes and the pointers are an argument error with or without a device)
+  int rc = loss_spec_check(loss, "resid_odometry_robust_normal_eq_dev");
+  if (rc) return rc;
+  NHIP_REQUIRE(n_factors >= 0 && n_poses >= 0, "resid_odometry_robust_normal_eq_dev: negative size (n_factors %d, n_poses %d)",
+               n_factors, n_poses);
+  NHIP_REQUIRE(d_t_odom && d_r_odom && d_pose_i && d_pose_j && d_poses && d_out,
+               "resid_odometry_robust_normal_eq_dev: null pointer (only d_weights may be null)");
+  if ((rc = require_device())) return rc;
+  return launch_resid_odometry_robust_normal_eq(d_t_odom, d_r_odom, d_pose_i, d_pose_j, n_factors, translation_weight,
+                                                rotation_weight, loss->kind, loss->scale, d_poses, n_poses, d_out, d_weights,
+                                                static_cast<hipStream_t>(stream));
+}
+
 // ---------------------------------------------------------------- HITL point selection
 // the accepted ranges of include/nautilus_hip.h
 static int hitl_spec_check(const nhip_hitl_spec_t *s, const char *who) {

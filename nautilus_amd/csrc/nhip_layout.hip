@@ -1,5 +1,6 @@
 // nhip_layout.hip -- the tables of a grid spec and the arithmetic of the ABI that needs no device: slot layout, blur
-// taps, quantiser thresholds, rotation tables, records to transforms, sums to scores.  Nothing here calls HIP.
+// taps, quantiser thresholds, rotation tables, records to transforms, sums to scores, the robust loss' spec check.  Nothing
+// here calls HIP.
 #include <map>
 #include <mutex>
 
@@ -148,6 +149,17 @@ int make_tables(const nhip_grid_spec_t *spec, const GridLayout &L, GridTables *T
     make_thresholds(L.K, spec->floor_p, 65535, v.data());
   }
   T->thr16 = v.data();
+  return NHIP_OK;
+}
+
+// ---------------------------------------------------------------- the robust loss' spec (host)
+// the accepted ranges of include/nautilus_hip.h
+int loss_spec_check(const nhip_loss_spec_t *loss, const char *who) {
+  NHIP_REQUIRE(loss, "%s: null loss spec", who);
+  NHIP_REQUIRE(loss->kind >= NHIP_LOSS_NONE && loss->kind <= NHIP_LOSS_CAUCHY, "%s: loss kind %d outside 0..3", who, loss->kind);
+  NHIP_REQUIRE(loss->flags == 0, "%s: loss flags %d: none is defined", who, loss->flags);
+  NHIP_REQUIRE(loss->kind == NHIP_LOSS_NONE || (std::isfinite(loss->scale) && loss->scale > 0.0),
+               "%s: loss scale %g must be finite and > 0", who, loss->scale);
   return NHIP_OK;
 }
 

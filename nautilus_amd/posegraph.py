@@ -189,10 +189,16 @@ class HipBackend:
                                                               d_line_poses.shape[0], d_out.data_ptr(), sp))
         return d_out
 
-    def odometry_normal_eq_dev(self, factors, d_poses):
+    def odometry_normal_eq_dev(self, factors, d_poses, d_weights=None, loss=None):
         """The normal equations of OdometryFactors at the (n, 3) float64 device tensor d_poses: (F, 28) float64 on the
-        device over [pose_i | pose_j] (nhip_resid_odometry_normal_eq_dev).  The factors' arrays go up once."""
+        device over [pose_i | pose_j] (nhip_resid_odometry_normal_eq_dev).  The factors' arrays go up once.
+        Factors that carry a loss (factors.loss, or `loss` in its place) go through nhip_resid_odometry_robust_normal_eq_dev:
+        the rows of the reweighted factors, rho in slot 27, and {s, rho, rho', sqrt(rho')} per factor into the (F, 4) float64
+        device tensor d_weights if one is given.  Without a loss the call is the plain one."""
         torch, fac = self.torch, factors
+        loss = loss if loss is not None else getattr(fac, "loss", None)
+        if d_weights is not None and loss is None:
+            raise ValueError("odometry_normal_eq_dev: d_weights needs factors with a loss")
         d_out = torch.empty((fac.n, 28), dtype=torch.float64, device=self.dev)
         if fac.n == 0:
             return d_out
@@ -200,6 +206,13 @@ class HipBackend:
             t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
             fac._dev = (self.dev, t(fac.t_odom), t(fac.r_odom), t(fac.pose_i), t(fac.pose_j))
         _, d_t, d_r, d_i, d_j = fac._dev
+        if loss is not None:
+            spec = loss.spec()
+            check(self.lib.nhip_resid_odometry_robust_normal_eq_dev(
+                d_t.data_ptr(), d_r.data_ptr(), d_i.data_ptr(), d_j.data_ptr(), fac.n, fac.tw, fac.rw, C.byref(spec),
+                d_poses.data_ptr(), d_poses.shape[0], d_out.data_ptr(), None if d_weights is None else d_weights.data_ptr(),
+                C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)))
+            return d_out
         check(self.lib.nhip_resid_odometry_normal_eq_dev(d_t.data_ptr(), d_r.data_ptr(), d_i.data_ptr(), d_j.data_ptr(), fac.n,
                                                          fac.tw, fac.rw, d_poses.data_ptr(), d_poses.shape[0], d_out.data_ptr(),
                                                          C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)))
@@ -441,9 +454,12 @@ class _FeatureIcp:
 
 
 class OdometryFactors:
-    """Batched OdometryResidual blocks: r = (w_t (T_i + T_odom - T_j), w_r wrap(th_i + R_odom - th_j))."""
+    """Batched OdometryResidual blocks: r = (w_t (T_i + T_odom - T_j), w_r wrap(th_i + R_odom - th_j)).
+    loss: None, or the loss.Loss every factor is reweighted by ("Robust loss"); evaluate() returns the
+    plain r and J either way, the linear paths apply the loss."""
 
-    def __init__(self, pose_i, pose_j, t_odom, r_odom, tw=1.0, rw=1.0):
+    def __init__(self, pose_i, pose_j, t_odom, r_odom, tw=1.0, rw=1.0, loss=None):
+        self.loss = loss
         self.n = len(pose_i)
         self.pose_i = np.ascontiguousarray(pose_i, dtype=np.int32)
         self.pose_j = np.ascontiguousarray(pose_j, dtype=np.int32)
@@ -465,7 +481,7 @@ def odometry_factors_from_poses(odom, **kw):
     return OdometryFactors(np.arange(n - 1), np.arange(1, n), d[:, :2], d[:, 2], **kw)
 
 
-def loop_closure_factors(poses, pairs_src, pairs_tgt, rel, **kw):
+def loop_closure_factors(poses, pairs_src, pairs_tgt, rel, loss=None, **kw):
     """One odometry-style constraint per accepted loop closure: the matcher says where scan src sits
     in scan tgt's frame; expressed in the functor's world-frame convention around the current estimate
     of the TARGET pose: T_src - T_tgt = R(th_tgt) t_rel, th_src - th_tgt = th_rel."""
@@ -475,7 +491,7 @@ def loop_closure_factors(poses, pairs_src, pairs_tgt, rel, **kw):
         t_odom.append(pred[:2] - poses[t][:2])
         r_odom.append(r[2])
     return OdometryFactors(np.asarray(pairs_tgt), np.asarray(pairs_src), np.asarray(t_odom).reshape(-1, 2),
-                           np.asarray(r_odom), **kw)
+                           np.asarray(r_odom), loss=loss, **kw)
 
 
 class HitlConstraint:
@@ -560,8 +576,9 @@ class _DeviceLinearStep:
 
 class PoseGraph:
     def __init__(self, xy, normals, offsets, odom, window=10, kind=_lib.NHIP_LIDAR_POINT, outlier_threshold=0.25,
-                 odom_weights=(1.0, 1.0), device="cuda:0", initial=None, backend=None, features=None):
-        """features: None -- every point of scan i against scan j, evaluated as `kind`; or the pair of packed clouds
+                 odom_weights=(1.0, 1.0), device="cuda:0", initial=None, backend=None, features=None, odom_loss=None):
+        """odom_loss: None, or the loss.Loss of the odometry chain's factors (as add_loop_closures' for the closures).
+        features: None -- every point of scan i against scan j, evaluated as `kind`; or the pair of packed clouds
         ((xy_p, nrm_p, off_p), (xy_e, nrm_e, off_e)) of HipBackend.features(): the reference's FEATURE mode, planar points as
         LIDARNormalResidual blocks and edge points as LIDARPointResidual blocks (xy, normals, offsets and kind are then unused)."""
         self.n = len(odom)
@@ -574,7 +591,7 @@ class PoseGraph:
                 self.icp = self.backend.icp(xy, normals, offsets, bs, bt, outlier_threshold)
             else:
                 self.icp = _FeatureIcp(self.backend, features, bs, bt, outlier_threshold)
-        self.odo = odometry_factors_from_poses(odom, tw=odom_weights[0], rw=odom_weights[1])
+        self.odo = odometry_factors_from_poses(odom, tw=odom_weights[0], rw=odom_weights[1], loss=odom_loss)
         self.lc = None
         self.hitl = []
         self.linear_stats = {k: 0 for k in LINEAR_STATS}  # of this graph's solve(linear_solver="device") calls
@@ -583,8 +600,33 @@ class PoseGraph:
         # odometry factors always come from `odom`; the estimate may start elsewhere (previous window pass)
         self.poses = np.array(odom if initial is None else initial, dtype=np.float64)
 
-    def add_loop_closures(self, pairs_src, pairs_tgt, rel, weights=(10.0, 10.0)):
-        self.lc = loop_closure_factors(self.poses, pairs_src, pairs_tgt, rel, tw=weights[0], rw=weights[1])
+    def add_loop_closures(self, pairs_src, pairs_tgt, rel, weights=(10.0, 10.0), loss=None):
+        """One odometry-style factor per record (loop_closure_factors), weighted `weights`.  loss: None -- every record
+        enters at full weight -- or a loss.Loss: each solve reweights every record by sqrt(rho'(s)) of its own weighted
+        squared residual s at the poses it evaluates, and the cost becomes Ceres' robust cost (DESIGN.md section 3,
+        "Robust loss"); closure_weights() reports the weights."""
+        self.lc = loop_closure_factors(self.poses, pairs_src, pairs_tgt, rel, loss=loss, tw=weights[0], rw=weights[1])
+
+    def closure_weights(self, poses=None):
+        """(F, 4) float64 {s, rho, rho', sqrt(rho')} of the loop-closure factors at `poses` (default: the current estimate).
+        On a backend with odometry_normal_eq_dev they are the kernel's weights output; on any other, loss.Loss' on the
+        backend's residuals.  Without a loss: s, s, 1, 1."""
+        from .loss import Loss
+        if self.lc is None or self.lc.n == 0:
+            return np.zeros((0, 4))
+        poses = np.ascontiguousarray(self.poses if poses is None else poses, dtype=np.float64).reshape(-1, 3)
+        loss = self.lc.loss if self.lc.loss is not None else Loss("none")
+        be = self.backend
+        if hasattr(be, "odometry_normal_eq_dev"):
+            with clocked("path"):
+                d_w = be.torch.empty((self.lc.n, 4), dtype=be.torch.float64, device=be.dev)
+                be.odometry_normal_eq_dev(self.lc, be.torch.from_numpy(poses).to(be.dev), d_weights=d_w, loss=loss)
+                out = d_w.cpu().numpy()
+                check(be.lib.nhip_dev_status(C.c_void_p(be.torch.cuda.current_stream(be.dev).cuda_stream), None))
+            return out
+        with clocked("path"):
+            r, _, _ = self.lc.evaluate(be, poses)
+        return loss.weights(r)
 
     def add_hitl(self, constraint):
         """A HitlConstraint (points on the host, evaluated point by point through backend.point_to_line) or a
@@ -628,12 +670,15 @@ class PoseGraph:
             with clocked("path"):
                 r, ji, jj = fac.evaluate(self.backend, poses)
             J = np.concatenate([ji, jj], axis=2)  # (F, 3, 6)
+            rho = None
+            if fac.loss is not None:  # (the reweighted factor: r~ = w r, J~ = w J, its cost rho / 2)
+                r, J, rho = fac.loss.rows(r, J)
             Hf = np.einsum("fki,fkj->fij", J, J)
             gf = np.einsum("fki,fk->fi", J, r)
             idf = np.concatenate([3 * fac.pose_i[:, None] + np.arange(3), 3 * fac.pose_j[:, None] + np.arange(3)], axis=1)
             coo.append(_coo_blocks(idf, Hf))
             np.add.at(g, idf.ravel(), gf.ravel())
-            cost += 0.5 * float((r * r).sum())
+            cost += 0.5 * float((r * r).sum() if rho is None else rho.sum())
         for c, con in enumerate(self.hitl):
             if hasattr(con, "d_points"):
                 # a DeviceHitlConstraint: 28 doubles per block from the device, over [the block's pose | chosen_line_pose c]
@@ -671,6 +716,8 @@ class PoseGraph:
         problem with the pose just before the earlier of the two held constant instead of pose 0;
         returns the top-left 2 x 2 (translation) of each 3 x 3 block, float32 like the reference
         (dtype=np.float64: the blocks before that cast).
+        With a robust loss on the odometry or loop-closure factors, J is the reweighted J~ = sqrt(rho') J at the current
+        estimate, as ceres::Covariance sees it: both linear solvers go through _assemble / _evaluate_device.
         linear_solver "host": J^T J comes from the backend's per-block normal equations; the sparse solves are host
         work, one factorisation per gauge.  "device": the system is evaluated and assembled on the GPU as for
         solve(linear_solver="device") (the same backend and constraints are needed: TypeError otherwise) and the wanted
@@ -838,12 +885,12 @@ class PoseGraph:
 def solve_growing_window(xy, normals, offsets, odom, window_min=1, window_max=10, iterations=4,
                          kind=_lib.NHIP_LIDAR_POINT, outlier_threshold=0.25, odom_weights=(1.0, 1.0),
                          device="cuda:0", verbose=False, backend=None, initial=None, hitl=(), loop_closures=None, features=None,
-                         linear_solver="host"):
+                         linear_solver="host", lc_loss=None):
     """Solver::OptimizeOverGrowingWindow (solver.cc:339-355): for every window size from
     lidar_constraint_amount_min to _max the problem is rebuilt -- odometry factors, HITL residuals
     (AddHITLResiduals) plus fresh correspondences for all (i, j) blocks of the window, searched at the current
-    estimate -- and solved.  features: as PoseGraph's (FEATURE mode); linear_solver: as PoseGraph.solve's.  Returns (PoseGraph of the last
-    pass, poses)."""
+    estimate -- and solved.  features: as PoseGraph's (FEATURE mode); linear_solver: as PoseGraph.solve's; lc_loss: the loss.Loss
+    add_loop_closures gets in every pass (None: none).  Returns (PoseGraph of the last pass, poses)."""
     poses = np.array(odom if initial is None else initial, dtype=np.float64)
     backend = backend if backend is not None else HipBackend(device)
     if features is None and hasattr(backend, "reserve_icp"):  # (feature clouds: a few points per scan, nothing to reserve)
@@ -856,7 +903,7 @@ def solve_growing_window(xy, normals, offsets, odom, window_min=1, window_max=10
         for con in hitl:
             pg.add_hitl(con)
         if loop_closures is not None:
-            pg.add_loop_closures(*loop_closures)
+            pg.add_loop_closures(*loop_closures, loss=lc_loss)
         poses, hist = pg.solve(iterations=iterations, verbose=verbose, linear_solver=linear_solver)
         if verbose:
             print("window %d: cost %.6g -> %.6g" % (w, hist[0], hist[-1]))
