@@ -366,10 +366,15 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : BNB_THREADS, SPLIT ? SPL
     if (threadIdx.x == 0) P.keys[pair] = fkey;
     return;
   }
+  // the terms of (cos, sin) of all of this wave's rotations, lane-wise: their loads fly under the staging below
+  const RotationTerms terms = rotation_terms_of_wave<WAVES>(P, pair, wave, lane);
   if (POOL_LDS) {  // the target's pooled table -> LDS
     const uint4 *gp = reinterpret_cast<const uint4 *>(grid + P.grid_bytes + P.skip_bytes);
     uint4 *sp = reinterpret_cast<uint4 *>(s_pool);
-    // (four loads in flight per thread: 35 KB are 4.4 rounds of 512 threads, and a round trip each was 10 % of the pair)
+    // (four loads per thread and round: 35 KB are 4.4 rounds of 512 threads, and a round trip each was 10 % of the pair.
+    //  As compiled each load is sunk into the guard of its write and awaited there; holding all four in flight through an
+    //  opaque copy before the first write was measured and bought nothing -- the other workgroup of the CU computes
+    //  meanwhile -- profiles/r15_bounds_round_trips.txt.)
     const int32_t n16 = (int32_t)(P.pool_bytes / 16);
     for (int32_t i = threadIdx.x; i < n16; i += 4 * THREADS) {
       uint4 v[4];
@@ -381,17 +386,22 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : BNB_THREADS, SPLIT ? SPL
     }
   }
   const __amdgpu_buffer_rsrc_t prs = uniform_rsrc(grid + P.grid_bytes + P.skip_bytes, P.pool_bytes);
+  float cfs, sfs;  // lane i: the wave's i-th rotation
+  rotation_of(terms, &cfs, &sfs);
   __syncthreads();
 
   // (1) bounds of every block of every rotation this wave owns; the wave's own best bound
   const uint32_t scale = CB == 1 ? 1u : 257u;
   unsigned long long wbest = 0ull;  // (U << 32) | (k << 8 | slot)
-  for (int32_t k = wave; k < P.n_theta; k += WAVES) {
-    float cf, sf;
-    rotation_k(P, pair, k, &cf, &sf);
+  PointSlots slots;  // chunks 0 and 1 of the scan: primed here, loaded again by every rotation's last turn
+  prime_slots(pts, wave < P.n_theta ? n_pts : 0, lane, slots);  // (a wave without a rotation loads nothing)
+  int32_t mine = 0;  // the wave's rotations so far: the lane that holds the next one's (cos, sin)
+  for (int32_t k = wave; k < P.n_theta; k += WAVES, mine++) {
+    const float cf = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cfs), mine));
+    const float sf = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sfs), mine));
     uint32_t umax = 0u;
     uint32_t tot[2];
-    coarse_rotation<POOL_LDS>(P, s_pool, prs, pts, n_pts, cf, sf, cx, cy, lane, s_list + wave * LIST_ENTRIES, tot);
+    coarse_rotation<POOL_LDS>(P, s_pool, prs, pts, n_pts, slots, cf, sf, cx, cy, lane, s_list + wave * LIST_ENTRIES, tot);
     if (lane < 128 - NB * NB) s_U[k * 128 + NB * NB + lane] = 0u;  // (the row's unused tail)
 #pragma unroll
     for (int i = 0; i < 2; i++) {

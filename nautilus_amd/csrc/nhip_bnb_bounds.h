@@ -1,8 +1,9 @@
 // nhip_bnb_bounds.h -- the three upper bounds of the branch-and-bound matcher's kernels (nhip_bnb.hip).
 //
 // Owns: coarse_rotation -- the bounds of all 11 x 11 blocks of one rotation from the pooled table, gathered per RUN of
-// points that share a pooled entry (the run lists: LIST_ENTRIES words of LDS per wave) -- with slot_block, the layout its
-// totals come out in; sub_bounds -- the four 4 x 4 sub-block bounds of one block, from the points; strip_bounds_c -- the
+// points that share a pooled entry (the run lists: LIST_ENTRIES words of LDS per wave) -- with PointSlots / prime_slots, its
+// point prefetch's registers, which the caller keeps from rotation to rotation, and slot_block, the layout its totals come
+// out in; sub_bounds -- the four 4 x 4 sub-block bounds of one block, from the points; strip_bounds_c -- the
 // same for a strip of up to three blocks, from the origins a wave holds (CellList) or their runs by level-2 entry (RunList).
 // Assumes: the pooled tables behind the stored image as the table build leaves them (nhip_grid_blur.hip,
 // nhip_grid_tables.hip: zero rows below the pooled image, a pitch that is a multiple of 16, offsets below
@@ -33,10 +34,25 @@ namespace {
 // wave reduces early when a pass would take some lane past that, otherwise once per rotation.
 constexpr uint32_t LANE_WEIGHT = 64u;
 
+// The two slots of coarse_rotation's point prefetch (see there).  A wave primes them once, before its first rotation; every
+// rotation leaves them holding -- or awaiting -- chunks 0 and 1 again, which are the next rotation's first.
+struct PointSlots {
+  float2 q0, q1;
+};
+__device__ __forceinline__ void prime_slots(const float2 *pts, int32_t n_pts, int lane, PointSlots &S) {
+  S.q0 = S.q1 = make_float2(0.f, 0.f);
+  if (n_pts > 0) {  // (an empty scan loads nothing)
+    const int32_t last = n_pts - 1;
+    S.q0 = pts[min(lane, last)];
+    __builtin_amdgcn_sched_barrier(0);
+    S.q1 = pts[min(64 + lane, last)];
+  }
+}
+
 template <bool POOL_LDS>
 __device__ __forceinline__ void coarse_rotation(const BnbParams &P, const uint8_t *pool, __amdgpu_buffer_rsrc_t prs,
-                                                const float2 *pts, int32_t n_pts, float cf, float sf, int32_t cx,
-                                                int32_t cy, int lane, uint32_t *list, uint32_t (&tot)[2]) {
+                                                const float2 *pts, int32_t n_pts, PointSlots &S, float cf, float sf,
+                                                int32_t cx, int32_t cy, int lane, uint32_t *list, uint32_t (&tot)[2]) {
   const int32_t DP = P.pool_pitch;
   const uint32_t zero_a = (uint32_t)(((P.rows + BNB_B - 1) / BNB_B) * DP);  // NB + 1 rows of zeros below the pooled image
   tot[0] = tot[1] = 0u;
@@ -56,9 +72,12 @@ __device__ __forceinline__ void coarse_rotation(const BnbParams &P, const uint8_
   auto gather = [&](uint32_t a, uint32_t cnt) {
     const uint32_t se = __umul24(a & 3u, 0x10001u) + 0x0c020c00u, so = se + 0x00010001u;
     const uint32_t *q = reinterpret_cast<const uint32_t *>(pool + (a & ~3u));
-#pragma unroll
-    for (int y = 0; y < NB; y++) {
-      uint32_t w0, w1, w2, w3;
+    auto add_row = [&](int y, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
+      E[y][0] += __umul24(__builtin_amdgcn_perm(w1, w0, se), cnt); O[y][0] += __umul24(__builtin_amdgcn_perm(w1, w0, so), cnt);
+      E[y][1] += __umul24(__builtin_amdgcn_perm(w2, w1, se), cnt); O[y][1] += __umul24(__builtin_amdgcn_perm(w2, w1, so), cnt);
+      E[y][2] += __umul24(__builtin_amdgcn_perm(w3, w2, se), cnt); O[y][2] = mad24(__builtin_amdgcn_perm(w3, w2, so), cnt, O[y][2]);
+    };
+    auto load_row = [&](int y, uint32_t &w0, uint32_t &w1, uint32_t &w2, uint32_t &w3) {
       if (POOL_LDS) {
         const uint32_t *row = q + (y * DP) / 4;  // DP is a multiple of 16
         w0 = row[0]; w1 = row[1]; w2 = row[2]; w3 = row[3];
@@ -66,9 +85,21 @@ __device__ __forceinline__ void coarse_rotation(const BnbParams &P, const uint8_
         const u32x4 r4 = __builtin_amdgcn_raw_buffer_load_b128(prs, (int)((a & ~3u) + (uint32_t)(y * DP)), 0, 0);
         w0 = r4.x; w1 = r4.y; w2 = r4.z; w3 = r4.w;
       }
-      E[y][0] += __umul24(__builtin_amdgcn_perm(w1, w0, se), cnt); O[y][0] += __umul24(__builtin_amdgcn_perm(w1, w0, so), cnt);
-      E[y][1] += __umul24(__builtin_amdgcn_perm(w2, w1, se), cnt); O[y][1] += __umul24(__builtin_amdgcn_perm(w2, w1, so), cnt);
-      E[y][2] += __umul24(__builtin_amdgcn_perm(w3, w2, se), cnt); O[y][2] = mad24(__builtin_amdgcn_perm(w3, w2, so), cnt, O[y][2]);
+    };
+    // One row ahead: row y + 1's four dwords are in flight while row y is added, so that the wait before a row's adds
+    // leaves the next row's reads outstanding -- an LDS round trip per row, eleven per pass, was fully exposed (the
+    // scheduler issued a row's reads only after the adds of the row before; the global pool's buffer loads each behind a
+    // full wait: profiles/r15_bounds_round_trips_isa.txt).  Four more registers; every by-rotation instantiation stays
+    // below 124.  The barriers keep the order the source has; the reads of the last row are awaited alone.
+    uint32_t n0, n1, n2, n3;
+    load_row(0, n0, n1, n2, n3);
+#pragma unroll
+    for (int y = 0; y < NB; y++) {
+      const uint32_t w0 = n0, w1 = n1, w2 = n2, w3 = n3;
+      if (y + 1 < NB) load_row(y + 1, n0, n1, n2, n3);
+      __builtin_amdgcn_sched_barrier(0);
+      add_row(y, w0, w1, w2, w3);
+      __builtin_amdgcn_sched_barrier(0);
     }
   };
   // the transposing reduction of the 128 packed sums (see the layout above); clears the accumulators
@@ -188,7 +219,7 @@ __device__ __forceinline__ void coarse_rotation(const BnbParams &P, const uint8_
   //    registers); lanes past the scan's end are dropped by `live` as before;
   //  - both slots load on every turn and only the second BODY is predicated (a break between the bodies leaves a path
   //    into the header on which the first slot's load is the youngest);
-  //  - the priming loads are issued first slot first.
+  //  - the priming loads (prime_slots) are issued first slot first.
   // Nothing else of the loop uses the vector-memory counter out of order: the gather's loads (global form) are awaited
   // inside their pass, and the run list is LDS.
   auto offsets = [&](float2 pt, int32_t c) {  // pooled offsets of chunk c from its points
@@ -201,23 +232,26 @@ __device__ __forceinline__ void coarse_rotation(const BnbParams &P, const uint8_
     }
     return a;
   };
+  // The slots outlive the rotation (S, primed by the caller before the wave's first): the last turn, whose loads would lie
+  // past the scan's end, loads chunks 0 and 1 again -- the same points for every rotation, with the priming loads' clamp
+  // for scans shorter than 128 points -- so the next rotation's first chunks arrive behind this one's drain turn and
+  // reduction, and the drain turn awaits no load.  (Before: the drain turn waited for two clamped loads nobody used, and
+  // every rotation began with two priming loads and nothing to hide them behind.)
   constexpr int PD = 2;
   if (n_pts > 0) {  // (an empty scan loads nothing)
     const int32_t last = n_pts - 1;
-    float2 q0 = pts[min(lane, last)];
-    __builtin_amdgcn_sched_barrier(0);
-    float2 q1 = pts[min(64 + lane, last)];
     for (int32_t c = 0; c < n_pts; c += 64 * PD) {
+      const int32_t cn = c + 64 * PD < n_pts ? c + 64 * PD : 0;  // (wave-uniform)
       {
-        float2 pt = q0;
+        float2 pt = S.q0;
         asm volatile("" : "+v"(pt.x), "+v"(pt.y));
-        q0 = pts[min(c + 64 * PD + lane, last)];
+        S.q0 = pts[min(cn + lane, last)];
         feed(offsets(pt, c), c, true);
       }
       {
-        float2 pt = q1;
+        float2 pt = S.q1;
         asm volatile("" : "+v"(pt.x), "+v"(pt.y));
-        q1 = pts[min(c + 64 * PD + 64 + lane, last)];
+        S.q1 = pts[min(cn + 64 + lane, last)];
         if (c + 64 < n_pts) feed(offsets(pt, c + 64), c + 64, true);
       }
     }

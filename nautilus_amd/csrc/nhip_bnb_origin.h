@@ -2,7 +2,8 @@
 // a point's lookup window starts under one rotation, and how a wave keeps a whole rotation's origins.
 //
 // Owns: window_origin (the spec's cell from single-precision arithmetic, with its double-precision rare path; LEAN: the
-// form of the bounds phase, exact to the pooled entry), the rotation's (cos, sin) (rotation_k), patch_origin, the packed
+// form of the bounds phase, exact to the pooled entry), the rotation's (cos, sin) (rotation_k = rotation_terms + rotation_of;
+// rotation_terms_of_wave: all of a wave's rotations at once, one per lane), patch_origin, the packed
 // per-wave list of a rotation's origins in LDS (cache_origins, origin_of, org_row / org_col / org_cnt), the shorter list
 // of their runs by level-2 entry (run_row2 / run_col2 / run_cnt), and the wave-uniform buffer descriptor every gather
 // here reads through (uniform_rsrc, the u32xN load types, idx_guard).
@@ -132,13 +133,45 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void *base,
 
 __device__ __forceinline__ uint32_t idx_guard(bool live, uint32_t v) { return live ? v : 0u; }
 
-__device__ __forceinline__ void rotation_k(const BnbParams &P, int32_t pair, int32_t k, float *cf, float *sf) {
-  // R(theta0) * R(delta_k), composed in double with individually rounded ops (as csm_correlate_kernel)
-  const double c0 = P.rot0_cs[2 * pair], s0 = P.rot0_cs[2 * pair + 1];
+// R(theta0) * R(delta_k), composed in double with individually rounded ops (as csm_correlate_kernel): the four terms
+// from memory, and (cos, sin) from them.
+struct RotationTerms {
+  double c0, s0, cd, sd;
+};
+__device__ __forceinline__ RotationTerms rotation_terms(const BnbParams &P, int32_t pair, int32_t k) {
+  RotationTerms T;
+  T.c0 = P.rot0_cs[2 * pair];
+  T.s0 = P.rot0_cs[2 * pair + 1];
   const int32_t kd = k + (P.pair_kbase ? P.pair_kbase[pair] : 0);  // (the pair's rotation k is entry kbase + k of the table)
-  const double cd = P.delta_cs[2 * kd], sd = P.delta_cs[2 * kd + 1];
-  *cf = __double2float_rn(__dsub_rn(__dmul_rn(c0, cd), __dmul_rn(s0, sd)));
-  *sf = __double2float_rn(__dadd_rn(__dmul_rn(s0, cd), __dmul_rn(c0, sd)));
+  T.cd = P.delta_cs[2 * kd];
+  T.sd = P.delta_cs[2 * kd + 1];
+  return T;
+}
+__device__ __forceinline__ void rotation_of(const RotationTerms &T, float *cf, float *sf) {
+  *cf = __double2float_rn(__dsub_rn(__dmul_rn(T.c0, T.cd), __dmul_rn(T.s0, T.sd)));
+  *sf = __double2float_rn(__dadd_rn(__dmul_rn(T.s0, T.cd), __dmul_rn(T.c0, T.sd)));
+}
+__device__ __forceinline__ void rotation_k(const BnbParams &P, int32_t pair, int32_t k, float *cf, float *sf) {
+  rotation_of(rotation_terms(P, pair, k), cf, sf);
+}
+
+// The rotations of one wave of the bounds loop (csm_bnb_kernel: k = wave, wave + WAVES, ...), all at once: lane i returns
+// the terms of the wave's i-th rotation, k = wave + WAVES * i; the caller composes them (rotation_of) and its loop takes
+// (cos, sin) out of the two registers by v_readlane.  rotation_k at the head of every rotation was three dependent round trips with nothing to hide behind
+// (rot0_cs[pair], pair_kbase[pair], delta_cs[kd]; profiles/r15_bounds_round_trips_isa.txt); here they are paid once per
+// wave, in parallel over its rotations, and the caller puts the staging of the pooled table between the loads (this
+// function) and rotation_of.  The lanes past the wave's last rotation read that rotation's entry again: no address is
+// formed that the loop would not read itself, under a pair_kbase too.  A wave without a rotation (wave >= n_theta) loads
+// nothing.  The values are rotation_k's, bit for bit: the same two functions compute them.
+template <int WAVES>
+__device__ __forceinline__ RotationTerms rotation_terms_of_wave(const BnbParams &P, int32_t pair, int32_t wave, int lane) {
+  static_assert(MAX_ROT <= 64 * WAVES, "a wave's rotations fit its lanes");
+  RotationTerms T = {1.0, 0.0, 1.0, 0.0};
+  if (wave < P.n_theta) {
+    const int32_t mine = (P.n_theta - 1 - wave) / WAVES + 1;  // (>= 1)
+    T = rotation_terms(P, pair, wave + WAVES * min(lane, mine - 1));
+  }
+  return T;
 }
 
 // Byte offset (into the grid slot) of the aligned dword that holds the first cell of a point's 8 x 8 patch of block
