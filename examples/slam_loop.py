@@ -58,7 +58,7 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False, normals="bag", lc_submap=0,
         linear_solver="host", lc_gate="geometric", lc_max_score=5000.0, map_output=None, grid_output=None, lc_verify=None,
         lc_max_violation=None, lc_top_k=5, lc_consistency=False, lc_min_set=3, _lc_corrupt=None, lc_sequence=0, lc_sequence_step=1,
-        lc_loss=None, lc_loss_scale=1.0):
+        lc_loss=None, lc_loss_scale=1.0, movers=0, drop_transients=False):
     """min_scatter_score: LCCandidateFilter's threshold is 0.70 (lc_candidate_filter.cc:76); scans of the synthetic
     24 m x 16 m room score ~0.4, so callers on that world pass a lower one.
     hitl_device: the HITL constraint's points are selected and packed on the GPU (hitl.select, under the "path" clock) and
@@ -114,6 +114,13 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     residual.  The result then also reports lc_loss, lc_loss_scale and, after the closure solve, lc_weights ([src, tgt, rho'] per
     accepted record), lc_weight_min, lc_downweighted (records with rho' < 0.5), lc_downweighted_pairs and
     lc_downweighted_rel_err_m.  Works with world > 1 (the solve is replicated).
+    movers N > 0: N synthetic walkers are added to the bag (synth.add_movers: discs of radius 0.3 m that walk the robot's own loop
+    at twice its speed, each starting further ahead); the result reports movers and mover_returns.
+    drop_transients: after the growing-window solve, at the solved poses, the scans are traced into the occupancy planes and every
+    return is classified by them ("Transient returns"; backend.drop_transients, in-stream on the GPU); the
+    clouds without their transient returns are what the loop-closure tables, map_output and grid_output are made from.  The
+    result reports transient_stats (transient.STATS_FIELDS), transient_s and, with movers, the shares of the walkers' and of the
+    other returns that were flagged.  Not with world > 1.  Both are off by default and change nothing then.
     _lc_corrupt: TEST ONLY -- a callable (src, tgt, rel, good) -> rel that replaces the records' transforms before the consistency
     filter and the constraints (tests/test_consistency_loop_gpu.py displaces accepted records with it).
     With world > 1 (one process per GPU under torch.distributed): the window ICP solve is replicated -- its
@@ -125,7 +132,16 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     bag = synth.SynthBag(n_scans, dense=True, seed=seed, spacing=spacing)
     odom = synth.odometry_from_truth(bag.truth, sigma_t=drift_t, sigma_th_deg=drift_th_deg, seed=seed)
     odom = odom - odom[0] + bag.truth[0]  # both tracks start at the same anchor (pose 0 is held constant)
-    xy, off = csm.pack_scans(bag.scans)
+    scans, mover_mask = bag.scans, None
+    if int(movers) < 0:
+        raise ValueError("run: movers %r must be >= 0" % (movers,))
+    if movers:
+        ahead = lambda k: (lambda i: tuple(bag.truth[(2 * i + 15 + 40 * k) % n_scans, :2]))
+        scans, masks = synth.add_movers(bag.scans, bag.truth, [(ahead(k), 0.3) for k in range(int(movers))])
+        mover_mask = np.concatenate(masks)
+    if drop_transients and world > 1:
+        raise ValueError("run: drop_transients with world > 1 (the filter has no sharded path)")
+    xy, off = csm.pack_scans(scans)
     nrm = np.concatenate(bag.normals).astype(np.float32)
     kind = _lib.NHIP_LIDAR_NORMAL if residual == "normal" else _lib.NHIP_LIDAR_POINT
     if residual not in ("normal", "point", "feature"):
@@ -200,6 +216,24 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     pcg_phase("icp")
     out["err_icp_m"] = posegraph.trajectory_error(poses, bag.truth)
     out["icp_correspondences"] = pg.icp.n_corr
+    if movers:
+        out["movers"], out["mover_returns"] = int(movers), int(mover_mask.sum())
+
+    # ---- the clouds the loop-closure tables and the maps are made from: the scans, or the scans without their transient returns
+    xy_lc, off_lc = xy, off
+    if drop_transients:
+        if not hasattr(backend, "drop_transients"):
+            raise RuntimeError("run: drop_transients needs a backend with drop_transients(); backend %r has none" % (backend.name,))
+        from nautilus_amd import transient
+        t0 = time.perf_counter()
+        static = backend.drop_transients(poses, xy=xy, offsets=off)  # (outside the stage clocks: not a solve stage)
+        out["transient_s"] = time.perf_counter() - t0
+        xy_lc, off_lc = static.xy, static.offsets
+        out["transient_stats"] = {k: int(v) for k, v in zip(transient.STATS_FIELDS, static.stats)}
+        if movers:
+            flagged = static.labels == 1
+            out["transient_mover_share"] = float(flagged[mover_mask].mean()) if mover_mask.any() else None
+            out["transient_other_share"] = float(flagged[~mover_mask].mean())
 
     def appearance_pairs(ids):
         """lc_gate "appearance": the K nearest earlier scans of every scan of `ids` by ring descriptor (place.py), more than 20
@@ -292,29 +326,29 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
             def match_shard(src_s, slot_s, th_s, ids_s):
                 if len(src_s) == 0:
                     return np.zeros(0, dtype=csm.MATCH_DTYPE)
-                m_, spec_search["spec"], spec_search["search"] = backend.match(xy, off, src_s, ids_s[slot_s], th_s, cell_bits)
+                m_, spec_search["spec"], spec_search["search"] = backend.match(xy_lc, off_lc, src_s, ids_s[slot_s], th_s, cell_bits)
                 return m_
             with posegraph.clocked("path"):
                 m = sharding.distributed_match(match_shard, src, tgt, theta0, rank, world, device=device)
             spec, search = csm.grid_spec(30.0, 0.05, 2.0, 1e-10, 40, cell_bits), csm.search_spec()
         elif lc_submap and "submap_radius" in inspect.signature(backend.match).parameters:
             with posegraph.clocked("path"):
-                m, spec, search = backend.match(xy, off, src, tgt, theta0, cell_bits, submap_radius=lc_submap, poses=poses)
+                m, spec, search = backend.match(xy_lc, off_lc, src, tgt, theta0, cell_bits, submap_radius=lc_submap, poses=poses)
         elif lc_submap:
             with posegraph.clocked("marshal"):
-                xy_m, off_m, tgt_m = hostside.submap_extra_scans(xy, off, poses, tgt, lc_submap)
+                xy_m, off_m, tgt_m = hostside.submap_extra_scans(xy_lc, off_lc, poses, tgt, lc_submap)
             with posegraph.clocked("path"):
                 m, spec, search = backend.match(xy_m, off_m, src, tgt_m, theta0, cell_bits)
         elif lc_verify and "freespace" in inspect.signature(backend.match).parameters:
             from nautilus_amd import freespace
             with posegraph.clocked("path"):
-                m, spec, search, fs_counts = backend.match(xy, off, src, tgt, theta0, cell_bits, freespace=freespace.default_spec())
+                m, spec, search, fs_counts = backend.match(xy_lc, off_lc, src, tgt, theta0, cell_bits, freespace=freespace.default_spec())
         else:
             with posegraph.clocked("path"):
-                m, spec, search = backend.match(xy, off, src, tgt, theta0, cell_bits)
+                m, spec, search = backend.match(xy_lc, off_lc, src, tgt, theta0, cell_bits)
             if lc_verify:  # (a backend without the parameter: the plain numpy host path, as submap_extra_scans is for submaps)
                 with posegraph.clocked("marshal"):
-                    fs_counts = hostside.freespace_counts(xy, off, src, tgt, theta0, m, spec, search)
+                    fs_counts = hostside.freespace_counts(xy_lc, off_lc, src, tgt, theta0, m, spec, search)
         out["t_csm_s"] = time.perf_counter() - t0
         with posegraph.clocked("marshal"):  # (records -> (tx, ty, theta) as consumed at solver.cc:640-644, vectorised)
             rel = np.stack([(m["ix"].astype(np.float64) - (search.nx - 1) // 2) * spec.res,
@@ -388,7 +422,7 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
                 con = backend.hitl_select(xy, off, poses, lines[0], lines[1])
         else:
             with posegraph.clocked("hitl_select"):
-                a_poses, b_poses = hostside.hitl_relevant_poses(poses, bag.scans, lines[0], lines[1])
+                a_poses, b_poses = hostside.hitl_relevant_poses(poses, scans, lines[0], lines[1])
             with posegraph.clocked("marshal"):
                 con = posegraph.HitlConstraint(lines[0], lines[1], a_poses, b_poses)
         out["hitl_line_a_poses"], out["hitl_line_b_poses"] = con.n_a, con.n_b
@@ -409,7 +443,7 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         if not hasattr(backend, "vectorize"):
             raise RuntimeError("run: map_output needs a backend with vectorize(); backend %r has none" % (backend.name,))
         t0 = time.perf_counter()
-        map_lines, _, map_stats = backend.vectorize(poses, xy=xy, offsets=off)  # (outside the stage clocks: not a solve stage)
+        map_lines, _, map_stats = backend.vectorize(poses, xy=xy_lc, offsets=off_lc)  # (outside the stage clocks: not a solve stage)
         out["vectorize_s"] = time.perf_counter() - t0
         if rank == 0:
             hostside.write_map_lines(map_output, map_lines)
@@ -422,7 +456,7 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         from nautilus_amd import occupancy
         grid_spec = occupancy.window_spec(poses)
         t0 = time.perf_counter()
-        grid, _, _, grid_stats = backend.occupancy_grid(poses, spec=grid_spec, xy=xy, offsets=off)  # (outside the stage clocks)
+        grid, _, _, grid_stats = backend.occupancy_grid(poses, spec=grid_spec, xy=xy_lc, offsets=off_lc)  # (outside the stage clocks)
         out["occupancy_s"] = time.perf_counter() - t0
         if rank == 0:
             hostside.write_occupancy_map(grid_output, grid, grid_spec)
@@ -510,6 +544,11 @@ if __name__ == "__main__":
                     help="vectorise the final poses' map on the GPU and write it there, one 'x1,y1,x2,y2' line per wall segment")
     ap.add_argument("--grid-output", metavar="STEM", default=None,
                     help="ray-trace the final poses' occupancy grid on the GPU and write STEM.pgm and STEM.yaml (map_server's pair)")
+    ap.add_argument("--movers", type=int, default=0, metavar="N",
+                    help="add N synthetic walkers to the bag: discs of radius 0.3 m whose returns replace the walls' behind them")
+    ap.add_argument("--drop-transients", action="store_true",
+                    help="after the growing-window solve, classify every return by the occupancy planes of all scans on the GPU and "
+                         "make the loop-closure tables, --map-output and --grid-output from the scans without their transient returns")
     ap.add_argument("-v", action="store_true")
     a = ap.parse_args()
     if not 0 <= a.lc_submap < LC_MIN_SEPARATION:
@@ -543,8 +582,14 @@ if __name__ == "__main__":
               linear_solver=a.linear_solver, lc_gate=a.lc_gate, lc_max_score=a.lc_max_score, map_output=a.map_output,
               grid_output=a.grid_output, lc_verify=a.lc_verify, lc_max_violation=a.lc_max_violation, lc_top_k=a.lc_top_k,
               lc_consistency=a.lc_consistency, lc_min_set=a.lc_min_set, lc_sequence=seq_w, lc_sequence_step=seq_step,
-              lc_loss=None if a.lc_loss == "none" else a.lc_loss, lc_loss_scale=a.lc_loss_scale)
+              lc_loss=None if a.lc_loss == "none" else a.lc_loss, lc_loss_scale=a.lc_loss_scale, movers=a.movers,
+              drop_transients=a.drop_transients)
     res["world_size"] = world
+    if rank == 0 and "transient_stats" in res:
+        s = res["transient_stats"]
+        print("transients: kept %d of %d returns (static %d, transient %d, unobserved %d, invalid %d); %d of %d scans kept none"
+              % (s["points_static"] + s["points_unobserved"], sum(s[k] for k in list(s)[:4]), s["points_static"], s["points_transient"],
+                 s["points_unobserved"], s["points_invalid"], s["scans_emptied"], s["scans_processed"]))
     if rank == 0:
         print(json.dumps(res))
     if "RANK" in os.environ:

@@ -67,7 +67,7 @@ const char *nhip_version(void);
  * the capacity of nhip_submaps_gather_dev, 2048 contributor id of nhip_bsr_assemble_dev, 4096 block column of
  * nhip_bsr_assemble_dev / nhip_bsr_pcg_dev / nhip_bsr_pcg_columns_dev, 8192 gauge or right-hand-side index of
  * nhip_bsr_pcg_columns_dev, 16384 scan offset of nhip_vectorize_dev /
- * nhip_occupancy_dev / nhip_place_describe_dev, 32768 source scan, grid slot or record index of a pair of
+ * nhip_occupancy_dev / nhip_place_describe_dev / nhip_transient_filter_dev, 32768 source scan, grid slot or record index of a pair of
  * nhip_freespace_check_dev, 65536 scan id of the list of nhip_place_match_dev / nhip_place_seq_match_dev, 131072 degree and 262144
  * member index of nhip_consistency_set_dev.  Clears the record
  * (in the order of `stream`).
@@ -803,6 +803,56 @@ int nhip_occupancy_dev(const float *d_xy, const int32_t *d_offsets, const float 
                        const nhip_occupancy_spec_t *spec, int32_t *d_hits, int32_t *d_misses, int8_t *d_grid, int64_t *d_stats,
                        void *stream);
 
+/* K19: TRANSIENT RETURNS -- every return of every scan classified by the two planes of the occupancy grid under it, and the
+ * returns that are not transient packed into clouds of the layout every other entry point takes (DESIGN.md section 3,
+ * "Transient returns"; tests/transient_reference.py and hostside.transient_filter restate it in numpy).  A wall cell is hit
+ * by many scans and seen through by few; a cell where someone stood for one scan is hit once and seen through by every later
+ * scan.  Build-defined and deterministic; all integer after the cells; the planes are read as they are and never written.
+ *   cell     as K14's end cells: scan i's affine (nhip_map_pose_affines) in float, floor((double)v / res) per axis.
+ *   label 3  INVALID: the point or its world point is not finite, or a floor has magnitude >= 2^62.  No scan is dropped as a
+ *            whole: an affine that is not finite makes every point of its scan invalid.  A point of the cloud that belongs to
+ *            no scan (or to one whose offsets are not a scan) keeps this label too.
+ *   label 2  UNOBSERVED: the cell lies outside the window (cell_x0, cell_y0, width, height); the test is made in int64.
+ *   counts   S = the sum of hits over the cells of the (2 support_radius + 1)^2 neighbourhood that lie inside the window;
+ *            m = misses at the point's own cell; both int64.
+ *   label 1  TRANSIENT: m >= min_through and 1000 S <= transient_permille (S + m); equality on either side counts.
+ *   label 0  STATIC: everything else.
+ *   kept     labels 0 and 2, in the layout of the input: out_offsets (n_scans + 1), out_xy (the kept points in the scan frame,
+ *            bit copies, in their order inside each scan, scans in order), out_index (the index of each kept point in the
+ *            input cloud, so that normals or intensities can be gathered alongside).
+ *   stats    8 int64: {points static, transient, unobserved, invalid, scans processed, scans whose offsets are not a scan,
+ *            scans that had points and kept none, 0}.
+ * Accepted ranges (anything else is NHIP_ERR_ARG before anything is launched, with or without a device): res finite and > 0;
+ * width, height 1..16384; support_radius 0..4; min_through 1..2^30; transient_permille 0..1000; flags 0; reserved 0;
+ * n_scans >= 0; n_points >= 0. */
+typedef struct nhip_transient_spec {
+  double res;                 /* metres per cell (0.05): the occupancy spec's */
+  int32_t cell_x0;            /* the window of the planes: the occupancy spec's */
+  int32_t cell_y0;
+  int32_t width;
+  int32_t height;
+  int32_t support_radius;     /* hits are summed over (2 r + 1)^2 cells (1): a grazing beam ends one cell along its wall */
+  int32_t min_through;        /* scans that must have seen through the cell (2) */
+  int32_t transient_permille; /* hits per 1000 observations up to which the return is transient (500) */
+  int32_t flags;              /* 0 */
+  int32_t reserved;           /* 0 */
+} nhip_transient_spec_t;
+/* the defaults of the table above; the window is 0 and is the caller's to set; pure host */
+int nhip_transient_spec_default(nhip_transient_spec_t *out);
+/* The whole step on the caller's buffers and stream; never allocates, needs no workspace, enqueues and returns without
+ * waiting -- in-stream after nhip_occupancy_dev it reads the planes that call wrote, with no synchronisation between.
+ * n_points: the capacity of the clouds, input and output alike (d_xy, d_out_xy: 2 floats per point, 8-byte aligned;
+ * d_labels: a byte per point; d_out_index: an int32 per point).  d_affines: 4 floats per scan.  d_hits, d_misses: int32
+ * [height][width].  d_out_offsets: n_scans + 1 int32.  d_stats: 8 int64.  n_scans = 0 is a call: out_offsets[0] = 0, the
+ * stats zero, every label 3.  The offsets are read by the kernels: a scan whose first offset is negative, whose end lies
+ * before its start or whose end lies beyond n_points is treated as empty, counted in the stats, and nhip_dev_status() reports
+ * the first such scan in scan order (kind 16384, the offset at fault and its index in d_offsets); the other scans are not
+ * affected.  Scans are expected not to overlap in the cloud; if they do, the kept points are cut at n_points, the capacity of
+ * the outputs, and a shared point carries the label of whichever scan wrote last. */
+int nhip_transient_filter_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, int32_t n_points, const float *d_affines,
+                              const nhip_transient_spec_t *spec, const int32_t *d_hits, const int32_t *d_misses, uint8_t *d_labels,
+                              float *d_out_xy, int32_t *d_out_offsets, int32_t *d_out_index, int64_t *d_stats, void *stream);
+
 /* K15: FREE-SPACE CHECK of match records ("Free-space check"; tests/freespace_reference.py restates it
  * in numpy).  A record's score says how much of the source landed on the target's blurred hits; the check says where the rest
  * landed.  Build-defined and deterministic; all integer after the cells; no matcher kernel is involved.
@@ -1113,6 +1163,14 @@ int nhip_vectorize(const nhip_scans_t *scans, const double *poses, const nhip_ve
  * and misses are also inputs: they are uploaded first. */
 int nhip_occupancy(const nhip_scans_t *scans, const double *poses, const nhip_occupancy_spec_t *spec, int32_t *hits,
                    int32_t *misses, int8_t *grid, int64_t *stats);
+
+/* nhip_transient_filter_dev on uploaded scans (n_points: the points the handle holds), with host poses (3 doubles per scan),
+ * host planes (hits, misses: width x height int32, uploaded, not modified) and host outputs (labels: a byte per point;
+ * out_xy: 2 floats per point; out_offsets: n_scans + 1 int32; out_index: an int32 per point; stats: 8 int64); allocates and
+ * frees its device buffers.  Only the first out_offsets[n_scans] entries of out_xy and out_index are written. */
+int nhip_transient_filter(const nhip_scans_t *scans, const double *poses, const nhip_transient_spec_t *spec, const int32_t *hits,
+                          const int32_t *misses, uint8_t *labels, float *out_xy, int32_t *out_offsets, int32_t *out_index,
+                          int64_t *stats);
 
 /* nhip_freespace_check_dev on handles: the pair arguments of nhip_csm_match, the records it returned (host memory) and
  * counts (8 int32 per pair, host memory).  `scans` must be the scans `grids` was built from: the first call on a grids handle

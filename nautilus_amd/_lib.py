@@ -91,6 +91,12 @@ class OccupancySpec(C.Structure):
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class TransientSpec(C.Structure):
+    _fields_ = [("res", C.c_double), ("cell_x0", C.c_int32), ("cell_y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("support_radius", C.c_int32), ("min_through", C.c_int32), ("transient_permille", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class FreespaceSpec(C.Structure):
     _fields_ = [("hit_radius", C.c_int32), ("end_margin", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
@@ -228,6 +234,9 @@ PROTOTYPES = {
     "nhip_occupancy_spec_default": (C.c_int, [_P(OccupancySpec)]),
     "nhip_occupancy_dev": (C.c_int, [_vp, _vp, _vp, _i32, _P(OccupancySpec), _vp, _vp, _vp, _vp, _vp]),
     "nhip_occupancy": (C.c_int, [_vp, _vp, _P(OccupancySpec), _vp, _vp, _vp, _vp]),
+    "nhip_transient_spec_default": (C.c_int, [_P(TransientSpec)]),
+    "nhip_transient_filter_dev": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _P(TransientSpec), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nhip_transient_filter": (C.c_int, [_vp, _vp, _P(TransientSpec), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nhip_freespace_spec_default": (C.c_int, [_P(FreespaceSpec)]),
     "nhip_freespace_planes_bytes": (_i64, [_P(GridSpec), _i64]),
     "nhip_freespace_trace_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(GridSpec), _vp, _vp, _vp]),

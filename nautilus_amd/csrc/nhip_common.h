@@ -390,6 +390,22 @@ struct OccParams {    // plain data: travels in the kernels' parameter blocks
 int launch_occupancy(const OccParams &P, bool clear, const float *d_xy, const int32_t *d_offsets, const float *d_affines,
                      hipStream_t s);
 
+// transient returns (nhip_transient.hip, K19); the spec has passed transient_spec_check (nhip_host_transient.hip)
+struct TransientParams {  // plain data: travels in the kernels' parameter blocks
+  int32_t width, height, cell_x0, cell_y0, support_radius, min_through, transient_permille, n_scans, n_points;
+  double res, inv_res;
+  const int32_t *hits, *misses;  // read as they are, never written
+  uint8_t *labels;               // n_points
+  float2 *out_xy;                // n_points
+  int32_t *out_offsets;          // n_scans + 1
+  int32_t *out_index;            // n_points
+  long long *stats;   // 8 words: {points static, transient, unobserved, invalid, scans processed, scans whose offsets are not
+                      // a scan, scans that had points and kept none, 0}
+  uint32_t *status;
+};
+// clears the stats and sets every label to 3, then classify, offsets and pack
+int launch_transient(const TransientParams &P, const float *d_xy, const int32_t *d_offsets, const float *d_affines, hipStream_t s);
+
 // free-space check of match records (nhip_freespace.hip, K15); the specs have passed the checks of nhip_host_freespace.hip
 struct FsParams {     // plain data: travels in the kernels' parameter blocks (the trace reads the first group, the check both)
   const float2 *xy;

@@ -375,7 +375,7 @@ int nhip_dev_status(void *stream, int32_t info[4]) {
                      : w[1] == BAD_CONTRIB_ID    ? "contributor id (nhip_bsr_assemble_dev: d_contrib; index = the block)"
                      : w[1] == BAD_BLOCK_COLUMN  ? "block column (nhip_bsr_assemble_dev / nhip_bsr_pcg_dev: d_col; index = the block)"
                      : w[1] == BAD_SYSTEM_ID     ? "gauge or right-hand-side index (nhip_bsr_pcg_columns_dev: d_gauge / d_rhs_index; index = the system)"
-                     : w[1] == BAD_MAP_SCAN_OFFSETS ? "scan offset (nhip_vectorize_dev / nhip_occupancy_dev / nhip_place_describe_dev: d_offsets)"
+                     : w[1] == BAD_MAP_SCAN_OFFSETS ? "scan offset (nhip_vectorize_dev / nhip_occupancy_dev / nhip_place_describe_dev / nhip_transient_filter_dev: d_offsets)"
                      : w[1] == BAD_PLACE_ID ? "scan id (nhip_place_match_dev / nhip_place_seq_match_dev: d_ids)"
                      : w[1] == BAD_FREESPACE_PAIR ? "source scan, grid slot or record index of a pair (nhip_freespace_check_dev; index = the pair)"
                                              : "id";

@@ -278,6 +278,79 @@ def freespace_counts(xy, offsets, pair_src, pair_tgt, theta0, matches, grid_spec
     return counts
 
 
+def transient_spec_check(spec):
+    """The accepted ranges of nhip_transient_spec_t (include/nautilus_hip.h); ValueError otherwise."""
+    res = float(spec.res)
+    if not (math.isfinite(res) and res > 0):
+        raise ValueError("transient_filter: res must be finite and > 0")
+    for name, lo, hi in (("width", 1, 16384), ("height", 1, 16384), ("support_radius", 0, 4), ("min_through", 1, 1 << 30),
+                         ("transient_permille", 0, 1000), ("flags", 0, 0), ("reserved", 0, 0)):
+        if not lo <= int(getattr(spec, name)) <= hi:
+            raise ValueError("transient_filter: %s %d outside %d..%d" % (name, int(getattr(spec, name)), lo, hi))
+
+
+def transient_filter(xy, offsets, poses, spec, hits, misses):
+    """Transient returns in plain numpy on the host ("Transient returns"; the device form is
+    nhip_transient_filter_dev, and transient.filter returns the same five arrays bit for bit): every return of the packed
+    scans at `poses` classified by the occupancy planes `hits` and `misses` (int32 (H, W), read only) under it, the returns
+    that are not transient packed.  spec: anything with the fields of nhip_transient_spec_t (transient.spec_from(occupancy
+    spec)).  Returns (out_xy float32 (kept, 2), out_offsets int32 (n_scans + 1,), out_index int32 (kept,), labels uint8
+    (n_points,): 0 static, 1 transient, 2 unobserved, 3 invalid, stats int64 (8,): transient.STATS_FIELDS).  The hit support
+    S of a cell is read from a summed-area table of `hits`.  A scan whose offsets are not a scan is empty and counted
+    (stats[5]); nothing is raised for it."""
+    from .vectorize import pose_affines
+    transient_spec_check(spec)
+    f = np.float32
+    xy = np.ascontiguousarray(xy, dtype=f).reshape(-1, 2)
+    off = np.asarray(offsets, dtype=np.int64)
+    n_scans, n_points = len(off) - 1, len(xy)
+    aff = pose_affines(poses)
+    if len(aff) != n_scans:
+        raise ValueError("transient_filter: %d poses for %d scans" % (len(aff), n_scans))
+    w, h, r, res = int(spec.width), int(spec.height), int(spec.support_radius), float(spec.res)
+    x0, y0 = int(spec.cell_x0), int(spec.cell_y0)
+    H = np.asarray(hits).reshape(h, w).astype(np.int64)
+    M = np.asarray(misses).reshape(h, w).astype(np.int64)
+    area = np.zeros((h + 1, w + 1), np.int64)  # area[y, x] = the sum of H[:y, :x] (< 2^59: no sum wraps)
+    area[1:, 1:] = H.cumsum(axis=0).cumsum(axis=1)
+    labels = np.full(n_points, 3, np.uint8)
+    stats, index, out_off = np.zeros(8, np.int64), [], np.zeros(n_scans + 1, np.int32)
+    stats[4], n_kept = n_scans, 0
+    for i in range(n_scans):
+        b, e = int(off[i]), int(off[i + 1])
+        out_off[i] = n_kept
+        if b < 0 or e < b or e > n_points:
+            stats[5] += 1
+            continue
+        p = xy[b:e]
+        c, s, tx, ty = (f(v) for v in aff[i])
+        with np.errstate(invalid="ignore", over="ignore"):
+            wx = ((c * p[:, 0]).astype(f) + ((-s) * p[:, 1]).astype(f)).astype(f) + tx
+            wy = ((s * p[:, 0]).astype(f) + (c * p[:, 1]).astype(f)).astype(f) + ty
+            wpt = np.stack([wx.astype(f), wy.astype(f)], axis=1).astype(np.float64)
+            fl = np.floor(wpt / res)
+            valid = np.isfinite(p).all(axis=1) & np.isfinite(wpt).all(axis=1) & (np.abs(fl) < 2.0 ** 62).all(axis=1)
+        lab = np.full(len(p), 3, np.uint8)
+        cell = np.where(valid[:, None], fl, 0.0).astype(np.int64) - (x0, y0)  # (window coordinates, int64)
+        inside = valid & (cell >= 0).all(axis=1) & (cell[:, 0] < w) & (cell[:, 1] < h)
+        lab[valid & ~inside] = 2
+        cx, cy = cell[inside, 0], cell[inside, 1]
+        xa, xb = np.maximum(cx - r, 0), np.minimum(cx + r, w - 1) + 1
+        ya, yb = np.maximum(cy - r, 0), np.minimum(cy + r, h - 1) + 1
+        S = area[yb, xb] - area[ya, xb] - area[yb, xa] + area[ya, xa]
+        m = M[cy, cx]
+        lab[inside] = ((m >= int(spec.min_through)) & (1000 * S <= int(spec.transient_permille) * (S + m))).astype(np.uint8)
+        labels[b:e] = lab
+        stats[:4] += np.bincount(lab, minlength=4)
+        kept = np.nonzero((lab & 1) == 0)[0]
+        stats[6] += int(len(p) > 0 and len(kept) == 0)
+        index.append((b + kept).astype(np.int32))
+        n_kept += len(kept)
+    out_index = np.concatenate(index).astype(np.int32) if index else np.zeros(0, np.int32)
+    out_off[n_scans] = len(out_index)
+    return xy[out_index], out_off, out_index, labels, stats
+
+
 def place_descriptors(xy, offsets, spec):
     """The ring descriptors of the packed scans in plain numpy ("Place descriptors"; the device form is
     nhip_place_describe_dev): (D uint64 (n_scans, R), bits int32 (n_scans,)).  The tables are the library's

@@ -132,6 +132,21 @@ class HipBackend:
             raise RuntimeError("HipBackend.occupancy_grid: no clouds on the device yet (the first icp() batch uploads them): pass xy, offsets")
         return occupancy.occupancy_grid_on_device(held[1], held[3], int(held[3].numel()) - 1, poses, spec)
 
+    def drop_transients(self, poses, occ_spec=None, xy=None, offsets=None, **overrides):
+        """The scans without their transient returns at `poses` (transient.py): one occupancy trace, then the filter on its
+        planes, in-stream -- transient.StaticScans, whose (xy, offsets) stand in for the input's.  Runs on the clouds the
+        arena already holds, or on xy and offsets, exactly as vectorize() chooses.  occ_spec=None: the occupancy defaults on
+        the window of every pose +- 30 m; overrides: fields of the transient spec (support_radius, min_through,
+        transient_permille)."""
+        from . import occupancy, transient
+        occ_spec = occupancy.window_spec(poses) if occ_spec is None else occ_spec
+        held = self.arena.clouds
+        if xy is not None and (held is None or held[4][0] is not xy):
+            return transient.static_scans(xy, offsets, poses, occ_spec, device=str(self.dev), **overrides)
+        if held is None:
+            raise RuntimeError("HipBackend.drop_transients: no clouds on the device yet (the first icp() batch uploads them): pass xy, offsets")
+        return transient.static_scans_on_device(held[1], held[3], int(held[3].numel()) - 1, poses, occ_spec, **overrides)
+
     def reserve_icp(self, offsets, window):
         """Work buffers for the largest problem of a growing-window solve (all (i, j), j in [i - window, i)): allocated once."""
         off = np.asarray(offsets, dtype=np.int64)

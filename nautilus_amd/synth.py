@@ -112,6 +112,38 @@ def ranges_to_cloud(r_row):
     return pts.astype(np.float32), keep
 
 
+def add_movers(scans, truth, movers):
+    """People walking through the bag.  movers: a list of (centres, radius) -- centres (n_scans, 2): the world position of a
+    disc in every scan (or a callable i -> (x, y)), radius in metres.  For each scan, every beam that meets a disc nearer
+    than its own return (and not nearer than RANGE_MIN) gets the disc's range instead; a beam's direction is that of its
+    point, so beams that had no return stay without one and every cloud keeps its length (normals stay aligned).  Returns
+    (new scans: a list of float32 (N_i, 2) clouds, masks: a list of bool (N_i,), True where the return now comes off a
+    mover).  Deterministic: no noise is added to the new ranges."""
+    truth = np.asarray(truth, dtype=np.float64).reshape(-1, 3)
+    out, masks = [], []
+    for i, pts in enumerate(scans):
+        p = np.asarray(pts, dtype=np.float32).reshape(-1, 2).copy()
+        rng_ = np.hypot(p[:, 0].astype(np.float64), p[:, 1].astype(np.float64))
+        d = p.astype(np.float64) / np.maximum(rng_, 1e-300)[:, None]
+        best, mask = rng_.copy(), np.zeros(len(p), bool)
+        c, s = math.cos(truth[i, 2]), math.sin(truth[i, 2])
+        for centres, radius in movers:
+            wx, wy = centres(i) if callable(centres) else np.asarray(centres, dtype=np.float64).reshape(-1, 2)[i]
+            dx, dy = float(wx) - truth[i, 0], float(wy) - truth[i, 1]
+            lx, ly = c * dx + s * dy, -s * dx + c * dy  # the centre in the sensor's frame
+            along = d[:, 0] * lx + d[:, 1] * ly
+            under = float(radius) ** 2 - ((lx * lx + ly * ly) - along * along)
+            with np.errstate(invalid="ignore"):
+                t = along - np.sqrt(under)
+            hit = (under >= 0) & (t >= RANGE_MIN) & (t < best)
+            best[hit] = t[hit]
+            mask |= hit
+        p[mask] = (d[mask] * best[mask, None]).astype(np.float32)
+        out.append(p)
+        masks.append(mask)
+    return out, masks
+
+
 class SynthBag:
     """n_scans scans + truth/odometry poses + per-point wall normals (scan frame)."""
 
