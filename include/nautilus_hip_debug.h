@@ -47,8 +47,13 @@ int nhip_bnb_stats(uint64_t *evaluated, uint64_t *total);
  * settled right after their bounds (nhip_csm_match_gated); out[16..18] = rotation passes of the kernels that keep a list
  * of level-2 runs (the split form's candidates, the hand-over kernel; not the seeds) that took their strip bounds from
  * it, that took them per stored cell because some group of 8 lanes would have held more than 257 points, and that did
- * because the rotation had more runs than the list holds -- all three stay 0 under NHIP_BNB_L2_RUNS=0; out[19..23]
- * unused, 0; (synchronises; resets) */
+ * because the rotation had more runs than the list holds -- all three stay 0 under NHIP_BNB_L2_RUNS=0; out[19..21]
+ * = the work at the lattice's edge, in blocks with fewer than 8 pose columns or rows (a lattice side that is no multiple
+ * of 8 has one such block column or row): such blocks refined through their sub-block bounds, 4 x 4 sub-blocks evaluated
+ * that hold no pose of the lattice, such blocks evaluated whole -- the matcher skips the former, so out[20] stays 0,
+ * and only an edge block with more than 4 pose columns and rows, which has a pose in all four sub-blocks, can be the
+ * latter: out[21] stays 0 on a lattice whose sides are 8 m + 0 .. 4 (the seed of a scan too long for the by-rotation
+ * form is a whole block wherever it lies, and is not counted); out[22..23] unused, 0; (synchronises; resets) */
 int nhip_bnb_stats_levels(uint64_t out[24]);
 /* ... and per pair of the last launch (4 x 4 sub-blocks evaluated exactly, a whole block counting four), before
  * nhip_bnb_stats resets the totals */

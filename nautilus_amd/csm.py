@@ -273,7 +273,8 @@ def bnb_stats_levels():
             "clk_slowest_wave": v[8], "clk_seeds": v[9], "clk_bounds": v[10], "clk_wave_phase3_100MHz": v[11],
             "pairs_handed_over": v[12], "clk_wave_second_kernel": v[13], "pose_evals16": v[14],
             "pairs_settled_by_gate": v[15], "passes_l2_runs": v[16], "passes_per_cell_field": v[17],
-            "passes_per_cell_capacity": v[18]}
+            "passes_per_cell_capacity": v[18], "edge_blocks_refined": v[19], "sub_blocks_without_pose": v[20],
+            "edge_blocks_whole": v[21]}
 
 
 def score_volume(scans, grids, src, slot, theta0, search, origin=(0, 0)):

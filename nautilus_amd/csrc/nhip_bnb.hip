@@ -17,7 +17,11 @@
 // 4 x 4 sub-blocks (second table, pooled over 7 x 7 cells at stride 4: one 16-byte read per point serves a strip of
 // three neighbouring blocks) and exact sums are gathered from the stored grid only for the sub-blocks whose bound
 // still reaches `best`, which rises as it goes.  Blocks and sub-blocks with a bound below best's sum cannot hold the
-// optimum, nor a tie with it, and are never touched.  On the 1081-beam workload 0.36 % of the poses are evaluated.
+// optimum, nor a tie with it, and are never touched.  Nor are the sub-blocks that hold no pose of the lattice: a side that
+// is no multiple of 8 (81 = 8 * 10 + 1) leaves the last block column / row with 1 .. 7 pose columns / rows, and the sub-blocks
+// beyond them -- 43 of a rotation's 484 at 81 x 81 -- carry the HIGHEST bounds of a landscape that rises towards the window's
+// edge while nothing in them can raise `best`; they are neither counted as alive nor evaluated (block_extent, sub_valid).
+// On the 1081-beam workload 0.36 % of the poses are evaluated.
 //
 // Parallelisation is the transpose of the exhaustive kernel's: LANES ARE POINTS (one point per lane and
 // 64-point chunk), REGISTERS ARE POSES -- byte sums SWAR-packed two per register -- and one transposing
@@ -86,7 +90,11 @@ constexpr int BNB_THREADS = 64 * BNB_WAVES;
 // ---- one candidate block: refine through the sub-block bounds, or evaluate whole --------------------------
 // `best` is the pair's running best key (LDS of the pair's workgroup, or keys[pair] in global memory for the
 // rotations handed to the second kernel).  A sub-block is skipped only if its bound is below the best SUM found so far: it cannot hold
-// the optimum nor a tie with it.  n[0] whole blocks evaluated, n[1] candidates refined, n[2] sub-blocks evaluated.
+// the optimum nor a tie with it.  n[0] whole blocks evaluated, n[1] candidates refined, n[2] sub-blocks evaluated,
+// n[3] poses of 16-bit grids read exactly; at the lattice's edge (blocks with fewer than 8 pose columns or rows): n[4] such
+// blocks refined, n[5] sub-blocks evaluated that hold no pose (stays 0), n[6] such blocks evaluated whole (only ones with
+// more than 4 pose columns and rows can be).
+constexpr int N_WORK = 7;
 struct PairCtx {
   const uint8_t *grid;
   const float2 *pts;
@@ -95,8 +103,10 @@ struct PairCtx {
 
 template <int CB>
 __device__ __forceinline__ void process_candidate(const BnbParams &P, const PairCtx &C, int32_t k, int32_t v, int lane,
-                                                  unsigned long long *best, uint32_t (&n)[4]) {
+                                                  unsigned long long *best, uint32_t (&n)[N_WORK]) {
   const int Y = v / NB, X = v - NB * Y;  // v: block index NB * Y + X
+  const int32_t vx = block_extent(P.nx, X), vy = block_extent(P.ny, Y);
+  const bool edge = vx < BNB_B || vy < BNB_B;
   float cf, sf;
   rotation_k(P, C.pair, k, &cf, &sf);
   if (P.levels >= 2) {
@@ -104,20 +114,22 @@ __device__ __forceinline__ void process_candidate(const BnbParams &P, const Pair
     uint32_t sb[4];
     sub_bounds(P, p4, C.pts, C.n_pts, cf, sf, C.cx, C.cy, Y, X, lane, CB == 1 ? 1u : 257u, sb);
     n[1]++;
+    n[4] += edge ? 1u : 0u;
     const uint32_t bsum = best_sum<false>(best);
     int alive = 0;
 #pragma unroll
-    for (int q = 0; q < 4; q++) alive += (sb[q] != 0u && sb[q] >= bsum) ? 1 : 0;
+    for (int q = 0; q < 4; q++) alive += (sub_valid(vy, vx, q >> 1, q & 1) && sb[q] != 0u && sb[q] >= bsum) ? 1 : 0;  // (as process_candidate_c)
     if (alive == 0) return;
     if (alive <= 2) {
       const __amdgpu_buffer_rsrc_t rsrc = uniform_rsrc(C.grid, P.grid_bytes + P.skip_bytes);
 #pragma unroll 1
       for (int q = 0; q < 4; q++) {
         const uint32_t b = q == 0 ? sb[0] : (q == 1 ? sb[1] : (q == 2 ? sb[2] : sb[3]));  // (no indexed array: scratch)
-        if (b == 0u || b < best_sum<false>(best)) continue;
+        if (!sub_valid(vy, vx, q >> 1, q & 1) || b == 0u || b < best_sum<false>(best)) continue;
         const unsigned long long key = eval_sub<CB>(P, rsrc, C.pts, C.n_pts, cf, sf, C.cx, C.cy, k, Y, X, q >> 1, q & 1, lane);
         wave_atomic_max(best, key, lane);
         n[2]++;
+        n[5] += sub_valid(vy, vx, q >> 1, q & 1) ? 0u : 1u;
       }
       return;
     }
@@ -125,6 +137,7 @@ __device__ __forceinline__ void process_candidate(const BnbParams &P, const Pair
   const unsigned long long key = eval_block<CB>(P, C.grid, C.pts, C.n_pts, cf, sf, C.cx, C.cy, k, Y, X, lane);
   wave_atomic_max(best, key, lane);
   n[0]++;
+  n[6] += edge ? 1u : 0u;
 }
 
 // ... with the rotation's origins held by the wave and the block's four sub-block bounds at hand.  `rsrc` is the
@@ -135,14 +148,22 @@ __device__ __forceinline__ void process_candidate_c(const BnbParams &P, __amdgpu
                                                     __amdgpu_buffer_rsrc_t rsrc16, const uint32_t *org, int32_t nch,
                                                     int32_t n_pts, int32_t k, int32_t Y, int32_t X,
                                                     uint32_t sb0, uint32_t sb1, uint32_t sb2, uint32_t sb3, int lane,
-                                                    unsigned long long *best, uint32_t &bcopy, uint32_t (&n)[4]) {
+                                                    unsigned long long *best, uint32_t &bcopy, uint32_t (&n)[N_WORK]) {
   const uint32_t bsum = best_sum_cached<GLOBAL>(best, bcopy);
-  const int alive = (sb0 != 0u && sb0 >= bsum) + (sb1 != 0u && sb1 >= bsum) + (sb2 != 0u && sb2 >= bsum) +
-                    (sb3 != 0u && sb3 >= bsum);
+  const int32_t vx = block_extent(P.nx, X), vy = block_extent(P.ny, Y);
+  const bool edge = vx < BNB_B || vy < BNB_B;
+  n[4] += edge ? 1u : 0u;
+  // Only sub-blocks that hold a pose of the lattice count and are evaluated.  The others lie beyond the window's edge; a
+  // landscape that rises towards it gives them the block's highest bounds, nothing they hold can raise the best, and so
+  // nothing ever pruned them.  (Scalar: X and Y are.)  Sub-block q = 2 sy + sx.
+  const bool ok0 = sub_valid(vy, vx, 0, 0), ok1 = sub_valid(vy, vx, 0, 1), ok2 = sub_valid(vy, vx, 1, 0), ok3 = sub_valid(vy, vx, 1, 1);
+  const int alive = (ok0 && sb0 != 0u && sb0 >= bsum) + (ok1 && sb1 != 0u && sb1 >= bsum) + (ok2 && sb2 != 0u && sb2 >= bsum) +
+                    (ok3 && sb3 != 0u && sb3 >= bsum);
   if (alive == 0) return;
   // a block with this many live sub-blocks is evaluated whole: one pass of 8 row loads per point instead of up to four
   // passes of 4, all 64 poses in one reduction (row-major planes: 2 beat 3, 7.70 -> 7.45 ms per 10,000 pairs; tiled planes:
-  // loads are cheaper and 3 beats 2, 6.37 -> 6.22 ms)
+  // loads are cheaper and 3 beats 2, 6.37 -> 6.22 ms).  A block at the lattice's edge with at most 4 pose columns or rows
+  // (81 = 8 * 10 + 1) has at most two sub-blocks with a pose and never goes whole.
   constexpr int WHOLE_MIN = 3;
   if (alive >= WHOLE_MIN) {
     int dy, dx;
@@ -156,12 +177,13 @@ __device__ __forceinline__ void process_candidate_c(const BnbParams &P, __amdgpu
       n[3] += refine16<GLOBAL>(P, rsrc16, org, nch, n_pts, k, ix, iy, total, true, lane, best, bcopy);
     }
     n[0]++;
+    n[6] += __ballot(ix < P.nx && iy < P.ny) != ~0ull ? 1u : 0u;  // (from the poses themselves, not from the extents)
     return;
   }
 #pragma unroll 1
   for (int q = 0; q < 4; q++) {
     const uint32_t b = q == 0 ? sb0 : (q == 1 ? sb1 : (q == 2 ? sb2 : sb3));
-    if (b == 0u || b < best_sum_cached<GLOBAL>(best, bcopy)) continue;
+    if (!sub_valid(vy, vx, q >> 1, q & 1) || b == 0u || b < best_sum_cached<GLOBAL>(best, bcopy)) continue;
     int dy, dx;
     const uint32_t total = sub_sums8(rsrc, pitch8, (uint32_t)P.hi_copy_bytes, org, nch, Y, X, q >> 1, q & 1, lane, &dy, &dx);
     const int32_t ix = BNB_B * X + BNB_B4 * (q & 1) + dx, iy = BNB_B * Y + BNB_B4 * (q >> 1) + dy;
@@ -173,6 +195,7 @@ __device__ __forceinline__ void process_candidate_c(const BnbParams &P, __amdgpu
       n[3] += refine16<GLOBAL>(P, rsrc16, org, nch, n_pts, k, ix, iy, total, lane < 16, lane, best, bcopy);
     }
     n[2]++;
+    n[5] += __ballot(ix < P.nx && iy < P.ny) == 0ull ? 1u : 0u;  // (from the poses themselves, not from sub_valid)
   }
 }
 
@@ -185,14 +208,21 @@ struct PhaseClocks {
 
 // The instrumented build's flush into stats[] (indices: include/nautilus_hip_debug.h): work counts n[0..3] as
 // process_candidate_c and rotation_pass count them, with the per-pair slot of `pair`, and / or a wave's phase clocks.
-// Either may be null.  (The product build passes a null `stats`: dead code there.)
-__device__ __forceinline__ void flush_stats(unsigned long long *stats, const uint32_t *n, int32_t pair, const PhaseClocks *clk) {
+// `edge`: a wave's three counts at the lattice's edge, n + 4.  Any may be null.  (The product build passes a null `stats`:
+// dead code there.)
+__device__ __forceinline__ void flush_stats(unsigned long long *stats, const uint32_t *n, int32_t pair, const PhaseClocks *clk,
+                                            const uint32_t *edge = nullptr) {
   if (n) {
     if (n[0]) atomicAdd(&stats[0], (unsigned long long)n[0]);
     if (n[1]) atomicAdd(&stats[2], (unsigned long long)n[1]);
     if (n[2]) atomicAdd(&stats[3], (unsigned long long)n[2]);
     if (n[3]) atomicAdd(&stats[14], (unsigned long long)n[3]);  // poses of 16-bit grids evaluated exactly (refine16)
     if (pair < BNB_STATS_PAIRS) atomicAdd(&stats[BNB_STATS_HEAD + pair], 4ull * n[0] + n[2]);
+  }
+  if (edge) {  // a wave's n[4..6]: the work at the lattice's edge
+    if (edge[0]) atomicAdd(&stats[19], (unsigned long long)edge[0]);
+    if (edge[1]) atomicAdd(&stats[20], (unsigned long long)edge[1]);
+    if (edge[2]) atomicAdd(&stats[21], (unsigned long long)edge[2]);
   }
   if (clk) {
     atomicAdd(&stats[5], (unsigned long long)clk->org);
@@ -213,7 +243,7 @@ template <int CB, bool GLOBAL, bool RUNS = false>
 __device__ __forceinline__ void rotation_pass(const BnbParams &P, const PairCtx &C, int32_t k, uint32_t u0, uint32_t u1,
                                               unsigned long long m0, unsigned long long m1, int lane,
                                               unsigned long long *best, uint32_t *done, uint32_t *org,
-                                              uint32_t (&n_work)[4], PhaseClocks &clk, uint32_t *runs = nullptr) {
+                                              uint32_t (&n_work)[N_WORK], PhaseClocks &clk, uint32_t *runs = nullptr) {
   long long t_mark = 0;
   float cf, sf;
   rotation_k(P, C.pair, k, &cf, &sf);
@@ -440,7 +470,7 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : BNB_THREADS, SPLIT ? SPL
     if ((uint32_t)(wbest >> 32) < (uint32_t)gfloor) wbest = 0ull;
   }
   // (2) seed: the wave's highest-bound block, evaluated exactly
-  uint32_t n_work[4] = {0u, 0u, 0u, 0u};
+  uint32_t n_work[N_WORK] = {};
   PairCtx C;
   C.grid = grid;
   C.pts = pts;
@@ -646,6 +676,7 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : BNB_THREADS, SPLIT ? SPL
     atomicAdd(&s_cnt[3], n_work[1]);
     atomicAdd(&s_cnt[4], n_work[2]);
     atomicAdd(&s_cnt[5], n_work[3]);
+    flush_stats(stats_g, nullptr, pair, nullptr, n_work + 4);
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -693,11 +724,11 @@ __global__ __launch_bounds__(256, 4) void csm_bnb_rot_kernel(BnbParams P) {
     read_entry(list + i, &pair, &k, &m0, &m1);
     PairCtx C;
     pair_context(P, pair, &C);
-    uint32_t n[4] = {0u, 0u, 0u, 0u};
+    uint32_t n[N_WORK] = {};
     // (no block bounds here: 0xffffffff lets every candidate through to its sub-block bounds, which are checked
     //  against the best as it stands in keys[pair])
     rotation_pass<CB, true, true>(P, C, k, 0xffffffffu, 0xffffffffu, m0, m1, lane, &P.keys[pair], nullptr, org, n, clk, runs);
-    if (BNB_STATS(P) && lane == 0) flush_stats(BNB_STATS(P), n, pair, nullptr);
+    if (BNB_STATS(P) && lane == 0) flush_stats(BNB_STATS(P), n, pair, nullptr, n + 4);
   }
   if (BNB_STATS(P) && lane == 0) {
     atomicAdd(&BNB_STATS(P)[13], (unsigned long long)(clock64() - t0));  // wave time in the second kernel
@@ -857,7 +888,7 @@ __global__ __launch_bounds__(CAND_THREADS, CB == 2 ? 5 : 4) void csm_bnb_cand_ke
   uint32_t *runs = s_run2 + (threadIdx.x >> 6) * RUN_WAVE;
   PairCtx C;
   pair_context(P, pair, &C);
-  uint32_t n_work[4] = {0u, 0u, 0u, 0u};
+  uint32_t n_work[N_WORK] = {};
   PhaseClocks clk = {0, 0, 0, 0u, 0u, 0u};
   const long long t0 = BNB_STATS(P) ? clock64() : 0;
   for (;;) {
@@ -875,7 +906,7 @@ __global__ __launch_bounds__(CAND_THREADS, CB == 2 ? 5 : 4) void csm_bnb_cand_ke
   }
   if (BNB_STATS(P) && lane == 0) {
     atomicAdd(&BNB_STATS(P)[13], (unsigned long long)(clock64() - t0));
-    flush_stats(BNB_STATS(P), n_work, pair, &clk);
+    flush_stats(BNB_STATS(P), n_work, pair, &clk, n_work + 4);
   }
   if (BNB_TIMELINE(P) && lane == 0 && pair < BNB_STATS_PAIRS)
     atomicMax(&BNB_TIMELINE(P)[5 * (size_t)BNB_STATS_PAIRS + 2 + pair], wall_clock64());

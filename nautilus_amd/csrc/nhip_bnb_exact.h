@@ -52,6 +52,15 @@ __device__ __forceinline__ unsigned long long best_key(const BnbParams &P, int32
   return key;
 }
 
+// ---- the lattice inside a block ----------------------------------------------------------------------------------
+// Of the 8 pose columns (rows) of block column (row) B, the first block_extent(n, B) are poses of a lattice of n columns
+// (rows): 8 everywhere but in the last block column (row) of a lattice that is no multiple of 8.  4 x 4 sub-block (sy, sx) of
+// a block with extents (vy, vx) holds a pose iff 4 sx < vx and 4 sy < vy.  Wave-uniform wherever the block is.
+__device__ __forceinline__ int32_t block_extent(int32_t n, int32_t B) { return min(max(n - BNB_B * B, 0), BNB_B); }
+__device__ __forceinline__ bool sub_valid(int32_t vy, int32_t vx, int32_t sy, int32_t sx) {
+  return BNB_B4 * sx < vx && BNB_B4 * sy < vy;
+}
+
 // ---- exact sums of one 8 x 8 block -----------------------------------------------------------------------
 // Returns the block's best key (sum << 32 | ~linear index) over its valid poses, the same in every lane.
 template <int CB>
@@ -310,6 +319,9 @@ __device__ __forceinline__ unsigned long long eval_sub(const BnbParams &P, __amd
 // + 16 further at its end.
 // 4 x 4 sub-block (sy, sx) of block (Y, X): four 8-byte row loads per point.  Returns the sum of this lane's pose
 // (*dy, *dx inside the sub-block; lanes 16.. hold copies of lanes 0..15).
+// (A sub-block at the lattice's upper edge holds poses in its first rows or columns only, and still reads all 4 x 8 bytes:
+//  reading only those rows, and 4 bytes of a single column, under wave-uniform branches was measured and lost -- the
+//  candidates' kernel 2.35 -> 2.42 ms, its code 4 KB longer; profiles/r16_lattice_edge.txt.)
 __device__ __forceinline__ uint32_t sub_sums8(__amdgpu_buffer_rsrc_t rsrc, uint32_t pitch, uint32_t copy_bytes, const uint32_t *org,
                                               int32_t nch, int32_t Y, int32_t X, int32_t sy, int32_t sx, int lane, int *dy, int *dx) {
   const uint32_t roff = (uint32_t)(BNB_B * Y + BNB_B4 * sy), coff = (uint32_t)(BNB_B * X + BNB_B4 * sx);
