@@ -1,9 +1,10 @@
-// nhip_host.h -- what the host units of the C ABI share (nhip_runtime, nhip_host_csm, nhip_dropin, nhip_host_solver, nhip_host_linsolve): the
-// pooled device buffer, the in-flight guard, the phase clocks, the scan and grid handles.  Host only: no kernel unit
-// includes it.
+// nhip_host.h -- what the host units of the C ABI share (nhip_runtime, nhip_dropin and every nhip_host_*.hip): the pooled
+// device buffer, the in-flight guard, the staged call of the handle forms, the phase clocks, the scan and grid handles.
+// Host only: no kernel unit includes it.
 #pragma once
 #include <atomic>
 #include <chrono>
+#include <deque>
 #include <mutex>
 
 #include "nhip_common.h"
@@ -39,6 +40,36 @@ struct DevBuf {
 // the two buffers of one keyed release (metas `meta_a`, `meta_b`), if both are still in the pool
 bool pool_take_pair(uint64_t meta_a, uint64_t meta_b, size_t need_a, size_t need_b, void **pa, size_t *ba, void **pb, size_t *bb);
 extern std::atomic<uint64_t> g_pool_key;
+
+// One call of a handle form (host arrays in, null stream, host arrays out): the device buffers it stages, its copies and
+// the wait it owes.  Errors are sticky: after the first one every in / out / fetch does nothing and returns null, and the
+// form asks ok() once before it launches, so no null pointer reaches a launcher.  A buffer's size, its copy's size and its
+// element type come from one (T, count).
+class Staged {
+ public:
+  Staged() = default;
+  Staged(const Staged &) = delete;
+  Staged &operator=(const Staged &) = delete;
+  ~Staged();  // work enqueued and not waited for (an error path): waits for the device, then the buffers go back to the pool
+  template <class T> T *out(size_t count) { return static_cast<T *>(stage(nullptr, count * sizeof(T))); }  // (0: a placeholder, not null)
+  template <class T> T *inout(const T *host, size_t count) { return static_cast<T *>(stage(host, count * sizeof(T))); }
+  template <class T> const T *in(const T *host, size_t count) { return inout(host, count); }  // (null host: nothing is copied)
+  template <class T> void fetch(T *host, const T *dev, size_t count) { download(host, dev, count * sizeof(T)); }  // (null host: nothing)
+  bool ok() const { return rc_ == NHIP_OK; }
+  void launched(int rc);  // a launcher's return code: non-zero is the call's error; either way work may be in flight from here
+  int finish();           // the first error, or NHIP_OK with the null stream drained (the downloads did that, if there were any)
+
+ private:
+  void *stage(const void *host, size_t bytes);
+  void download(void *host, const void *dev, size_t bytes);
+  std::deque<DevBuf> bufs_;  // (a deque: growing it moves no DevBuf)
+  int rc_ = NHIP_OK;
+  bool inflight_ = false;
+};
+
+inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }  // (a: a power of two)
+
+constexpr size_t STATS_WORDS = 8;  // a stats block: eight words (int64 in most units, int32 in vectorize)
 
 }  // namespace nhip
 

@@ -10,6 +10,7 @@ using namespace nhip;
 namespace {
 
 constexpr int32_t CHECK_EVERY_DEFAULT = 8;  // (nhip_vectorize's default)
+constexpr size_t RECORD_DOUBLES = 8;        // a match record as the adjacency kernel reads it (include/nautilus_hip.h)
 
 int64_t up256(int64_t v) { return (v + 255) / 256 * 256; }
 int64_t words_of(int32_t M) { return ((int64_t)M + 63) / 64; }
@@ -90,8 +91,7 @@ int nhip_consistency_adjacency_dev(const double *d_records, int32_t M, const nhi
   if (rc || (rc = count_check(M, "consistency_adjacency_dev"))) return rc;
   if ((rc = require_device())) return rc;
   NHIP_REQUIRE(d_stats && (M == 0 || (d_records && d_adj && d_deg)), "consistency_adjacency_dev: null pointer");
-  NHIP_REQUIRE((reinterpret_cast<uintptr_t>(d_records) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_adj) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(d_stats) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_deg) & 3) == 0,
+  NHIP_REQUIRE(aligned(d_records, 8) && aligned(d_adj, 8) && aligned(d_stats, 8) && aligned(d_deg, 4),
                "consistency_adjacency_dev: d_records, d_adj and d_stats must be 8-byte aligned, d_deg 4-byte");
   return launch_consistency_adjacency(d_records, M, tol_of(*spec), reinterpret_cast<unsigned long long *>(d_adj), d_deg,
                                       reinterpret_cast<long long *>(d_stats), static_cast<hipStream_t>(stream));
@@ -107,8 +107,7 @@ int nhip_consistency_set_dev(const uint64_t *d_adj, const int32_t *d_deg, int32_
                (long long)workspace_bytes_given, (long long)workspace_bytes(M));
   if ((rc = require_device())) return rc;
   NHIP_REQUIRE(d_n_members && d_stats && d_workspace && (M == 0 || (d_adj && d_deg && d_members)), "consistency_set_dev: null pointer");
-  NHIP_REQUIRE((reinterpret_cast<uintptr_t>(d_adj) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_stats) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(d_workspace) & 255) == 0,
+  NHIP_REQUIRE(aligned(d_adj, 8) && aligned(d_stats, 8) && aligned(d_workspace, 256),
                "consistency_set_dev: d_adj and d_stats must be 8-byte aligned, d_workspace 256-byte");
   return consistency_set_run(d_adj, d_deg, M, *spec, check_every ? check_every : CHECK_EVERY_DEFAULT, d_members, d_n_members, d_stats,
                              d_workspace, static_cast<hipStream_t>(stream));
@@ -120,25 +119,22 @@ int nhip_consistency(const double *records, int32_t M, const nhip_consistency_sp
   if (rc || (rc = count_check(M, "consistency"))) return rc;
   if ((rc = require_device())) return rc;
   NHIP_REQUIRE(n_members && stats && (M == 0 || (records && members)), "consistency: null pointer");
-  const size_t m1 = (size_t)(M > 0 ? M : 1);
-  DevBuf dr, dm, dn, ds, dw;
-  if ((rc = dr.alloc(64 * m1)) || (rc = dm.alloc(4 * m1)) || (rc = dn.alloc(4)) || (rc = ds.alloc(64)) ||
-      (rc = dw.alloc((size_t)workspace_bytes(M))))
-    return rc;
-  InFlight inflight;
-  if (M) NHIP_TRY_HIP(hipMemcpy(dr.p, records, 64 * (size_t)M, hipMemcpyHostToDevice));
-  uint8_t *base = dw.as<uint8_t>();
-  unsigned long long *d_adj = reinterpret_cast<unsigned long long *>(base + adj_offset());
-  int32_t *d_deg = reinterpret_cast<int32_t *>(base + deg_offset(M));
-  if ((rc = launch_consistency_adjacency(dr.as<const double>(), M, tol_of(*spec), d_adj, d_deg, ds.as<long long>(), nullptr))) return rc;
-  if ((rc = consistency_set_run(reinterpret_cast<const uint64_t *>(d_adj), d_deg, M, *spec, CHECK_EVERY_DEFAULT, dm.as<int32_t>(),
-                                dn.as<int32_t>(), ds.as<int64_t>(), dw.p, nullptr)))
-    return rc;
-  if (M) NHIP_TRY_HIP(hipMemcpy(members, dm.p, 4 * (size_t)M, hipMemcpyDeviceToHost));
-  NHIP_TRY_HIP(hipMemcpy(n_members, dn.p, 4, hipMemcpyDeviceToHost));
-  NHIP_TRY_HIP(hipMemcpy(stats, ds.p, 64, hipMemcpyDeviceToHost));
-  InFlight::done();  // (the downloads above synchronised the null stream)
-  return NHIP_OK;
+  Staged st;
+  const double *dr = st.in(records, RECORD_DOUBLES * (size_t)M);
+  int32_t *dm = st.out<int32_t>((size_t)M), *dn = st.out<int32_t>(1);
+  int64_t *ds = st.out<int64_t>(STATS_WORDS);
+  uint8_t *base = st.out<uint8_t>((size_t)workspace_bytes(M));
+  if (st.ok()) {
+    unsigned long long *d_adj = reinterpret_cast<unsigned long long *>(base + adj_offset());
+    int32_t *d_deg = reinterpret_cast<int32_t *>(base + deg_offset(M));
+    st.launched(launch_consistency_adjacency(dr, M, tol_of(*spec), d_adj, d_deg, reinterpret_cast<long long *>(ds), nullptr));
+    if (st.ok())
+      st.launched(consistency_set_run(reinterpret_cast<const uint64_t *>(d_adj), d_deg, M, *spec, CHECK_EVERY_DEFAULT, dm, dn, ds, base, nullptr));
+  }
+  st.fetch(members, dm, (size_t)M);
+  st.fetch(n_members, dn, 1);
+  st.fetch(stats, ds, STATS_WORDS);
+  return st.finish();
 }
 
 }  // extern "C"

@@ -586,22 +586,15 @@ int nhip_csm_scores(const nhip_scans_t *scans, const nhip_grids_t *grids, int32_
   if ((rc = nhip_csm_rot0(&theta0, nullptr, 1, rot0))) return rc;
   if ((rc = nhip_csm_delta_table(search, delta.data()))) return rc;
   const size_t vol = (size_t)search->n_theta * search->nx * search->ny;
-  DevBuf d_rot0, d_delta, d_vol;
-  if ((rc = d_rot0.alloc(sizeof(rot0))) || (rc = d_delta.alloc(sizeof(double) * delta.size())) ||
-      (rc = d_vol.alloc(sizeof(int32_t) * vol)))
-    return rc;
-  NHIP_TRY_HIP(hipMemcpy(d_rot0.p, rot0, sizeof(rot0), hipMemcpyHostToDevice));
-  NHIP_TRY_HIP(hipMemcpy(d_delta.p, delta.data(), sizeof(double) * delta.size(), hipMemcpyHostToDevice));
+  Staged st;
   MatchJob job = job_on(scans->xy, scans->offsets, *grids, grids->spec);  // (one pair, passed by value below: no pair arrays, ids, keys or records)
-  job.rot0_cs = d_rot0.as<const double>();
-  job.delta_cs = d_delta.as<const double>();
+  job.rot0_cs = st.in(rot0, 2);
+  job.delta_cs = st.in(delta.data(), delta.size());
   job.search = search;
-  InFlight inflight;
-  rc = launch_csm_scores(job, src, slot, origin_x, origin_y, d_vol.as<int32_t>());
-  if (rc) return rc;
-  NHIP_TRY_HIP(hipMemcpy(out_sums, d_vol.p, sizeof(int32_t) * vol, hipMemcpyDeviceToHost));  // (synchronises the null stream)
-  InFlight::done();
-  return NHIP_OK;
+  int32_t *d_vol = st.out<int32_t>(vol);
+  if (st.ok()) st.launched(launch_csm_scores(job, src, slot, origin_x, origin_y, d_vol));
+  st.fetch(out_sums, d_vol, vol);
+  return st.finish();
 }
 
 int nhip_bnb_stats_per_pair(uint64_t *evaluated, int32_t n_pairs) {

@@ -74,20 +74,19 @@ int nhip_features_extract(const nhip_scans_t *scans, const nhip_feature_spec_t *
   NHIP_REQUIRE(scans && (scans->n_scans == 0 || (planar_idx && planar_count && edge_idx && edge_count)), "features_extract: bad arguments");
   if (scans->n_scans == 0) return NHIP_OK;
   const size_t N = (size_t)scans->n_scans, np = N * (size_t)spec->max_planar, ne = N * (size_t)spec->max_edge;
-  DevBuf dpi, dpc, dei, dec, dsc;
-  if ((rc = dpi.alloc(4 * np)) || (rc = dpc.alloc(4 * N)) || (rc = dei.alloc(4 * ne)) || (rc = dec.alloc(4 * N))) return rc;
-  if (scores && scans->n_points && (rc = dsc.alloc(8 * (size_t)scans->n_points))) return rc;
-  InFlight inflight;
-  rc = launch_feat_extract(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), scans->n_scans, *spec, dpi.as<int32_t>(),
-                           dpc.as<int32_t>(), dei.as<int32_t>(), dec.as<int32_t>(), dsc.as<double>(), nullptr);
-  if (rc) return rc;
-  NHIP_TRY_HIP(hipMemcpy(planar_idx, dpi.p, 4 * np, hipMemcpyDeviceToHost));
-  NHIP_TRY_HIP(hipMemcpy(planar_count, dpc.p, 4 * N, hipMemcpyDeviceToHost));
-  NHIP_TRY_HIP(hipMemcpy(edge_idx, dei.p, 4 * ne, hipMemcpyDeviceToHost));
-  NHIP_TRY_HIP(hipMemcpy(edge_count, dec.p, 4 * N, hipMemcpyDeviceToHost));
-  if (dsc.p) NHIP_TRY_HIP(hipMemcpy(scores, dsc.p, 8 * (size_t)scans->n_points, hipMemcpyDeviceToHost));
-  InFlight::done();  // (the downloads above synchronised the null stream)
-  return NHIP_OK;
+  const size_t pts = (size_t)scans->n_points;
+  Staged st;
+  int32_t *dpi = st.out<int32_t>(np), *dpc = st.out<int32_t>(N), *dei = st.out<int32_t>(ne), *dec = st.out<int32_t>(N);
+  double *dsc = scores && pts ? st.out<double>(pts) : nullptr;  // (null: the kernel keeps no scores)
+  if (st.ok())
+    st.launched(launch_feat_extract(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), scans->n_scans, *spec, dpi, dpc,
+                                    dei, dec, dsc, nullptr));
+  st.fetch(planar_idx, dpi, np);
+  st.fetch(planar_count, dpc, N);
+  st.fetch(edge_idx, dei, ne);
+  st.fetch(edge_count, dec, N);
+  st.fetch(scores, dsc, pts);
+  return st.finish();
 }
 
 }  // extern "C"

@@ -8,6 +8,8 @@ using namespace nhip;
 
 namespace {
 
+constexpr size_t FS_COUNTS = 8;  // int32 counts per pair (include/nautilus_hip.h)
+
 // the accepted ranges of include/nautilus_hip.h
 int freespace_spec_check(const nhip_freespace_spec_t *s, const char *who) {
   NHIP_REQUIRE(s, "%s: null free-space spec", who);
@@ -51,7 +53,19 @@ FsParams fs_params(const GridLayout &L, const nhip_grid_spec_t &grid_spec, const
   return P;
 }
 
-bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+// the fields of a check beside fs_params': the pair arrays, the lattice, the spec, the counts
+void fs_check_fields(FsParams &P, const int32_t *d_pair_src, const int32_t *d_pair_slot, const int32_t *d_pair_origin,
+                     const double *d_rot0_cs, const double *d_delta_cs, const nhip_match_t *d_matches, int32_t n_pairs,
+                     const nhip_search_t &search, const nhip_freespace_spec_t &fs_spec, int32_t *d_counts) {
+  P.pair_src = d_pair_src, P.pair_slot = d_pair_slot, P.pair_origin = d_pair_origin;
+  P.rot0_cs = d_rot0_cs, P.delta_cs = d_delta_cs;
+  P.matches = d_matches;
+  P.counts = d_counts;
+  P.n_pairs = n_pairs;
+  P.n_theta = search.n_theta, P.nx = search.nx, P.ny = search.ny;
+  P.hx = (search.nx - 1) / 2, P.hy = (search.ny - 1) / 2;
+  P.hit_radius = fs_spec.hit_radius, P.end_margin = fs_spec.end_margin;
+}
 
 }  // namespace
 
@@ -107,14 +121,7 @@ int nhip_freespace_check_dev(const float *d_xy, const int32_t *d_offsets, int32_
   NHIP_REQUIRE(aligned(d_grids, 4) && aligned(d_free, 4) && aligned(d_matches, 4) && aligned(d_counts, 4),
                "freespace_check_dev: d_grids, d_free, d_matches and d_counts must be 4-byte aligned");
   FsParams P = fs_params(L, *grid_spec, d_xy, d_offsets, n_scans, d_grids, n_grids, const_cast<uint8_t *>(d_free));
-  P.pair_src = d_pair_src, P.pair_slot = d_pair_slot, P.pair_origin = d_pair_origin;
-  P.rot0_cs = d_rot0_cs, P.delta_cs = d_delta_cs;
-  P.matches = d_matches;
-  P.counts = d_counts;
-  P.n_pairs = n_pairs;
-  P.n_theta = search->n_theta, P.nx = search->nx, P.ny = search->ny;
-  P.hx = (search->nx - 1) / 2, P.hy = (search->ny - 1) / 2;
-  P.hit_radius = fs_spec->hit_radius, P.end_margin = fs_spec->end_margin;
+  fs_check_fields(P, d_pair_src, d_pair_slot, d_pair_origin, d_rot0_cs, d_delta_cs, d_matches, n_pairs, *search, *fs_spec, d_counts);
   return launch_fs_check(P, static_cast<hipStream_t>(stream));
 }
 
@@ -143,56 +150,38 @@ int nhip_csm_freespace(const nhip_scans_t *scans, const nhip_grids_t *grids, con
     NHIP_REQUIRE(g->target_ids[(size_t)t] < scans->n_scans, "csm_freespace: slot %d was built from scan %d; these scans hold %d", t,
                  g->target_ids[(size_t)t], scans->n_scans);
   if (n_pairs == 0) return NHIP_OK;
-  InFlight inflight;
+  const size_t N = (size_t)n_pairs;
   {
     // the handle's planes: traced by the first check, under the handle's mutex (concurrent calls are ordered, the loser finds
-    // them traced)
+    // them traced).  A staged call of its own: it has finished, and its list is back in the pool, before the lock is released.
     std::lock_guard<std::mutex> lock(g->mu);
     if (!g->free_traced) {
-      DevBuf ids;
-      if ((rc = g->free_planes.alloc((size_t)g->n * (size_t)L.hits_bytes)) || (rc = ids.alloc(sizeof(int32_t) * (size_t)g->n))) return rc;
-      NHIP_TRY_HIP(hipMemcpy(ids.p, g->target_ids.data(), sizeof(int32_t) * (size_t)g->n, hipMemcpyHostToDevice));
+      if ((rc = g->free_planes.alloc((size_t)g->n * (size_t)L.hits_bytes))) return rc;
+      Staged tr;
       FsParams T = fs_params(L, g->spec, scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), scans->n_scans,
                              g->grids.as<const uint8_t>(), g->n, g->free_planes.as<uint8_t>());
-      T.target_ids = ids.as<const int32_t>();
+      T.target_ids = tr.in(g->target_ids.data(), (size_t)g->n);
       T.n_targets = g->n;
-      if ((rc = launch_fs_trace(T, nullptr))) return rc;
-      NHIP_TRY_HIP(hipStreamSynchronize(nullptr));  // (`ids` goes back to the pool)
+      if (tr.ok()) tr.launched(launch_fs_trace(T, nullptr));
+      if ((rc = tr.finish())) return rc;  // (waits for the null stream)
       g->free_traced = true;
     }
   }
-  std::vector<double> rot0(2 * (size_t)n_pairs), delta(2 * (size_t)search->n_theta);
+  std::vector<double> rot0(2 * N), delta(2 * (size_t)search->n_theta);
   if ((rc = nhip_csm_rot0(theta0, nullptr, n_pairs, rot0.data()))) return rc;
   if ((rc = nhip_csm_delta_table(search, delta.data()))) return rc;
-  DevBuf d_src, d_slot, d_rot0, d_delta, d_org, d_m, d_counts;
-  if ((rc = d_src.alloc(sizeof(int32_t) * (size_t)n_pairs)) || (rc = d_slot.alloc(sizeof(int32_t) * (size_t)n_pairs)) ||
-      (rc = d_rot0.alloc(sizeof(double) * rot0.size())) || (rc = d_delta.alloc(sizeof(double) * delta.size())) ||
-      (rc = d_m.alloc(sizeof(nhip_match_t) * (size_t)n_pairs)) || (rc = d_counts.alloc(sizeof(int32_t) * 8 * (size_t)n_pairs)))
-    return rc;
-  NHIP_TRY_HIP(hipMemcpy(d_src.p, pair_src, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice));
-  NHIP_TRY_HIP(hipMemcpy(d_slot.p, pair_slot, sizeof(int32_t) * (size_t)n_pairs, hipMemcpyHostToDevice));
-  NHIP_TRY_HIP(hipMemcpy(d_rot0.p, rot0.data(), sizeof(double) * rot0.size(), hipMemcpyHostToDevice));
-  NHIP_TRY_HIP(hipMemcpy(d_delta.p, delta.data(), sizeof(double) * delta.size(), hipMemcpyHostToDevice));
-  NHIP_TRY_HIP(hipMemcpy(d_m.p, matches, sizeof(nhip_match_t) * (size_t)n_pairs, hipMemcpyHostToDevice));
-  if (pair_origin) {
-    if ((rc = d_org.alloc(sizeof(int32_t) * 2 * (size_t)n_pairs))) return rc;
-    NHIP_TRY_HIP(hipMemcpy(d_org.p, pair_origin, sizeof(int32_t) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice));
-  }
+  Staged st;
+  const int32_t *d_src = st.in(pair_src, N), *d_slot = st.in(pair_slot, N);
+  const double *d_rot0 = st.in(rot0.data(), rot0.size()), *d_delta = st.in(delta.data(), delta.size());
+  const nhip_match_t *d_m = st.in(matches, N);
+  int32_t *d_counts = st.out<int32_t>(FS_COUNTS * N);
+  const int32_t *d_org = pair_origin ? st.in(pair_origin, 2 * N) : nullptr;  // (null: every pair's window at the slot's origin)
   FsParams P = fs_params(L, g->spec, scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), scans->n_scans,
                          g->grids.as<const uint8_t>(), g->n, g->free_planes.as<uint8_t>());
-  P.pair_src = d_src.as<const int32_t>(), P.pair_slot = d_slot.as<const int32_t>();
-  P.pair_origin = pair_origin ? d_org.as<const int32_t>() : nullptr;
-  P.rot0_cs = d_rot0.as<const double>(), P.delta_cs = d_delta.as<const double>();
-  P.matches = d_m.as<const nhip_match_t>();
-  P.counts = d_counts.as<int32_t>();
-  P.n_pairs = n_pairs;
-  P.n_theta = search->n_theta, P.nx = search->nx, P.ny = search->ny;
-  P.hx = (search->nx - 1) / 2, P.hy = (search->ny - 1) / 2;
-  P.hit_radius = fs_spec->hit_radius, P.end_margin = fs_spec->end_margin;
-  if ((rc = launch_fs_check(P, nullptr))) return rc;
-  NHIP_TRY_HIP(hipMemcpy(counts, d_counts.p, sizeof(int32_t) * 8 * (size_t)n_pairs, hipMemcpyDeviceToHost));  // (synchronises the null stream)
-  InFlight::done();
-  return NHIP_OK;
+  fs_check_fields(P, d_src, d_slot, d_org, d_rot0, d_delta, d_m, n_pairs, *search, *fs_spec, d_counts);
+  if (st.ok()) st.launched(launch_fs_check(P, nullptr));
+  st.fetch(counts, d_counts, FS_COUNTS * N);
+  return st.finish();
 }
 
 }  // extern "C"

@@ -58,17 +58,15 @@ int nhip_normals_estimate(const nhip_scans_t *scans, const nhip_normals_spec_t *
   NHIP_REQUIRE(scans && (scans->n_points == 0 || normals), "normals_estimate: bad arguments");
   if (scans->n_scans == 0 || scans->n_points == 0) return NHIP_OK;
   const size_t np = (size_t)scans->n_points;
-  DevBuf dn, di;
-  if ((rc = dn.alloc(8 * np))) return rc;
-  if (info && (rc = di.alloc(16 * np))) return rc;
-  InFlight inflight;
-  rc = launch_normals_estimate(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), scans->n_scans, *spec, limit,
-                               dn.as<float>(), di.as<int32_t>(), nullptr);
-  if (rc) return rc;
-  NHIP_TRY_HIP(hipMemcpy(normals, dn.p, 8 * np, hipMemcpyDeviceToHost));
-  if (di.p) NHIP_TRY_HIP(hipMemcpy(info, di.p, 16 * np, hipMemcpyDeviceToHost));
-  InFlight::done();  // (the downloads above synchronised the null stream)
-  return NHIP_OK;
+  Staged st;
+  float *dn = st.out<float>(2 * np);
+  int32_t *di = info ? st.out<int32_t>(4 * np) : nullptr;  // (null: the kernel keeps no info)
+  if (st.ok())
+    st.launched(launch_normals_estimate(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), scans->n_scans, *spec, limit,
+                                        dn, di, nullptr));
+  st.fetch(normals, dn, 2 * np);
+  st.fetch(info, di, 4 * np);
+  return st.finish();
 }
 
 }  // extern "C"

@@ -62,8 +62,7 @@ int nhip_occupancy_dev(const float *d_xy, const int32_t *d_offsets, const float 
   if ((rc = require_device())) return rc;
   NHIP_REQUIRE(d_hits && d_misses && d_grid && d_stats && (n_scans == 0 || (d_xy && d_offsets && d_affines)),
                "occupancy_dev: null pointer");
-  NHIP_REQUIRE(((reinterpret_cast<uintptr_t>(d_hits) | reinterpret_cast<uintptr_t>(d_misses)) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(d_grid) & 3) == 0 && (reinterpret_cast<uintptr_t>(d_stats) & 7) == 0,
+  NHIP_REQUIRE(aligned(d_hits, 16) && aligned(d_misses, 16) && aligned(d_grid, 4) && aligned(d_stats, 8),
                "occupancy_dev: d_hits and d_misses must be 16-byte aligned, d_grid 4-byte, d_stats 8-byte");
   return occupancy_run(d_xy, d_offsets, d_affines, n_scans, *spec, d_hits, d_misses, d_grid, d_stats, static_cast<hipStream_t>(stream));
 }
@@ -75,27 +74,21 @@ int nhip_occupancy(const nhip_scans_t *scans, const double *poses, const nhip_oc
   NHIP_REQUIRE(scans && hits && misses && grid && stats && (scans->n_scans == 0 || poses), "occupancy: bad arguments");
   const int32_t n = scans->n_scans;
   const size_t cells = (size_t)spec->width * (size_t)spec->height;
-  std::vector<float> aff(4 * (size_t)(n > 0 ? n : 1));
+  const bool keep = spec->flags & NHIP_OCC_ACCUMULATE;  // (the planes given are uploaded and added to)
+  std::vector<float> aff(4 * (size_t)n);
   if ((rc = nhip_map_pose_affines(poses, n, aff.data()))) return rc;
-  DevBuf da, dh, dm, dg, ds;
-  if ((rc = da.alloc(4 * aff.size())) || (rc = dh.alloc(4 * cells)) || (rc = dm.alloc(4 * cells)) || (rc = dg.alloc(cells + 4)) ||
-      (rc = ds.alloc(64)))
-    return rc;
-  InFlight inflight;
-  NHIP_TRY_HIP(hipMemcpy(da.p, aff.data(), 4 * aff.size(), hipMemcpyHostToDevice));
-  if (spec->flags & NHIP_OCC_ACCUMULATE) {
-    NHIP_TRY_HIP(hipMemcpy(dh.p, hits, 4 * cells, hipMemcpyHostToDevice));
-    NHIP_TRY_HIP(hipMemcpy(dm.p, misses, 4 * cells, hipMemcpyHostToDevice));
-  }
-  rc = occupancy_run(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), da.as<const float>(), n, *spec,
-                     dh.as<int32_t>(), dm.as<int32_t>(), dg.as<int8_t>(), ds.as<int64_t>(), nullptr);
-  if (rc) return rc;
-  NHIP_TRY_HIP(hipMemcpy(hits, dh.p, 4 * cells, hipMemcpyDeviceToHost));
-  NHIP_TRY_HIP(hipMemcpy(misses, dm.p, 4 * cells, hipMemcpyDeviceToHost));
-  NHIP_TRY_HIP(hipMemcpy(grid, dg.p, cells, hipMemcpyDeviceToHost));
-  NHIP_TRY_HIP(hipMemcpy(stats, ds.p, 64, hipMemcpyDeviceToHost));
-  InFlight::done();  // (the downloads above synchronised the null stream)
-  return NHIP_OK;
+  Staged st;
+  const float *da = st.in(aff.data(), aff.size());
+  int32_t *dh = st.inout(keep ? hits : nullptr, cells), *dm = st.inout(keep ? misses : nullptr, cells);
+  int8_t *dg = st.out<int8_t>(cells + 4);  // (the kernel writes the grid in words)
+  int64_t *ds = st.out<int64_t>(STATS_WORDS);
+  if (st.ok())
+    st.launched(occupancy_run(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), da, n, *spec, dh, dm, dg, ds, nullptr));
+  st.fetch(hits, dh, cells);
+  st.fetch(misses, dm, cells);
+  st.fetch(grid, dg, cells);
+  st.fetch(stats, ds, STATS_WORDS);
+  return st.finish();
 }
 
 }  // extern "C"

@@ -34,6 +34,13 @@ void place_tables(const nhip_place_spec_t &s, float *edge2, float *dir) {
   for (int j = 0; j < 32; j++) dir[2 * j] = (float)std::cos(two_pi * j / 64), dir[2 * j + 1] = (float)std::sin(two_pi * j / 64);
 }
 
+PlaceTables place_tables_of(const nhip_place_spec_t &s) {
+  PlaceTables T;
+  T.n_rings = s.n_rings;
+  place_tables(s, T.edge2, T.dir);
+  return T;
+}
+
 int64_t place_row_bytes(int32_t n_ids) { return 2 * (((int64_t)n_ids + 63) & ~63ll); }
 
 // the arguments have been checked
@@ -106,6 +113,42 @@ int place_seq_run(const uint64_t *d_desc, const int32_t *d_bits, int32_t n_scans
   return launch_place_seq_match(P, (int32_t)S, s);
 }
 
+// ---- the handle forms ----
+// what they ask of their list: ids of the handle's scans, strictly ascending
+int place_ids_check(const int32_t *ids, int32_t n_ids, int32_t n_scans, const char *who) {
+  for (int32_t b = 0; b < n_ids; b++) {
+    NHIP_REQUIRE(ids[b] >= 0 && ids[b] < n_scans, "%s: ids[%d] = %d outside the %d scans", who, b, ids[b], n_scans);
+    NHIP_REQUIRE(b == 0 || ids[b] > ids[b - 1], "%s: ids[%d] = %d after %d: the list must ascend strictly", who, b, ids[b], ids[b - 1]);
+  }
+  return NHIP_OK;
+}
+
+// on checked arguments: describe every scan, then match the list -- window sums where `seq` is given, single scans otherwise
+int place_candidates_run(const nhip_scans_t *scans, const int32_t *ids, int32_t n_ids, const nhip_place_spec_t &spec,
+                         const nhip_place_seq_spec_t *seq, int32_t *records, int64_t *stats, uint64_t *desc, int32_t *bits) {
+  const int32_t n = scans->n_scans;
+  const size_t n_desc = (size_t)spec.n_rings * (size_t)n;
+  const size_t n_rec = (seq ? 8 : 4) * (size_t)spec.top_k * (size_t)n_ids;  // (int32 words: a sequence record is twice a single one)
+  const int64_t ws_bytes = seq ? nhip_place_seq_workspace_bytes(&spec, seq, n, n_ids) : nhip_place_workspace_bytes(&spec, n_ids);
+  Staged st;
+  uint64_t *dd = st.out<uint64_t>(n_desc);
+  int32_t *db = st.out<int32_t>((size_t)n);
+  const int32_t *di = st.in(ids, (size_t)n_ids);
+  int32_t *dr = st.out<int32_t>(n_rec);
+  int64_t *ds = st.out<int64_t>(STATS_WORDS);
+  uint8_t *dw = st.out<uint8_t>((size_t)ws_bytes);
+  if (st.ok())
+    st.launched(launch_place_describe(place_tables_of(spec), scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), n, dd, db, nullptr));
+  if (st.ok())
+    st.launched(seq ? place_seq_run(dd, db, n, di, n_ids, spec, *seq, dr, ds, dw, ws_bytes, nullptr)
+                    : place_match_run(dd, db, n, di, n_ids, spec, dr, ds, dw, ws_bytes, nullptr));
+  st.fetch(records, dr, n_rec);
+  st.fetch(stats, ds, STATS_WORDS);
+  st.fetch(desc, dd, n_desc);
+  st.fetch(bits, db, (size_t)n);
+  return st.finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -147,11 +190,8 @@ int nhip_place_describe_dev(const float *d_xy, const int32_t *d_offsets, int32_t
   NHIP_REQUIRE(n_scans >= 0, "place_describe_dev: n_scans %d must be >= 0", n_scans);
   if ((rc = require_device())) return rc;
   NHIP_REQUIRE(n_scans == 0 || (d_xy && d_offsets && d_desc && d_bits), "place_describe_dev: null pointer");
-  NHIP_REQUIRE((reinterpret_cast<uintptr_t>(d_desc) & 7) == 0, "place_describe_dev: d_desc must be 8-byte aligned");
-  PlaceTables T;
-  T.n_rings = spec->n_rings;
-  place_tables(*spec, T.edge2, T.dir);
-  return launch_place_describe(T, d_xy, d_offsets, n_scans, d_desc, d_bits, static_cast<hipStream_t>(stream));
+  NHIP_REQUIRE(aligned(d_desc, 8), "place_describe_dev: d_desc must be 8-byte aligned");
+  return launch_place_describe(place_tables_of(*spec), d_xy, d_offsets, n_scans, d_desc, d_bits, static_cast<hipStream_t>(stream));
 }
 
 int nhip_place_match_dev(const uint64_t *d_desc, const int32_t *d_bits, int32_t n_scans, const int32_t *d_ids, int32_t n_ids,
@@ -163,8 +203,7 @@ int nhip_place_match_dev(const uint64_t *d_desc, const int32_t *d_bits, int32_t 
                n_ids, PLACE_MAX_IDS);
   if ((rc = require_device())) return rc;
   NHIP_REQUIRE(d_stats && (n_ids == 0 || (d_desc && d_bits && d_ids && d_records && d_workspace)), "place_match_dev: null pointer");
-  NHIP_REQUIRE((reinterpret_cast<uintptr_t>(d_desc) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_stats) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(d_workspace) & 1) == 0,
+  NHIP_REQUIRE(aligned(d_desc, 8) && aligned(d_stats, 8) && aligned(d_workspace, 2),
                "place_match_dev: d_desc and d_stats must be 8-byte aligned, d_workspace 2-byte");
   return place_match_run(d_desc, d_bits, n_scans, d_ids, n_ids, *spec, d_records, d_stats, d_workspace, workspace_bytes,
                          static_cast<hipStream_t>(stream));
@@ -175,35 +214,8 @@ int nhip_place_candidates(const nhip_scans_t *scans, const int32_t *ids, int32_t
   int rc = place_spec_check(spec, true, "place_candidates");
   if (rc || (rc = require_device())) return rc;
   NHIP_REQUIRE(scans && stats && n_ids >= 0 && n_ids <= PLACE_MAX_IDS && (n_ids == 0 || (ids && records)), "place_candidates: bad arguments");
-  const int32_t n = scans->n_scans;
-  for (int32_t b = 0; b < n_ids; b++) {
-    NHIP_REQUIRE(ids[b] >= 0 && ids[b] < n, "place_candidates: ids[%d] = %d outside the %d scans", b, ids[b], n);
-    NHIP_REQUIRE(b == 0 || ids[b] > ids[b - 1], "place_candidates: ids[%d] = %d after %d: the list must ascend strictly", b, ids[b], ids[b - 1]);
-  }
-  const size_t R = (size_t)spec->n_rings, K = (size_t)spec->top_k;
-  const int64_t ws_bytes = nhip_place_workspace_bytes(spec, n_ids);
-  DevBuf dd, db, di, dr, ds, dw;
-  if ((rc = dd.alloc(8 * R * (size_t)(n > 0 ? n : 1))) || (rc = db.alloc(4 * (size_t)(n > 0 ? n : 1))) ||
-      (rc = di.alloc(4 * (size_t)(n_ids > 0 ? n_ids : 1))) || (rc = dr.alloc(16 * K * (size_t)(n_ids > 0 ? n_ids : 1))) ||
-      (rc = ds.alloc(64)) || (rc = dw.alloc((size_t)ws_bytes)))
-    return rc;
-  InFlight inflight;
-  if (n_ids) NHIP_TRY_HIP(hipMemcpy(di.p, ids, 4 * (size_t)n_ids, hipMemcpyHostToDevice));
-  PlaceTables T;
-  T.n_rings = spec->n_rings;
-  place_tables(*spec, T.edge2, T.dir);
-  if ((rc = launch_place_describe(T, scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), n, dd.as<uint64_t>(),
-                                  db.as<int32_t>(), nullptr)))
-    return rc;
-  if ((rc = place_match_run(dd.as<const uint64_t>(), db.as<const int32_t>(), n, di.as<const int32_t>(), n_ids, *spec, dr.as<int32_t>(),
-                            ds.as<int64_t>(), dw.p, ws_bytes, nullptr)))
-    return rc;
-  if (n_ids) NHIP_TRY_HIP(hipMemcpy(records, dr.p, 16 * K * (size_t)n_ids, hipMemcpyDeviceToHost));
-  NHIP_TRY_HIP(hipMemcpy(stats, ds.p, 64, hipMemcpyDeviceToHost));
-  if (desc && n) NHIP_TRY_HIP(hipMemcpy(desc, dd.p, 8 * R * (size_t)n, hipMemcpyDeviceToHost));
-  if (bits && n) NHIP_TRY_HIP(hipMemcpy(bits, db.p, 4 * (size_t)n, hipMemcpyDeviceToHost));
-  InFlight::done();  // (the downloads above synchronised the null stream)
-  return NHIP_OK;
+  if ((rc = place_ids_check(ids, n_ids, scans->n_scans, "place_candidates"))) return rc;
+  return place_candidates_run(scans, ids, n_ids, *spec, nullptr, records, stats, desc, bits);
 }
 
 int nhip_place_seq_spec_default(nhip_place_seq_spec_t *out) {
@@ -238,8 +250,7 @@ int nhip_place_seq_match_dev(const uint64_t *d_desc, const int32_t *d_bits, int3
   if ((rc = require_device())) return rc;
   NHIP_REQUIRE(d_stats && (n_ids == 0 || (d_ids && d_records && d_workspace && (n_scans == 0 || (d_desc && d_bits)))),
                "place_seq_match_dev: null pointer");
-  NHIP_REQUIRE((reinterpret_cast<uintptr_t>(d_desc) & 7) == 0 && (reinterpret_cast<uintptr_t>(d_stats) & 7) == 0 &&
-                   (reinterpret_cast<uintptr_t>(d_workspace) & 1) == 0,
+  NHIP_REQUIRE(aligned(d_desc, 8) && aligned(d_stats, 8) && aligned(d_workspace, 2),
                "place_seq_match_dev: d_desc and d_stats must be 8-byte aligned, d_workspace 2-byte");
   return place_seq_run(d_desc, d_bits, n_scans, d_ids, n_ids, *spec, *seq, d_records, d_stats, d_workspace, workspace_bytes,
                        static_cast<hipStream_t>(stream));
@@ -250,33 +261,8 @@ int nhip_place_seq_candidates(const nhip_scans_t *scans, const int32_t *ids, int
   int rc = place_seq_spec_check(spec, seq, "place_seq_candidates");
   if (rc || (rc = require_device())) return rc;
   NHIP_REQUIRE(scans && stats && n_ids >= 0 && n_ids <= PLACE_MAX_IDS && (n_ids == 0 || (ids && records)), "place_seq_candidates: bad arguments");
-  const int32_t n = scans->n_scans;
-  for (int32_t b = 0; b < n_ids; b++) {
-    NHIP_REQUIRE(ids[b] >= 0 && ids[b] < n, "place_seq_candidates: ids[%d] = %d outside the %d scans", b, ids[b], n);
-    NHIP_REQUIRE(b == 0 || ids[b] > ids[b - 1], "place_seq_candidates: ids[%d] = %d after %d: the list must ascend strictly", b, ids[b], ids[b - 1]);
-  }
-  const size_t R = (size_t)spec->n_rings, K = (size_t)spec->top_k;
-  const int64_t ws_bytes = nhip_place_seq_workspace_bytes(spec, seq, n, n_ids);
-  DevBuf dd, db, di, dr, ds, dw;
-  if ((rc = dd.alloc(8 * R * (size_t)(n > 0 ? n : 1))) || (rc = db.alloc(4 * (size_t)(n > 0 ? n : 1))) ||
-      (rc = di.alloc(4 * (size_t)(n_ids > 0 ? n_ids : 1))) || (rc = dr.alloc(32 * K * (size_t)(n_ids > 0 ? n_ids : 1))) ||
-      (rc = ds.alloc(64)) || (rc = dw.alloc((size_t)ws_bytes)))
-    return rc;
-  InFlight inflight;
-  if (n_ids) NHIP_TRY_HIP(hipMemcpy(di.p, ids, 4 * (size_t)n_ids, hipMemcpyHostToDevice));
-  PlaceTables T;
-  T.n_rings = spec->n_rings;
-  place_tables(*spec, T.edge2, T.dir);
-  if ((rc = launch_place_describe(T, scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), n, dd.as<uint64_t>(),
-                                  db.as<int32_t>(), nullptr)))
-    return rc;
-  if ((rc = place_seq_run(dd.as<const uint64_t>(), db.as<const int32_t>(), n, di.as<const int32_t>(), n_ids, *spec, *seq,
-                          dr.as<int32_t>(), ds.as<int64_t>(), dw.p, ws_bytes, nullptr)))
-    return rc;
-  if (n_ids) NHIP_TRY_HIP(hipMemcpy(records, dr.p, 32 * K * (size_t)n_ids, hipMemcpyDeviceToHost));
-  NHIP_TRY_HIP(hipMemcpy(stats, ds.p, 64, hipMemcpyDeviceToHost));
-  InFlight::done();  // (the downloads above synchronised the null stream)
-  return NHIP_OK;
+  if ((rc = place_ids_check(ids, n_ids, scans->n_scans, "place_seq_candidates"))) return rc;
+  return place_candidates_run(scans, ids, n_ids, *spec, seq, records, stats, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -206,7 +206,7 @@ int nhip_hitl_select_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_
   if ((rc = require_device())) return rc;
   NHIP_REQUIRE(d_totals && (n_scans == 0 || (d_xy && d_offsets && d_pose_f32 && d_class && d_counts && d_scan_block && d_scan_offset)),
                "hitl_select_dev: null pointer");
-  NHIP_REQUIRE((reinterpret_cast<uintptr_t>(d_pose_f32) & 15) == 0, "hitl_select_dev: d_pose_f32 must be 16-byte aligned");
+  NHIP_REQUIRE(aligned(d_pose_f32, 16), "hitl_select_dev: d_pose_f32 must be 16-byte aligned");
   return launch_hitl_select(d_xy, d_offsets, n_scans, d_pose_f32, *spec, d_class, d_counts, d_scan_block, d_scan_offset, d_totals,
                             static_cast<hipStream_t>(stream));
 }
@@ -259,7 +259,7 @@ int nhip_lc_chi_square_gate_dev(const double *d_poses, int32_t n_poses, const in
   if (rc) return rc;
   NHIP_REQUIRE(n_pairs >= 0 && n_poses >= 0 && (n_pairs == 0 || (d_poses && d_pair_src && d_pair_tgt && d_cov && d_scores && d_flags)),
                "lc_chi_square_gate_dev: bad arguments");
-  NHIP_REQUIRE((reinterpret_cast<uintptr_t>(d_cov) & 15) == 0, "lc_chi_square_gate_dev: d_cov must be 16-byte aligned");
+  NHIP_REQUIRE(aligned(d_cov, 16), "lc_chi_square_gate_dev: d_cov must be 16-byte aligned");
   return launch_lc_chi_square(d_poses, n_poses, d_pair_src, d_pair_tgt, d_cov, n_pairs, max_score, d_scores, d_flags,
                               static_cast<hipStream_t>(stream));
 }
@@ -275,22 +275,16 @@ int nhip_lc_chi_square_gate(const double *poses, int32_t n_poses, const int32_t 
                  "lc_chi_square_gate: pair %d (%d, %d) out of range", i, pair_src[i], pair_tgt[i]);
   if (n == 0) return NHIP_OK;
   const size_t N = (size_t)n;
-  DevBuf dp, ds, dt, dc, dsc, df;
-  if ((rc = dp.alloc(sizeof(double) * 3 * (size_t)n_poses)) || (rc = ds.alloc(4 * N)) || (rc = dt.alloc(4 * N)) ||
-      (rc = dc.alloc(16 * N)) || (rc = dsc.alloc(8 * N)) || (rc = df.alloc(N)))
-    return rc;
-  NHIP_TRY_HIP(hipMemcpy(dp.p, poses, sizeof(double) * 3 * (size_t)n_poses, hipMemcpyHostToDevice));
-  NHIP_TRY_HIP(hipMemcpy(ds.p, pair_src, 4 * N, hipMemcpyHostToDevice));
-  NHIP_TRY_HIP(hipMemcpy(dt.p, pair_tgt, 4 * N, hipMemcpyHostToDevice));
-  NHIP_TRY_HIP(hipMemcpy(dc.p, cov, 16 * N, hipMemcpyHostToDevice));
-  InFlight inflight;
-  rc = launch_lc_chi_square(dp.as<const double>(), n_poses, ds.as<const int32_t>(), dt.as<const int32_t>(), dc.as<const float>(), n,
-                            max_score, dsc.as<double>(), df.as<uint8_t>(), nullptr);
-  if (rc) return rc;
-  NHIP_TRY_HIP(hipMemcpy(scores, dsc.p, 8 * N, hipMemcpyDeviceToHost));
-  NHIP_TRY_HIP(hipMemcpy(flags, df.p, N, hipMemcpyDeviceToHost));
-  InFlight::done();  // (the downloads above synchronised the null stream)
-  return NHIP_OK;
+  Staged st;
+  const double *dp = st.in(poses, 3 * (size_t)n_poses);
+  const int32_t *ds = st.in(pair_src, N), *dt = st.in(pair_tgt, N);
+  const float *dc = st.in(cov, 4 * N);
+  double *dsc = st.out<double>(N);
+  uint8_t *df = st.out<uint8_t>(N);
+  if (st.ok()) st.launched(launch_lc_chi_square(dp, n_poses, ds, dt, dc, n, max_score, dsc, df, nullptr));
+  st.fetch(scores, dsc, N);
+  st.fetch(flags, df, N);
+  return st.finish();
 }
 
 int nhip_lc_scatter_scores(const nhip_scans_t *scans, double *scores) {
@@ -298,14 +292,12 @@ int nhip_lc_scatter_scores(const nhip_scans_t *scans, double *scores) {
   if (rc) return rc;
   NHIP_REQUIRE(scans && (scores || scans->n_scans == 0), "lc_scatter_scores: bad arguments");
   if (scans->n_scans == 0) return NHIP_OK;
-  DevBuf d;
-  if ((rc = d.alloc(sizeof(double) * (size_t)scans->n_scans))) return rc;
-  InFlight inflight;
-  rc = launch_lc_scatter_scores(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), scans->n_scans, d.as<double>(), nullptr);
-  if (rc) return rc;
-  NHIP_TRY_HIP(hipMemcpy(scores, d.p, sizeof(double) * (size_t)scans->n_scans, hipMemcpyDeviceToHost));
-  InFlight::done();  // (the downloads above synchronised the null stream)
-  return NHIP_OK;
+  Staged st;
+  double *d = st.out<double>((size_t)scans->n_scans);
+  if (st.ok())
+    st.launched(launch_lc_scatter_scores(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), scans->n_scans, d, nullptr));
+  st.fetch(scores, d, (size_t)scans->n_scans);
+  return st.finish();
 }
 
 int nhip_lc_pair_gate(const double *poses, int32_t n_poses, const int32_t *candidates, int32_t n, double max_range,
@@ -316,18 +308,13 @@ int nhip_lc_pair_gate(const double *poses, int32_t n_poses, const int32_t *candi
   for (int32_t i = 0; i < n; i++)
     NHIP_REQUIRE(candidates[i] >= 0 && candidates[i] < n_poses, "lc_pair_gate: candidate %d out of range", candidates[i]);
   if (n == 0) return NHIP_OK;
-  DevBuf dp, dc, df;
-  if ((rc = dp.alloc(sizeof(double) * 3 * (size_t)n_poses)) || (rc = dc.alloc(sizeof(int32_t) * (size_t)n)) ||
-      (rc = df.alloc((size_t)n * n)))
-    return rc;
-  NHIP_TRY_HIP(hipMemcpy(dp.p, poses, sizeof(double) * 3 * (size_t)n_poses, hipMemcpyHostToDevice));
-  NHIP_TRY_HIP(hipMemcpy(dc.p, candidates, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  InFlight inflight;
-  rc = launch_lc_pair_gate(dp.as<const double>(), n_poses, dc.as<const int32_t>(), n, max_range, min_separation, df.as<uint8_t>(), nullptr);
-  if (rc) return rc;
-  NHIP_TRY_HIP(hipMemcpy(flags, df.p, (size_t)n * n, hipMemcpyDeviceToHost));
-  InFlight::done();  // (the downloads above synchronised the null stream)
-  return NHIP_OK;
+  Staged st;
+  const double *dp = st.in(poses, 3 * (size_t)n_poses);
+  const int32_t *dc = st.in(candidates, (size_t)n);
+  uint8_t *df = st.out<uint8_t>((size_t)n * n);
+  if (st.ok()) st.launched(launch_lc_pair_gate(dp, n_poses, dc, n, max_range, min_separation, df, nullptr));
+  st.fetch(flags, df, (size_t)n * n);
+  return st.finish();
 }
 
 // ---------------------------------------------------------------- residual batches and the host-buffer residual forms
@@ -517,14 +504,6 @@ int nhip_resid_batch_free(nhip_resid_batch_t *batch) {
   return NHIP_OK;
 }
 
-// upload n bytes (n may be 0)
-static int up(DevBuf &d, const void *h, size_t n) {
-  int rc = d.alloc(n);
-  if (rc) return rc;
-  if (n) NHIP_TRY_HIP(hipMemcpy(d.p, h, n, hipMemcpyHostToDevice));
-  return NHIP_OK;
-}
-
 int nhip_resid_odometry(const float *t_odom, const float *r_odom, const int32_t *pose_i,
                         const int32_t *pose_j, int32_t n, double tw, double rw, const double *poses,
                         int32_t n_poses, double *residuals, double *jac_i, double *jac_j) {
@@ -536,22 +515,18 @@ int nhip_resid_odometry(const float *t_odom, const float *r_odom, const int32_t 
   for (int32_t f = 0; f < n; f++)
     NHIP_REQUIRE(pose_i[f] >= 0 && pose_i[f] < n_poses && pose_j[f] >= 0 && pose_j[f] < n_poses,
                  "resid_odometry: factor %d pose index out of range", f);
-  DevBuf dt, dr, di, dj, dp, res, ji, jj;
-  if ((rc = up(dt, t_odom, sizeof(float) * 2 * (size_t)n)) || (rc = up(dr, r_odom, sizeof(float) * (size_t)n)) ||
-      (rc = up(di, pose_i, sizeof(int32_t) * (size_t)n)) || (rc = up(dj, pose_j, sizeof(int32_t) * (size_t)n)) ||
-      (rc = up(dp, poses, sizeof(double) * 3 * (size_t)n_poses)) || (rc = res.alloc(sizeof(double) * 3 * (size_t)n)) ||
-      (rc = ji.alloc(sizeof(double) * 9 * (size_t)n)) || (rc = jj.alloc(sizeof(double) * 9 * (size_t)n)))
-    return rc;
-  InFlight inflight;
-  rc = launch_resid_odometry(dt.as<const float>(), dr.as<const float>(), di.as<const int32_t>(), dj.as<const int32_t>(), n, tw, rw,
-                             dp.as<const double>(), n_poses, res.as<double>(), jac_i ? ji.as<double>() : nullptr,
-                             jac_j ? jj.as<double>() : nullptr, nullptr);
-  if (rc) return rc;
-  NHIP_TRY_HIP(hipMemcpy(residuals, res.p, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost));
-  if (jac_i) NHIP_TRY_HIP(hipMemcpy(jac_i, ji.p, sizeof(double) * 9 * (size_t)n, hipMemcpyDeviceToHost));
-  if (jac_j) NHIP_TRY_HIP(hipMemcpy(jac_j, jj.p, sizeof(double) * 9 * (size_t)n, hipMemcpyDeviceToHost));
-  InFlight::done();  // (the downloads above synchronised the null stream)
-  return NHIP_OK;
+  const size_t N = (size_t)n;
+  Staged st;
+  const float *dt = st.in(t_odom, 2 * N), *dr = st.in(r_odom, N);
+  const int32_t *di = st.in(pose_i, N), *dj = st.in(pose_j, N);
+  const double *dp = st.in(poses, 3 * (size_t)n_poses);
+  double *res = st.out<double>(3 * N), *ji = st.out<double>(9 * N), *jj = st.out<double>(9 * N);
+  if (st.ok())
+    st.launched(launch_resid_odometry(dt, dr, di, dj, n, tw, rw, dp, n_poses, res, jac_i ? ji : nullptr, jac_j ? jj : nullptr, nullptr));
+  st.fetch(residuals, res, 3 * N);
+  st.fetch(jac_i, ji, 9 * N);
+  st.fetch(jac_j, jj, 9 * N);
+  return st.finish();
 }
 
 int nhip_resid_point_to_line(const float *segments, const float *points, const int32_t *point_block,
@@ -571,24 +546,19 @@ int nhip_resid_point_to_line(const float *segments, const float *points, const i
   for (int64_t i = 0; i < n_points; i++)
     NHIP_REQUIRE(point_block[i] >= 0 && point_block[i] < n_blocks, "resid_point_to_line: point %lld block out of range",
                  (long long)i);
-  DevBuf ds, dpt, dpb, dbp, dbl, dp, dl, res, j0, j1;
-  if ((rc = up(ds, segments, sizeof(float) * 4 * (size_t)n_blocks)) || (rc = up(dpt, points, sizeof(float) * 2 * (size_t)n_points)) ||
-      (rc = up(dpb, point_block, sizeof(int32_t) * (size_t)n_points)) || (rc = up(dbp, block_pose, sizeof(int32_t) * (size_t)n_blocks)) ||
-      (rc = up(dbl, block_line, sizeof(int32_t) * (size_t)n_blocks)) || (rc = up(dp, poses, sizeof(double) * 3 * (size_t)n_poses)) ||
-      (rc = up(dl, line_poses, sizeof(double) * 3 * (size_t)n_line_poses)) || (rc = res.alloc(sizeof(double) * (size_t)n_points)) ||
-      (rc = j0.alloc(sizeof(double) * 3 * (size_t)n_points)) || (rc = j1.alloc(sizeof(double) * 3 * (size_t)n_points)))
-    return rc;
-  InFlight inflight;
-  rc = launch_resid_point_to_line(ds.as<const float>(), dpt.as<const float>(), dpb.as<const int32_t>(), n_points,
-                                  dbp.as<const int32_t>(), dbl.as<const int32_t>(), n_blocks, dp.as<const double>(), n_poses,
-                                  dl.as<const double>(), n_line_poses, res.as<double>(), jac_pose ? j0.as<double>() : nullptr,
-                                  jac_line ? j1.as<double>() : nullptr, nullptr);
-  if (rc) return rc;
-  NHIP_TRY_HIP(hipMemcpy(residuals, res.p, sizeof(double) * (size_t)n_points, hipMemcpyDeviceToHost));
-  if (jac_pose) NHIP_TRY_HIP(hipMemcpy(jac_pose, j0.p, sizeof(double) * 3 * (size_t)n_points, hipMemcpyDeviceToHost));
-  if (jac_line) NHIP_TRY_HIP(hipMemcpy(jac_line, j1.p, sizeof(double) * 3 * (size_t)n_points, hipMemcpyDeviceToHost));
-  InFlight::done();  // (the downloads above synchronised the null stream)
-  return NHIP_OK;
+  const size_t NP = (size_t)n_points, NB = (size_t)n_blocks;
+  Staged st;
+  const float *ds = st.in(segments, 4 * NB), *dpt = st.in(points, 2 * NP);
+  const int32_t *dpb = st.in(point_block, NP), *dbp = st.in(block_pose, NB), *dbl = st.in(block_line, NB);
+  const double *dp = st.in(poses, 3 * (size_t)n_poses), *dl = st.in(line_poses, 3 * (size_t)n_line_poses);
+  double *res = st.out<double>(NP), *j0 = st.out<double>(3 * NP), *j1 = st.out<double>(3 * NP);
+  if (st.ok())
+    st.launched(launch_resid_point_to_line(ds, dpt, dpb, n_points, dbp, dbl, n_blocks, dp, n_poses, dl, n_line_poses, res,
+                                           jac_pose ? j0 : nullptr, jac_line ? j1 : nullptr, nullptr));
+  st.fetch(residuals, res, NP);
+  st.fetch(jac_pose, j0, 3 * NP);
+  st.fetch(jac_line, j1, 3 * NP);
+  return st.finish();
 }
 
 // ---------------------------------------------------------------- multi-GPU all-gather

@@ -64,7 +64,7 @@ int nhip_transient_filter_dev(const float *d_xy, const int32_t *d_offsets, int32
   NHIP_REQUIRE(d_hits && d_misses && d_out_offsets && d_stats && (n_scans == 0 || (d_offsets && d_affines)) &&
                    (n_points == 0 || (d_xy && d_labels && d_out_xy && d_out_index)),
                "transient_filter_dev: null pointer");
-  NHIP_REQUIRE(((reinterpret_cast<uintptr_t>(d_xy) | reinterpret_cast<uintptr_t>(d_out_xy) | reinterpret_cast<uintptr_t>(d_stats)) & 7) == 0,
+  NHIP_REQUIRE(aligned(d_xy, 8) && aligned(d_out_xy, 8) && aligned(d_stats, 8),
                "transient_filter_dev: d_xy, d_out_xy and d_stats must be 8-byte aligned");
   return transient_run(d_xy, d_offsets, n_scans, n_points, d_affines, *spec, d_hits, d_misses, d_labels, d_out_xy, d_out_offsets,
                        d_out_index, d_stats, static_cast<hipStream_t>(stream));
@@ -79,31 +79,26 @@ int nhip_transient_filter(const nhip_scans_t *scans, const double *poses, const 
   NHIP_REQUIRE(scans->n_points >= 0 && scans->n_points <= INT32_MAX, "transient_filter: the handle holds more than 2^31 - 1 points");
   const int32_t n = scans->n_scans, np = (int32_t)scans->n_points;
   NHIP_REQUIRE(np == 0 || (labels && out_xy && out_index), "transient_filter: null output");
-  const size_t cells = (size_t)spec->width * (size_t)spec->height, cap = (size_t)(np > 0 ? np : 1);
-  std::vector<float> aff(4 * (size_t)(n > 0 ? n : 1));
+  const size_t cells = (size_t)spec->width * (size_t)spec->height;
+  std::vector<float> aff(4 * (size_t)n);
   if ((rc = nhip_map_pose_affines(poses, n, aff.data()))) return rc;
-  DevBuf da, dh, dm, dl, dx, doff, di, ds;
-  if ((rc = da.alloc(4 * aff.size())) || (rc = dh.alloc(4 * cells)) || (rc = dm.alloc(4 * cells)) || (rc = dl.alloc(cap)) ||
-      (rc = dx.alloc(8 * cap)) || (rc = doff.alloc(4 * ((size_t)n + 1))) || (rc = di.alloc(4 * cap)) || (rc = ds.alloc(64)))
-    return rc;
-  InFlight inflight;
-  NHIP_TRY_HIP(hipMemcpy(da.p, aff.data(), 4 * aff.size(), hipMemcpyHostToDevice));
-  NHIP_TRY_HIP(hipMemcpy(dh.p, hits, 4 * cells, hipMemcpyHostToDevice));
-  NHIP_TRY_HIP(hipMemcpy(dm.p, misses, 4 * cells, hipMemcpyHostToDevice));
-  rc = transient_run(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), n, np, da.as<const float>(), *spec,
-                     dh.as<const int32_t>(), dm.as<const int32_t>(), dl.as<uint8_t>(), dx.as<float>(), doff.as<int32_t>(),
-                     di.as<int32_t>(), ds.as<int64_t>(), nullptr);
-  if (rc) return rc;
-  NHIP_TRY_HIP(hipMemcpy(out_offsets, doff.p, 4 * ((size_t)n + 1), hipMemcpyDeviceToHost));
-  NHIP_TRY_HIP(hipMemcpy(stats, ds.p, 64, hipMemcpyDeviceToHost));
-  const size_t kept = (size_t)(out_offsets[n] > 0 ? out_offsets[n] : 0);  // (<= np: the offsets kernel cuts it there)
-  if (np > 0) NHIP_TRY_HIP(hipMemcpy(labels, dl.p, (size_t)np, hipMemcpyDeviceToHost));
-  if (kept > 0) {
-    NHIP_TRY_HIP(hipMemcpy(out_xy, dx.p, 8 * kept, hipMemcpyDeviceToHost));
-    NHIP_TRY_HIP(hipMemcpy(out_index, di.p, 4 * kept, hipMemcpyDeviceToHost));
-  }
-  InFlight::done();  // (the downloads above synchronised the null stream)
-  return NHIP_OK;
+  Staged st;
+  const float *da = st.in(aff.data(), aff.size());
+  const int32_t *dh = st.in(hits, cells), *dm = st.in(misses, cells);
+  uint8_t *dl = st.out<uint8_t>((size_t)np);
+  float *dx = st.out<float>(2 * (size_t)np);
+  int32_t *doff = st.out<int32_t>((size_t)n + 1), *di = st.out<int32_t>((size_t)np);
+  int64_t *ds = st.out<int64_t>(STATS_WORDS);
+  if (st.ok())
+    st.launched(transient_run(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), n, np, da, *spec, dh, dm, dl, dx, doff,
+                              di, ds, nullptr));
+  st.fetch(out_offsets, doff, (size_t)n + 1);
+  st.fetch(stats, ds, STATS_WORDS);
+  const size_t kept = st.ok() && out_offsets[n] > 0 ? (size_t)out_offsets[n] : 0;  // (<= np: the offsets kernel cuts it there)
+  st.fetch(labels, dl, (size_t)np);
+  st.fetch(out_xy, dx, 2 * kept);
+  st.fetch(out_index, di, kept);
+  return st.finish();
 }
 
 }  // extern "C"

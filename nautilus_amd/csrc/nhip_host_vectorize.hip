@@ -10,6 +10,7 @@ using namespace nhip;
 namespace {
 
 constexpr int VQ = 14;
+constexpr size_t REC_WORDS = 10;  // a segment record: ten int64 words (include/nautilus_hip.h)
 
 // the accepted ranges of include/nautilus_hip.h
 int vectorize_spec_check(const nhip_vectorize_spec_t *s, const char *who) {
@@ -78,7 +79,7 @@ int vectorize_run(const float *d_xy, const int32_t *d_offsets, const float *d_af
     NHIP_TRY_HIP(hipMemcpyAsync(&end, &P.st->end, sizeof(end), hipMemcpyDeviceToHost, s));
     NHIP_TRY_HIP(hipStreamSynchronize(s));
   }
-  NHIP_TRY_HIP(hipMemcpyAsync(d_stats, P.st->stats, 8 * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  NHIP_TRY_HIP(hipMemcpyAsync(d_stats, P.st->stats, STATS_WORDS * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   NHIP_TRY_HIP(hipStreamSynchronize(s));
   return NHIP_OK;
 }
@@ -188,7 +189,7 @@ int nhip_vectorize_dev(const float *d_xy, const int32_t *d_offsets, const float 
   vec_layout(*spec, max_cells, &L);
   NHIP_REQUIRE(workspace_bytes >= L.bytes, "vectorize_dev: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
                (long long)L.bytes);
-  NHIP_REQUIRE((reinterpret_cast<uintptr_t>(d_workspace) & 255) == 0, "vectorize_dev: d_workspace must be 256-byte aligned");
+  NHIP_REQUIRE(aligned(d_workspace, 256), "vectorize_dev: d_workspace must be 256-byte aligned");
   return vectorize_run(d_xy, d_offsets, d_affines, n_scans, *spec, max_cells, max_rounds, check_every, d_records, d_stats,
                        d_workspace, static_cast<hipStream_t>(stream));
 }
@@ -200,22 +201,21 @@ int nhip_vectorize(const nhip_scans_t *scans, const double *poses, const nhip_ve
   if ((rc = require_device())) return rc;
   NHIP_REQUIRE(scans && stats && (spec->max_segments == 0 || records) && (scans->n_scans == 0 || poses), "vectorize: bad arguments");
   const int32_t n = scans->n_scans;
-  std::vector<float> aff(4 * (size_t)(n > 0 ? n : 1));
+  std::vector<float> aff(4 * (size_t)n);
   if ((rc = nhip_map_pose_affines(poses, n, aff.data()))) return rc;
   VecLayout L;
   vec_layout(*spec, max_cells, &L);
-  const size_t rec_bytes = 80 * (size_t)(spec->max_segments > 0 ? spec->max_segments : 1);
-  DevBuf da, dr, ds, dw;
-  if ((rc = da.alloc(4 * aff.size())) || (rc = dr.alloc(rec_bytes)) || (rc = ds.alloc(32)) || (rc = dw.alloc((size_t)L.bytes))) return rc;
-  InFlight inflight;
-  NHIP_TRY_HIP(hipMemcpy(da.p, aff.data(), 4 * aff.size(), hipMemcpyHostToDevice));
-  rc = vectorize_run(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), da.as<const float>(), n, *spec, max_cells,
-                     max_rounds, check_every, dr.as<int64_t>(), ds.as<int32_t>(), dw.p, nullptr);
-  if (rc) return rc;
-  NHIP_TRY_HIP(hipMemcpy(stats, ds.p, 32, hipMemcpyDeviceToHost));
-  if (stats[1] > 0) NHIP_TRY_HIP(hipMemcpy(records, dr.p, 80 * (size_t)stats[1], hipMemcpyDeviceToHost));
-  InFlight::done();  // (the downloads above synchronised the null stream)
-  return NHIP_OK;
+  Staged st;
+  const float *da = st.in(aff.data(), aff.size());
+  int64_t *dr = st.out<int64_t>(REC_WORDS * (size_t)spec->max_segments);
+  int32_t *ds = st.out<int32_t>(STATS_WORDS);
+  uint8_t *dw = st.out<uint8_t>((size_t)L.bytes);
+  if (st.ok())
+    st.launched(vectorize_run(scans->xy.as<const float>(), scans->offsets.as<const int32_t>(), da, n, *spec, max_cells, max_rounds,
+                              check_every, dr, ds, dw, nullptr));
+  st.fetch(stats, ds, STATS_WORDS);
+  st.fetch(records, dr, st.ok() && stats[1] > 0 ? REC_WORDS * (size_t)stats[1] : 0);
+  return st.finish();
 }
 
 int nhip_vectorize_endpoints(const nhip_vectorize_spec_t *spec, const int64_t *records, int32_t n, float *lines) {

@@ -309,6 +309,52 @@ void DevBuf::adopt(void *q, size_t n) {
   device = current_device();
 }
 
+// ---------------------------------------------------------------- the staged call of the handle forms
+// The call keeps its own in-flight state: it does not lean on the thread-local flag above, on where the form declares it,
+// or on which buffer is released first.  The destructor's body runs before any member is destroyed.
+Staged::~Staged() {
+  if (inflight_) {
+    PhaseClock pc(PH_FREE);  // (where DevBuf::free counts the same wait)
+    (void)hipDeviceSynchronize();
+    (void)hipGetLastError();
+  }
+}
+void *Staged::stage(const void *host, size_t bytes) {
+  if (rc_) return nullptr;
+  bufs_.emplace_back();
+  DevBuf &d = bufs_.back();
+  if ((rc_ = d.alloc(bytes))) return nullptr;
+  if (host && bytes) {
+    hipError_t e = hipMemcpy(d.p, host, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      rc_ = hip_fail(e, "hipMemcpy, host to device", __FILE__, __LINE__);
+      return nullptr;
+    }
+  }
+  return d.p;
+}
+void Staged::download(void *host, const void *dev, size_t bytes) {
+  if (rc_ || !host || !dev || !bytes) return;
+  hipError_t e = hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    rc_ = hip_fail(e, "hipMemcpy, device to host", __FILE__, __LINE__);
+    return;
+  }
+  inflight_ = false;  // (a blocking copy on the null stream: what the call enqueued there has finished)
+}
+void Staged::launched(int rc) {
+  inflight_ = true;  // (a launcher that fails may have enqueued part of its work)
+  if (!rc_) rc_ = rc;
+}
+int Staged::finish() {
+  if (!rc_ && inflight_) {
+    hipError_t e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) return rc_ = hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__);
+    inflight_ = false;
+  }
+  return rc_;
+}
+
 }  // namespace nhip
 
 using namespace nhip;
