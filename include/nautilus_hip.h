@@ -69,7 +69,10 @@ const char *nhip_version(void);
  * nhip_bsr_pcg_columns_dev, 16384 scan offset of nhip_vectorize_dev /
  * nhip_occupancy_dev / nhip_place_describe_dev / nhip_transient_filter_dev, 32768 source scan, grid slot or record index of a pair of
  * nhip_freespace_check_dev, 65536 scan id of the list of nhip_place_match_dev / nhip_place_seq_match_dev, 131072 degree and 262144
- * member index of nhip_consistency_set_dev.  Clears the record
+ * member index of nhip_consistency_set_dev, 524288 occupied cells beyond max_cells of nhip_mapwin_cells_dev (value: the cells
+ * needed; index = height) or a row_ptr entry that is not a row in nhip_mapwin_gather_dev (index = the map row), 1048576 window
+ * points beyond out_capacity of nhip_mapwin_gather_dev (value: the points needed, at most 2^31 - 1; index = n_queries).
+ * Clears the record
  * (in the order of `stream`).
  * ONE record per DEVICE, shared by every stream and host thread that uses the library on it: a host with several streams
  * on one device learns THAT an id was bad and which, not on which stream; a call that finds a record consumes it -- reports
@@ -853,6 +856,71 @@ int nhip_transient_filter_dev(const float *d_xy, const int32_t *d_offsets, int32
                               const nhip_transient_spec_t *spec, const int32_t *d_hits, const int32_t *d_misses, uint8_t *d_labels,
                               float *d_out_xy, int32_t *d_out_offsets, int32_t *d_out_index, int64_t *d_stats, void *stream);
 
+/* K20: MAP WINDOWS -- the target clouds of scans that are localised in a finished occupancy grid: for every query the crop of
+ * the grid's occupied cells around the world cell of its prior pose, as a cloud of the layout every other entry point takes, so
+ * that nhip_grid_build_dev builds the query's table from it and nhip_csm_match_dev matches the scan against it (DESIGN.md
+ * section 3, "Map windows"; tests/localize_reference.py and hostside.map_cells / map_windows restate it).  Build-defined and
+ * deterministic: no atomics on any output, the same input gives the same bits.
+ *   occupied a cell of the int8 grid [height][width] whose value >= occ_min, a signed compare (-1, unknown, never is).
+ *   cells    row_ptr[height + 1] and cols[n_occ], int32: the local x indices of the occupied cells of map row y are
+ *            cols[row_ptr[y] .. row_ptr[y + 1]), ascending.  More occupied cells than max_cells: nothing is packed, EVERY
+ *            entry of row_ptr is 0 (a gather over the result sees an empty map) and nhip_dev_status() reports it (kind 524288,
+ *            value: the cells needed).
+ *   origin   of a query: the world cell of its prior, (floor(x / res), floor(y / res)) in double (nhip_mapwin_origins); its
+ *            theta0 is the prior's heading.
+ *   window   the target frame is the WORLD frame moved to the lower-left corner of the origin cell (ox, oy); it is not
+ *            rotated and nothing is resampled.  World cell (wx, wy) belongs to the window iff kx = wx - ox and ky = wy - oy
+ *            both lie in [-side/2, side - side/2 - 1] (tested in int64); its point is x = (float)(((double)kx + 0.5) * res),
+ *            y likewise: one double multiply, one rounding to float.  The table build's side/2 + floor((double)v / res)
+ *            returns the cell side/2 + k for it.  A window's points are in row order (y ascending, then x ascending), windows
+ *            in query order: out_xy, out_offsets[n_queries + 1].  A window that misses the map is an empty scan.
+ *   capacity more window points than out_capacity (or than 2^31 - 1): nothing is stored, every entry of out_offsets is 0 and
+ *            nhip_dev_status() reports it (kind 1048576, value: the points needed).
+ *   stats    8 int64: {occupied cells of the map (also when they were not packed), queries, points stored, empty windows,
+ *            largest window, 1 if the cells did not fit, 1 if the points did not fit, 0}.  nhip_mapwin_cells_dev writes words 0
+ *            and 5 and clears the others; nhip_mapwin_gather_dev writes words 1 - 4 and 6 and leaves the others as they are: one
+ *            block given to both calls in turn holds the whole record.
+ *   pose     from a record of the matcher with pair_origin 0 (host, double): x = (ox + ix - (nx - 1) / 2) res, y likewise,
+ *            theta = angle_mod(theta0 + (itheta - (n_theta - 1) / 2) theta_step); a rejected record gives NaN
+ *            (nautilus_amd/localize.py: compose).
+ * Accepted ranges (anything else is NHIP_ERR_ARG before anything is launched, with or without a device): res finite and > 0;
+ * width, height 1..16384; side 2..8192; occ_min 1..100; flags 0; reserved 0; max_cells >= 0; n_queries >= 0;
+ * out_capacity >= 0. */
+typedef struct nhip_mapwin_spec {
+  double res;        /* metres per cell: the occupancy spec's, and the grid spec's of the tables */
+  int32_t cell_x0;   /* the map's window: the occupancy spec's */
+  int32_t cell_y0;
+  int32_t width;
+  int32_t height;
+  int32_t side;      /* the target table's side in cells: nhip_grid_layout(spec).side */
+  int32_t occ_min;   /* a cell is occupied iff its value >= occ_min (100) */
+  int32_t flags;     /* 0 */
+  int32_t reserved;  /* 0 */
+} nhip_mapwin_spec_t;
+/* the defaults of the table above; the map's window and side are 0 and are the caller's to set; pure host */
+int nhip_mapwin_spec_default(nhip_mapwin_spec_t *out);
+/* origins (2 int32 per query: ox, oy) and theta0 (a double per query, may be NULL) of n priors (3 doubles each: x, y, heading);
+ * pure host.  A pose that is not finite or whose floor has magnitude >= 2^30 is NHIP_ERR_ARG, the message names its index. */
+int nhip_mapwin_origins(const double *poses, int32_t n, double res, int32_t *origins, double *theta0);
+/* bytes of the gather's workspace for n_queries queries (the per-window counts; > 0 for every n_queries >= 0, else 0); pure host */
+int64_t nhip_mapwin_workspace_bytes(int32_t n_queries);
+/* The occupied cells of the grid, on the caller's buffers and stream; never allocates, enqueues and returns without waiting.
+ * d_grid: int8 [height][width], any alignment; d_row_ptr: height + 1 int32; d_cols: max_cells int32 (may be NULL with
+ * max_cells 0); d_stats: 8 int64, 8-byte aligned. */
+int nhip_mapwin_cells_dev(const int8_t *d_grid, const nhip_mapwin_spec_t *spec, int32_t max_cells, int32_t *d_row_ptr,
+                          int32_t *d_cols, int64_t *d_stats, void *stream);
+/* The windows of n_queries origins (d_origins: 2 int32 each, any values) from the cells nhip_mapwin_cells_dev wrote (d_cols
+ * holds d_row_ptr[height] entries), on the caller's buffers and stream; never allocates, enqueues and returns without waiting.
+ * d_out_xy: out_capacity points of 2 floats, 8-byte aligned (may be NULL with out_capacity 0); d_out_offsets: n_queries + 1
+ * int32; d_stats: 8 int64, 8-byte aligned; d_workspace: nhip_mapwin_workspace_bytes(n_queries) bytes, 4-byte aligned.  A window
+ * costs `side` row lookups and its own output: the map is not read per query.  The entries of d_row_ptr are checked before
+ * they become addresses: a row whose range is not inside [0, d_row_ptr[height]] is an empty row and nhip_dev_status() reports
+ * it (kind 524288); the entries of d_cols are only compared and converted, never addresses.  n_queries = 0 is a call:
+ * out_offsets[0] = 0. */
+int nhip_mapwin_gather_dev(const int32_t *d_row_ptr, const int32_t *d_cols, const nhip_mapwin_spec_t *spec, const int32_t *d_origins,
+                           int32_t n_queries, float *d_out_xy, int64_t out_capacity, int32_t *d_out_offsets, int64_t *d_stats,
+                           void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* K15: FREE-SPACE CHECK of match records ("Free-space check"; tests/freespace_reference.py restates it
  * in numpy).  A record's score says how much of the source landed on the target's blurred hits; the check says where the rest
  * landed.  Build-defined and deterministic; all integer after the cells; no matcher kernel is involved.
@@ -1171,6 +1239,14 @@ int nhip_occupancy(const nhip_scans_t *scans, const double *poses, const nhip_oc
 int nhip_transient_filter(const nhip_scans_t *scans, const double *poses, const nhip_transient_spec_t *spec, const int32_t *hits,
                           const int32_t *misses, uint8_t *labels, float *out_xy, int32_t *out_offsets, int32_t *out_index,
                           int64_t *stats);
+
+/* nhip_mapwin_cells_dev + nhip_mapwin_gather_dev on host memory: grid (width x height int8), origins (2 int32 per query) and the
+ * outputs out_xy (room for `capacity` points of 2 floats; may be NULL with capacity 0), out_offsets (n_queries + 1 int32) and
+ * stats (8 int64).  The cell list is sized from the grid, so only the points can fail to fit: the call then returns NHIP_OK
+ * with every offset 0 and stats[6] = 1, and nhip_dev_status() reports it.  Only the first out_offsets[n_queries] points of
+ * out_xy are written.  Allocates and frees its device buffers. */
+int nhip_map_windows(const int8_t *grid, const nhip_mapwin_spec_t *spec, const int32_t *origins, int32_t n_queries, float *out_xy,
+                     int64_t capacity, int32_t *out_offsets, int64_t *stats);
 
 /* nhip_freespace_check_dev on handles: the pair arguments of nhip_csm_match, the records it returned (host memory) and
  * counts (8 int32 per pair, host memory).  `scans` must be the scans `grids` was built from: the first call on a grids handle

@@ -97,6 +97,11 @@ class TransientSpec(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class MapwinSpec(C.Structure):
+    _fields_ = [("res", C.c_double), ("cell_x0", C.c_int32), ("cell_y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("side", C.c_int32), ("occ_min", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FreespaceSpec(C.Structure):
     _fields_ = [("hit_radius", C.c_int32), ("end_margin", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
@@ -237,6 +242,12 @@ PROTOTYPES = {
     "nhip_transient_spec_default": (C.c_int, [_P(TransientSpec)]),
     "nhip_transient_filter_dev": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _P(TransientSpec), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nhip_transient_filter": (C.c_int, [_vp, _vp, _P(TransientSpec), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nhip_mapwin_spec_default": (C.c_int, [_P(MapwinSpec)]),
+    "nhip_mapwin_origins": (C.c_int, [_vp, _i32, _f64, _vp, _vp]),
+    "nhip_mapwin_workspace_bytes": (_i64, [_i32]),
+    "nhip_mapwin_cells_dev": (C.c_int, [_vp, _P(MapwinSpec), _i32, _vp, _vp, _vp, _vp]),
+    "nhip_mapwin_gather_dev": (C.c_int, [_vp, _vp, _P(MapwinSpec), _vp, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "nhip_map_windows": (C.c_int, [_vp, _P(MapwinSpec), _vp, _i32, _vp, _i64, _vp, _vp]),
     "nhip_freespace_spec_default": (C.c_int, [_P(FreespaceSpec)]),
     "nhip_freespace_planes_bytes": (_i64, [_P(GridSpec), _i64]),
     "nhip_freespace_trace_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(GridSpec), _vp, _vp, _vp]),

@@ -55,7 +55,8 @@ constexpr uint32_t BAD_TARGET_ID = 1u, BAD_PAIR_SRC = 2u, BAD_PAIR_SLOT = 4u, BA
                    BAD_SCAN_ID = 32u, BAD_FEATURE_IDX = 64u, BAD_FEATURE_COUNT = 128u, BAD_SCAN_OFFSETS = 256u,
                    BAD_MEMBER_ID = 512u, BAD_SUBMAP_CAPACITY = 1024u, BAD_CONTRIB_ID = 2048u, BAD_BLOCK_COLUMN = 4096u,
                    BAD_SYSTEM_ID = 8192u, BAD_MAP_SCAN_OFFSETS = 16384u, BAD_FREESPACE_PAIR = 32768u, BAD_PLACE_ID = 65536u,
-                   BAD_CONSISTENCY_DEGREE = 131072u, BAD_CONSISTENCY_MEMBER = 262144u;
+                   BAD_CONSISTENCY_DEGREE = 131072u, BAD_CONSISTENCY_MEMBER = 262144u, BAD_MAPWIN_CELLS = 524288u,
+                   BAD_MAPWIN_POINTS = 1048576u;
 constexpr int DEV_STATUS_WORDS = 4;  // {OR of the kinds seen, kind / value / index of the first report}
 uint32_t *dev_status();              // of the current device (allocated on the device's first use; null if that failed)
 #ifdef __HIPCC__
@@ -405,6 +406,22 @@ struct TransientParams {  // plain data: travels in the kernels' parameter block
 };
 // clears the stats and sets every label to 3, then classify, offsets and pack
 int launch_transient(const TransientParams &P, const float *d_xy, const int32_t *d_offsets, const float *d_affines, hipStream_t s);
+
+// map windows (nhip_mapwin.hip, K20); the spec has passed mapwin_spec_check (nhip_host_mapwin.hip)
+struct MapwinParams {  // plain data: travels in the kernels' parameter blocks
+  int32_t width, height, cell_x0, cell_y0, side, occ_min;
+  double res;
+  long long *stats;   // 8 words: {occupied cells, queries, points stored, empty windows, largest window, cells overflow, points
+                      // overflow, 0}: the cells call writes words 0 and 5 and clears the rest, the gather writes 1 - 4 and 6
+  uint32_t *status;
+};
+// row count, scan (with the capacity decision) and row pack: row_ptr[height + 1], cols[<= max_cells]
+int launch_mapwin_cells(const MapwinParams &P, const int8_t *d_grid, int32_t max_cells, int32_t *d_row_ptr, int32_t *d_cols,
+                        hipStream_t s);
+// window count into d_counts (n_queries int32 of the workspace), scan (with the capacity decision) and window pack
+int launch_mapwin_gather(const MapwinParams &P, const int32_t *d_row_ptr, const int32_t *d_cols, const int32_t *d_origins,
+                         int32_t n_queries, float *d_out_xy, int64_t out_capacity, int32_t *d_out_offsets, int32_t *d_counts,
+                         hipStream_t s);
 
 // free-space check of match records (nhip_freespace.hip, K15); the specs have passed the checks of nhip_host_freespace.hip
 struct FsParams {     // plain data: travels in the kernels' parameter blocks (the trace reads the first group, the check both)

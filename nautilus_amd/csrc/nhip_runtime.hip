@@ -424,6 +424,8 @@ int nhip_dev_status(void *stream, int32_t info[4]) {
                      : w[1] == BAD_MAP_SCAN_OFFSETS ? "scan offset (nhip_vectorize_dev / nhip_occupancy_dev / nhip_place_describe_dev / nhip_transient_filter_dev: d_offsets)"
                      : w[1] == BAD_PLACE_ID ? "scan id (nhip_place_match_dev / nhip_place_seq_match_dev: d_ids)"
                      : w[1] == BAD_FREESPACE_PAIR ? "source scan, grid slot or record index of a pair (nhip_freespace_check_dev; index = the pair)"
+                     : w[1] == BAD_MAPWIN_CELLS ? "occupied-cell count beyond max_cells (nhip_mapwin_cells_dev; index = height) or row_ptr entry that is not a row (nhip_mapwin_gather_dev; index = the map row)"
+                     : w[1] == BAD_MAPWIN_POINTS ? "window point count (nhip_mapwin_gather_dev: more than out_capacity; index = n_queries)"
                                              : "id";
   set_error("an id read from device memory was out of range: %s = %d at index %d (kinds seen since the last check: 0x%x); "
             "the kernels treated every such entry as empty", what, (int32_t)w[2], (int32_t)w[3], w[0]);

@@ -711,6 +711,151 @@ def read_occupancy_map(path_stem):
     return grid, info
 
 
+def occupancy_map_window(grid, info):
+    """(res, cell_x0, cell_y0, width, height) of a map read_occupancy_map returned: the YAML's origin is the window's corner in
+    metres, a whole number of cells."""
+    res = float(info["resolution"])
+    h, w = np.asarray(grid).shape
+    return res, int(round(info["origin"][0] / res)), int(round(info["origin"][1] / res)), int(w), int(h)
+
+
+def mapwin_spec_check(spec):
+    """The accepted ranges of nhip_mapwin_spec_t (include/nautilus_hip.h); ValueError otherwise."""
+    res = float(spec.res)
+    if not (math.isfinite(res) and res > 0):
+        raise ValueError("map_windows: res must be finite and > 0")
+    for name, lo, hi in (("width", 1, 16384), ("height", 1, 16384), ("side", 2, 8192), ("occ_min", 1, 100), ("flags", 0, 0),
+                         ("reserved", 0, 0)):
+        if not lo <= int(getattr(spec, name)) <= hi:
+            raise ValueError("map_windows: %s %d outside %d..%d" % (name, int(getattr(spec, name)), lo, hi))
+
+
+def map_window_origins(priors, res):
+    """The origins of priors (n, 3) in a map of `res` metres per cell ("Map windows", item 2; held equal
+    to nhip_mapwin_origins): (origins int32 (n, 2): the world cell (floor(x / res), floor(y / res)) of each, theta0 float64
+    (n,): its heading).  ValueError for a pose that is not finite or 2^30 cells or more from the origin, naming its index."""
+    P = np.asarray(priors, dtype=np.float64).reshape(-1, 3)
+    res = float(res)
+    if not (math.isfinite(res) and res > 0):
+        raise ValueError("map_window_origins: res must be finite and > 0")
+    bad = np.nonzero(~np.isfinite(P).all(axis=1))[0]
+    if len(bad):
+        raise ValueError("map_window_origins: pose %d is not finite" % bad[0])
+    fl = np.floor(P[:, :2] / res)
+    bad = np.nonzero((np.abs(fl) >= 2.0 ** 30).any(axis=1))[0]
+    if len(bad):
+        raise ValueError("map_window_origins: pose %d lies 2^30 cells or more from the origin" % bad[0])
+    return fl.astype(np.int32), P[:, 2].copy()
+
+
+def map_cells(grid, spec):
+    """The occupied cells of an occupancy grid, row by row ("Map windows", item 1; the device form is nhip_mapwin_cells_dev):
+    (row_ptr int32 (height + 1,), cols int32 (n_occ,)) -- cols[row_ptr[y]:row_ptr[y + 1]] are the local x indices of the cells
+    of row y whose int8 value is >= spec.occ_min, ascending."""
+    mapwin_spec_check(spec)
+    g = np.asarray(grid, dtype=np.int8).reshape(int(spec.height), int(spec.width))
+    ys, xs = np.nonzero(g >= int(spec.occ_min))  # (row-major: y ascending, then x ascending)
+    row_ptr = np.concatenate([[0], np.cumsum(np.bincount(ys, minlength=g.shape[0]))]).astype(np.int32)
+    return row_ptr, xs.astype(np.int32)
+
+
+def map_windows(grid, spec, origins):
+    """The windows of an occupancy grid around `origins` (n, 2) in plain numpy ("Map windows", items 3 and 5; the device form
+    is nhip_mapwin_gather_dev behind nhip_mapwin_cells_dev, and localize.windows returns the same three arrays bit for bit):
+    (xy float32 (n_points, 2), offsets int32 (n + 1,), stats int64 (8,): localize.STATS_FIELDS).  Window q holds the occupied
+    world cells (wx, wy) with wx - ox and wy - oy in [-side/2, side - side/2 - 1], as the points ((k + 0.5) res) of the frame
+    whose origin is the lower-left corner of world cell (ox, oy), y ascending then x ascending.  The capacity is unbounded
+    here: the two overflow words of the stats are 0."""
+    row_ptr, cols = map_cells(grid, spec)
+    org = np.asarray(origins, dtype=np.int64).reshape(-1, 2)
+    side, half, res = int(spec.side), int(spec.side) // 2, float(spec.res)
+    w, h, x0, y0 = int(spec.width), int(spec.height), int(spec.cell_x0), int(spec.cell_y0)
+    rows = np.repeat(np.arange(h, dtype=np.int64), np.diff(row_ptr))  # the map row of every entry of cols
+    parts, offsets = [], np.zeros(len(org) + 1, np.int64)
+    for q, (ox, oy) in enumerate(org):
+        y_lo, y_hi = max(oy - half - y0, 0), min(oy - half + side - 1 - y0, h - 1)
+        x_lo, x_hi = max(ox - half - x0, 0), min(ox - half + side - 1 - x0, w - 1)
+        n = 0
+        if y_lo <= y_hi and x_lo <= x_hi:
+            b, e = int(row_ptr[y_lo]), int(row_ptr[y_hi + 1])
+            c = cols[b:e].astype(np.int64)
+            keep = (c >= x_lo) & (c <= x_hi)
+            kx, ky = c[keep] + x0 - ox, rows[b:e][keep] + y0 - oy
+            parts.append(np.stack([((kx.astype(np.float64) + 0.5) * res).astype(np.float32),
+                                   ((ky.astype(np.float64) + 0.5) * res).astype(np.float32)], axis=1))
+            n = len(kx)
+        offsets[q + 1] = offsets[q] + n
+    if offsets[-1] > 2 ** 31 - 1:
+        raise ValueError("map_windows: %d points, more than 2^31 - 1" % offsets[-1])
+    xy = np.concatenate(parts).astype(np.float32) if parts else np.zeros((0, 2), np.float32)
+    counts = np.diff(offsets)
+    stats = np.array([len(cols), len(org), offsets[-1], int((counts == 0).sum()), int(counts.max()) if len(org) else 0, 0, 0, 0], np.int64)
+    return xy, offsets.astype(np.int32), stats
+
+
+def localize_compose(records, origins, theta0, grid_spec, search):
+    """World poses (n, 3) float64 from match records against map windows ("Map windows", item 6): the matcher's conventions
+    (csm.match_to_transform) with pair_origin 0 in the frame whose origin is the corner of world cell (ox, oy), all in double:
+    x = (ox + ix - (nx - 1) / 2) res, y likewise, theta = angle_mod(theta0 + (itheta - (n_theta - 1) / 2) theta_step).  A
+    rejected record (itheta -1: a gated match) gives NaN."""
+    rec = np.asarray(records)
+    org = np.asarray(origins, dtype=np.int64).reshape(-1, 2)
+    th0 = np.asarray(theta0, dtype=np.float64).reshape(-1)
+    if not (len(rec) == len(org) == len(th0)):
+        raise ValueError("localize_compose: %d records, %d origins, %d headings" % (len(rec), len(org), len(th0)))
+    res = float(grid_spec.res)
+    out = np.empty((len(rec), 3), np.float64)
+    out[:, 0] = (org[:, 0] + rec["ix"].astype(np.int64) - (int(search.nx) - 1) // 2).astype(np.float64) * res
+    out[:, 1] = (org[:, 1] + rec["iy"].astype(np.int64) - (int(search.ny) - 1) // 2).astype(np.float64) * res
+    a = th0 + (rec["itheta"].astype(np.int64) - (int(search.n_theta) - 1) // 2).astype(np.float64) * float(search.theta_step)
+    out[:, 2] = a - 2.0 * math.pi * np.rint(a / (2.0 * math.pi))
+    out[rec["itheta"] < 0] = np.nan
+    return out
+
+
+def localize(backend, xy, offsets, priors, grid, occ_spec, occ_min=100, cell_bits=16, grid_spec=None, search=None):
+    """Scans localised in a finished occupancy grid through ANY backend with a match() method (the host route to
+    HipBackend.localize, as submap_extra_scans is to submap tables): scan q of the packed scans (xy, offsets) is matched from
+    priors[q] (x, y, heading) against the window of `grid` (int8 (H, W), window and res of occ_spec) around the prior's world
+    cell.  The windows are made in numpy (map_windows), one per distinct origin, and appended to the bag as extra scans;
+    backend.match(xy, offsets, pair_src, pair_tgt, theta0, cell_bits=) then sees ordinary pairs.  grid_spec / search: passed on
+    to match() when given (a backend whose match() takes them), else the backend's own (BASELINE config #2) -- either way the
+    spec match() returns must have the map's res.  Returns the dict of localize.localize: poses (n, 3) float64, records,
+    origins int32 (n, 2), rejected (bool), points_per_window."""
+    from . import csm
+    off = np.asarray(offsets, dtype=np.int32)
+    n = len(off) - 1
+    P = np.asarray(priors, dtype=np.float64).reshape(-1, 3)
+    if len(P) != n:
+        raise ValueError("localize: %d priors for %d scans" % (len(P), n))
+    gs = grid_spec if grid_spec is not None else csm.grid_spec(30.0, 0.05, 2.0, 1e-10, 40, cell_bits)
+    if float(gs.res) != float(occ_spec.res):
+        raise ValueError("localize: the tables' res %r is not the map's %r" % (float(gs.res), float(occ_spec.res)))
+    mw = _MapwinFields(occ_spec, csm.grid_layout(gs).side, occ_min)
+    origins, theta0 = map_window_origins(P, mw.res)
+    uniq, slot = np.unique(origins, axis=0, return_inverse=True)
+    slot = np.asarray(slot).reshape(-1)
+    wxy, woff, _ = map_windows(grid, mw, uniq)
+    xy2 = np.concatenate([np.asarray(xy, dtype=np.float32).reshape(-1, 2), wxy])
+    off2 = np.concatenate([off, off[-1] + woff[1:]]).astype(np.int32)
+    kw = {} if grid_spec is None and search is None else dict(grid_spec=grid_spec, search=search)
+    rec, spec, srch = backend.match(xy2, off2, np.arange(n, dtype=np.int32), (n + slot).astype(np.int32), theta0,
+                                    cell_bits=cell_bits, **kw)[:3]
+    if float(spec.res) != mw.res or csm.grid_layout(spec).side != mw.side:
+        raise ValueError("localize: the backend matched at res %r on tables of another side; the map's res is %r" % (float(spec.res), mw.res))
+    return {"poses": localize_compose(rec, origins, theta0, spec, srch), "records": rec, "origins": origins,
+            "rejected": np.asarray(rec["itheta"] < 0), "points_per_window": np.diff(woff)[slot].astype(np.int32)}
+
+
+class _MapwinFields:
+    """The fields of nhip_mapwin_spec_t from an occupancy spec (anything with res and the window), for the numpy statements."""
+
+    def __init__(self, occ_spec, side, occ_min=100):
+        self.res, self.cell_x0, self.cell_y0 = float(occ_spec.res), int(occ_spec.cell_x0), int(occ_spec.cell_y0)
+        self.width, self.height, self.side, self.occ_min, self.flags, self.reserved = \
+            int(occ_spec.width), int(occ_spec.height), int(side), int(occ_min), 0, 0
+
+
 def hitl_segments(msg):
     """LineSegmentsFromHitlMsg (solver.cc:467-478): msg = dict with line_a_start, line_a_end, line_b_start,
     line_b_end, each (x, y[, z]) -> two LineSegment<float> as (x0, y0, x1, y1) float32 rows."""

@@ -322,7 +322,17 @@ class HipBackend:
                                                float(max_score), _lib.ptr(scores), _lib.ptr(flags)))
         return scores, flags
 
-    def match(self, xy, offsets, pair_src, pair_tgt, theta0, cell_bits=16, submap_radius=0, poses=None, freespace=None):
+    def localize(self, xy, offsets, priors, grid, occ_spec, grid_spec=None, search=None, min_score=None, cell_bits=16, **kw):
+        """The packed scans localised in a finished occupancy grid from their prior poses, on this backend's device
+        (localize.localize; DESIGN.md section 3, "Map windows"): the windows of the grid around the priors gathered on the GPU,
+        their tables built, every scan matched against its own.  Returns the dict of poses (n, 3), records, origins, rejected
+        and points_per_window."""
+        from . import localize
+        return localize.localize(xy, offsets, priors, grid, occ_spec, grid_spec=grid_spec, search=search, min_score=min_score,
+                                 cell_bits=cell_bits, device=str(self.dev), **kw)
+
+    def match(self, xy, offsets, pair_src, pair_tgt, theta0, cell_bits=16, submap_radius=0, poses=None, freespace=None,
+              grid_spec=None, search=None):
         """Batched loop-closure scan matching (BASELINE config #2 lattice): (records, spec, search).
         Only the scans the list names go to the device (the candidate scans of a 10,000-scan bag are ~150: 1.3 MB instead
         of the bag's 86 MB, whose upload cost more than matching the 3,275 pairs).
@@ -332,12 +342,14 @@ class HipBackend:
         freespace: a freespace.spec() -- the free-space check of every record ("Free-space check") is made
         inside the call, while the tables are on the device: the targets' free planes traced, the records classified where
         the matcher left them; returns (records, spec, search, counts int32 (n, 8)).  None: the three-tuple, no extra launch.
-        Not with submap_radius > 0 (a submap's free space needs one ray origin per member)."""
+        Not with submap_radius > 0 (a submap's free space needs one ray origin per member).
+        grid_spec, search: another table spec / lattice than config #2's (tests on small tables, hostside.localize); None: those."""
         from . import csm, hostside
         if freespace is not None and int(submap_radius) > 0:
             raise ValueError("match: freespace with submap_radius %d: the free-space check has no submap targets" % int(submap_radius))
-        spec = csm.grid_spec(30.0, 0.05, 2.0, 1e-10, 40, cell_bits)
-        search = csm.search_spec(61, 81, 81, math.radians(1.0))
+        spec = csm.grid_spec(30.0, 0.05, 2.0, 1e-10, 40, cell_bits) if grid_spec is None else grid_spec
+        search = csm.search_spec(61, 81, 81, math.radians(1.0)) if search is None else \
+            _lib.Search(search.n_theta, search.nx, search.ny, search.flags, search.theta_step)  # (a copy: the flags are edited below)
         pair_src, pair_tgt = np.asarray(pair_src), np.asarray(pair_tgt)
         submap_radius = int(submap_radius)
         if submap_radius < 0 or (submap_radius > 0 and poses is None):
