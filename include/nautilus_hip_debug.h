@@ -26,7 +26,8 @@ int nhip_host_phases(double out[8]);
  * 2 split form in several rounds on the caller's stream, 3 split form in rounds with the candidates on the library's
  * helper stream of the current device; out[1] pairs per round; out[2] rounds' state the workspace holds; out[3] rounds;
  * out[4] 1 when NHIP_SEARCH_SHORT_SCANS was honoured; out[5] hand-over kernel launched; out[6] bit 0: instrumented build,
- * bit 1: the kernels that keep a list of level-2 runs take their strip bounds from it (clear: NHIP_BNB_L2_RUNS=0);
+ * bit 1: the kernels that keep a list of level-2 runs take their strip bounds from it (clear: NHIP_BNB_L2_RUNS=0),
+ * bit 2: the candidates' kernels take two live sub-blocks side by side in one pass (clear: NHIP_BNB_PAIR_SUBS=0);
  * out[7] n_pairs. */
 int nhip_csm_last_launch(int32_t out[8]);
 /* What the calling thread's last nhip_csm_get_transformation did: {the coarse optimum's score, the form the fine level ran in
@@ -53,7 +54,10 @@ int nhip_bnb_stats(uint64_t *evaluated, uint64_t *total);
  * that hold no pose of the lattice, such blocks evaluated whole -- the matcher skips the former, so out[20] stays 0,
  * and only an edge block with more than 4 pose columns and rows, which has a pose in all four sub-blocks, can be the
  * latter: out[21] stays 0 on a lattice whose sides are 8 m + 0 .. 4 (the seed of a scan too long for the by-rotation
- * form is a whole block wherever it lies, and is not counted); out[22..23] unused, 0; (synchronises; resets) */
+ * form is a whole block wherever it lies, and is not counted); out[22] = passes of exact sums that took TWO 4 x 4
+ * sub-blocks side by side on a strip's sub-block row at once (the split form's candidates and the hand-over kernel; each
+ * adds 2 to out[3], which keeps its meaning), out[23] = those of them whose window reaches across a block boundary -- both
+ * stay 0 under NHIP_BNB_PAIR_SUBS=0 and in the kernel that works a pair from start to end (synchronises; resets) */
 int nhip_bnb_stats_levels(uint64_t out[24]);
 /* ... and per pair of the last launch (4 x 4 sub-blocks evaluated exactly, a whole block counting four), before
  * nhip_bnb_stats resets the totals */

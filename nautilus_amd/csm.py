@@ -274,7 +274,7 @@ def bnb_stats_levels():
             "pairs_handed_over": v[12], "clk_wave_second_kernel": v[13], "pose_evals16": v[14],
             "pairs_settled_by_gate": v[15], "passes_l2_runs": v[16], "passes_per_cell_field": v[17],
             "passes_per_cell_capacity": v[18], "edge_blocks_refined": v[19], "sub_blocks_without_pose": v[20],
-            "edge_blocks_whole": v[21]}
+            "edge_blocks_whole": v[21], "pair_passes": v[22], "pair_passes_across_blocks": v[23]}
 
 
 def score_volume(scans, grids, src, slot, theta0, search, origin=(0, 0)):
@@ -320,7 +320,7 @@ def last_launch():
     form = {0: "fused", 1: "split, one round", 2: "split, rounds on one stream", 3: "split, rounds overlapped on the helper stream"}
     return {"form": form.get(out[0], "?"), "form_id": out[0], "pairs_per_round": out[1], "rounds_of_state": out[2],
             "rounds": out[3], "short_scans": bool(out[4]), "hand_over_kernel": bool(out[5]), "instrumented": bool(out[6] & 1),
-            "l2_runs": bool(out[6] & 2), "n_pairs": out[7]}
+            "l2_runs": bool(out[6] & 2), "pair_subs": bool(out[6] & 4), "n_pairs": out[7]}
 
 
 def drop_in_cache_stats():

@@ -93,8 +93,9 @@ constexpr int BNB_THREADS = 64 * BNB_WAVES;
 // the optimum nor a tie with it.  n[0] whole blocks evaluated, n[1] candidates refined, n[2] sub-blocks evaluated,
 // n[3] poses of 16-bit grids read exactly; at the lattice's edge (blocks with fewer than 8 pose columns or rows): n[4] such
 // blocks refined, n[5] sub-blocks evaluated that hold no pose (stays 0), n[6] such blocks evaluated whole (only ones with
-// more than 4 pose columns and rows can be).
-constexpr int N_WORK = 7;
+// more than 4 pose columns and rows can be); n[7] passes that took two sub-blocks side by side at once (each adds 2 to
+// n[2]), n[8] those of them that reach across a block boundary.
+constexpr int N_WORK = 9;
 struct PairCtx {
   const uint8_t *grid;
   const float2 *pts;
@@ -143,12 +144,13 @@ __device__ __forceinline__ void process_candidate(const BnbParams &P, const Pair
 // ... with the rotation's origins held by the wave and the block's four sub-block bounds at hand.  `rsrc` is the
 // 8-bit plane the exact block sums are taken on (8-bit grids: the image; 16-bit grids: the plane of high bytes) and
 // `pitch8` its pitch; `rsrc16` the 16-bit image (CB == 2).
-template <int CB, bool GLOBAL>
+template <int CB, bool GLOBAL, bool PAIR>
 __device__ __forceinline__ void process_candidate_c(const BnbParams &P, __amdgpu_buffer_rsrc_t rsrc, uint32_t pitch8,  // (CB 2: tiles per row)
                                                     __amdgpu_buffer_rsrc_t rsrc16, const uint32_t *org, int32_t nch,
                                                     int32_t n_pts, int32_t k, int32_t Y, int32_t X,
                                                     uint32_t sb0, uint32_t sb1, uint32_t sb2, uint32_t sb3, int lane,
-                                                    unsigned long long *best, uint32_t &bcopy, uint32_t (&n)[N_WORK]) {
+                                                    unsigned long long *best, uint32_t &bcopy, uint32_t (&n)[N_WORK],
+                                                    int t, uint32_t &mk0, uint32_t &mk1) {  // block t of its strip
   const uint32_t bsum = best_sum_cached<GLOBAL>(best, bcopy);
   const int32_t vx = block_extent(P.nx, X), vy = block_extent(P.ny, Y);
   const bool edge = vx < BNB_B || vy < BNB_B;
@@ -180,22 +182,97 @@ __device__ __forceinline__ void process_candidate_c(const BnbParams &P, __amdgpu
     n[6] += __ballot(ix < P.nx && iy < P.ny) != ~0ull ? 1u : 0u;  // (from the poses themselves, not from the extents)
     return;
   }
+  if (!PAIR) {  // one pass per sub-block, block by block
 #pragma unroll 1
-  for (int q = 0; q < 4; q++) {
-    const uint32_t b = q == 0 ? sb0 : (q == 1 ? sb1 : (q == 2 ? sb2 : sb3));
-    if (!sub_valid(vy, vx, q >> 1, q & 1) || b == 0u || b < best_sum_cached<GLOBAL>(best, bcopy)) continue;
-    int dy, dx;
-    const uint32_t total = sub_sums8(rsrc, pitch8, (uint32_t)P.hi_copy_bytes, org, nch, Y, X, q >> 1, q & 1, lane, &dy, &dx);
-    const int32_t ix = BNB_B * X + BNB_B4 * (q & 1) + dx, iy = BNB_B * Y + BNB_B4 * (q >> 1) + dy;
-    if (CB == 1) {
-      const unsigned long long key = best_key(P, k, ix, iy, total, 8);  // (lanes 16.. hold copies)
-      wave_atomic_max(best, key, lane);
-      if (GLOBAL) bcopy = max(bcopy, (uint32_t)(key >> 32));
-    } else {
-      n[3] += refine16<GLOBAL>(P, rsrc16, org, nch, n_pts, k, ix, iy, total, lane < 16, lane, best, bcopy);
+    for (int q = 0; q < 4; q++) {
+      const uint32_t b = q == 0 ? sb0 : (q == 1 ? sb1 : (q == 2 ? sb2 : sb3));
+      if (!sub_valid(vy, vx, q >> 1, q & 1) || b == 0u || b < best_sum_cached<GLOBAL>(best, bcopy)) continue;
+      int dy, dx;
+      const uint32_t total = sub_sums8(rsrc, pitch8, (uint32_t)P.hi_copy_bytes, org, nch, Y, X, q >> 1, q & 1, lane, &dy, &dx);
+      const int32_t ix = BNB_B * X + BNB_B4 * (q & 1) + dx, iy = BNB_B * Y + BNB_B4 * (q >> 1) + dy;
+      if (CB == 1) {
+        const unsigned long long key = best_key(P, k, ix, iy, total, 8);  // (lanes 16.. hold copies)
+        wave_atomic_max(best, key, lane);
+        if (GLOBAL) bcopy = max(bcopy, (uint32_t)(key >> 32));
+      } else {
+        n[3] += refine16<GLOBAL>(P, rsrc16, org, nch, n_pts, k, ix, iy, total, lane < 16, lane, best, bcopy);
+      }
+      n[2]++;
+      n[5] += __ballot(ix < P.nx && iy < P.ny) == 0ull ? 1u : 0u;  // (from the poses themselves, not from sub_valid)
     }
-    n[2]++;
-    n[5] += __ballot(ix < P.nx && iy < P.ny) == 0ull ? 1u : 0u;  // (from the poses themselves, not from sub_valid)
+    return;
+  }
+  // the live valid sub-blocks of a block that does not go whole: noted per sub-block row of the strip (bit 2 t + sx), taken
+  // by strip_sub_blocks once the strip's blocks are through
+  mk0 |= (uint32_t)((ok0 && sb0 != 0u && sb0 >= bsum) | ((ok1 && sb1 != 0u && sb1 >= bsum) << 1)) << (2 * t);
+  mk1 |= (uint32_t)((ok2 && sb2 != 0u && sb2 >= bsum) | ((ok3 && sb3 != 0u && sb3 >= bsum) << 1)) << (2 * t);
+}
+
+// ... and the sub-blocks process_candidate_c noted: mk0 / mk1 over the strip's up to six sub-block columns c = 2 t + sx, for
+// sy = 0 / 1; sb[4 t + 2 sy + sx] their bounds.  Each mask is walked from the left, every bound re-tested against the best
+// right before its pass.  Two set neighbours whose bounds both still reach the best share ONE pass (pair_sums8: four row
+// loads per chunk where two passes of sub_sums8 take eight) -- inside a block (c even) and, with PAIR_CROSS, across the
+// boundary to the strip's next block (c odd); a sub-block without such a neighbour has its own pass.  Every pose evaluated is a
+// pose of the lattice with its exact sum, every sub-block whose bound reaches the final best is still evaluated, and the
+// keys are maxima: records and sums do not depend on the pairing.  P.pair_subs == 0: one pass per sub-block.
+#ifndef NHIP_BNB_PAIR_CROSS
+// (1: pairs across a block boundary too -- 30 % more pairs on the bench list, measured 0.01 - 0.03 ms faster than without,
+//  which is inside the run-to-run spread: not shipped; profiles/r17_pair_passes.txt)
+#define NHIP_BNB_PAIR_CROSS 0
+#endif
+constexpr bool PAIR_CROSS = NHIP_BNB_PAIR_CROSS != 0;
+__device__ __forceinline__ uint32_t pick6(const uint32_t (&r)[6], int c) {  // (selects, not an indexed array: scratch)
+  return c == 0 ? r[0] : (c == 1 ? r[1] : (c == 2 ? r[2] : (c == 3 ? r[3] : (c == 4 ? r[4] : r[5]))));
+}
+template <int CB, bool GLOBAL>
+__device__ __forceinline__ void strip_sub_blocks(const BnbParams &P, __amdgpu_buffer_rsrc_t rsrc, uint32_t pitch8,
+                                                 __amdgpu_buffer_rsrc_t rsrc16, const uint32_t *org, int32_t nch, int32_t n_pts,
+                                                 int32_t k, int32_t Y, int32_t X0, const uint32_t (&sb)[12], uint32_t mk0,
+                                                 uint32_t mk1, int lane, unsigned long long *best, uint32_t &bcopy,
+                                                 uint32_t (&n)[N_WORK]) {
+#pragma unroll 1
+  for (int sy = 0; sy < 2; sy++) {
+    uint32_t mk = sy ? mk1 : mk0;
+    if (mk == 0u) continue;
+    uint32_t row[6];
+#pragma unroll
+    for (int c = 0; c < 6; c++) row[c] = sy ? sb[4 * (c >> 1) + 2 + (c & 1)] : sb[4 * (c >> 1) + (c & 1)];
+#pragma unroll 1
+    while (mk != 0u) {
+      const int c = (int)__builtin_ctz(mk);
+      mk &= mk - 1u;
+      const uint32_t bsum = best_sum_cached<GLOBAL>(best, bcopy);
+      if (pick6(row, c) < bsum) continue;  // the best has risen meanwhile
+      const int32_t X = X0 + (c >> 1), sx = c & 1;
+      const bool two = P.pair_subs != 0 && ((mk >> (c + 1)) & 1u) != 0u && (PAIR_CROSS || sx == 0) && pick6(row, c + 1) >= bsum;
+      int dy, dx;
+      uint32_t total;
+      if (two) {
+        mk &= ~(1u << (c + 1));
+        total = pair_sums8(rsrc, pitch8, (uint32_t)P.hi_copy_bytes, org, nch, Y, X, sy, sx, lane, &dy, &dx);
+      } else {
+        total = sub_sums8(rsrc, pitch8, (uint32_t)P.hi_copy_bytes, org, nch, Y, X, sy, sx, lane, &dy, &dx);
+      }
+      const int32_t ix = BNB_B * X + BNB_B4 * sx + dx, iy = BNB_B * Y + BNB_B4 * sy + dy;
+      if (CB == 1) {
+        const unsigned long long key = best_key(P, k, ix, iy, total, 16);  // (lanes 32.. hold copies; a single's: lanes 16..)
+        wave_atomic_max(best, key, lane);
+        if (GLOBAL) bcopy = max(bcopy, (uint32_t)(key >> 32));
+      } else {
+        n[3] += refine16<GLOBAL>(P, rsrc16, org, nch, n_pts, k, ix, iy, total, lane < (two ? 32 : 16), lane, best, bcopy);
+      }
+      // (from the poses themselves, not from sub_valid: a pair's halves are the lanes with dx < 4 and dx >= 4)
+      const bool pose = ix < P.nx && iy < P.ny;
+      if (two) {
+        n[2] += 2u;
+        n[5] += (__ballot(pose && dx < BNB_B4) == 0ull ? 1u : 0u) + (__ballot(pose && dx >= BNB_B4) == 0ull ? 1u : 0u);
+        n[7]++;
+        n[8] += (uint32_t)sx;
+      } else {
+        n[2]++;
+        n[5] += __ballot(pose) == 0ull ? 1u : 0u;
+      }
+    }
   }
 }
 
@@ -208,7 +285,7 @@ struct PhaseClocks {
 
 // The instrumented build's flush into stats[] (indices: include/nautilus_hip_debug.h): work counts n[0..3] as
 // process_candidate_c and rotation_pass count them, with the per-pair slot of `pair`, and / or a wave's phase clocks.
-// `edge`: a wave's three counts at the lattice's edge, n + 4.  Any may be null.  (The product build passes a null `stats`:
+// `edge`: a wave's three counts at the lattice's edge and its two of pair passes, n + 4.  Any may be null.  (The product build passes a null `stats`:
 // dead code there.)
 __device__ __forceinline__ void flush_stats(unsigned long long *stats, const uint32_t *n, int32_t pair, const PhaseClocks *clk,
                                             const uint32_t *edge = nullptr) {
@@ -219,10 +296,12 @@ __device__ __forceinline__ void flush_stats(unsigned long long *stats, const uin
     if (n[3]) atomicAdd(&stats[14], (unsigned long long)n[3]);  // poses of 16-bit grids evaluated exactly (refine16)
     if (pair < BNB_STATS_PAIRS) atomicAdd(&stats[BNB_STATS_HEAD + pair], 4ull * n[0] + n[2]);
   }
-  if (edge) {  // a wave's n[4..6]: the work at the lattice's edge
+  if (edge) {  // a wave's n[4..8]: the work at the lattice's edge, the pair passes
     if (edge[0]) atomicAdd(&stats[19], (unsigned long long)edge[0]);
     if (edge[1]) atomicAdd(&stats[20], (unsigned long long)edge[1]);
     if (edge[2]) atomicAdd(&stats[21], (unsigned long long)edge[2]);
+    if (edge[3]) atomicAdd(&stats[22], (unsigned long long)edge[3]);
+    if (edge[4]) atomicAdd(&stats[23], (unsigned long long)edge[4]);
   }
   if (clk) {
     atomicAdd(&stats[5], (unsigned long long)clk->org);
@@ -236,10 +315,14 @@ __device__ __forceinline__ void flush_stats(unsigned long long *stats, const uin
 
 // ---- one rotation of one pair: its candidate blocks (masks m0 | m1 over block index b = NB * Y + X, bounds u0 / u1
 // lane-wise) through sub-block bounds and exact sums, origins held in registers.  `done`: the workgroup's bound row
-// of this rotation, where finished blocks are zeroed (seeds), or null.  RUNS: the wave has RUN_WAVE words at `runs` for
+// of this rotation, where finished blocks are zeroed (seeds), or null.  PAIR: the sub-blocks of the strip's blocks that do
+// not go whole are taken after its blocks, two side by side in one pass where both are alive (strip_sub_blocks); without
+// it block by block, one pass each.  The candidates' kernels pair; csm_bnb_kernel -- the seeds, which take one block each,
+// and the fused form's own rotations -- does not: the pair pass is 10 KB of code, and that kernel's by-rotation
+// instantiations are at or past the 64 KB of the instruction cache as they are (profiles/r17_pair_passes_isa.txt).  RUNS: the wave has RUN_WAVE words at `runs` for
 // the rotation's runs by level-2 entry, and the strip bounds walk those (unless P.l2_runs is off, or cache_origins
 // reports that this rotation's runs do not fit the list or its 16-bit fields: then, as without RUNS, per cell).
-template <int CB, bool GLOBAL, bool RUNS = false>
+template <int CB, bool GLOBAL, bool PAIR, bool RUNS = false>
 __device__ __forceinline__ void rotation_pass(const BnbParams &P, const PairCtx &C, int32_t k, uint32_t u0, uint32_t u1,
                                               unsigned long long m0, unsigned long long m1, int lane,
                                               unsigned long long *best, uint32_t *done, uint32_t *org,
@@ -287,6 +370,7 @@ __device__ __forceinline__ void rotation_pass(const BnbParams &P, const PairCtx 
 #pragma unroll
       for (int q = 0; q < 12; q++) sb[q] = 0xffffffffu;
     }
+    uint32_t mk0 = 0u, mk1 = 0u;  // the live sub-blocks of the strip's blocks that do not go whole, per sy
 #pragma unroll 1
     for (int t = 0; t < len; t++) {
       const int b = b0 + t;
@@ -298,10 +382,15 @@ __device__ __forceinline__ void rotation_pass(const BnbParams &P, const PairCtx 
       const uint32_t s0 = t == 0 ? sb[0] : (t == 1 ? sb[4] : sb[8]), s1 = t == 0 ? sb[1] : (t == 1 ? sb[5] : sb[9]);
       const uint32_t s2 = t == 0 ? sb[2] : (t == 1 ? sb[6] : sb[10]), s3 = t == 0 ? sb[3] : (t == 1 ? sb[7] : sb[11]);
       if (BNB_STATS(P)) t_mark = clock64();
-      process_candidate_c<CB, GLOBAL>(P, rsrc, pitch8, rsrc16, org, nch, C.n_pts, k, Y, X0 + t, s0, s1, s2, s3, lane, best,
-                                      bcopy, n_work);
+      process_candidate_c<CB, GLOBAL, PAIR>(P, rsrc, pitch8, rsrc16, org, nch, C.n_pts, k, Y, X0 + t, s0, s1, s2, s3, lane, best,
+                                      bcopy, n_work, t, mk0, mk1);
       if (BNB_STATS(P)) clk.eval += clock64() - t_mark;
       if (done && wave_leader(lane)) done[b] = 0u;
+    }
+    if (PAIR && (mk0 | mk1) != 0u) {
+      if (BNB_STATS(P)) t_mark = clock64();
+      strip_sub_blocks<CB, GLOBAL>(P, rsrc, pitch8, rsrc16, org, nch, C.n_pts, k, Y, X0, sb, mk0, mk1, lane, best, bcopy, n_work);
+      if (BNB_STATS(P)) clk.eval += clock64() - t_mark;
     }
   }
 }
@@ -554,7 +643,7 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : BNB_THREADS, SPLIT ? SPL
         }
         have = true;
       }
-      if (have) rotation_pass<CB, false>(P, C, k, u0, u1, m0, m1, lane, s_best, done, org, n_work, clk);
+      if (have) rotation_pass<CB, false, false>(P, C, k, u0, u1, m0, m1, lane, s_best, done, org, n_work, clk);
       if (state == SEED) {
         __syncthreads();
         if (BNB_TIMELINE(P) && threadIdx.x == 0 && pair < BNB_STATS_PAIRS) BNB_TIMELINE(P)[4 * pair + 2] = wall_clock64();
@@ -702,8 +791,10 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : BNB_THREADS, SPLIT ? SPL
 // Second kernel: the rotations of the pairs with many candidates, one wave per (pair, rotation), every wave of the
 // chip.  The pair's running best is keys[pair] (left by its workgroup after the seeds, raised by every wave that
 // works on the pair); a block is skipped when that has passed its bound.
+// (16-bit grids: compiled for five waves per SIMD like the candidates' kernel below -- the 96 registers it had before the
+//  pair pass, which it otherwise passes by two; the instrumented build keeps its own 105)
 template <int CB>
-__global__ __launch_bounds__(256, 4) void csm_bnb_rot_kernel(BnbParams P) {
+__global__ __launch_bounds__(256, CB == 2 && !NHIP_BNB_INSTR ? 5 : 4) void csm_bnb_rot_kernel(BnbParams P) {
   const int lane = threadIdx.x & 63;
   // workgroup b works on the list of XCD b & 7 (blocks b and b + 8 share an XCD)
   const uint32_t xcd = blockIdx.x & 7u;
@@ -727,7 +818,7 @@ __global__ __launch_bounds__(256, 4) void csm_bnb_rot_kernel(BnbParams P) {
     uint32_t n[N_WORK] = {};
     // (no block bounds here: 0xffffffff lets every candidate through to its sub-block bounds, which are checked
     //  against the best as it stands in keys[pair])
-    rotation_pass<CB, true, true>(P, C, k, 0xffffffffu, 0xffffffffu, m0, m1, lane, &P.keys[pair], nullptr, org, n, clk, runs);
+    rotation_pass<CB, true, true, true>(P, C, k, 0xffffffffu, 0xffffffffu, m0, m1, lane, &P.keys[pair], nullptr, org, n, clk, runs);
     if (BNB_STATS(P) && lane == 0) flush_stats(BNB_STATS(P), n, pair, nullptr, n + 4);
   }
   if (BNB_STATS(P) && lane == 0) {
@@ -902,7 +993,7 @@ __global__ __launch_bounds__(CAND_THREADS, CB == 2 ? 5 : 4) void csm_bnb_cand_ke
     const unsigned long long m0 = __ballot(u0 != 0u && u0 >= bsum);
     const unsigned long long m1 = __ballot(u1 != 0u && u1 >= bsum && lane + 64 < NB * NB);
     if ((m0 | m1) == 0ull) continue;
-    rotation_pass<CB, true, true>(P, C, k, u0, u1, m0, m1, lane, best, nullptr, org, n_work, clk, runs);
+    rotation_pass<CB, true, true, true>(P, C, k, u0, u1, m0, m1, lane, best, nullptr, org, n_work, clk, runs);
   }
   if (BNB_STATS(P) && lane == 0) {
     atomicAdd(&BNB_STATS(P)[13], (unsigned long long)(clock64() - t0));

@@ -2,8 +2,8 @@
 // stored cells over a scan's points, for the poses of a block or sub-block, and the key of the best of them.
 //
 // Owns four kinds: eval_block / eval_sub -- from the points, on the stored image (the general kernel and the seeds of
-// long scans); block_sums8 / sub_sums8 -- from the origins a wave holds, on the tiled 8-bit plane (the cells of 8-bit
-// grids, the high bytes of 16-bit ones); pose_sum16 / refine16 -- single poses of 16-bit grids that the high-byte bound
+// long scans); block_sums8 / sub_sums8 / pair_sums8 -- from the origins a wave holds, on the tiled 8-bit plane (the cells
+// of 8-bit grids, the high bytes of 16-bit ones: a whole block, one sub-block, two sub-blocks side by side); pose_sum16 / refine16 -- single poses of 16-bit grids that the high-byte bound
 // admits, from the tiled 16-bit image; and best_key / best_sum / best_sum_cached -- the pair's running best,
 // key = sum << 32 | ~linear index, so that the maximum key is the maximum sum at the smallest index.
 // Assumes: the slot layout of nhip_layout.hip (every offset an evaluation forms lies inside the descriptor it is given),
@@ -444,6 +444,65 @@ __device__ __forceinline__ uint32_t block_sums8(__amdgpu_buffer_rsrc_t rsrc, uin
   rs_step<4, 16>(V, lane & 16);
   rs_step<2, 32>(V, lane & 32);
   const int r = 8 * (2 * ((lane >> 5) & 1) + ((lane >> 4) & 1)) + 4 * ((lane >> 2) & 1) + 2 * ((lane >> 1) & 1) + (lane & 1);
+  const int f = (lane >> 3) & 1, d = r & 3;
+  *dy = r >> 2;
+  *dx = 4 * (d >> 1) + (d & 1) + 2 * f;
+  return V[0];
+}
+
+// Two 4 x 4 sub-blocks side by side in ONE pass: the 4 rows x 8 pose columns from row 8 Y + 4 sy, column 8 X + 4 sx0 on --
+// sub-blocks (sy, 0) and (sy, 1) of block (Y, X) for sx0 = 0, or (sy, 1) of it and (sy, 0) of block (Y, X + 1) for sx0 = 1.
+// The 12-byte row load block_sums8 issues covers both (sub_sums8's 8 bytes: one), so the pair costs four row loads per
+// chunk, one origin decode and one reduction where two passes of sub_sums8 cost eight, two and two.  One group of four rows
+// exactly as block_sums8's (the same choice of copy: 12 bytes from a 4-aligned column start in a tile's first half in one
+// of the two), 16 packed accumulators, 12 row registers.  Lane l holds the sum of pose (*dy in 0..3, *dx in 0..7) of the
+// window; lanes 32.. hold copies of lanes 0..31.
+__device__ __forceinline__ uint32_t pair_sums8(__amdgpu_buffer_rsrc_t rsrc, uint32_t pitch, uint32_t copy_bytes, const uint32_t *org,
+                                               int32_t nch, int32_t Y, int32_t X, int32_t sy, int32_t sx0, int lane, int *dy, int *dx) {
+  const uint32_t roff = (uint32_t)(BNB_B * Y + BNB_B4 * sy), coff = (uint32_t)(BNB_B * X + BNB_B4 * sx0);
+  const uint32_t wrap = pitch * HI_TILE_BYTES - HI_TILE_BYTES;  // from a tile's last row to the next tile's first
+  // (the fields of block_sums8: a byte sum per 16-bit field through the three packed steps, i.e. over 8 lanes, which hold
+  //  at most 257 points -- cache_origins -- of at most 255 each; 32 bits from the unpack on)
+  static_assert(257u * 255u <= 0xffffu, "a packed field holds the byte sums of the 8 lanes it is reduced over");
+  uint32_t E[4][2], O[4][2];
+#pragma unroll
+  for (int y = 0; y < 4; y++) E[y][0] = E[y][1] = O[y][0] = O[y][1] = 0u;
+#pragma unroll
+  for (int r = 0; r < OC; r++) {
+    if (r >= nch) continue;
+    const uint32_t o = origin_of(org, r);
+    const uint32_t cn = org_cnt(o);
+    const uint32_t row0 = org_row(o) + roff, col0 = org_col(o) + coff, col4 = col0 & ~3u;
+    const uint32_t q = row0 & 7u, sh = (col0 & 3u) * 8u;
+    const uint32_t g = hi_tiled(row0, col4, (col4 >> 3) & 1u, pitch, copy_bytes);
+    u32x3 w[4];
+#pragma unroll
+    for (int y = 0; y < 4; y++)
+      w[y] = __builtin_amdgcn_raw_buffer_load_b96(rsrc, (int)(g + (q + (uint32_t)y >= 8u ? wrap : 0u) + 16u * (uint32_t)y), 0, 0);
+#pragma unroll
+    for (int y = 0; y < 4; y++) {
+      const uint32_t n0 = __builtin_amdgcn_alignbit(w[y].y, w[y].x, sh);
+      const uint32_t n1 = __builtin_amdgcn_alignbit(w[y].z, w[y].y, sh);
+      E[y][0] += __umul24(n0 & M8, cn); O[y][0] += __umul24(n0 >> 8, cn);
+      E[y][1] += __umul24(n1 & M8, cn); O[y][1] += __umul24(n1 >> 8, cn);
+    }
+  }
+  uint32_t R[16];  // R[4 y + d]: d = 0: dx 0, 2; 1: dx 1, 3; 2: dx 4, 6; 3: dx 5, 7
+#pragma unroll
+  for (int y = 0; y < 4; y++) {
+    R[4 * y + 0] = E[y][0];
+    R[4 * y + 1] = O[y][0] - ((E[y][0] >> 16) << 8);
+    R[4 * y + 2] = E[y][1];
+    R[4 * y + 3] = O[y][1] - ((E[y][1] >> 16) << 8);
+  }
+  rs_step<16, 1>(R, lane & 1);
+  rs_step<8, 2>(R, lane & 2);
+  rs_step<4, 4>(R, lane & 4);
+  uint32_t V[4] = {R[0] & 0xffffu, R[0] >> 16, R[1] & 0xffffu, R[1] >> 16};
+  rs_step<4, 8>(V, lane & 8);
+  rs_step<2, 16>(V, lane & 16);
+  V[0] = add_xor<32>(V[0]);
+  const int r = 8 * ((lane >> 4) & 1) + 4 * ((lane >> 2) & 1) + 2 * ((lane >> 1) & 1) + (lane & 1);
   const int f = (lane >> 3) & 1, d = r & 3;
   *dy = r >> 2;
   *dx = 4 * (d >> 1) + (d & 1) + 2 * f;

@@ -103,6 +103,7 @@ BnbPlan bnb_plan(const GridLayout &L, const nhip_search_t *search, int32_t n_pai
   p.cb = L.cb;
   p.levels = is(tunable("NHIP_BNB_LEVELS"), '1') ? 1 : 2;  // (1: without the sub-block bounds)
   p.l2_runs = !is(tunable("NHIP_BNB_L2_RUNS"), '0');       // (0: strip bounds per stored cell everywhere -- the A/B, tests)
+  p.pair_subs = !is(tunable("NHIP_BNB_PAIR_SUBS"), '0');   // (0: one pass of exact sums per sub-block -- the A/B, tests)
   p.general_all = is(tunable("NHIP_BNB_QUEUE"), '1');      // (the general path for every scan)
   static_assert(NHIP_SHORT_SCAN_POINTS == 64 * OCL, "the header's promise is the by-rotation form's limit");
   p.short_scans = (search->flags & NHIP_SEARCH_SHORT_SCANS) != 0 && !p.general_all && (uint32_t)(L.S + 2 * L.pad) < ORG_LIMIT;
@@ -210,7 +211,7 @@ static thread_local BnbPlan t_last_plan = {};
 void bnb_last_launch(int32_t out[8]) {
   const BnbPlan &p = t_last_plan;
   const int32_t info[8] = {p.form, (int32_t)p.batch, (int32_t)p.slots, (int32_t)p.rounds, p.short_scans, p.second,
-                           (int32_t)p.instrumented | ((int32_t)p.l2_runs << 1), p.n_pairs};
+                           (int32_t)p.instrumented | ((int32_t)p.l2_runs << 1) | ((int32_t)p.pair_subs << 2), p.n_pairs};
   memcpy(out, info, sizeof(info));
 }
 
@@ -240,6 +241,7 @@ static void fill_bnb_params(BnbParams &P, const MatchJob &job, const BnbPlan &pl
   P.inv_res_f = (float)P.inv_res;
   P.levels = plan.levels;
   P.l2_runs = plan.l2_runs;
+  P.pair_subs = plan.pair_subs;
   P.general_all = plan.general_all;
   P.short_scans = plan.short_scans;
   P.heavy_min = plan.heavy_min;

@@ -120,6 +120,7 @@ struct BnbParams {
   float inv_res_f;  // RN_f32(1 / res): the single-precision path of the window origins
   ScoreGate gate;   // the caller's min_score (nhip_csm_match_gated): a pair's best starts at its floor key (nhip_csm_shared.h)
   int32_t l2_runs;  // strip bounds from the list of level-2 runs where a kernel keeps one (0: NHIP_BNB_L2_RUNS=0, per cell everywhere)
+  int32_t pair_subs;  // two live sub-blocks side by side on a strip's sub-block row share one pass (0: NHIP_BNB_PAIR_SUBS=0, one pass each)
 };
 
 // The kernel launches of one batch in each build: launchers_product() (nhip_bnb.hip), launchers_instr()

@@ -236,6 +236,7 @@ struct BnbPlan {
   int32_t n_pairs, cb, levels;
   bool second, general_all, short_scans, pool_lds, instrumented, stats, timeline;
   bool l2_runs;      // strip bounds over runs of level-2 entries in the kernels that keep that list (NHIP_BNB_L2_RUNS=0: per cell)
+  bool pair_subs;    // two live side-by-side sub-blocks of a strip in one pass of exact sums (NHIP_BNB_PAIR_SUBS=0: one pass each)
   bool sized_split;  // the size rule (bnb_workspace_bytes) gives this list room for the split form
   uint32_t rot_cap, heavy_min, keep_ranks, split_min, split_max;  // split_max 0: by the round's length
   int64_t batch, slots, slot_bytes, rounds;  // pairs per round (0: fused), rounds' state the workspace holds, bytes of one
