@@ -34,7 +34,7 @@
  * There is no CPU fallback anywhere: without a gfx950 device compute calls fail with
  * NHIP_ERR_NODEV.
  * The instruments -- counters, timers, launch reports, downloads of the matcher's private planes -- are declared in
- * nautilus_hip_debug.h, not here.
+ * nautilus_hip_debug.h, not here (one exception, at the end of this file: nhip_bnb_stats_chunks).
  */
 #ifndef NAUTILUS_HIP_H_
 #define NAUTILUS_HIP_H_
@@ -1372,6 +1372,17 @@ int nhip_resid_point_to_line(const float *segments, const float *points, const i
  * never need it.  A Python host does the same with torch.distributed (nautilus_amd/sharding.py). */
 int nhip_allgather_matches(void *comm, const nhip_match_t *d_local, int32_t n_local,
                            nhip_match_t *d_all, void *stream);
+
+/* ------------------------------------------------------------------ one instrument declared here
+ * (the set of nautilus_hip_debug.h is closed -- tests/test_abi.py lists it name by name; read this one as part of it, after
+ * nhip_bnb_stats_levels there.)  With NHIP_BNB_STATS=1, in the instrumented build: the chunk visits of the exact sums in the
+ * kernels that keep a list of level-2 runs (the split form's candidates, the hand-over kernel; not the seeds), since the
+ * last call -- a visit is one 64-entry chunk of a rotation's cell list taken by one pass.  out[0] = visits of the passes
+ * on the 8-bit plane (a sub-block, two side by side, a whole block) if every pass took every chunk of the list, out[1] =
+ * visits made: the passes leave out the chunks in which no entry has a level-2 byte that is not zero for a sub-block of
+ * the pass, i.e. whose windows hold only empty cells; out[2], out[3] = the same two for the single poses of 16-bit grids
+ * read from the 16-bit image.  out[1] == out[0] and out[3] == out[2] under NHIP_BNB_ZERO_CHUNKS=0 (synchronises; resets). */
+int nhip_bnb_stats_chunks(uint64_t out[4]);
 
 #ifdef __cplusplus
 }

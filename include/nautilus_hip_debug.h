@@ -27,7 +27,9 @@ int nhip_host_phases(double out[8]);
  * helper stream of the current device; out[1] pairs per round; out[2] rounds' state the workspace holds; out[3] rounds;
  * out[4] 1 when NHIP_SEARCH_SHORT_SCANS was honoured; out[5] hand-over kernel launched; out[6] bit 0: instrumented build,
  * bit 1: the kernels that keep a list of level-2 runs take their strip bounds from it (clear: NHIP_BNB_L2_RUNS=0),
- * bit 2: the candidates' kernels take two live sub-blocks side by side in one pass (clear: NHIP_BNB_PAIR_SUBS=0);
+ * bit 2: the candidates' kernels take two live sub-blocks side by side in one pass (clear: NHIP_BNB_PAIR_SUBS=0),
+ * bit 3: their exact sums leave out the chunks of the cell list whose windows hold only empty cells (clear:
+ * NHIP_BNB_ZERO_CHUNKS=0; what that saves is counted by nhip_bnb_stats_chunks, declared at the end of nautilus_hip.h);
  * out[7] n_pairs. */
 int nhip_csm_last_launch(int32_t out[8]);
 /* What the calling thread's last nhip_csm_get_transformation did: {the coarse optimum's score, the form the fine level ran in

@@ -277,6 +277,13 @@ def bnb_stats_levels():
             "edge_blocks_whole": v[21], "pair_passes": v[22], "pair_passes_across_blocks": v[23]}
 
 
+def bnb_stats_chunks():
+    """Chunk visits of the exact sums in the kernels that keep a run list, since the last call (nhip_bnb_stats_chunks)."""
+    v = (C.c_uint64 * 4)()
+    check(_lib.load().nhip_bnb_stats_chunks(v))
+    return {"chunk_visits_full": v[0], "chunk_visits": v[1], "pose_chunk_visits_full": v[2], "pose_chunk_visits": v[3]}
+
+
 def score_volume(scans, grids, src, slot, theta0, search, origin=(0, 0)):
     out = np.zeros((search.n_theta, search.nx, search.ny), dtype=np.int32)
     check(_lib.load().nhip_csm_scores(scans._h, grids._h, int(src), int(slot), float(theta0),
@@ -320,7 +327,8 @@ def last_launch():
     form = {0: "fused", 1: "split, one round", 2: "split, rounds on one stream", 3: "split, rounds overlapped on the helper stream"}
     return {"form": form.get(out[0], "?"), "form_id": out[0], "pairs_per_round": out[1], "rounds_of_state": out[2],
             "rounds": out[3], "short_scans": bool(out[4]), "hand_over_kernel": bool(out[5]), "instrumented": bool(out[6] & 1),
-            "l2_runs": bool(out[6] & 2), "pair_subs": bool(out[6] & 4), "n_pairs": out[7]}
+            "l2_runs": bool(out[6] & 2), "pair_subs": bool(out[6] & 4), "zero_chunks": bool(out[6] & 8),
+            "n_pairs": out[7]}
 
 
 def drop_in_cache_stats():

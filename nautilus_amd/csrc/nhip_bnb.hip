@@ -38,7 +38,9 @@
 // pairs are shared by several workgroups); csm_bnb_rot_kernel<CB>: rotations handed over by pairs with flat landscapes
 // in small batches.  Exact sums of 16-bit grids run on the plane of high bytes (256 sum(hi) + 255 n bounds a pose's sum;
 // only the poses that bound admits read 16-bit cells), which -- like the copy of the cells those reads use -- is stored
-// in tiles of one cache line, because what a gather costs here is the number of distinct lines per load.
+// in tiles of one cache line, because what a gather costs here is the number of distinct lines per load.  The two kernels
+// that keep a rotation's runs by level-2 entry (candidates, hand-over) take their exact sums only over the 64-entry chunks
+// of the origin list in which some entry's level-2 byte says a cell can be non-zero for the poses of the pass (chunk_mask).
 //
 // This file: candidate processing, the kernels, their launchers.  What they are built from lies in headers that only
 // this file includes: nhip_bnb_wave.h (lane exchanges, wave reductions), nhip_bnb_origin.h (window origins),
@@ -94,13 +96,43 @@ constexpr int BNB_THREADS = 64 * BNB_WAVES;
 // n[3] poses of 16-bit grids read exactly; at the lattice's edge (blocks with fewer than 8 pose columns or rows): n[4] such
 // blocks refined, n[5] sub-blocks evaluated that hold no pose (stays 0), n[6] such blocks evaluated whole (only ones with
 // more than 4 pose columns and rows can be); n[7] passes that took two sub-blocks side by side at once (each adds 2 to
-// n[2]), n[8] those of them that reach across a block boundary.
-constexpr int N_WORK = 9;
+// n[2]), n[8] those of them that reach across a block boundary; the kernels that keep a run list: n[9] chunks of the cell
+// list a pass of exact sums on the 8-bit plane would visit without the chunk masks (the list's chunks per pass), n[10]
+// chunks visited; n[11], n[12] the same two for the poses of 16-bit grids read exactly.
+constexpr int N_WORK = 13;
 struct PairCtx {
   const uint8_t *grid;
   const float2 *pts;
   int32_t n_pts, cx, cy, pair;
 };
+
+// ---- which chunks of the cell list a pass of exact sums must visit
+// An entry of the cell list adds nothing to any pose of a sub-block whose level-2 byte is 0 for it: that byte is the
+// maximum (16-bit grids: ceil(max / 257)) over the 7 x 7 cells that hold every window the sub-block's poses read from any
+// origin inside the entry's 4 x 4 level-2 entry.  The strip bounds load exactly those bytes, per RUN of the list (runs of
+// consecutive entries with one level-2 entry), and leave per run the twelve-bit set of the strip's bytes that are not
+// zero (`note`, nhip_bnb_bounds.h strip_sums); cache_origins left per run the chunks of the cell list its cells lie in
+// (`span`: first chunk | reaches the next << 5).  A pass over the sub-blocks `fields` (bits 4 t + sy + 2 sx) visits the
+// chunks of the runs that have one of those bytes set -- a superset of the chunks that hold a cell that is not zero -- so
+// every sum is the full list's.  nrc <= 0 (no usable run list, or P.zero_chunks off): every chunk, `full`.
+struct ChunkNotes {
+  const uint16_t *note;  // the lane's word of run chunk 0
+  const uint8_t *span;   // the lane's byte of run chunk 0
+  int32_t nrc;           // chunks of the run list (wave-uniform)
+  uint32_t full;         // (1 << chunks of the cell list) - 1
+};
+__device__ __forceinline__ uint32_t chunk_mask(const ChunkNotes &N, uint32_t fields) {
+  if (N.nrc <= 0) return N.full;
+  uint32_t acc = 0u;
+#pragma unroll
+  for (int j = 0; j < RUN_CHUNKS; j++) {
+    // (both reads lie inside the wave's arrays whatever nrc is; past it the words are stale and not used)
+    const uint32_t f = N.note[64 * j], s = N.span[64 * j];
+    const uint32_t chunks = (1u + ((s >> 5) << 1)) << (s & 31u);
+    acc |= (j < N.nrc && (f & fields) != 0u) ? chunks : 0u;
+  }
+  return wave_or(acc) & N.full;
+}
 
 template <int CB>
 __device__ __forceinline__ void process_candidate(const BnbParams &P, const PairCtx &C, int32_t k, int32_t v, int lane,
@@ -143,14 +175,16 @@ __device__ __forceinline__ void process_candidate(const BnbParams &P, const Pair
 
 // ... with the rotation's origins held by the wave and the block's four sub-block bounds at hand.  `rsrc` is the
 // 8-bit plane the exact block sums are taken on (8-bit grids: the image; 16-bit grids: the plane of high bytes) and
-// `pitch8` its pitch; `rsrc16` the 16-bit image (CB == 2).
-template <int CB, bool GLOBAL, bool PAIR>
+// `pitch8` its pitch; `rsrc16` the 16-bit image (CB == 2).  ZC: the kernel keeps what chunk_mask needs (`CN`), and the
+// exact sums walk the chunks it names.
+template <int CB, bool GLOBAL, bool PAIR, bool ZC = false>
 __device__ __forceinline__ void process_candidate_c(const BnbParams &P, __amdgpu_buffer_rsrc_t rsrc, uint32_t pitch8,  // (CB 2: tiles per row)
                                                     __amdgpu_buffer_rsrc_t rsrc16, const uint32_t *org, int32_t nch,
                                                     int32_t n_pts, int32_t k, int32_t Y, int32_t X,
                                                     uint32_t sb0, uint32_t sb1, uint32_t sb2, uint32_t sb3, int lane,
                                                     unsigned long long *best, uint32_t &bcopy, uint32_t (&n)[N_WORK],
-                                                    int t, uint32_t &mk0, uint32_t &mk1) {  // block t of its strip
+                                                    int t, uint32_t &mk0, uint32_t &mk1,  // block t of its strip
+                                                    const ChunkNotes &CN = ChunkNotes()) {
   const uint32_t bsum = best_sum_cached<GLOBAL>(best, bcopy);
   const int32_t vx = block_extent(P.nx, X), vy = block_extent(P.ny, Y);
   const bool edge = vx < BNB_B || vy < BNB_B;
@@ -169,14 +203,26 @@ __device__ __forceinline__ void process_candidate_c(const BnbParams &P, __amdgpu
   constexpr int WHOLE_MIN = 3;
   if (alive >= WHOLE_MIN) {
     int dy, dx;
-    const uint32_t total = block_sums8(rsrc, pitch8, (uint32_t)P.hi_copy_bytes, org, nch, Y, X, lane, &dy, &dx);
+    // (ZC: a whole block's pass covers its four sub-blocks: the chunks of the runs with any of the block's four bytes set)
+    const uint32_t visit = ZC ? chunk_mask(CN, 0xfu << (4 * t)) : 0u;
+    const uint32_t total = ZC ? block_sums8_masked(rsrc, pitch8, (uint32_t)P.hi_copy_bytes, org, visit, Y, X, lane, &dy, &dx)
+                              : block_sums8(rsrc, pitch8, (uint32_t)P.hi_copy_bytes, org, nch, Y, X, lane, &dy, &dx);
     const int32_t ix = BNB_B * X + dx, iy = BNB_B * Y + dy;
+    if (ZC) {
+      n[9] += (uint32_t)nch;
+      n[10] += (uint32_t)__builtin_popcount(visit);
+    }
     if (CB == 1) {
       const unsigned long long key = best_key(P, k, ix, iy, total, 32);
       wave_atomic_max(best, key, lane);  // (generic address: LDS or global)
       if (GLOBAL) bcopy = max(bcopy, (uint32_t)(key >> 32));
     } else {
-      n[3] += refine16<GLOBAL>(P, rsrc16, org, nch, n_pts, k, ix, iy, total, true, lane, best, bcopy);
+      const uint32_t read = refine16<GLOBAL, ZC>(P, rsrc16, org, nch, n_pts, k, ix, iy, total, true, lane, best, bcopy, visit);
+      n[3] += read;
+      if (ZC) {
+        n[11] += read * (uint32_t)nch;
+        n[12] += read * (uint32_t)__builtin_popcount(visit);
+      }
     }
     n[0]++;
     n[6] += __ballot(ix < P.nx && iy < P.ny) != ~0ull ? 1u : 0u;  // (from the poses themselves, not from the extents)
@@ -229,7 +275,7 @@ __device__ __forceinline__ void strip_sub_blocks(const BnbParams &P, __amdgpu_bu
                                                  __amdgpu_buffer_rsrc_t rsrc16, const uint32_t *org, int32_t nch, int32_t n_pts,
                                                  int32_t k, int32_t Y, int32_t X0, const uint32_t (&sb)[12], uint32_t mk0,
                                                  uint32_t mk1, int lane, unsigned long long *best, uint32_t &bcopy,
-                                                 uint32_t (&n)[N_WORK]) {
+                                                 uint32_t (&n)[N_WORK], const ChunkNotes &CN) {
 #pragma unroll 1
   for (int sy = 0; sy < 2; sy++) {
     uint32_t mk = sy ? mk1 : mk0;
@@ -247,11 +293,17 @@ __device__ __forceinline__ void strip_sub_blocks(const BnbParams &P, __amdgpu_bu
       const bool two = P.pair_subs != 0 && ((mk >> (c + 1)) & 1u) != 0u && (PAIR_CROSS || sx == 0) && pick6(row, c + 1) >= bsum;
       int dy, dx;
       uint32_t total;
+      // the chunks to visit: those of the runs whose level-2 byte of the sub-block -- of either of a pair's two, which lie
+      // two bits apart in the block's four -- is not zero (a pair across a block boundary, compiled out: every chunk)
+      const uint32_t field = 1u << (4 * (c >> 1) + sy + 2 * sx);
+      const uint32_t visit = two ? (sx == 0 ? chunk_mask(CN, field | (field << 2)) : CN.full) : chunk_mask(CN, field);
+      n[9] += (uint32_t)nch;
+      n[10] += (uint32_t)__builtin_popcount(visit);
       if (two) {
         mk &= ~(1u << (c + 1));
-        total = pair_sums8(rsrc, pitch8, (uint32_t)P.hi_copy_bytes, org, nch, Y, X, sy, sx, lane, &dy, &dx);
+        total = pair_sums8_masked(rsrc, pitch8, (uint32_t)P.hi_copy_bytes, org, visit, Y, X, sy, sx, lane, &dy, &dx);
       } else {
-        total = sub_sums8(rsrc, pitch8, (uint32_t)P.hi_copy_bytes, org, nch, Y, X, sy, sx, lane, &dy, &dx);
+        total = sub_sums8_masked(rsrc, pitch8, (uint32_t)P.hi_copy_bytes, org, visit, Y, X, sy, sx, lane, &dy, &dx);
       }
       const int32_t ix = BNB_B * X + BNB_B4 * sx + dx, iy = BNB_B * Y + BNB_B4 * sy + dy;
       if (CB == 1) {
@@ -259,7 +311,10 @@ __device__ __forceinline__ void strip_sub_blocks(const BnbParams &P, __amdgpu_bu
         wave_atomic_max(best, key, lane);
         if (GLOBAL) bcopy = max(bcopy, (uint32_t)(key >> 32));
       } else {
-        n[3] += refine16<GLOBAL>(P, rsrc16, org, nch, n_pts, k, ix, iy, total, lane < (two ? 32 : 16), lane, best, bcopy);
+        const uint32_t read = refine16<GLOBAL, true>(P, rsrc16, org, nch, n_pts, k, ix, iy, total, lane < (two ? 32 : 16), lane, best, bcopy, visit);
+        n[3] += read;
+        n[11] += read * (uint32_t)nch;
+        n[12] += read * (uint32_t)__builtin_popcount(visit);
       }
       // (from the poses themselves, not from sub_valid: a pair's halves are the lanes with dx < 4 and dx >= 4)
       const bool pose = ix < P.nx && iy < P.ny;
@@ -285,16 +340,22 @@ struct PhaseClocks {
 
 // The instrumented build's flush into stats[] (indices: include/nautilus_hip_debug.h): work counts n[0..3] as
 // process_candidate_c and rotation_pass count them, with the per-pair slot of `pair`, and / or a wave's phase clocks.
-// `edge`: a wave's three counts at the lattice's edge and its two of pair passes, n + 4.  Any may be null.  (The product build passes a null `stats`:
+// `edge`: a wave's three counts at the lattice's edge and its two of pair passes, n + 4 (`chunks`: and its four of chunk
+// visits behind them, the kernels that keep a run list).  Any may be null.  (The product build passes a null `stats`:
 // dead code there.)
 __device__ __forceinline__ void flush_stats(unsigned long long *stats, const uint32_t *n, int32_t pair, const PhaseClocks *clk,
-                                            const uint32_t *edge = nullptr) {
+                                            const uint32_t *edge = nullptr, bool chunks = false) {
   if (n) {
     if (n[0]) atomicAdd(&stats[0], (unsigned long long)n[0]);
     if (n[1]) atomicAdd(&stats[2], (unsigned long long)n[1]);
     if (n[2]) atomicAdd(&stats[3], (unsigned long long)n[2]);
     if (n[3]) atomicAdd(&stats[14], (unsigned long long)n[3]);  // poses of 16-bit grids evaluated exactly (refine16)
     if (pair < BNB_STATS_PAIRS) atomicAdd(&stats[BNB_STATS_HEAD + pair], 4ull * n[0] + n[2]);
+  }
+  if (edge && chunks) {  // a wave's n[9..12]: the chunk visits of its exact sums (behind the per-pair counts)
+    unsigned long long *at = stats + BNB_STATS_HEAD + (size_t)BNB_STATS_PAIRS;
+    for (int i = 0; i < BNB_STATS_CHUNKS; i++)
+      if (edge[5 + i]) atomicAdd(&at[i], (unsigned long long)edge[5 + i]);
   }
   if (edge) {  // a wave's n[4..8]: the work at the lattice's edge, the pair passes
     if (edge[0]) atomicAdd(&stats[19], (unsigned long long)edge[0]);
@@ -326,13 +387,17 @@ template <int CB, bool GLOBAL, bool PAIR, bool RUNS = false>
 __device__ __forceinline__ void rotation_pass(const BnbParams &P, const PairCtx &C, int32_t k, uint32_t u0, uint32_t u1,
                                               unsigned long long m0, unsigned long long m1, int lane,
                                               unsigned long long *best, uint32_t *done, uint32_t *org,
-                                              uint32_t (&n_work)[N_WORK], PhaseClocks &clk, uint32_t *runs = nullptr) {
+                                              uint32_t (&n_work)[N_WORK], PhaseClocks &clk, uint32_t *runs = nullptr,
+                                              uint16_t *note = nullptr, uint8_t *span = nullptr) {
   long long t_mark = 0;
   float cf, sf;
   rotation_k(P, C.pair, k, &cf, &sf);
   if (BNB_STATS(P)) t_mark = clock64();
   int32_t nrc = RUNS_NONE;
-  const int32_t nch = cache_origins<RUNS>(P, C.pts, C.n_pts, cf, sf, C.cx, C.cy, lane, org, true, runs, RUNS && P.l2_runs != 0, &nrc);
+  const int32_t nch = cache_origins<RUNS>(P, C.pts, C.n_pts, cf, sf, C.cx, C.cy, lane, org, true, runs, RUNS && P.l2_runs != 0, &nrc, span);
+  // (RUNS: the chunks of the cell list the exact sums visit come from the run list's notes, which the strip bounds write --
+  //  without a usable run list, or without strip bounds, P.levels == 1: all)
+  const ChunkNotes CN = {note + lane, span + lane, RUNS && P.zero_chunks != 0 && P.levels >= 2 ? nrc : 0, (1u << nch) - 1u};
   if (BNB_STATS(P)) clk.org += clock64() - t_mark;
   if (RUNS && BNB_STATS(P)) {
     clk.run_passes += nrc > 0 ? 1u : 0u;
@@ -362,7 +427,7 @@ __device__ __forceinline__ void rotation_pass(const BnbParams &P, const PairCtx 
     uint32_t bcopy = GLOBAL ? best_sum<true>(best) : 0u;  // (one look per strip at a best in global memory)
     if (P.levels >= 2) {
       if (BNB_STATS(P)) t_mark = clock64();
-      if (RUNS && nrc > 0) strip_bounds_c<RunList<RUN_CHUNKS>>(P, p4, runs + lane, nrc, Y, X0, len, CB == 1 ? 1u : 257u, sb);
+      if (RUNS && nrc > 0) strip_bounds_c<RunList<RUN_CHUNKS>, RUNS>(P, p4, runs + lane, nrc, Y, X0, len, CB == 1 ? 1u : 257u, sb, note + lane);
       else strip_bounds_c<CellList>(P, p4, org, nch, Y, X0, len, CB == 1 ? 1u : 257u, sb);
       if (BNB_STATS(P)) clk.strip += clock64() - t_mark;
       n_work[1] += (uint32_t)len;
@@ -382,14 +447,14 @@ __device__ __forceinline__ void rotation_pass(const BnbParams &P, const PairCtx 
       const uint32_t s0 = t == 0 ? sb[0] : (t == 1 ? sb[4] : sb[8]), s1 = t == 0 ? sb[1] : (t == 1 ? sb[5] : sb[9]);
       const uint32_t s2 = t == 0 ? sb[2] : (t == 1 ? sb[6] : sb[10]), s3 = t == 0 ? sb[3] : (t == 1 ? sb[7] : sb[11]);
       if (BNB_STATS(P)) t_mark = clock64();
-      process_candidate_c<CB, GLOBAL, PAIR>(P, rsrc, pitch8, rsrc16, org, nch, C.n_pts, k, Y, X0 + t, s0, s1, s2, s3, lane, best,
-                                      bcopy, n_work, t, mk0, mk1);
+      process_candidate_c<CB, GLOBAL, PAIR, RUNS>(P, rsrc, pitch8, rsrc16, org, nch, C.n_pts, k, Y, X0 + t, s0, s1, s2, s3, lane, best,
+                                            bcopy, n_work, t, mk0, mk1, CN);
       if (BNB_STATS(P)) clk.eval += clock64() - t_mark;
       if (done && wave_leader(lane)) done[b] = 0u;
     }
     if (PAIR && (mk0 | mk1) != 0u) {
       if (BNB_STATS(P)) t_mark = clock64();
-      strip_sub_blocks<CB, GLOBAL>(P, rsrc, pitch8, rsrc16, org, nch, C.n_pts, k, Y, X0, sb, mk0, mk1, lane, best, bcopy, n_work);
+      strip_sub_blocks<CB, GLOBAL>(P, rsrc, pitch8, rsrc16, org, nch, C.n_pts, k, Y, X0, sb, mk0, mk1, lane, best, bcopy, n_work, CN);
       if (BNB_STATS(P)) clk.eval += clock64() - t_mark;
     }
   }
@@ -803,8 +868,12 @@ __global__ __launch_bounds__(256, CB == 2 && !NHIP_BNB_INSTR ? 5 : 4) void csm_b
   const RotEntry *list = P.rot_list + (size_t)xcd * P.rot_cap;
   __shared__ uint32_t s_org2[4 * ORG_WAVE];
   __shared__ uint32_t s_run2[4 * RUN_WAVE];
+  __shared__ uint16_t s_note2[4 * RUN_WAVE];  // (per run: the strip's level-2 bytes that are not zero, the cell chunks)
+  __shared__ uint8_t s_span2[4 * RUN_WAVE];
   uint32_t *org = s_org2 + (threadIdx.x >> 6) * ORG_WAVE + lane;
   uint32_t *runs = s_run2 + (threadIdx.x >> 6) * RUN_WAVE;
+  uint16_t *note = s_note2 + (threadIdx.x >> 6) * RUN_WAVE;
+  uint8_t *span = s_span2 + (threadIdx.x >> 6) * RUN_WAVE;
   PhaseClocks clk = {0, 0, 0, 0u, 0u, 0u};
   const long long t0 = BNB_STATS(P) ? clock64() : 0;
   for (;;) {
@@ -818,8 +887,8 @@ __global__ __launch_bounds__(256, CB == 2 && !NHIP_BNB_INSTR ? 5 : 4) void csm_b
     uint32_t n[N_WORK] = {};
     // (no block bounds here: 0xffffffff lets every candidate through to its sub-block bounds, which are checked
     //  against the best as it stands in keys[pair])
-    rotation_pass<CB, true, true, true>(P, C, k, 0xffffffffu, 0xffffffffu, m0, m1, lane, &P.keys[pair], nullptr, org, n, clk, runs);
-    if (BNB_STATS(P) && lane == 0) flush_stats(BNB_STATS(P), n, pair, nullptr, n + 4);
+    rotation_pass<CB, true, true, true>(P, C, k, 0xffffffffu, 0xffffffffu, m0, m1, lane, &P.keys[pair], nullptr, org, n, clk, runs, note, span);
+    if (BNB_STATS(P) && lane == 0) flush_stats(BNB_STATS(P), n, pair, nullptr, n + 4, true);
   }
   if (BNB_STATS(P) && lane == 0) {
     atomicAdd(&BNB_STATS(P)[13], (unsigned long long)(clock64() - t0));  // wave time in the second kernel
@@ -952,7 +1021,10 @@ constexpr int CAND_THREADS = 64 * CAND_WAVES;
 template <int CB>
 __global__ __launch_bounds__(CAND_THREADS, CB == 2 ? 5 : 4) void csm_bnb_cand_kernel(BnbParams P) {
   __shared__ uint32_t s_org2[CAND_WAVES * ORG_WAVE];
-  __shared__ uint32_t s_run2[CAND_WAVES * RUN_WAVE];  // (25.6 KB with the origins: five workgroups per CU have 32 KB each)
+  __shared__ uint32_t s_run2[CAND_WAVES * RUN_WAVE];  // (25.6 KB with the origins ...
+  __shared__ uint16_t s_note2[CAND_WAVES * RUN_WAVE];  //  ... and 6 KB of notes per run for the chunk masks: 31.0 KB; five
+  __shared__ uint8_t s_span2[CAND_WAVES * RUN_WAVE];   //  workgroups per CU have 32 KB each)
+  static_assert(CAND_WAVES * (ORG_WAVE * 4 + RUN_WAVE * 4 + RUN_NOTE_BYTES) + 16 <= 32 * 1024, "five workgroups per CU");
   __shared__ unsigned long long s_best2;
   __shared__ uint32_t s_next2;
   const int lane = threadIdx.x & 63;
@@ -977,6 +1049,8 @@ __global__ __launch_bounds__(CAND_THREADS, CB == 2 ? 5 : 4) void csm_bnb_cand_ke
   const uint32_t *rows = P.ps_rows + (size_t)pair * (size_t)P.n_theta * 128u;
   uint32_t *org = s_org2 + (threadIdx.x >> 6) * ORG_WAVE + lane;
   uint32_t *runs = s_run2 + (threadIdx.x >> 6) * RUN_WAVE;
+  uint16_t *note = s_note2 + (threadIdx.x >> 6) * RUN_WAVE;
+  uint8_t *span = s_span2 + (threadIdx.x >> 6) * RUN_WAVE;
   PairCtx C;
   pair_context(P, pair, &C);
   uint32_t n_work[N_WORK] = {};
@@ -993,11 +1067,11 @@ __global__ __launch_bounds__(CAND_THREADS, CB == 2 ? 5 : 4) void csm_bnb_cand_ke
     const unsigned long long m0 = __ballot(u0 != 0u && u0 >= bsum);
     const unsigned long long m1 = __ballot(u1 != 0u && u1 >= bsum && lane + 64 < NB * NB);
     if ((m0 | m1) == 0ull) continue;
-    rotation_pass<CB, true, true, true>(P, C, k, u0, u1, m0, m1, lane, best, nullptr, org, n_work, clk, runs);
+    rotation_pass<CB, true, true, true>(P, C, k, u0, u1, m0, m1, lane, best, nullptr, org, n_work, clk, runs, note, span);
   }
   if (BNB_STATS(P) && lane == 0) {
     atomicAdd(&BNB_STATS(P)[13], (unsigned long long)(clock64() - t0));
-    flush_stats(BNB_STATS(P), n_work, pair, &clk, n_work + 4);
+    flush_stats(BNB_STATS(P), n_work, pair, &clk, n_work + 4, true);
   }
   if (BNB_TIMELINE(P) && lane == 0 && pair < BNB_STATS_PAIRS)
     atomicMax(&BNB_TIMELINE(P)[5 * (size_t)BNB_STATS_PAIRS + 2 + pair], wall_clock64());

@@ -4,7 +4,8 @@
 // points that share a pooled entry (the run lists: LIST_ENTRIES words of LDS per wave) -- with PointSlots / prime_slots, its
 // point prefetch's registers, which the caller keeps from rotation to rotation, and slot_block, the layout its totals come
 // out in; sub_bounds -- the four 4 x 4 sub-block bounds of one block, from the points; strip_bounds_c -- the
-// same for a strip of up to three blocks, from the origins a wave holds (CellList) or their runs by level-2 entry (RunList).
+// same for a strip of up to three blocks, from the origins a wave holds (CellList) or their runs by level-2 entry (RunList),
+// which can also note per run which of the strip's bytes are not zero (NOTE: what the exact sums' chunk masks are made of).
 // Assumes: the pooled tables behind the stored image as the table build leaves them (nhip_grid_blur.hip,
 // nhip_grid_tables.hip: zero rows below the pooled image, a pitch that is a multiple of 16, offsets below
 // 1 << RUN_SHIFT), 16-bit packed fields (LANE_WEIGHT, 18 chunks of 64 points).  Every bound is at least the largest sum of the poses it covers; nothing here reads the stored cells.
@@ -352,10 +353,20 @@ struct RunList {
   static __device__ __forceinline__ uint32_t count(uint32_t e) { return run_cnt(e); }
 };
 
+// The bytes of a dword that are not zero, as bits 0 .. 3 (SWAR: bit 7 of every byte says so; one multiply gathers the four)
+__device__ __forceinline__ uint32_t nonzero_bytes(uint32_t n) {
+  const uint32_t t = ((((n & 0x7f7f7f7fu) + 0x7f7f7f7fu) | n) & 0x80808080u) >> 7;
+  return (t * 0x01020408u) >> 24;  // (bit 8 i -> bit 24 + i; no two products meet, so nothing carries)
+}
+
 // The packed sums of a strip over the list (`list`: the lane's word of chunk 0; nch: the list's chunks, wave-uniform) ...
-template <class LIST>
+// NOTE (run lists): every lane also leaves, per run, which of the strip's twelve level-2 bytes are not zero, in `note`
+// (the lane's 16-bit word of chunk 0; bit 4 t + sy + 2 sx, the bytes' own order; a lane without a run: 0) -- the exact sums
+// leave out the chunks of the cell list that hold only runs whose bytes are zero for the sub-blocks they take.
+template <class LIST, bool NOTE = false>
 __device__ __forceinline__ void strip_sums(const BnbParams &P, __amdgpu_buffer_rsrc_t p4, const uint32_t *list, int32_t nch,
-                                           int32_t Y, int32_t X0, int len, uint32_t (&E)[3], uint32_t (&O)[3]) {
+                                           int32_t Y, int32_t X0, int len, uint32_t (&E)[3], uint32_t (&O)[3],
+                                           uint16_t *note = nullptr) {
   const uint32_t DP = (uint32_t)P.pool4_pitch;
   const uint32_t off = (uint32_t)(2 * Y) * DP + (uint32_t)(4 * X0);
   constexpr int ROUNDS = LIST::ROUNDS, H = LIST::H;
@@ -399,24 +410,28 @@ __device__ __forceinline__ void strip_sums(const BnbParams &P, __amdgpu_buffer_r
       E[0] += __umul24(n0 & M8, cn[j]); O[0] += __umul24((n0 >> 8) & M8, cn[j]);
       E[1] += __umul24(n1 & M8, cn[j]); O[1] += __umul24((n1 >> 8) & M8, cn[j]);
       E[2] += __umul24(n2 & M8, cn[j]); O[2] += __umul24((n2 >> 8) & M8, cn[j]);
+      if (NOTE) {
+        const uint32_t f = nonzero_bytes(n0) | (nonzero_bytes(n1) << 4) | (nonzero_bytes(n2) << 8);
+        note[64 * (H * h + j)] = (uint16_t)(cn[j] != 0u ? f : 0u);
+      }
     }
   }
 }
 
 // ... and the twelve bounds from them
-template <class LIST>
+template <class LIST, bool NOTE = false>
 __device__ __forceinline__ void strip_bounds_c(const BnbParams &P, __amdgpu_buffer_rsrc_t p4, const uint32_t *list,
                                                int32_t nch, int32_t Y, int32_t X0, int len, uint32_t scale,
-                                               uint32_t (&out)[12]) {
+                                               uint32_t (&out)[12], uint16_t *note = nullptr) {
   uint32_t E[3] = {0u, 0u, 0u}, O[3] = {0u, 0u, 0u};  // 16-bit fields: at most 257 points per group of 8 lanes (cache_origins)
   if (std::is_same<LIST, CellList>::value) {
     strip_sums<CellList>(P, p4, list, nch, Y, X0, len, E, O);
   } else {
     static_assert(RUN_CHUNKS == 8, "the rounds below cover the run list");
-    if (nch <= 4) strip_sums<RunList<4>>(P, p4, list, nch, Y, X0, len, E, O);
-    else if (nch == 5) strip_sums<RunList<5>>(P, p4, list, nch, Y, X0, len, E, O);
-    else if (nch == 6) strip_sums<RunList<6>>(P, p4, list, nch, Y, X0, len, E, O);
-    else strip_sums<RunList<8>>(P, p4, list, nch, Y, X0, len, E, O);
+    if (nch <= 4) strip_sums<RunList<4>, NOTE>(P, p4, list, nch, Y, X0, len, E, O, note);
+    else if (nch == 5) strip_sums<RunList<5>, NOTE>(P, p4, list, nch, Y, X0, len, E, O, note);
+    else if (nch == 6) strip_sums<RunList<6>, NOTE>(P, p4, list, nch, Y, X0, len, E, O, note);
+    else strip_sums<RunList<8>, NOTE>(P, p4, list, nch, Y, X0, len, E, O, note);
   }
   // sums over the wave without LDS: the packed fields over groups of 8 lanes (quad permutations, then the mirror image
   // of the half row holds the other quad's sum), unpacked, over the row of 16 (its mirror image), then down the rows

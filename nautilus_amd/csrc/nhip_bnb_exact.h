@@ -3,7 +3,8 @@
 //
 // Owns four kinds: eval_block / eval_sub -- from the points, on the stored image (the general kernel and the seeds of
 // long scans); block_sums8 / sub_sums8 / pair_sums8 -- from the origins a wave holds, on the tiled 8-bit plane (the cells
-// of 8-bit grids, the high bytes of 16-bit ones: a whole block, one sub-block, two sub-blocks side by side); pose_sum16 / refine16 -- single poses of 16-bit grids that the high-byte bound
+// of 8-bit grids, the high bytes of 16-bit ones: a whole block, one sub-block, two sub-blocks side by side), and their
+// *_masked forms over the chunks of the list a mask names (the candidates' kernels); pose_sum16 / refine16 -- single poses of 16-bit grids that the high-byte bound
 // admits, from the tiled 16-bit image; and best_key / best_sum / best_sum_cached -- the pair's running best,
 // key = sum << 32 | ~linear index, so that the maximum key is the maximum sum at the smallest index.
 // Assumes: the slot layout of nhip_layout.hip (every offset an evaluation forms lies inside the descriptor it is given),
@@ -509,6 +510,197 @@ __device__ __forceinline__ uint32_t pair_sums8(__amdgpu_buffer_rsrc_t rsrc, uint
   return V[0];
 }
 
+// ---- the same three sums over SOME chunks of the list (the candidates' kernels) ----------------------------------
+// `mask` (wave-uniform): bit c set = chunk c of the cell list is visited.  The caller leaves out only chunks whose every
+// entry reads nothing but zero cells for the poses of the pass (nhip_bnb.hip chunk_mask), so each sum is what the functions
+// above return over chunks 0 .. nch - 1, bit for bit.  The loops are rolled walks over the set bits -- lowest bit, clear it,
+// the entry at org + 64 c -- where those are unrolled over OC chunks with static offsets: a third of their code.
+// sub_sums8 keeps its two chunks in flight per turn (an odd last chunk has a turn of its own: no load is issued for a
+// chunk that is not there), pair_sums8 takes two as well, block_sums8 its one chunk in two groups of four rows.
+__device__ __forceinline__ int next_chunk(uint32_t &mask) {
+  const int c = (int)__builtin_ctz(mask);
+  mask &= mask - 1u;
+  return c;
+}
+
+__device__ __forceinline__ uint32_t sub_sums8_masked(__amdgpu_buffer_rsrc_t rsrc, uint32_t pitch, uint32_t copy_bytes, const uint32_t *org,
+                                                     uint32_t mask, int32_t Y, int32_t X, int32_t sy, int32_t sx, int lane, int *dy, int *dx) {
+  const uint32_t roff = (uint32_t)(BNB_B * Y + BNB_B4 * sy), coff = (uint32_t)(BNB_B * X + BNB_B4 * sx);
+  const uint32_t wrap = pitch * HI_TILE_BYTES - HI_TILE_BYTES;  // from a tile's last row to the next tile's first
+  uint32_t E[4] = {0u, 0u, 0u, 0u}, O[4] = {0u, 0u, 0u, 0u};
+  auto load = [&](int c, u32x2 (&w)[4], uint32_t &sh, uint32_t &cn) {
+    const uint32_t o = org[64 * c];
+    cn = org_cnt(o);
+    const uint32_t row0 = org_row(o) + roff, col0 = org_col(o) + coff, col4 = col0 & ~3u;
+    const uint32_t cp = (col4 >> 3) & 1u, q = row0 & 7u;
+    const uint32_t v0 = hi_tiled(row0, col4, cp, pitch, copy_bytes);
+    sh = (col0 & 3u) * 8u;
+#pragma unroll
+    for (int y = 0; y < 4; y++)
+      w[y] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)(v0 + (q + (uint32_t)y >= 8u ? wrap : 0u) + 16u * (uint32_t)y), 0, 0);
+  };
+  auto add = [&](const u32x2 (&w)[4], uint32_t sh, uint32_t cn) {
+#pragma unroll
+    for (int y = 0; y < 4; y++) {
+      const uint32_t n = __builtin_amdgcn_alignbit(w[y].y, w[y].x, sh);
+      E[y] += __umul24(n & M8, cn);
+      O[y] += __umul24(n >> 8, cn);
+    }
+  };
+#pragma unroll 1
+  while ((mask & (mask - 1u)) != 0u) {  // two chunks or more are left
+    u32x2 wa[4], wb[4];
+    uint32_t sa, sb, ca, cb;
+    load(next_chunk(mask), wa, sa, ca);
+    load(next_chunk(mask), wb, sb, cb);
+    add(wa, sa, ca);
+    add(wb, sb, cb);
+  }
+  if (mask != 0u) {
+    u32x2 wa[4];
+    uint32_t sa, ca;
+    load(next_chunk(mask), wa, sa, ca);
+    add(wa, sa, ca);
+  }
+  uint32_t R[8];  // R[2 y + d]: d = 0: dx 0, 2; d = 1: dx 1, 3
+#pragma unroll
+  for (int y = 0; y < 4; y++) {
+    R[2 * y] = E[y];
+    R[2 * y + 1] = O[y] - ((E[y] >> 16) << 8);
+  }
+  rs_step<8, 1>(R, lane & 1);
+  rs_step<4, 2>(R, lane & 2);
+  rs_step<2, 4>(R, lane & 4);
+  uint32_t V[2] = {R[0] & 0xffffu, R[0] >> 16};
+  rs_step<2, 8>(V, lane & 8);
+  V[0] = add_xor<16>(V[0]);
+  V[0] = add_xor<32>(V[0]);
+  *dy = ((lane >> 1) & 1) + 2 * ((lane >> 2) & 1);
+  *dx = (lane & 1) + 2 * ((lane >> 3) & 1);
+  return V[0];
+}
+
+__device__ __forceinline__ uint32_t block_sums8_masked(__amdgpu_buffer_rsrc_t rsrc, uint32_t pitch, uint32_t copy_bytes, const uint32_t *org,
+                                                       uint32_t mask, int32_t Y, int32_t X, int lane, int *dy, int *dx) {
+  const uint32_t roff = (uint32_t)(BNB_B * Y), coff = (uint32_t)(BNB_B * X);
+  const uint32_t wrap = pitch * HI_TILE_BYTES - HI_TILE_BYTES;  // from a tile's last row to the next tile's first
+  uint32_t E[8][2], O[8][2];
+#pragma unroll
+  for (int y = 0; y < 8; y++) E[y][0] = E[y][1] = O[y][0] = O[y][1] = 0u;
+#pragma unroll 1
+  while (mask != 0u) {
+    constexpr int ROWS = 4;  // (as block_sums8: two groups of four rows)
+    const uint32_t o = org[64 * next_chunk(mask)];
+    const uint32_t cn = org_cnt(o);
+    const uint32_t row0 = org_row(o) + roff, col0 = org_col(o) + coff, col4 = col0 & ~3u;
+    const uint32_t q = row0 & 7u, sh = (col0 & 3u) * 8u;
+    const uint32_t g = hi_tiled(row0, col4, (col4 >> 3) & 1u, pitch, copy_bytes);
+#pragma unroll
+    for (int y0 = 0; y0 < 8; y0 += ROWS) {
+      u32x3 w[ROWS];
+#pragma unroll
+      for (int y = 0; y < ROWS; y++)
+        w[y] = __builtin_amdgcn_raw_buffer_load_b96(rsrc, (int)(g + (q + (uint32_t)(y0 + y) >= 8u ? wrap : 0u) + 16u * (uint32_t)(y0 + y)), 0, 0);
+#pragma unroll
+      for (int y = 0; y < ROWS; y++) {
+        const uint32_t n0 = __builtin_amdgcn_alignbit(w[y].y, w[y].x, sh);
+        const uint32_t n1 = __builtin_amdgcn_alignbit(w[y].z, w[y].y, sh);
+        E[y0 + y][0] += __umul24(n0 & M8, cn); O[y0 + y][0] += __umul24(n0 >> 8, cn);
+        E[y0 + y][1] += __umul24(n1 & M8, cn); O[y0 + y][1] += __umul24(n1 >> 8, cn);
+      }
+    }
+  }
+  uint32_t R[32];  // R[4 y + d]: d = 0: dx 0, 2; 1: dx 1, 3; 2: dx 4, 6; 3: dx 5, 7
+#pragma unroll
+  for (int y = 0; y < 8; y++) {
+    R[4 * y + 0] = E[y][0];
+    R[4 * y + 1] = O[y][0] - ((E[y][0] >> 16) << 8);
+    R[4 * y + 2] = E[y][1];
+    R[4 * y + 3] = O[y][1] - ((E[y][1] >> 16) << 8);
+  }
+  rs_step<32, 1>(R, lane & 1);
+  rs_step<16, 2>(R, lane & 2);
+  rs_step<8, 4>(R, lane & 4);
+  uint32_t V[8];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    V[2 * i] = R[i] & 0xffffu;
+    V[2 * i + 1] = R[i] >> 16;
+  }
+  rs_step<8, 8>(V, lane & 8);
+  rs_step<4, 16>(V, lane & 16);
+  rs_step<2, 32>(V, lane & 32);
+  const int r = 8 * (2 * ((lane >> 5) & 1) + ((lane >> 4) & 1)) + 4 * ((lane >> 2) & 1) + 2 * ((lane >> 1) & 1) + (lane & 1);
+  const int f = (lane >> 3) & 1, d = r & 3;
+  *dy = r >> 2;
+  *dx = 4 * (d >> 1) + (d & 1) + 2 * f;
+  return V[0];
+}
+
+__device__ __forceinline__ uint32_t pair_sums8_masked(__amdgpu_buffer_rsrc_t rsrc, uint32_t pitch, uint32_t copy_bytes, const uint32_t *org,
+                                                      uint32_t mask, int32_t Y, int32_t X, int32_t sy, int32_t sx0, int lane, int *dy, int *dx) {
+  const uint32_t roff = (uint32_t)(BNB_B * Y + BNB_B4 * sy), coff = (uint32_t)(BNB_B * X + BNB_B4 * sx0);
+  const uint32_t wrap = pitch * HI_TILE_BYTES - HI_TILE_BYTES;  // from a tile's last row to the next tile's first
+  uint32_t E[4][2], O[4][2];
+#pragma unroll
+  for (int y = 0; y < 4; y++) E[y][0] = E[y][1] = O[y][0] = O[y][1] = 0u;
+  auto load = [&](int c, u32x3 (&w)[4], uint32_t &sh, uint32_t &cn) {
+    const uint32_t o = org[64 * c];
+    cn = org_cnt(o);
+    const uint32_t row0 = org_row(o) + roff, col0 = org_col(o) + coff, col4 = col0 & ~3u;
+    const uint32_t q = row0 & 7u;
+    sh = (col0 & 3u) * 8u;
+    const uint32_t g = hi_tiled(row0, col4, (col4 >> 3) & 1u, pitch, copy_bytes);
+#pragma unroll
+    for (int y = 0; y < 4; y++)
+      w[y] = __builtin_amdgcn_raw_buffer_load_b96(rsrc, (int)(g + (q + (uint32_t)y >= 8u ? wrap : 0u) + 16u * (uint32_t)y), 0, 0);
+  };
+  auto add = [&](const u32x3 (&w)[4], uint32_t sh, uint32_t cn) {
+#pragma unroll
+    for (int y = 0; y < 4; y++) {
+      const uint32_t n0 = __builtin_amdgcn_alignbit(w[y].y, w[y].x, sh);
+      const uint32_t n1 = __builtin_amdgcn_alignbit(w[y].z, w[y].y, sh);
+      E[y][0] += __umul24(n0 & M8, cn); O[y][0] += __umul24(n0 >> 8, cn);
+      E[y][1] += __umul24(n1 & M8, cn); O[y][1] += __umul24(n1 >> 8, cn);
+    }
+  };
+#pragma unroll 1
+  while ((mask & (mask - 1u)) != 0u) {  // two chunks or more are left
+    u32x3 wa[4], wb[4];
+    uint32_t sa, sb, ca, cb;
+    load(next_chunk(mask), wa, sa, ca);
+    load(next_chunk(mask), wb, sb, cb);
+    add(wa, sa, ca);
+    add(wb, sb, cb);
+  }
+  if (mask != 0u) {
+    u32x3 wa[4];
+    uint32_t sa, ca;
+    load(next_chunk(mask), wa, sa, ca);
+    add(wa, sa, ca);
+  }
+  uint32_t R[16];  // R[4 y + d]: d = 0: dx 0, 2; 1: dx 1, 3; 2: dx 4, 6; 3: dx 5, 7
+#pragma unroll
+  for (int y = 0; y < 4; y++) {
+    R[4 * y + 0] = E[y][0];
+    R[4 * y + 1] = O[y][0] - ((E[y][0] >> 16) << 8);
+    R[4 * y + 2] = E[y][1];
+    R[4 * y + 3] = O[y][1] - ((E[y][1] >> 16) << 8);
+  }
+  rs_step<16, 1>(R, lane & 1);
+  rs_step<8, 2>(R, lane & 2);
+  rs_step<4, 4>(R, lane & 4);
+  uint32_t V[4] = {R[0] & 0xffffu, R[0] >> 16, R[1] & 0xffffu, R[1] >> 16};
+  rs_step<4, 8>(V, lane & 8);
+  rs_step<2, 16>(V, lane & 16);
+  V[0] = add_xor<32>(V[0]);
+  const int r = 8 * ((lane >> 4) & 1) + 4 * ((lane >> 2) & 1) + 2 * ((lane >> 1) & 1) + (lane & 1);
+  const int f = (lane >> 3) & 1, d = r & 3;
+  *dy = r >> 2;
+  *dx = 4 * (d >> 1) + (d & 1) + 2 * f;
+  return V[0];
+}
+
 // ---- 16-bit cells: a pose's exact sum from the stored image -------------------------------------------------
 // sum over the scan's points of the 16-bit cell that pose (ix, iy) of the rotation reads: one 2-byte load per point
 __device__ __forceinline__ uint32_t pose_sum16(const BnbParams &P, __amdgpu_buffer_rsrc_t rsrc16, const uint32_t *org,
@@ -524,17 +716,34 @@ __device__ __forceinline__ uint32_t pose_sum16(const BnbParams &P, __amdgpu_buff
   }
   return wave_sum(acc);
 }
+// ... over the chunks of `mask` (as above: a chunk left out adds 0; the loads stay unrolled, all in flight at once)
+__device__ __forceinline__ uint32_t pose_sum16_masked(const BnbParams &P, __amdgpu_buffer_rsrc_t rsrc16, const uint32_t *org,
+                                                      uint32_t mask, int32_t ix, int32_t iy) {
+  uint32_t acc = 0u;
+#pragma unroll
+  for (int c = 0; c < OCL; c++) {
+    if (((mask >> c) & 1u) == 0u) continue;
+    const uint32_t o = origin_of(org, c);
+    acc += org_cnt(o) * (uint32_t)__builtin_amdgcn_raw_buffer_load_b16(
+                            rsrc16, (int)t16_tiled(org_row(o) + (uint32_t)iy, org_col(o) + (uint32_t)ix, (uint32_t)P.t16_tpr), 0, 0);
+  }
+  return wave_sum(acc);
+}
 
-// Two stages for 16-bit cells.  `hsum` is the lane's pose sum over the plane of HIGH bytes (what sub_sums8 /
+// Two stages for 16-bit cells. `hsum` is the lane's pose sum over the plane of HIGH bytes (what sub_sums8 /
 // block_sums8 return on that plane, at the cost of 8-bit cells); a cell is 256 * high + low with low <= 255, so
 //     256 * hsum + 255 * points  >=  the pose's 16-bit sum.
 // Only poses whose bound reaches the best sum found so far can hold the optimum or a tie with it; their exact sums
 // are read from the 16-bit image, highest bound first (it raises the best fastest), until no pose of the block is
 // left above it.  Near the optimum that is a handful of poses; elsewhere none.  Returns the number evaluated.
-template <bool GLOBAL>
+// MASKED: the poses' sums are taken over the chunks of `mask`, the mask of the pass that gave `hsum` -- it keeps every
+// chunk that holds a cell that is not zero for any pose of the pass, 16-bit cell or high byte alike (the level-2 byte of a
+// 16-bit grid is ceil(max / 257): zero only where every cell is).  The bound keeps the scan's point count.
+template <bool GLOBAL, bool MASKED = false>
 __device__ __forceinline__ uint32_t refine16(const BnbParams &P, __amdgpu_buffer_rsrc_t rsrc16, const uint32_t *org,
                                              int32_t nch, int32_t n_pts, int32_t k, int32_t ix, int32_t iy, uint32_t hsum,
-                                             bool mine, int lane, unsigned long long *best, uint32_t &bcopy) {
+                                             bool mine, int lane, unsigned long long *best, uint32_t &bcopy,
+                                             uint32_t mask = 0u) {
   const bool valid = mine && ix < P.nx && iy < P.ny;
   uint32_t ub = valid ? 256u * hsum + 255u * (uint32_t)n_pts : 0u;  // (points <= 1088: no overflow)
   uint32_t n_eval = 0u;
@@ -543,7 +752,7 @@ __device__ __forceinline__ uint32_t refine16(const BnbParams &P, __amdgpu_buffer
     if (top == 0u || top < best_sum_cached<GLOBAL>(best, bcopy)) break;
     const int j = (int)__builtin_ctzll(__ballot(ub == top));  // (top != 0: a lane holds it)
     const int32_t jx = __builtin_amdgcn_readlane(ix, j), jy = __builtin_amdgcn_readlane(iy, j);
-    const uint32_t sum = pose_sum16(P, rsrc16, org, nch, jx, jy);
+    const uint32_t sum = MASKED ? pose_sum16_masked(P, rsrc16, org, mask, jx, jy) : pose_sum16(P, rsrc16, org, nch, jx, jy);
     const uint32_t lin = (uint32_t)((k * P.nx + jx) * P.ny + jy);
     const unsigned long long key = ((unsigned long long)sum << 32) | (0xffffffffu - lin);
     wave_atomic_max(best, key, lane);  // (generic address: LDS or global)

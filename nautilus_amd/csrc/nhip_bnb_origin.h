@@ -5,7 +5,8 @@
 // form of the bounds phase, exact to the pooled entry), the rotation's (cos, sin) (rotation_k = rotation_terms + rotation_of;
 // rotation_terms_of_wave: all of a wave's rotations at once, one per lane), patch_origin, the packed
 // per-wave list of a rotation's origins in LDS (cache_origins, origin_of, org_row / org_col / org_cnt), the shorter list
-// of their runs by level-2 entry (run_row2 / run_col2 / run_cnt), and the wave-uniform buffer descriptor every gather
+// of their runs by level-2 entry (run_row2 / run_col2 / run_cnt; per run the chunks of the cell list its cells lie in,
+// run_span), and the wave-uniform buffer descriptor every gather
 // here reads through (uniform_rsrc, the u32xN load types, idx_guard).
 // Assumes: BnbParams as launch_csm_bnb fills it (nhip_bnb_host.hip); a wave's list has ORG_WAVE words of LDS of its
 // own, its run list RUN_WAVE; rows and columns of a stored grid below ORG_LIMIT for the packed form.  Included by
@@ -240,14 +241,15 @@ enum : int32_t { RUNS_NONE = 0, RUNS_FIELD = -1, RUNS_FULL = -2 };
 // 8-bit ones (the multiply-adds that replace the adds cost what the loads saved); with the tiled planes both widths
 // merge (8-bit: 6.31 -> 6.25 ms).
 // RUNS (with `runs`, the wave's RUN_WAVE words, and want_runs, wave-uniform): the run list is written in the same sweep
-// and *run_chunks says what became of it (above).
+// and *run_chunks says what became of it (above); run_span (RUN_WAVE bytes of the wave's, or null): per run written, the
+// chunk of the cell list that holds its first cell | 32 if its last cell lies in the next (nhip_bnb.hip chunk_mask).
 // RING: the form of the loop over the scan's chunks, see there -- the ring of the candidates' kernels (the callers with
 // RUNS) or the slots of the seeds.
 template <bool RUNS = false, bool RING = RUNS>
 __device__ __forceinline__ int32_t cache_origins(const BnbParams &P, const float2 *pts, int32_t n_pts, float cf, float sf,
                                                  int32_t cx, int32_t cy, int lane, uint32_t *org, bool merged,
                                                  uint32_t *runs = nullptr, bool want_runs = false,
-                                                 int32_t *run_chunks = nullptr) {
+                                                 int32_t *run_chunks = nullptr, uint8_t *run_span = nullptr) {
   uint32_t *base = org - lane;  // the wave's list
   const bool with_runs = RUNS && want_runs;
   if (RUNS) *run_chunks = RUNS_NONE;
@@ -293,6 +295,17 @@ __device__ __forceinline__ int32_t cache_origins(const BnbParams &P, const float
         const uint32_t cnt2 = rest2 ? (uint32_t)__builtin_ctzll(rest2) + 1u : (uint32_t)(64 - lane);
         const uint32_t at = rtail + __builtin_amdgcn_mbcnt_hi((uint32_t)(H2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)H2, 0u));
         if (head2 && at < (uint32_t)RUN_WAVE) runs[at] = (o & RUN_KEY_MASK) | cnt2;
+        if (run_span) {
+          // The chunks of the cell list the run's cells lie in.  A run's head is a cell's head too: its first cell is entry
+          // first = (entries before this chunk's) + (heads below the lane), its cells are the heads among its cnt2 lanes --
+          // at most 64, so they end in the first cell's chunk or the next.
+          const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(H >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)H, 0u));
+          const uint32_t first = tail - (uint32_t)__builtin_popcountll(H) + below;
+          const uint32_t end = (uint32_t)lane + cnt2;  // (<= 64)
+          const unsigned long long upto = end >= 64u ? H : H & ((1ull << end) - 1ull);
+          const uint32_t last = first + (uint32_t)__builtin_popcountll(upto) - below - 1u;
+          if (head2 && at < (uint32_t)RUN_WAVE) run_span[at] = (uint8_t)((first >> 6) | ((last >> 6) != (first >> 6) ? 32u : 0u));
+        }
         rtail += (uint32_t)__builtin_popcountll(H2);
       }
     };

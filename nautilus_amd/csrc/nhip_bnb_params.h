@@ -30,6 +30,11 @@ constexpr uint32_t ORG_LIMIT = 1u << 13;           // rows / columns of a stored
 // consecutive origins inside one 4 x 4 level-2 entry, which is all the strip bounds read (nhip_bnb_origin.h has the format).
 constexpr int RUN_CHUNKS = 8;                      // 64-entry chunks of runs a wave holds: 512 runs (a 1081-beam scan: ~300)
 constexpr int RUN_WAVE = RUN_CHUNKS * 64;          // words of LDS per wave
+// Beside the run list those kernels keep, per run, the strip's level-2 bytes that are not zero (a 16-bit word: bit 4 t + sy +
+// 2 sx for sub-block (sy, sx) of the strip's block t, written by the strip bounds) and the chunks of the cell list the run's
+// cells lie in (a byte: first chunk | reaches the next << 5, written with the run list): what the exact sums need to leave
+// out the chunks of the cell list that hold only empty windows (nhip_bnb.hip chunk_mask).  3 bytes per run.
+constexpr int RUN_NOTE_BYTES = RUN_WAVE * 3;
 
 // ---- the dynamic LDS of csm_bnb_kernel, in this order (the kernel carves it, bnb_plan and launch_main size it):
 //   first region   the pooled table while the bounds are computed (if staged), then the waves' window origins
@@ -58,6 +63,7 @@ constexpr size_t lds_bytes(size_t first, int32_t n_theta, bool split) {
 
 constexpr int BNB_STATS_PAIRS = 1 << 20;           // per-pair counters kept by NHIP_BNB_STATS=1
 constexpr int BNB_STATS_HEAD = 24;    // totals: 4 counts, shader-clock sums of the by-rotation kernel, the strip paths (see nhip_bnb_stats_levels)
+constexpr int BNB_STATS_CHUNKS = 4;   // behind the per-pair counts: chunk visits of the exact sums (see nhip_bnb_stats_chunks)
 
 // One rotation of a pair with many candidates, handed to the second kernel: (pair, rotation) and the mask of its
 // 121 candidate blocks.
@@ -121,6 +127,7 @@ struct BnbParams {
   ScoreGate gate;   // the caller's min_score (nhip_csm_match_gated): a pair's best starts at its floor key (nhip_csm_shared.h)
   int32_t l2_runs;  // strip bounds from the list of level-2 runs where a kernel keeps one (0: NHIP_BNB_L2_RUNS=0, per cell everywhere)
   int32_t pair_subs;  // two live sub-blocks side by side on a strip's sub-block row share one pass (0: NHIP_BNB_PAIR_SUBS=0, one pass each)
+  int32_t zero_chunks;  // exact sums leave out the cell-list chunks whose windows hold only empty cells (0: NHIP_BNB_ZERO_CHUNKS=0, every chunk)
 };
 
 // The kernel launches of one batch in each build: launchers_product() (nhip_bnb.hip), launchers_instr()

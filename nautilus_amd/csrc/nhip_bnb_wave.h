@@ -160,6 +160,17 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
   const auto s32 = __builtin_amdgcn_permlane32_swap(v, v, false, false);
   return max(s32[0], s32[1]);
 }
+// the bitwise OR over the 64 lanes, by the same route (wave-uniform, in a scalar register)
+__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
+  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);
+  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);
+  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xF, 0xF, false);
+  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, false);
+  const auto s16 = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+  v = s16[0] | s16[1];
+  const auto s32 = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)(s32[0] | s32[1]));
+}
 // the same over 64-bit keys (both halves take the same route; every lane ends with the wave's maximum)
 template <int CTRL>
 __device__ __forceinline__ unsigned long long max_dpp_u64(unsigned long long v) {

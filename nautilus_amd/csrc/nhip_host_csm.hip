@@ -630,4 +630,13 @@ int nhip_bnb_stats_levels(uint64_t out[24]) {
   return NHIP_OK;
 }
 
+int nhip_bnb_stats_chunks(uint64_t out[4]) {
+  NHIP_REQUIRE(out != nullptr, "bnb_stats_chunks: null out");
+  unsigned long long v[4];
+  int rc = bnb_stats_chunks_read(v);
+  if (rc) return rc;
+  for (int i = 0; i < 4; i++) out[i] = v[i];
+  return NHIP_OK;
+}
+
 }  // extern "C"
