@@ -8,6 +8,10 @@ by the odometry increments, drift included: the occupied cells around the prior 
 section 3, "Map windows") and the best pose of the lattice is the answer.  Prints one JSON line: queries, rejected, position
 and heading errors against the truth, points per window.
 
+  --no-prior        the same run with the odometry priors replaced by global localisation ("Range
+                    signatures"): K proposals per scan from the range signatures of the map alone, every one of them matched,
+                    the best-scoring one kept.  The JSON line gains the winning ranks.
+
   --backend hip     the product: HipBackend.occupancy_grid and HipBackend.localize, everything on the GPU
   --backend oracle  no device: the numpy statement of the occupancy grid the tests keep, hostside.localize (windows in numpy)
                     and the CPU oracle's matcher
@@ -37,7 +41,8 @@ def compose(pose, rel):
     return np.array([pose[0] + c * rel[0] - s * rel[1], pose[1] + s * rel[0] + c * rel[1], pose[2] + rel[2]])
 
 
-def run(n_scans=120, n_map=80, backend="hip", map_poses="truth", stem="localize_map", min_score=None, device="cuda:0", every=1):
+def run(n_scans=120, n_map=80, backend="hip", map_poses="truth", stem="localize_map", min_score=None, device="cuda:0", every=1,
+        no_prior=False):
     bag = synth.SynthBag(n_scans)
     if not 0 < n_map < n_scans:
         raise ValueError("run: %d of %d scans for the map" % (n_map, n_scans))
@@ -70,7 +75,16 @@ def run(n_scans=120, n_map=80, backend="hip", map_poses="truth", stem="localize_
     q = np.arange(n_map, n_scans, max(int(every), 1))
     priors = np.array([compose(poses[n_map - 1], relative(bag.odom[n_map - 1], bag.odom[i])) for i in q])
     qxy, qoff = csm.pack_scans([bag.scans[i] for i in q])
-    if backend == "hip":
+    if no_prior:
+        r = be.global_localize(qxy, qoff, grid, window, min_score=min_score) if backend == "hip" else \
+            hostside.global_localize(be, qxy, qoff, grid, window)
+        won = np.maximum(r["rank"], 0)
+        proposed = r["proposals"][np.arange(len(q)), won]
+        priors = np.where(np.isnan(proposed), priors, proposed)  # (what "prior_error" reports: the winning proposals)
+        # (a window per proposal: the winner's points are not kept apart; the map's occupied cells stand in for them)
+        r = {"poses": r["poses"], "records": r["records"][np.arange(len(q)), won], "rejected": r["rank"] < 0, "ranks": r["rank"],
+             "points_per_window": np.full(len(q), int((grid == 100).sum()), np.int32)}
+    elif backend == "hip":
         r = be.localize(qxy, qoff, priors, grid, window, min_score=min_score)
     else:
         r = hostside.localize(be, qxy, qoff, priors, grid, window)
@@ -80,7 +94,8 @@ def run(n_scans=120, n_map=80, backend="hip", map_poses="truth", stem="localize_
     ang = np.degrees(np.abs(csm.angle_mod(e[:, 2])))
     pe = priors - bag.truth[q]
     ppw = r["points_per_window"]
-    return {"backend": be.name, "n_scans": n_scans, "map_scans": n_map, "map_poses": map_poses, "map": [stem + ".pgm", stem + ".yaml"],
+    extra = {"no_prior": True, "ranks": [int(v) for v in r["ranks"]]} if no_prior else {}
+    return {**extra, "backend": be.name, "n_scans": n_scans, "map_scans": n_map, "map_poses": map_poses, "map": [stem + ".pgm", stem + ".yaml"],
             "map_cells": [int(width), int(height)], "map_cells_occupied": int((grid == 100).sum()),
             "queries": int(len(q)), "rejected": int(r["rejected"].sum()),
             "prior_error_max_m": float(np.hypot(pe[:, 0], pe[:, 1]).max()),
@@ -103,5 +118,6 @@ if __name__ == "__main__":
     ap.add_argument("--map", metavar="STEM", default="localize_map", help="writes STEM.pgm and STEM.yaml, then reads them back")
     ap.add_argument("--min-score", type=float, default=None, help="--backend hip: reject matches that score below this")
     ap.add_argument("--every", type=int, default=1, help="localise every n-th of the remaining scans")
+    ap.add_argument("--no-prior", action="store_true", help="global localisation: proposals from the map's range signatures, no odometry")
     a = ap.parse_args()
-    print(json.dumps(run(a.scans, a.map_scans, a.backend, a.map_poses, a.map, a.min_score, every=a.every)))
+    print(json.dumps(run(a.scans, a.map_scans, a.backend, a.map_poses, a.map, a.min_score, every=a.every, no_prior=a.no_prior)))

@@ -71,7 +71,9 @@ const char *nhip_version(void);
  * nhip_freespace_check_dev, 65536 scan id of the list of nhip_place_match_dev / nhip_place_seq_match_dev, 131072 degree and 262144
  * member index of nhip_consistency_set_dev, 524288 occupied cells beyond max_cells of nhip_mapwin_cells_dev (value: the cells
  * needed; index = height) or a row_ptr entry that is not a row in nhip_mapwin_gather_dev (index = the map row), 1048576 window
- * points beyond out_capacity of nhip_mapwin_gather_dev (value: the points needed, at most 2^31 - 1; index = n_queries).
+ * points beyond out_capacity of nhip_mapwin_gather_dev (value: the points needed, at most 2^31 - 1; index = n_queries), 2097152
+ * anchors beyond max_anchors of nhip_rangesig_anchors_dev (value: the anchors found; index = max_anchors) or an entry of the ray
+ * table that is not a ray in nhip_rangesig_map_dev (value: its n; index = the ray).
  * Clears the record
  * (in the order of `stream`).
  * ONE record per DEVICE, shared by every stream and host thread that uses the library on it: a host with several streams
@@ -921,6 +923,99 @@ int nhip_mapwin_gather_dev(const int32_t *d_row_ptr, const int32_t *d_cols, cons
                            int32_t n_queries, float *d_out_xy, int64_t out_capacity, int32_t *d_out_offsets, int64_t *d_stats,
                            void *d_workspace, int64_t workspace_bytes, void *stream);
 
+/* K21: RANGE SIGNATURES -- global localisation: priors for scans that have NO prior, from the finished occupancy grid alone
+ * ("Range signatures"; tests/rangesig_reference.py and hostside.range_signatures / scan_signatures /
+ * signature_candidates restate it).  Every free lattice cell of the map (an anchor) gets 64 bytes, the quantised distance to
+ * the nearest wall in each of 64 sectors, ray-cast in the grid; every scan the same 64 bytes from its returns; a scan is placed
+ * at an anchor under the best of the 64 rotations by the sum of absolute differences of the bytes.  Integer after the float
+ * comparisons of a scan's points; no output depends on an order: the same input gives the same bits.
+ *   lattice  node (i, j) is the local cell (i stride + stride/2, j stride + stride/2), if that lies in the window; it is an
+ *            ANCHOR iff the cell's value is in [0, free_max].  The anchor list holds the anchors in row-major order (j, then
+ *            i), int32[4] = {cx, cy, i, j} each.  Of more anchors than max_anchors the first max_anchors are written;
+ *            nhip_dev_status() reports it (kind 2097152, value: the anchors found, index = max_anchors).  Entries of the list
+ *            behind the anchors found are four -1; an entry whose cell is not in the window is no anchor to the later calls:
+ *            its signature is 64 x 255 and it is in no record.
+ *   rays     nhip_rangesig_tables: ray t = 0 .. 64 m - 1 of an anchor points at phi = (t + 1/2) (2 pi / 64) / m and ends
+ *            (dx, dy) = (lrint(L cos phi), lrint(L sin phi)) cells away, n = max(|dx|, |dy|); step k = 1 .. n is the cell
+ *            anchor + (rdiv(k dx, n), rdiv(k dy, n)), rdiv(a, n) = floor((2 a + n) / (2 n)): the occupancy grid's ray.  The ray
+ *            ends at the first step whose cell is outside the window (255), unknown (value < 0: 255) or a wall (value >=
+ *            occ_min: min(254, (k scale) >> 16), scale = lrint(2^16 sqrt(dx dx + dy dy) res / (n unit))); no end by n: 255.
+ *            With NHIP_RANGESIG_UNKNOWN_STOPS in flags an unknown cell gives its range as a wall does: in a map ray-traced
+ *            from scans the cells in front of a wall that were hit in some scans and seen through in others are unknown.
+ *            Byte j of the signature is the least value of rays j m .. j m + m - 1.
+ *   scan     a point (x, y) falls in the sector of "place descriptors" (the same float operations); r2 = fl(fl(x x) + fl(y
+ *            y)), dropped unless finite; its byte is #{k in 1..254 : r2 >= edge2[k]}, edge2[k] = e e (one float multiply), e
+ *            = (float)((double)unit k).  Byte j is the least byte of the points in sector j, 255 without one.  Offsets that
+ *            are not a scan give 64 x 255 and are reported (kind 16384).
+ *   cost     cost(q, a, s) = sum over the sectors j with Q[j] != 255 of |Q[j] - A[(j + s) mod 64]|; cost(q, a) the least
+ *            over s = 0 .. 63, shift the smallest such s; key = cost 64 + shift.  The heading of the proposal is
+ *            angle_mod(shift 2 pi / 64).
+ *   records  per query top_k records int32[4] = {index into the anchor list, shift, cost, valid}, valid = #{j : Q[j] != 255}:
+ *            the anchors in ascending (key, index) order, one accepted iff no accepted one lies within min_sep lattice steps
+ *            (Chebyshev distance on (i, j)); unfilled records four -1; a query with valid < min_sectors has none.
+ *   stats    8 int64: {lattice nodes, anchors found, anchors that did not fit, rays that ended on a wall, in unknown, outside or
+ *            at n, queries without a record, records written}.  nhip_rangesig_anchors_dev writes words 0 - 2 and clears the
+ *            rest, nhip_rangesig_map_dev writes 3 - 5, nhip_rangesig_match_dev 6 and 7: one block given to the calls in turn
+ *            holds the whole record.
+ *   prior    (host, double) x = (cell_x0 + cx + 0.5) res, y likewise, heading as above (nautilus_amd/rangesig.py: priors).
+ * Accepted ranges (anything else is NHIP_ERR_ARG before anything is launched, with or without a device): res finite and > 0;
+ * width, height 1..16384; occ_min 1..127; free_max 0..occ_min - 1; stride 1..1024; max_ray_cells 1..4096; rays_per_sector 1,
+ * 2, 4 or 8; unit finite and > 0, with n scale < 2^31 for every ray; top_k 1..16; min_sep 0..64; min_sectors 1..64; flags 0 or
+ * NHIP_RANGESIG_UNKNOWN_STOPS; reserved 0; max_anchors, n_anchors 0..2^20; n_queries, n_scans >= 0. */
+typedef struct nhip_rangesig_spec {
+  double res;               /* metres per cell: the map's */
+  double unit;              /* metres per step of a signature byte (0.125) */
+  int32_t cell_x0;          /* the map's window: the occupancy spec's */
+  int32_t cell_y0;
+  int32_t width;
+  int32_t height;
+  int32_t occ_min;          /* a cell >= occ_min stops a ray (100) */
+  int32_t free_max;         /* a cell in [0, free_max] may hold an anchor (0) */
+  int32_t stride;           /* cells between lattice nodes (10) */
+  int32_t max_ray_cells;    /* L: a ray's length in cells (600) */
+  int32_t rays_per_sector;  /* m (4) */
+  int32_t top_k;            /* records per query (5) */
+  int32_t min_sep;          /* lattice steps between two records of a query, exclusive (2) */
+  int32_t min_sectors;      /* sectors with a return a query needs (8) */
+  int32_t flags;            /* 0 or NHIP_RANGESIG_UNKNOWN_STOPS */
+  int32_t reserved;         /* 0 */
+} nhip_rangesig_spec_t;
+#define NHIP_RANGESIG_SECTORS 64
+#define NHIP_RANGESIG_UNKNOWN_STOPS 1 /* flags: an unknown cell ends a ray with its range, as a wall does, not with 255 */
+#define NHIP_RANGESIG_WORKSPACE_MAX (64ll << 20) /* what nhip_rangesig_workspace_bytes asks for at most, one key row excepted */
+/* the defaults of the table above; the map's window is 0 and is the caller's to set; pure host */
+int nhip_rangesig_spec_default(nhip_rangesig_spec_t *out);
+/* rays: 64 m x int32[4] = {dx, dy, n, scale}; edge2: 255 floats, edge2[0] = 0; either may be NULL; pure host.  The `dir` table
+ * of the sectors is nhip_place_tables'. */
+int nhip_rangesig_tables(const nhip_rangesig_spec_t *spec, int32_t *rays, float *edge2);
+/* bytes of the workspace nhip_rangesig_anchors_dev and nhip_rangesig_match_dev take for a list of n_anchors entries and
+ * n_queries queries: a row of 4-byte keys per query (rows of ceil(n_anchors / 64) 64 keys) if those fit
+ * NHIP_RANGESIG_WORKSPACE_MAX, else as many rows as do, at least one; never less than the 65,792 bytes of the anchors' row counts.  -1 on a
+ * bad argument; pure host */
+int64_t nhip_rangesig_workspace_bytes(const nhip_rangesig_spec_t *spec, int32_t n_anchors, int32_t n_queries);
+/* The anchor list of a grid, on the caller's buffers and stream; never allocates, enqueues and returns without waiting.
+ * d_grid: int8 [height][width], any alignment; d_anchors: max_anchors x int32[4], 16-byte aligned (may be NULL with
+ * max_anchors 0); d_stats: 8 int64, 8-byte aligned; d_workspace: nhip_rangesig_workspace_bytes(spec, 0, 0) bytes or more, 4-byte
+ * aligned. */
+int nhip_rangesig_anchors_dev(const int8_t *d_grid, const nhip_rangesig_spec_t *spec, int32_t max_anchors, int32_t *d_anchors,
+                              int64_t *d_stats, void *d_workspace, int64_t workspace_bytes, void *stream);
+/* The map signatures of the n_anchors entries of d_anchors: d_sig[n_anchors][64] bytes, 4-byte aligned.  d_rays: the table of
+ * nhip_rangesig_tables in device memory (64 m x int32[4]); its entries and the anchors' cells are checked before a cell index
+ * becomes an address: an entry with n outside 1..4096, |dx| or |dy| above n, or n scale >= 2^31 is a ray that ends at n at
+ * once, reported with kind 2097152 (index = the ray).  Same rules as above. */
+int nhip_rangesig_map_dev(const int8_t *d_grid, const nhip_rangesig_spec_t *spec, const int32_t *d_rays, const int32_t *d_anchors,
+                          int32_t n_anchors, uint8_t *d_sig, int64_t *d_stats, void *stream);
+/* The scan signatures of n_scans packed scans: d_sig[n_scans][64] bytes, 4-byte aligned.  Same rules as above. */
+int nhip_rangesig_scans_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_scans, const nhip_rangesig_spec_t *spec,
+                            uint8_t *d_sig, void *stream);
+/* The records of n_queries query signatures against n_anchors map signatures (both plain bytes, [.][64], 4-byte aligned, any
+ * values) and their anchor list: d_records[n_queries][top_k][4] int32.  The query rows are taken in chunks of what the
+ * workspace holds (at least one row of ceil(n_anchors / 64) 64 keys of 4 bytes, 4-byte aligned); the records are the same for
+ * any chunking.  Same rules as above. */
+int nhip_rangesig_match_dev(const uint8_t *d_query_sig, int32_t n_queries, const uint8_t *d_map_sig, const int32_t *d_anchors,
+                            int32_t n_anchors, const nhip_rangesig_spec_t *spec, int32_t *d_records, int64_t *d_stats,
+                            void *d_workspace, int64_t workspace_bytes, void *stream);
+
 /* K15: FREE-SPACE CHECK of match records ("Free-space check"; tests/freespace_reference.py restates it
  * in numpy).  A record's score says how much of the source landed on the target's blurred hits; the check says where the rest
  * landed.  Build-defined and deterministic; all integer after the cells; no matcher kernel is involved.
@@ -1247,6 +1342,16 @@ int nhip_transient_filter(const nhip_scans_t *scans, const double *poses, const 
  * out_xy are written.  Allocates and frees its device buffers. */
 int nhip_map_windows(const int8_t *grid, const nhip_mapwin_spec_t *spec, const int32_t *origins, int32_t n_queries, float *out_xy,
                      int64_t capacity, int32_t *out_offsets, int64_t *stats);
+
+/* The four range-signature calls on host memory: grid (width x height int8), the packed scans xy (2 floats per point) and
+ * offsets (n_scans + 1 int32, ascending from 0: anything else is NHIP_ERR_ARG before a launch), and the outputs records
+ * (n_scans x top_k x 4 int32), anchors (room for max_anchors x 4 int32; may be NULL with max_anchors 0), n_anchors (one int32:
+ * the entries written), stats (8 int64) and, unless NULL, map_sig (max_anchors x 64 bytes) and scan_sig (n_scans x 64 bytes).
+ * More anchors than max_anchors: the first max_anchors are matched, stats[2] says how many were left out and
+ * nhip_dev_status() reports it.  Allocates and frees its device buffers; the key workspace is nhip_rangesig_workspace_bytes. */
+int nhip_rangesig_candidates(const int8_t *grid, const nhip_rangesig_spec_t *spec, const float *xy, const int32_t *offsets,
+                             int32_t n_scans, int32_t max_anchors, int32_t *records, int32_t *anchors, int32_t *n_anchors,
+                             int64_t *stats, uint8_t *map_sig, uint8_t *scan_sig);
 
 /* nhip_freespace_check_dev on handles: the pair arguments of nhip_csm_match, the records it returned (host memory) and
  * counts (8 int32 per pair, host memory).  `scans` must be the scans `grids` was built from: the first call on a grids handle

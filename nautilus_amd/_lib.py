@@ -25,6 +25,8 @@ NHIP_TIMER_OCC_TRACE, NHIP_TIMER_OCC_CLASSIFY = 12, 13
 NHIP_OCC_ACCUMULATE = 1
 NHIP_PLACE_PAST_ONLY = 1
 NHIP_PLACE_WORKSPACE_MAX = 64 << 20
+NHIP_RANGESIG_WORKSPACE_MAX = 64 << 20
+NHIP_RANGESIG_UNKNOWN_STOPS = 1
 NHIP_CONSISTENCY_STATE_BYTES = 8448
 NHIP_LOSS_NONE, NHIP_LOSS_HUBER, NHIP_LOSS_SOFT_L1, NHIP_LOSS_CAUCHY = 0, 1, 2, 3
 
@@ -100,6 +102,13 @@ class TransientSpec(C.Structure):
 class MapwinSpec(C.Structure):
     _fields_ = [("res", C.c_double), ("cell_x0", C.c_int32), ("cell_y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
                 ("side", C.c_int32), ("occ_min", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RangesigSpec(C.Structure):
+    _fields_ = [("res", C.c_double), ("unit", C.c_double), ("cell_x0", C.c_int32), ("cell_y0", C.c_int32), ("width", C.c_int32),
+                ("height", C.c_int32), ("occ_min", C.c_int32), ("free_max", C.c_int32), ("stride", C.c_int32),
+                ("max_ray_cells", C.c_int32), ("rays_per_sector", C.c_int32), ("top_k", C.c_int32), ("min_sep", C.c_int32),
+                ("min_sectors", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
 class FreespaceSpec(C.Structure):
@@ -249,6 +258,14 @@ PROTOTYPES = {
     "nhip_mapwin_cells_dev": (C.c_int, [_vp, _P(MapwinSpec), _i32, _vp, _vp, _vp, _vp]),
     "nhip_mapwin_gather_dev": (C.c_int, [_vp, _vp, _P(MapwinSpec), _vp, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "nhip_map_windows": (C.c_int, [_vp, _P(MapwinSpec), _vp, _i32, _vp, _i64, _vp, _vp]),
+    "nhip_rangesig_spec_default": (C.c_int, [_P(RangesigSpec)]),
+    "nhip_rangesig_tables": (C.c_int, [_P(RangesigSpec), _vp, _vp]),
+    "nhip_rangesig_workspace_bytes": (_i64, [_P(RangesigSpec), _i32, _i32]),
+    "nhip_rangesig_anchors_dev": (C.c_int, [_vp, _P(RangesigSpec), _i32, _vp, _vp, _vp, _i64, _vp]),
+    "nhip_rangesig_map_dev": (C.c_int, [_vp, _P(RangesigSpec), _vp, _vp, _i32, _vp, _vp, _vp]),
+    "nhip_rangesig_scans_dev": (C.c_int, [_vp, _vp, _i32, _P(RangesigSpec), _vp, _vp]),
+    "nhip_rangesig_match_dev": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _P(RangesigSpec), _vp, _vp, _vp, _i64, _vp]),
+    "nhip_rangesig_candidates": (C.c_int, [_vp, _P(RangesigSpec), _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nhip_freespace_spec_default": (C.c_int, [_P(FreespaceSpec)]),
     "nhip_freespace_planes_bytes": (_i64, [_P(GridSpec), _i64]),
     "nhip_freespace_trace_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(GridSpec), _vp, _vp, _vp]),

@@ -56,7 +56,7 @@ constexpr uint32_t BAD_TARGET_ID = 1u, BAD_PAIR_SRC = 2u, BAD_PAIR_SLOT = 4u, BA
                    BAD_MEMBER_ID = 512u, BAD_SUBMAP_CAPACITY = 1024u, BAD_CONTRIB_ID = 2048u, BAD_BLOCK_COLUMN = 4096u,
                    BAD_SYSTEM_ID = 8192u, BAD_MAP_SCAN_OFFSETS = 16384u, BAD_FREESPACE_PAIR = 32768u, BAD_PLACE_ID = 65536u,
                    BAD_CONSISTENCY_DEGREE = 131072u, BAD_CONSISTENCY_MEMBER = 262144u, BAD_MAPWIN_CELLS = 524288u,
-                   BAD_MAPWIN_POINTS = 1048576u;
+                   BAD_MAPWIN_POINTS = 1048576u, BAD_RANGESIG = 2097152u;
 constexpr int DEV_STATUS_WORDS = 4;  // {OR of the kinds seen, kind / value / index of the first report}
 uint32_t *dev_status();              // of the current device (allocated on the device's first use; null if that failed)
 #ifdef __HIPCC__
@@ -425,6 +425,33 @@ int launch_mapwin_cells(const MapwinParams &P, const int8_t *d_grid, int32_t max
 int launch_mapwin_gather(const MapwinParams &P, const int32_t *d_row_ptr, const int32_t *d_cols, const int32_t *d_origins,
                          int32_t n_queries, float *d_out_xy, int64_t out_capacity, int32_t *d_out_offsets, int32_t *d_counts,
                          hipStream_t s);
+
+// range signatures (nhip_rangesig.hip, K21); the spec has passed rangesig_spec_check (nhip_host_rangesig.hip)
+constexpr int32_t RANGESIG_MAX_ANCHORS = 1 << 20;
+constexpr int32_t RANGESIG_MAX_NODES_PER_AXIS = 16384;  // lattice rows: the anchors' row counts take 64 KB of the workspace
+constexpr int RANGESIG_QT = 8;                          // query rows a workgroup of the cost kernel takes with one load of its anchors
+struct RangesigParams {  // plain data: travels in the kernels' parameter blocks
+  int32_t width, height, occ_min, free_max, stride, rays_per_sector, top_k, min_sep, min_sectors, flags;
+  long long *stats;   // 8 words: {lattice nodes, anchors, anchors that did not fit, rays ended on a wall, in unknown, outside or at n,
+                      // queries without a record, records}: the anchors call writes 0 - 2 and clears the rest, the map call 3 - 5,
+                      // the match 6 and 7
+  uint32_t *status;
+};
+struct RangesigScanTables {  // plain data: travels in the scan kernel's parameter block (nhip_rangesig_tables / nhip_place_tables fill the same values)
+  float edge2[256];   // [0] = 0, [1..254] the squared edges, [255] unused
+  float dir[64];      // 32 x {cos, sin}
+};
+// fill with -1, row count, scan (with the capacity decision and the stats) and row pack; d_row_counts: the workspace, nj + 1 int32
+int launch_rangesig_anchors(const RangesigParams &P, const int8_t *d_grid, int32_t max_anchors, int32_t *d_anchors,
+                            int32_t *d_row_counts, hipStream_t s);
+int launch_rangesig_map(const RangesigParams &P, const int8_t *d_grid, const int32_t *d_rays, const int32_t *d_anchors,
+                        int32_t n_anchors, uint8_t *d_sig, hipStream_t s);
+int launch_rangesig_scans(const RangesigScanTables &T, const float *d_xy, const int32_t *d_offsets, int32_t n_scans, uint8_t *d_sig,
+                          hipStream_t s);
+// clears stats 6 and 7, then cost and selection kernels per chunk of `chunk_rows` query rows (d_keys holds that many rows of `pitch`)
+int launch_rangesig_match(const RangesigParams &P, const uint8_t *d_qsig, int32_t n_queries, const uint8_t *d_asig,
+                          const int32_t *d_anchors, int32_t n_anchors, int32_t *d_records, uint32_t *d_keys, int32_t pitch,
+                          int32_t chunk_rows, hipStream_t s);
 
 // free-space check of match records (nhip_freespace.hip, K15); the specs have passed the checks of nhip_host_freespace.hip
 struct FsParams {     // plain data: travels in the kernels' parameter blocks (the trace reads the first group, the check both)

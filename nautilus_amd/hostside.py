@@ -856,6 +856,185 @@ class _MapwinFields:
             int(occ_spec.width), int(occ_spec.height), int(side), int(occ_min), 0, 0
 
 
+def rangesig_spec_check(spec):
+    """The accepted ranges of nhip_rangesig_spec_t (include/nautilus_hip.h); ValueError otherwise."""
+    for name in ("res", "unit"):
+        v = float(getattr(spec, name))
+        if not (math.isfinite(v) and v > 0):
+            raise ValueError("range_signatures: %s must be finite and > 0" % name)
+    for name, lo, hi in (("width", 1, 16384), ("height", 1, 16384), ("occ_min", 1, 127), ("free_max", 0, int(spec.occ_min) - 1),
+                         ("stride", 1, 1024), ("max_ray_cells", 1, 4096), ("top_k", 1, 16), ("min_sep", 0, 64), ("min_sectors", 1, 64),
+                         ("flags", 0, 1), ("reserved", 0, 0)):
+        if not lo <= int(getattr(spec, name)) <= hi:
+            raise ValueError("range_signatures: %s %d outside %d..%d" % (name, int(getattr(spec, name)), lo, hi))
+    if int(spec.rays_per_sector) not in (1, 2, 4, 8):
+        raise ValueError("range_signatures: rays_per_sector %d is not 1, 2, 4 or 8" % int(spec.rays_per_sector))
+
+
+def range_signatures(grid, spec, rays=None):
+    """The anchors of an occupancy grid and their range signatures in plain numpy ("Range signatures", items
+    1 - 3; the device forms are nhip_rangesig_anchors_dev and nhip_rangesig_map_dev): (anchors int32 (A, 4) = {cx, cy, i, j},
+    sig uint8 (A, 64), stats int64 (8,): words 0 - 5 of rangesig.STATS_FIELDS).  rays: the table, int32 (64 m, 4) (None: the
+    library's, nhip_rangesig_tables: pure host).  All rays of all anchors walk together, a step at a time; a ray leaves the walk
+    where it ends."""
+    from . import rangesig
+    rangesig_spec_check(spec)
+    g = np.asarray(grid, dtype=np.int8).reshape(int(spec.height), int(spec.width))
+    H, W = g.shape
+    st, h, m = int(spec.stride), int(spec.stride) // 2, int(spec.rays_per_sector)
+    nodes = g[h::st, h::st]
+    jj, ii = np.nonzero((nodes >= 0) & (nodes <= int(spec.free_max)))  # (row-major: j ascending, then i)
+    anchors = np.stack([ii * st + h, jj * st + h, ii, jj], axis=1).astype(np.int32).reshape(-1, 4)
+    rays = (rangesig.tables(spec)[0] if rays is None else np.asarray(rays)).astype(np.int64).reshape(64 * m, 4)
+    A, R = len(anchors), 64 * m
+    val = np.full(A * R, 255, np.int64)
+    end = np.full(A * R, 2, np.int8)
+    live = np.arange(A * R)
+    ax, ay = anchors[:, 0].astype(np.int64), anchors[:, 1].astype(np.int64)
+    for k in range(1, int(rays[:, 2].max()) + 1 if A else 0):
+        t = live % R
+        live = live[rays[t, 2] >= k]  # (a ray that found nothing by its n: 255, already)
+        if not len(live):
+            break
+        a, t = live // R, live % R
+        n = rays[t, 2]
+        x = ax[a] + (2 * k * rays[t, 0] + n) // (2 * n)
+        y = ay[a] + (2 * k * rays[t, 1] + n) // (2 * n)
+        inside = (x >= 0) & (x < W) & (y >= 0) & (y < H)
+        live, x, y, t = live[inside], x[inside], y[inside], t[inside]
+        v = g[y, x].astype(np.int64)
+        unknown, wall = v < 0, v >= int(spec.occ_min)
+        end[live[unknown]] = 1
+        end[live[wall]] = 0
+        ranged = wall | unknown if int(spec.flags) & 1 else wall  # (NHIP_RANGESIG_UNKNOWN_STOPS: an unknown cell gives its range too)
+        val[live[ranged]] = np.minimum(254, (k * rays[t[ranged], 3]) >> 16)
+        live = live[~(unknown | wall)]
+    sig = val.reshape(A, 64, m).min(axis=2).astype(np.uint8)
+    stats = np.zeros(8, np.int64)
+    stats[0], stats[1] = nodes.size, A
+    stats[3:6] = np.bincount(end, minlength=3)[:3]
+    return anchors, sig, stats
+
+
+def scan_signatures(xy, offsets, spec):
+    """The range signatures of the packed scans in plain numpy ("Range signatures", item 4; the device form is
+    nhip_rangesig_scans_dev): uint8 (n_scans, 64).  The edges are the library's (nhip_rangesig_tables), the sectors the place
+    descriptor's (nhip_place_tables): both pure host."""
+    from . import place, rangesig
+    rangesig_spec_check(spec)
+    f = np.float32
+    edge2, dirs = rangesig.tables(spec)[1], place.tables()[1]
+    p = np.asarray(xy, dtype=f).reshape(-1, 2)
+    off = np.asarray(offsets, dtype=np.int64)
+    x, y = p[:, 0], p[:, 1]
+    with np.errstate(invalid="ignore", over="ignore"):
+        r2 = ((x * x).astype(f) + (y * y).astype(f)).astype(f)
+        kept = np.isfinite(r2)
+        q = np.searchsorted(edge2[1:255], r2, side="right")  # (#{k in 1..254: r2 >= edge2[k]}: the edges ascend)
+        neg = (y < 0) | ((y == 0) & (x < 0))
+        u, v = np.where(neg, -x, x).astype(f), np.where(neg, -y, y).astype(f)
+        sector = np.where(neg, 32, 0)
+        for j in range(1, 32):
+            sector = sector + (((dirs[j, 0] * v).astype(f) - (dirs[j, 1] * u).astype(f)).astype(f) >= 0)
+    scan = np.repeat(np.arange(len(off) - 1), np.diff(off))
+    sig = np.full((len(off) - 1, 64), 255, np.uint8)
+    np.minimum.at(sig, (scan[kept], sector[kept]), q[kept].astype(np.uint8))
+    return sig
+
+
+def signature_candidates(query_sig, map_sig, anchors, spec):
+    """The records of query signatures against map signatures in plain numpy ("Range signatures", items 5 and 6; the device form
+    is nhip_rangesig_match_dev): (records int32 (Q, K, 4) = {anchor, shift, cost, valid}, four -1 where unfilled; stats int64
+    (8,): words 6 and 7 of rangesig.STATS_FIELDS).  Any bytes are signatures; an anchor entry whose cell is outside the window is
+    no anchor."""
+    rangesig_spec_check(spec)
+    Qs = np.asarray(query_sig, dtype=np.uint8).reshape(-1, 64)
+    As = np.asarray(map_sig, dtype=np.uint8).reshape(-1, 64)
+    an = np.asarray(anchors, dtype=np.int64).reshape(-1, 4)
+    if len(an) != len(As):
+        raise ValueError("signature_candidates: %d anchors for %d signatures" % (len(an), len(As)))
+    K, sep = int(spec.top_k), int(spec.min_sep)
+    rec, stats = np.full((len(Qs), K, 4), -1, np.int32), np.zeros(8, np.int64)
+    ok = (an[:, 0] >= 0) & (an[:, 0] < int(spec.width)) & (an[:, 1] >= 0) & (an[:, 1] < int(spec.height))
+    idx = np.nonzero(ok)[0]
+    # A[(j + s) mod 64] for every anchor and shift: (64, A', 64) int16, 8 KB an anchor -- kept for all queries while the anchors
+    # are one chunk, made again per query and chunk beyond that
+    rolled = lambda rows: np.stack([np.roll(As[rows], -s, axis=1) for s in range(64)]).astype(np.int16)
+    chunks = [idx[c:c + 8192] for c in range(0, len(idx), 8192)]
+    kept = rolled(chunks[0]) if len(chunks) == 1 else None
+    for q, Q in enumerate(Qs):
+        mask = Q != 255
+        valid = int(mask.sum())
+        if valid >= int(spec.min_sectors) and len(idx):
+            keys = []
+            for rows in chunks:
+                rot = kept if kept is not None else rolled(rows)
+                cost = np.abs(rot[:, :, mask] - Q[mask].astype(np.int16)).sum(axis=2, dtype=np.int64)  # (64, rows)
+                shift = cost.argmin(axis=0)  # (the first minimum: the smallest shift)
+                keys.append(cost[shift, np.arange(len(rows))] * 64 + shift)
+            key = np.concatenate(keys)
+            order = np.lexsort((idx, key))
+            taken = np.zeros(len(idx), bool)  # accepted, or suppressed by an accepted one
+            for k in range(K):
+                left = order[~taken[order]]
+                if not len(left):
+                    break
+                b = left[0]
+                rec[q, k] = (idx[b], key[b] % 64, key[b] // 64, valid)
+                taken |= (np.abs(an[idx, 2] - an[idx[b], 2]) <= sep) & (np.abs(an[idx, 3] - an[idx[b], 3]) <= sep)
+        n = int((rec[q, :, 0] >= 0).sum())
+        stats[7] += n
+        stats[6] += n == 0
+    return rec, stats
+
+
+def global_localize(backend, xy, offsets, grid, occ_spec, spec=None, grid_spec=None, search=None, cell_bits=16, occ_min=100):
+    """Scans localised in a finished occupancy grid from NO prior, through ANY backend with a match() method (the host route to
+    HipBackend.global_localize): the signatures, the records and their priors in numpy (range_signatures, scan_signatures,
+    signature_candidates, rangesig.priors), then localize() above on the filled (scan, prior) entries, the scans repeated in
+    the packed cloud; per query the entry with the highest record score wins, ties to the lower rank.  spec: a RangesigSpec
+    (None: the defaults on occ_spec's window and res with NHIP_RANGESIG_UNKNOWN_STOPS, what a map ray-traced from scans needs).
+    Returns {"poses": (Q, 3) float64, NaN where no entry matched;
+    "rank": int32 (Q,), -1 likewise; "proposals": (Q, K, 3) float64; "candidates": int32 (Q, K, 4); "anchors": int32 (A, 4);
+    "records": MATCH_DTYPE (Q, K), itheta -1 for an unfilled or rejected entry; "stats": int64 (8,)}."""
+    from . import rangesig
+    spec = rangesig.spec(occ_spec, occ_min=int(occ_min), flags=rangesig.NHIP_RANGESIG_UNKNOWN_STOPS) if spec is None else spec
+    anchors, map_sig, stats = range_signatures(grid, spec)
+    cand, s2 = signature_candidates(scan_signatures(xy, offsets, spec), map_sig, anchors, spec)
+    stats[6:] = s2[6:]
+    return global_localize_finish(lambda *a, **kw: localize(backend, *a, **kw), xy, offsets, cand, anchors, spec, stats, grid, occ_spec,
+                                  dict(occ_min=occ_min, cell_bits=cell_bits, grid_spec=grid_spec, search=search))
+
+
+def global_localize_finish(localize_fn, xy, offsets, cand, anchors, spec, stats, grid, occ_spec, kw):
+    """The second half of global_localize, shared with relocalize.global_localize: the priors of the records, the (scan, prior)
+    entries through localize_fn(xy, offsets, priors, grid, occ_spec, **kw), and the winner per query."""
+    from . import csm, rangesig
+    proposals = rangesig.priors(cand, anchors, spec)
+    Q, K = cand.shape[:2]
+    qq, kk = np.nonzero(cand[:, :, 0] >= 0)  # (query by query, rank by rank)
+    p = np.asarray(xy, dtype=np.float32).reshape(-1, 2)
+    off = np.asarray(offsets, dtype=np.int64)
+    rec = np.zeros((Q, K), dtype=csm.MATCH_DTYPE)
+    rec["itheta"] = -1
+    rec["score"] = -np.inf
+    poses_all = np.full((Q, K, 3), np.nan)
+    if len(qq):
+        xy2 = np.concatenate([p[off[q]:off[q + 1]] for q in qq]) if len(p) else p
+        off2 = np.concatenate([[0], np.cumsum(np.diff(off)[qq])]).astype(np.int32)
+        r = localize_fn(xy2, off2, proposals[qq, kk], grid, occ_spec, **kw)
+        rec[qq, kk] = r["records"]
+        poses_all[qq, kk] = r["poses"]
+    score = np.where(rec["itheta"] >= 0, rec["score"].astype(np.float64), -np.inf)
+    rank = score.argmax(axis=1).astype(np.int32) if K else np.zeros(Q, np.int32)  # (the first maximum: the lower rank)
+    none = ~np.isfinite(score[np.arange(Q), rank]) if Q else np.zeros(0, bool)
+    poses = poses_all[np.arange(Q), rank]
+    poses[none] = np.nan
+    rank[none] = -1
+    return {"poses": poses, "rank": rank, "proposals": proposals, "candidates": cand, "anchors": anchors, "records": rec,
+            "stats": stats}
+
+
 def hitl_segments(msg):
     """LineSegmentsFromHitlMsg (solver.cc:467-478): msg = dict with line_a_start, line_a_end, line_b_start,
     line_b_end, each (x, y[, z]) -> two LineSegment<float> as (x0, y0, x1, y1) float32 rows."""

@@ -331,6 +331,15 @@ class HipBackend:
         return localize.localize(xy, offsets, priors, grid, occ_spec, grid_spec=grid_spec, search=search, min_score=min_score,
                                  cell_bits=cell_bits, device=str(self.dev), **kw)
 
+    def global_localize(self, xy, offsets, grid, occ_spec, spec=None, grid_spec=None, search=None, min_score=None, cell_bits=16, **kw):
+        """The packed scans localised in a finished occupancy grid from NO prior, on this backend's device
+        (relocalize.global_localize; DESIGN.md section 3, "Range signatures"): K proposals per scan from the range signatures of
+        the map, every (scan, proposal) entry through localize(), the best-scoring entry per scan.  Returns the dict of poses
+        (n, 3), rank, proposals, candidates, anchors, records and stats."""
+        from . import relocalize
+        return relocalize.global_localize(xy, offsets, grid, occ_spec, spec=spec, grid_spec=grid_spec, search=search, min_score=min_score,
+                                          cell_bits=cell_bits, device=str(self.dev), **kw)
+
     def match(self, xy, offsets, pair_src, pair_tgt, theta0, cell_bits=16, submap_radius=0, poses=None, freespace=None,
               grid_spec=None, search=None):
         """Batched loop-closure scan matching (BASELINE config #2 lattice): (records, spec, search).
