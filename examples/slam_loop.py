@@ -58,7 +58,7 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False, normals="bag", lc_submap=0,
         linear_solver="host", lc_gate="geometric", lc_max_score=5000.0, map_output=None, grid_output=None, lc_verify=None,
         lc_max_violation=None, lc_top_k=5, lc_consistency=False, lc_min_set=3, _lc_corrupt=None, lc_sequence=0, lc_sequence_step=1,
-        lc_loss=None, lc_loss_scale=1.0, movers=0, drop_transients=False):
+        lc_loss=None, lc_loss_scale=1.0, movers=0, drop_transients=False, lc_refine=None):
     """min_scatter_score: LCCandidateFilter's threshold is 0.70 (lc_candidate_filter.cc:76); scans of the synthetic
     24 m x 16 m room score ~0.4, so callers on that world pass a lower one.
     hitl_device: the HITL constraint's points are selected and packed on the GPU (hitl.select, under the "path" clock) and
@@ -101,6 +101,11 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     inside the grid.  A backend whose match() takes `freespace` checks on the device inside the call; any other is checked by
     hostside.freespace_counts.  The result reports lc_verified, lc_verify_rejected (they sum to the unverified run's
     lc_accepted) and the rms relative error of either set.  Not with world > 1 or lc_submap.
+    lc_refine: "icp" -- every record that passed the score gate is refined from its lattice pose (one cell, one degree) to a
+    sub-cell pose by point-to-line ICP against the target scan ("Match refinement"), before lc_verify and
+    lc_consistency; a backend with refine_matches() runs it on the device, any other is served by hostside.refine_matches.  A
+    pair with any flag other than NOT_CONVERGED keeps its lattice pose.  The result reports lc_refined, lc_refine_flags (a count
+    per flag), refine_s, and lc_rel_err_m of the poses actually used.  Not with world > 1.
     lc_consistency: the accepted records -- after the score gate and, with lc_verify, the free-space check -- are judged against
     each other ("Loop-closure consistency"): the cycle two records form with the estimate between their ends
     must close up to the drift the estimate can have gathered, and only the records of a greedily grown set of mutually consistent
@@ -168,6 +173,10 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         raise ValueError("run: lc_verify %r (None or \"free-space\")" % (lc_verify,))
     if lc_verify and (world > 1 or lc_submap):
         raise ValueError("run: lc_verify with world > 1 or lc_submap (the free-space check has no sharded path and no submap targets)")
+    if lc_refine not in (None, "icp"):
+        raise ValueError("run: lc_refine %r (None or \"icp\")" % (lc_refine,))
+    if lc_refine and world > 1:
+        raise ValueError("run: lc_refine with world > 1 (the refinement has no sharded path)")
     if lc_consistency and world > 1:
         raise ValueError("run: lc_consistency with world > 1 (the consistent set has no sharded path)")
     if lc_consistency and int(lc_min_set) < 0:
@@ -360,6 +369,22 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         # (csm_score_threshold = -5.0, config/default_config.lua:84-85); optima on the lattice border are open-ended
         good = inside & (m["score"] > csm_score_threshold)
         truth_rel = np.array([bag.true_relative(s, t) for s, t in zip(src, tgt)])
+        if lc_refine:
+            # the records that passed the score gate go from their lattice pose to the sub-cell pose of point-to-line ICP against
+            # the target SCAN (also where the table was a submap, which has no normals; the scans as ingested, with their normals)
+            t1 = time.perf_counter()
+            idx = np.nonzero(good)[0]
+            args = (xy, nrm, off, src[idx], tgt[idx], theta0[idx], m[idx], spec, search)
+            if hasattr(backend, "refine_matches"):
+                with posegraph.clocked("path"):
+                    refined = backend.refine_matches(*args)
+            else:  # (a backend without the method: the numpy host path)
+                with posegraph.clocked("marshal"):
+                    refined = hostside.refine_matches(*args)
+            used = hostside.refine_keeps_pose(refined)  # (any flag but NOT_CONVERGED: the lattice pose stays)
+            rel[idx[used]] = hostside.refined_to_transform(refined[used])
+            out["lc_refined"], out["refine_s"] = int(used.sum()), time.perf_counter() - t1
+            out["lc_refine_flags"] = hostside.refine_flag_counts(refined)
         rms = lambda sel: float(np.sqrt(np.mean(np.sum((rel[sel, :2] - truth_rel[sel, :2]) ** 2, axis=1)))) if sel.any() else None
         if lc_verify:
             from nautilus_amd import freespace
@@ -529,6 +554,9 @@ if __name__ == "__main__":
     ap.add_argument("--lc-max-violation", type=int, default=None, metavar="PERMILLE",
                     help="with --lc-verify: the largest share of a source's returns in the target's free space, plus its beams "
                          "through target hits, that is kept (default: freespace.DEFAULT_MAX_PERMILLE)")
+    ap.add_argument("--lc-refine", choices=["icp"], default=None,
+                    help="refine every match that passed the score gate from its lattice pose to a sub-cell pose by point-to-line "
+                         "ICP against the target scan, before --lc-verify and --lc-consistency (not with several ranks)")
     ap.add_argument("--lc-consistency", action="store_true",
                     help="keep only the accepted loop closures of a mutually consistent set (pairwise consistency of the cycles "
                          "they form with the estimate; not with several ranks)")
@@ -566,6 +594,8 @@ if __name__ == "__main__":
         ap.error("--lc-loss-scale %r: finite and > 0" % (a.lc_loss_scale,))
     rank, world, local = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")), \
         int(os.environ.get("LOCAL_RANK", "0"))
+    if a.lc_refine and world > 1:
+        ap.error("--lc-refine with several ranks (the refinement has no sharded path)")
     if "RANK" in os.environ:  # python -m torch.distributed.run --nproc-per-node N examples/slam_loop.py ...
         import torch
         import torch.distributed as dist
@@ -583,7 +613,7 @@ if __name__ == "__main__":
               grid_output=a.grid_output, lc_verify=a.lc_verify, lc_max_violation=a.lc_max_violation, lc_top_k=a.lc_top_k,
               lc_consistency=a.lc_consistency, lc_min_set=a.lc_min_set, lc_sequence=seq_w, lc_sequence_step=seq_step,
               lc_loss=None if a.lc_loss == "none" else a.lc_loss, lc_loss_scale=a.lc_loss_scale, movers=a.movers,
-              drop_transients=a.drop_transients)
+              drop_transients=a.drop_transients, lc_refine=a.lc_refine)
     res["world_size"] = world
     if rank == 0 and "transient_stats" in res:
         s = res["transient_stats"]

@@ -73,7 +73,8 @@ const char *nhip_version(void);
  * needed; index = height) or a row_ptr entry that is not a row in nhip_mapwin_gather_dev (index = the map row), 1048576 window
  * points beyond out_capacity of nhip_mapwin_gather_dev (value: the points needed, at most 2^31 - 1; index = n_queries), 2097152
  * anchors beyond max_anchors of nhip_rangesig_anchors_dev (value: the anchors found; index = max_anchors) or an entry of the ray
- * table that is not a ray in nhip_rangesig_map_dev (value: its n; index = the ray).
+ * table that is not a ray in nhip_rangesig_map_dev (value: its n; index = the ray), 4194304 source or target scan id of a pair
+ * of nhip_refine_icp_dev (index = the pair).
  * Clears the record
  * (in the order of `stream`).
  * ONE record per DEVICE, shared by every stream and host thread that uses the library on it: a host with several streams
@@ -1261,6 +1262,73 @@ int nhip_hitl_pack_dev(const float *d_xy, const int32_t *d_offsets, int32_t n_sc
                        const int32_t *d_counts, const int32_t *d_scan_block, const int32_t *d_scan_offset,
                        const int32_t *d_totals, int32_t n_blocks, int32_t n_points, float *d_points,
                        int32_t *d_block_offsets, int32_t *d_block_pose, void *stream);
+
+/* ------------------------------------------------------------------ K22: match refinement (point-to-line ICP from the lattice pose)
+ * A match record is a pose of the search lattice: one cell and one rotation step.  The refinement takes every pair of a
+ * list from its lattice pose to the sub-cell pose at which the source scan's points lie on the target SCAN's lines: a few
+ * Gauss-Newton updates on point-to-line residuals, one workgroup per pair, one launch for the list.  The rule -- every
+ * operation, the order of every sum -- is DESIGN.md section 3, "Match refinement"; tests/refine_reference.py restates it in
+ * numpy and the device equals it bit for bit.  A pose is (c, s, tx, ty) in double: q = R p + t takes a source point into
+ * the target's frame (nhip_match_to_transform's convention). */
+#define NHIP_REFINE_THRESHOLDS 16      /* slots of the spec's threshold table = the largest max_iterations */
+#define NHIP_REFINE_TARGET_MAX 2048    /* points of a target scan the kernel stages */
+#define NHIP_REFINE_TRACE_DOUBLES 64   /* per pair: (c, s, tx, ty) after update k at 4k ..; zeros behind the last update */
+#define NHIP_REFINE_SKIPPED 1u         /* pose0 not finite (a rejected record): NaNs returned */
+#define NHIP_REFINE_TARGET_TOO_LONG 2u /* the target has more than NHIP_REFINE_TARGET_MAX points: pose0 returned */
+#define NHIP_REFINE_FEW 4u             /* an evaluation kept fewer than min_corr correspondences: pose0 returned */
+#define NHIP_REFINE_SINGULAR 8u        /* a pivot <= 0 or lambda_min(H[0:2, 0:2]) / n_corr < min_spread: pose0 returned */
+#define NHIP_REFINE_RUNAWAY 16u        /* an update left the start by more than max_shift_m / max_turn_sin: pose0 returned */
+#define NHIP_REFINE_NOT_CONVERGED 32u  /* max_iterations updates without meeting the tolerances: the refined pose; informational */
+typedef struct nhip_refine_spec {
+  double thr0;          /* correspondence threshold of update 0 [m] (outlier_threshold, 0.25); the bucket grid's cells */
+  double shrink;        /* factor per update (0.5), in (0, 1] */
+  double thr_min;       /* floor of the thresholds (0.05), in (0, thr0] */
+  double step_tol_m;    /* stop when sqrt(dx^2 + dy^2) < step_tol_m and |dtheta| < step_tol_rad (1e-5 both) */
+  double step_tol_rad;
+  double min_spread;    /* 0.02 */
+  double max_shift_m;   /* 0.5 */
+  double max_turn_sin;  /* sin(5 deg), filled by the host */
+  float thr[NHIP_REFINE_THRESHOLDS]; /* thr[k] = (float)max(thr_min, thr0 * shrink^k), the power by repeated products in
+                           double; update k reads thr[k], the final evaluation thr[max_iterations - 1].  The kernel reads THIS
+                           table; a caller that edits thr0, shrink or thr_min fills it again (0 < thr[k] <= thr[0] = (float)thr0) */
+  int32_t max_iterations; /* 8; 1 .. NHIP_REFINE_THRESHOLDS */
+  int32_t min_corr;       /* 30; >= 3 */
+  int32_t flags;          /* 0 */
+  int32_t reserved;       /* 0 */
+} nhip_refine_spec_t;
+typedef struct nhip_refined {
+  double c, s, tx, ty;  /* the pose returned (see the flags) */
+  double info[6];       /* the final evaluation's H = sum J^T J over (x, y, theta): H00 H01 H02 H11 H12 H22 */
+  double cost;          /* its sum of squared residuals [m^2] */
+  int32_t n_corr;       /* its correspondences */
+  int32_t iterations;   /* updates performed */
+  uint32_t flags;       /* OR of NHIP_REFINE_* */
+  uint32_t pad;         /* 0 */
+} nhip_refined_t;
+/* the defaults above, the table filled; pure host */
+int nhip_refine_spec_default(nhip_refine_spec_t *out);
+/* Pure host: the start poses of n records, 4 doubles each: theta = theta0 + (itheta - (n_theta - 1) / 2) theta_step,
+ * t = (origin + i - (n - 1) / 2) res as nhip_match_to_transform forms them but in double; c = cos(theta), s = sin(theta)
+ * from libm.  A rejected record (itheta < 0) gives four NaNs.  pair_origin (2 per pair) may be NULL: zeros. */
+int nhip_refine_start_poses(const nhip_match_t *records, const double *theta0, const int32_t *pair_origin, int32_t n_pairs,
+                            const nhip_grid_spec_t *grid_spec, const nhip_search_t *search, double *pose0);
+/* The refinement of n_pairs pairs on device arrays: d_xy / d_normals (2 floats per point, the scan's frame), d_offsets
+ * (n_scans + 1), d_pair_src / d_pair_tgt (scan ids), d_pose0 (4 doubles per pair) in; d_out (n_pairs records) and, unless
+ * NULL, d_trace (NHIP_REFINE_TRACE_DOUBLES per pair) out.  Enqueues one kernel; allocates nothing.  A scan id outside
+ * [0, n_scans) is never dereferenced: the pair matches nothing (NHIP_REFINE_FEW, pose0) and nhip_dev_status() reports it
+ * (kind 4194304, index = the pair).  d_offsets itself must be valid, as for every "_dev" entry point: ascending, its last entry
+ * at most the points behind d_xy and d_normals; the kernel checks the ids, not the offsets.  A spec outside its ranges is
+ * NHIP_ERR_ARG with or without a device. */
+int nhip_refine_icp_dev(const float *d_xy, const float *d_normals, const int32_t *d_offsets, int32_t n_scans,
+                        const int32_t *d_pair_src, const int32_t *d_pair_tgt, const double *d_pose0, int32_t n_pairs,
+                        const nhip_refine_spec_t *spec, nhip_refined_t *d_out, double *d_trace, void *stream);
+/* The same on host arrays (n_points = offsets[n_scans] points): stages them, runs the kernel on the null stream, waits.
+ * Scan ids are checked on the host (NHIP_ERR_ARG).  trace may be NULL. */
+int nhip_refine_icp(const float *xy, const float *normals, const int32_t *offsets, int32_t n_scans, const int32_t *pair_src,
+                    const int32_t *pair_tgt, const double *pose0, int32_t n_pairs, const nhip_refine_spec_t *spec,
+                    nhip_refined_t *out, double *trace);
+/* Pure host: (tx, ty, theta = atan2(s, c)) of a refined record. */
+int nhip_refined_to_transform(const nhip_refined_t *r, double *tx, double *ty, double *theta);
 
 /* ------------------------------------------------------------------ handle API (host pointers) */
 typedef struct nhip_scans nhip_scans_t;

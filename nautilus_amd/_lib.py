@@ -115,6 +115,24 @@ class FreespaceSpec(C.Structure):
     _fields_ = [("hit_radius", C.c_int32), ("end_margin", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+NHIP_REFINE_THRESHOLDS, NHIP_REFINE_TARGET_MAX, NHIP_REFINE_TRACE_DOUBLES = 16, 2048, 64
+NHIP_REFINE_SKIPPED, NHIP_REFINE_TARGET_TOO_LONG, NHIP_REFINE_FEW, NHIP_REFINE_SINGULAR = 1, 2, 4, 8
+NHIP_REFINE_RUNAWAY, NHIP_REFINE_NOT_CONVERGED = 16, 32
+
+
+class RefineSpec(C.Structure):
+    _fields_ = [("thr0", C.c_double), ("shrink", C.c_double), ("thr_min", C.c_double), ("step_tol_m", C.c_double),
+                ("step_tol_rad", C.c_double), ("min_spread", C.c_double), ("max_shift_m", C.c_double),
+                ("max_turn_sin", C.c_double), ("thr", C.c_float * 16), ("max_iterations", C.c_int32), ("min_corr", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Refined(C.Structure):
+    _fields_ = [("c", C.c_double), ("s", C.c_double), ("tx", C.c_double), ("ty", C.c_double), ("info", C.c_double * 6),
+                ("cost", C.c_double), ("n_corr", C.c_int32), ("iterations", C.c_int32), ("flags", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
 class PlaceSpec(C.Structure):
     _fields_ = [("n_rings", C.c_int32), ("range_max", C.c_float), ("top_k", C.c_int32), ("min_separation", C.c_int32),
                 ("max_permille", C.c_int32), ("flags", C.c_int32)]
@@ -272,6 +290,11 @@ PROTOTYPES = {
     "nhip_freespace_check_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(GridSpec), _vp, _vp, _vp, _vp, _vp, _i32, _P(Search),
                                            _vp, _vp, _P(FreespaceSpec), _vp, _vp]),
     "nhip_csm_freespace": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _P(Search), _vp, _P(FreespaceSpec), _vp]),
+    "nhip_refine_spec_default": (C.c_int, [_P(RefineSpec)]),
+    "nhip_refine_start_poses": (C.c_int, [_vp, _vp, _vp, _i32, _P(GridSpec), _P(Search), _vp]),
+    "nhip_refine_icp_dev": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _P(RefineSpec), _vp, _vp, _vp]),
+    "nhip_refine_icp": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _P(RefineSpec), _vp, _vp]),
+    "nhip_refined_to_transform": (C.c_int, [_P(Refined), _P(_f64), _P(_f64), _P(_f64)]),
     "nhip_place_spec_default": (C.c_int, [_P(PlaceSpec)]),
     "nhip_place_tables": (C.c_int, [_P(PlaceSpec), _vp, _vp]),
     "nhip_place_workspace_bytes": (_i64, [_P(PlaceSpec), _i32]),

@@ -56,7 +56,7 @@ constexpr uint32_t BAD_TARGET_ID = 1u, BAD_PAIR_SRC = 2u, BAD_PAIR_SLOT = 4u, BA
                    BAD_MEMBER_ID = 512u, BAD_SUBMAP_CAPACITY = 1024u, BAD_CONTRIB_ID = 2048u, BAD_BLOCK_COLUMN = 4096u,
                    BAD_SYSTEM_ID = 8192u, BAD_MAP_SCAN_OFFSETS = 16384u, BAD_FREESPACE_PAIR = 32768u, BAD_PLACE_ID = 65536u,
                    BAD_CONSISTENCY_DEGREE = 131072u, BAD_CONSISTENCY_MEMBER = 262144u, BAD_MAPWIN_CELLS = 524288u,
-                   BAD_MAPWIN_POINTS = 1048576u, BAD_RANGESIG = 2097152u;
+                   BAD_MAPWIN_POINTS = 1048576u, BAD_RANGESIG = 2097152u, BAD_REFINE_ID = 4194304u;
 constexpr int DEV_STATUS_WORDS = 4;  // {OR of the kinds seen, kind / value / index of the first report}
 uint32_t *dev_status();              // of the current device (allocated on the device's first use; null if that failed)
 #ifdef __HIPCC__
@@ -473,6 +473,19 @@ struct FsParams {     // plain data: travels in the kernels' parameter blocks (t
 };
 int launch_fs_trace(const FsParams &P, hipStream_t s);
 int launch_fs_check(const FsParams &P, hipStream_t s);
+
+// match refinement (nhip_refine.hip, K22); the spec has passed refine_spec_check (nhip_host_refine.hip)
+struct RefineParams {  // plain data: travels in the kernel's parameter block
+  const float2 *xy, *normals;
+  const int32_t *offsets, *pair_src, *pair_tgt;
+  const double *pose0;   // 4 per pair
+  nhip_refined_t *out;
+  double *trace;         // NHIP_REFINE_TRACE_DOUBLES per pair, or null
+  int32_t n_scans, n_pairs;
+  uint32_t *status;
+  nhip_refine_spec_t spec;
+};
+int launch_refine_icp(const RefineParams &P, hipStream_t s);
 
 // place descriptors (nhip_place.hip, K16); the spec has passed place_spec_check (nhip_host_place.hip)
 constexpr int PLACE_MAX_RINGS = 32;        // of a descriptor

@@ -427,6 +427,7 @@ int nhip_dev_status(void *stream, int32_t info[4]) {
                      : w[1] == BAD_MAPWIN_CELLS ? "occupied-cell count beyond max_cells (nhip_mapwin_cells_dev; index = height) or row_ptr entry that is not a row (nhip_mapwin_gather_dev; index = the map row)"
                      : w[1] == BAD_MAPWIN_POINTS ? "window point count (nhip_mapwin_gather_dev: more than out_capacity; index = n_queries)"
                      : w[1] == BAD_RANGESIG ? "anchor count beyond max_anchors (nhip_rangesig_anchors_dev; index = max_anchors) or ray-table entry that is not a ray (nhip_rangesig_map_dev; index = the ray)"
+                     : w[1] == BAD_REFINE_ID ? "source or target scan id of a pair (nhip_refine_icp_dev: d_pair_src / d_pair_tgt; index = the pair)"
                                              : "id";
   set_error("an id read from device memory was out of range: %s = %d at index %d (kinds seen since the last check: 0x%x); "
             "the kernels treated every such entry as empty", what, (int32_t)w[2], (int32_t)w[3], w[0]);

@@ -1040,3 +1040,234 @@ def hitl_segments(msg):
     line_b_end, each (x, y[, z]) -> two LineSegment<float> as (x0, y0, x1, y1) float32 rows."""
     row = lambda a, b: [msg[a][0], msg[a][1], msg[b][0], msg[b][1]]
     return np.array([row("line_a_start", "line_a_end"), row("line_b_start", "line_b_end")], dtype=np.float32)
+
+
+# ---- match refinement (DESIGN.md section 3, "Match refinement"; the device form is nhip_refine_icp_dev, K22) ----
+REFINED_DTYPE = np.dtype([("c", "<f8"), ("s", "<f8"), ("tx", "<f8"), ("ty", "<f8"), ("info", "<f8", (6,)), ("cost", "<f8"),
+                          ("n_corr", "<i4"), ("iterations", "<i4"), ("flags", "<u4"), ("pad", "<u4")])
+REFINE_SKIPPED, REFINE_TARGET_TOO_LONG, REFINE_FEW, REFINE_SINGULAR, REFINE_RUNAWAY, REFINE_NOT_CONVERGED = 1, 2, 4, 8, 16, 32
+REFINE_FLAG_NAMES = {1: "SKIPPED", 2: "TARGET_TOO_LONG", 4: "FEW", 8: "SINGULAR", 16: "RUNAWAY", 32: "NOT_CONVERGED"}
+REFINE_THRESHOLDS, REFINE_TARGET_MAX = 16, 2048
+
+
+def refine_thresholds(thr0, shrink, thr_min):
+    """The spec's table: thr[k] = float32(max(thr_min, thr0 shrink^k)), the power by repeated products in double."""
+    out, v = np.zeros(REFINE_THRESHOLDS, np.float32), float(thr0)
+    for k in range(REFINE_THRESHOLDS):
+        out[k] = np.float32(v if v > float(thr_min) else float(thr_min))
+        v = v * float(shrink)
+    return out
+
+
+class RefineFields:
+    """The fields of nhip_refine_spec_t with nhip_refine_spec_default's values, for callers without the library."""
+
+    def __init__(self, **overrides):
+        self.thr0, self.shrink, self.thr_min = 0.25, 0.5, 0.05
+        self.step_tol_m = self.step_tol_rad = 1e-5
+        self.min_spread, self.max_shift_m, self.max_turn_sin = 0.02, 0.5, math.sin(5.0 * math.pi / 180.0)
+        self.max_iterations, self.min_corr, self.flags, self.reserved = 8, 30, 0, 0
+        for k, v in overrides.items():
+            if k != "thr" and not hasattr(self, k):
+                raise TypeError("RefineFields: no field %r" % k)
+            setattr(self, k, v)
+        if "thr" not in overrides:
+            self.thr = refine_thresholds(self.thr0, self.shrink, self.thr_min)
+
+
+def refine_spec_check(spec):
+    """The accepted ranges of nhip_refine_spec_t (include/nautilus_hip.h); ValueError otherwise."""
+    thr = np.asarray(list(spec.thr), dtype=np.float32)
+    n = int(spec.max_iterations)
+    if not 1 <= n <= REFINE_THRESHOLDS:
+        raise ValueError("refine: max_iterations %d outside 1..%d" % (n, REFINE_THRESHOLDS))
+    if int(spec.min_corr) < 3 or int(spec.flags) != 0 or int(spec.reserved) != 0:
+        raise ValueError("refine: min_corr below 3, or flags / reserved not 0")
+    if not (0 < thr[0] < 1e6) or not np.all((thr[:n] > 0) & (thr[:n] <= thr[0])):
+        raise ValueError("refine: thresholds outside (0, thr[0]]")
+    for f in ("step_tol_m", "step_tol_rad", "min_spread", "max_shift_m", "max_turn_sin"):
+        if not float(getattr(spec, f)) >= 0:
+            raise ValueError("refine: %s negative or NaN" % f)
+
+
+def refine_start_poses(records, theta0, grid_spec, search, pair_origin=None):
+    """nhip_refine_start_poses in Python: (n, 4) float64 (cos, sin, tx, ty) of the records' lattice poses, theta formed in
+    double and (cos, sin) from libm (math.cos / math.sin); four NaNs for a rejected record."""
+    n = len(records)
+    theta0 = np.asarray(theta0, dtype=np.float64).reshape(n)
+    org = np.zeros((n, 2), np.int64) if pair_origin is None else np.asarray(pair_origin, dtype=np.int64).reshape(n, 2)
+    out = np.full((n, 4), np.nan)
+    ht, hx, hy = (int(search.n_theta) - 1) // 2, (int(search.nx) - 1) // 2, (int(search.ny) - 1) // 2
+    step, res = float(search.theta_step), float(grid_spec.res)
+    for i in range(n):
+        it = int(records["itheta"][i])
+        if it < 0:
+            continue
+        theta = float(theta0[i]) + float(it - ht) * step
+        out[i] = (math.cos(theta), math.sin(theta), float(int(org[i, 0]) + int(records["ix"][i]) - hx) * res,
+                  float(int(org[i, 1]) + int(records["iy"][i]) - hy) * res)
+    return out
+
+
+def _refine_evaluate(src, src_ok, tgt, tgt_ok, tgn, pose, thr):
+    """One evaluation: the ten sums (H00 H01 H02 H11 H12 H22 g0 g1 g2 cost) and the count, in the rule's order."""
+    f = np.float32
+    c, s, tx, ty = pose
+    cf, sf, txf, tyf = f(c), f(s), f(tx), f(ty)
+    ns, nt = len(src), len(tgt)
+    rounds = (ns + 255) // 256
+    terms = np.zeros((rounds * 256, 10))
+    kept = np.zeros(rounds * 256, bool)
+    if ns and nt:
+        with np.errstate(all="ignore"):
+            px, py = src[:, 0], src[:, 1]
+            qx = ((cf * px).astype(f) + ((-sf) * py).astype(f)).astype(f) + txf
+            qy = ((sf * px).astype(f) + (cf * py).astype(f)).astype(f) + tyf
+            dx, dy = tgt[None, :, 0] - qx[:, None], tgt[None, :, 1] - qy[:, None]
+            d2 = dx * dx + dy * dy
+            d2[:, ~tgt_ok] = np.inf
+            d2[np.isnan(d2)] = np.inf
+            idx = np.argmin(d2, axis=1)  # (the first minimum: ties to the lowest index)
+            best = d2[np.arange(ns), idx]
+            g, gn = tgt[idx], tgn[idx]
+            keep = src_ok & (best < f(3.0e38)) & (np.sqrt(best) < f(thr)) & np.isfinite(gn).all(axis=1)
+            nx, ny = gn[:, 0].astype(np.float64), gn[:, 1].astype(np.float64)
+            dpx, dpy = px.astype(np.float64), py.astype(np.float64)
+            ex, ey = qx.astype(np.float64) - g[:, 0].astype(np.float64), qy.astype(np.float64) - g[:, 1].astype(np.float64)
+            r = nx * ex + ny * ey
+            a, b = -(s * dpx) - c * dpy, c * dpx - s * dpy
+            jt = nx * a + ny * b
+            t = np.stack([nx * nx, nx * ny, nx * jt, ny * ny, ny * jt, jt * jt, nx * r, ny * r, jt * r, r * r], axis=1)
+        terms[:ns] = np.where(keep[:, None], t, 0.0)  # (adding +0.0 leaves a lane's sum as it is, bit for bit)
+        kept[:ns] = keep
+    acc = np.zeros((256, 10))
+    with np.errstate(all="ignore"):
+        for k in range(rounds):  # point i belongs to lane i mod 256; a lane adds its points in ascending i
+            acc = acc + terms[256 * k:256 * (k + 1)]
+        while len(acc) > 1:  # adjacent-pair halving, eight levels
+            acc = acc[0::2] + acc[1::2]
+    return [float(v) for v in acc[0]], int(kept.sum())
+
+
+def refine_icp(xy, normals, offsets, pair_src, pair_tgt, pose0, spec=None):
+    """The match refinement in vectorised numpy on the host, equal to the device's bit for bit ("Match
+    refinement"): (refined REFINED_DTYPE (n,), trace float64 (n, 16, 4)) from the start poses pose0 (n, 4) = (cos, sin, tx,
+    ty).  Scan ids outside the scans raise ValueError."""
+    f = np.float32
+    spec = RefineFields() if spec is None else spec
+    refine_spec_check(spec)
+    xy, normals = np.asarray(xy, dtype=f).reshape(-1, 2), np.asarray(normals, dtype=f).reshape(-1, 2)
+    off = np.asarray(offsets, dtype=np.int64)
+    pair_src, pair_tgt = np.asarray(pair_src, dtype=np.int64).reshape(-1), np.asarray(pair_tgt, dtype=np.int64).reshape(-1)
+    n = len(pair_src)
+    pose0 = np.asarray(pose0, dtype=np.float64).reshape(n, 4)
+    n_scans = len(off) - 1
+    if n and (min(pair_src.min(), pair_tgt.min()) < 0 or max(pair_src.max(), pair_tgt.max()) >= n_scans):
+        raise ValueError("refine_icp: a pair names a scan outside the %d scans" % n_scans)
+    thr = np.asarray(list(spec.thr), dtype=f)
+    max_it, min_corr = int(spec.max_iterations), int(spec.min_corr)
+    tol_m, tol_rad = float(spec.step_tol_m), float(spec.step_tol_rad)
+    min_spread, max_shift, max_turn = float(spec.min_spread), float(spec.max_shift_m), float(spec.max_turn_sin)
+    out, trace = np.zeros(n, REFINED_DTYPE), np.zeros((n, REFINE_THRESHOLDS, 4))
+    limit = f(1.0e6)
+    with np.errstate(invalid="ignore"):
+        ok_all = (np.abs(xy[:, 0]) < limit) & (np.abs(xy[:, 1]) < limit)
+    for i in range(n):
+        c0, s0, tx0, ty0 = (float(v) for v in pose0[i])
+        rec = out[i]
+        rec["c"], rec["s"], rec["tx"], rec["ty"] = c0, s0, tx0, ty0
+        if not all(math.isfinite(v) for v in (c0, s0, tx0, ty0)):
+            rec["c"] = rec["s"] = rec["tx"] = rec["ty"] = np.nan
+            rec["flags"] = REFINE_SKIPPED
+            continue
+        sa, sb, ta, tb = off[pair_src[i]], off[pair_src[i] + 1], off[pair_tgt[i]], off[pair_tgt[i] + 1]
+        if tb - ta > REFINE_TARGET_MAX:
+            rec["flags"] = REFINE_TARGET_TOO_LONG
+            continue
+        data = (xy[sa:sb], ok_all[sa:sb], xy[ta:tb], ok_all[ta:tb], normals[ta:tb])
+        c, s, tx, ty = c0, s0, tx0, ty0
+        flags, it, converged = 0, 0, False
+        while it < max_it:
+            v, cnt = _refine_evaluate(*data, (c, s, tx, ty), thr[it])
+            if cnt < min_corr:
+                flags = REFINE_FEW
+                break
+            with np.errstate(all="ignore"):
+                d = _refine_solve(v, cnt, min_spread)
+            if d is None:
+                flags = REFINE_SINGULAR
+                break
+            dx, dy, dth = d
+            tx, ty = tx + dx, ty + dy
+            hu = dth * 0.5
+            u2 = hu * hu
+            den = 1.0 + u2
+            cd, sd = (1.0 - u2) / den, (2.0 * hu) / den
+            c, s = c * cd - s * sd, s * cd + c * sd
+            mx, my = tx - tx0, ty - ty0
+            if not (math.sqrt(mx * mx + my * my) <= max_shift) or not (abs(s * c0 - c * s0) <= max_turn):
+                flags = REFINE_RUNAWAY
+                break
+            trace[i, it] = (c, s, tx, ty)
+            it += 1
+            if math.sqrt(dx * dx + dy * dy) < tol_m and abs(dth) < tol_rad:
+                converged = True
+                break
+        if flags == 0:
+            flags = 0 if converged else REFINE_NOT_CONVERGED
+            v, cnt = _refine_evaluate(*data, (c, s, tx, ty), thr[max_it - 1])
+            if cnt < min_corr:
+                flags = REFINE_FEW
+            else:
+                rec["c"], rec["s"], rec["tx"], rec["ty"] = c, s, tx, ty
+                rec["info"], rec["cost"], rec["n_corr"] = v[:6], v[9], cnt
+        rec["iterations"], rec["flags"] = it, flags
+    return out, trace
+
+
+def _refine_solve(v, cnt, min_spread):
+    """H delta = -g by the square-root-free Cholesky of the rule, in Python floats (IEEE double): (dx, dy, dtheta), or None
+    for SINGULAR."""
+    H00, H01, H02, H11, H12, H22, g0, g1, g2 = (np.float64(x) for x in v[:9])  # (numpy scalars: a division by zero is inf / nan)
+    hm, hd = (H00 + H11) * 0.5, (H00 - H11) * 0.5
+    lam = hm - np.sqrt(hd * hd + H01 * H01)
+    d0 = H00
+    l10, l20 = H01 / d0, H02 / d0
+    d1 = H11 - l10 * H01
+    u = H12 - l20 * H01
+    l21 = u / d1
+    d2 = (H22 - l20 * H02) - l21 * u
+    if not (lam / np.float64(cnt) >= min_spread) or not (d0 > 0.0) or not (d1 > 0.0) or not (d2 > 0.0):
+        return None
+    y0 = -g0
+    y1 = -g1 - l10 * y0
+    y2 = (-g2 - l20 * y0) - l21 * y1
+    dth = y2 / d2
+    dy = y1 / d1 - l21 * dth
+    dx = (y0 / d0 - l10 * dy) - l20 * dth
+    return float(dx), float(dy), float(dth)
+
+
+def refine_matches(xy, normals, offsets, pair_src, pair_tgt, theta0, records, grid_spec, search, spec=None, pair_origin=None):
+    """The match records refined on the host: refine_start_poses, then refine_icp; the refined array (REFINED_DTYPE).  What
+    HipBackend.refine_matches returns, bit for bit; for a backend without that method (examples/slam_loop.py --lc-refine icp)."""
+    pose0 = refine_start_poses(records, theta0, grid_spec, search, pair_origin)
+    return refine_icp(xy, normals, offsets, pair_src, pair_tgt, pose0, spec)[0]
+
+
+def refine_keeps_pose(refined):
+    """Which refined records carry a refined pose: no flag, or NOT_CONVERGED alone (any other flag returned the start pose)."""
+    return (np.asarray(refined)["flags"] & ~np.uint32(REFINE_NOT_CONVERGED)) == 0
+
+
+def refine_flag_counts(refined):
+    """{flag name: refined records that carry it}."""
+    fl = np.asarray(refined)["flags"]
+    return {name: int(((fl & bit) != 0).sum()) for bit, name in sorted(REFINE_FLAG_NAMES.items())}
+
+
+def refined_to_transform(refined):
+    """(n, 3) float64 (tx, ty, theta = atan2(s, c)) of refined records."""
+    r = np.asarray(refined, dtype=REFINED_DTYPE).reshape(-1)
+    theta = np.array([math.atan2(s, c) for s, c in zip(r["s"], r["c"])], dtype=np.float64)  # (libm's, as the C helper's)
+    return np.stack([r["tx"], r["ty"], theta], axis=1)

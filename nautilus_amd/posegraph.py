@@ -300,6 +300,31 @@ class HipBackend:
         from . import consistency
         return consistency.consistent_set(consistency.prepare(poses, src, tgt, rel), spec)
 
+    def refine_matches(self, xy, normals, offsets, pair_src, pair_tgt, theta0, records, grid_spec, search, spec=None, pair_origin=None):
+        """The match records refined on the GPU from their lattice poses by point-to-line ICP against the target scans
+        (refine.py: nhip_refine_start_poses, nhip_refine_icp_dev; DESIGN.md section 3, "Match refinement"): the refined array
+        (hostside.REFINED_DTYPE), equal to hostside.refine_matches' bit for bit.  pair_tgt are scan ids."""
+        from . import refine
+        torch = self.torch
+        pair_src = np.ascontiguousarray(pair_src, dtype=np.int32).reshape(-1)
+        pair_tgt = np.ascontiguousarray(pair_tgt, dtype=np.int32).reshape(-1)
+        off = np.ascontiguousarray(offsets, dtype=np.int32)
+        n, n_scans = len(pair_src), len(off) - 1
+        if len(pair_tgt) != n or (n and (min(pair_src.min(), pair_tgt.min()) < 0 or max(pair_src.max(), pair_tgt.max()) >= n_scans)):
+            raise ValueError("refine_matches: pair arrays differ in length or name a scan outside the %d scans" % n_scans)
+        pose0 = refine.start_poses(records, theta0, grid_spec, search, pair_origin)
+        if n == 0:
+            return np.zeros(0, dtype=refine.REFINED_DTYPE)
+        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.dev)
+        d_xy, d_nrm = t(np.asarray(xy).reshape(-1, 2), np.float32), t(np.asarray(normals).reshape(-1, 2), np.float32)
+        if d_xy.shape != d_nrm.shape or d_xy.shape[0] != int(off[-1]):
+            raise ValueError("refine_matches: xy, normals and offsets disagree")
+        d_out = refine.icp_on_device(d_xy, d_nrm, t(off, np.int32), n_scans, t(pair_src, np.int32), t(pair_tgt, np.int32),
+                                     t(pose0, np.float64), n, spec)
+        out = refine.records_from(d_out)
+        check(self.lib.nhip_dev_status(C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream), None))
+        return out
+
     def pair_gate(self, poses, candidates, max_range, min_separation):
         P = np.ascontiguousarray(poses, dtype=np.float64)
         cand = np.ascontiguousarray(candidates, dtype=np.int32)
