@@ -64,12 +64,13 @@ def test_selection_is_bit_exact(backend, name):
     assert not con.chosen_line_pose.any() and _status()[0] == _lib.NHIP_OK
 
 
-def _select_raw(name, n_scans=None, pad=64):
+def _select_raw(name, n_scans=None, pad=64, table=None):
     """nhip_hitl_select_dev on the scans: host copies of (class bytes, counts, scan_block, scan_offset, totals), each with
-    `pad` sentinel entries behind it, and the device tensors."""
+    `pad` sentinel entries behind it, and the device tensors.  table: a scan table other than hitl_reference's (xy, offsets,
+    poses, scans), with name = its (line a, line b, width, threshold)."""
     import torch
-    s = HR.scans()
-    la, lb, w, thr = HR.CONFIGS[name]
+    s = HR.scans() if table is None else table
+    la, lb, w, thr = HR.CONFIGS[name] if table is None else name
     n = len(s.scans) if n_scans is None else n_scans
     n_pts = int(s.offsets[n])
     d_xy, d_off, d_aff = _dev(s.xy), _dev(s.offsets), _dev(hitl.pose_floats(s.poses))
