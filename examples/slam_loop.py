@@ -58,7 +58,8 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         min_scatter_score=0.70, csm_score_threshold=-5.0, spacing=0.25, hitl_device=False, normals="bag", lc_submap=0,
         linear_solver="host", lc_gate="geometric", lc_max_score=5000.0, map_output=None, grid_output=None, lc_verify=None,
         lc_max_violation=None, lc_top_k=5, lc_consistency=False, lc_min_set=3, _lc_corrupt=None, lc_sequence=0, lc_sequence_step=1,
-        lc_loss=None, lc_loss_scale=1.0, movers=0, drop_transients=False, lc_refine=None):
+        lc_loss=None, lc_loss_scale=1.0, movers=0, drop_transients=False, lc_refine=None, lc_factor=None,
+        lc_info_sigma_m=1.0):
     """min_scatter_score: LCCandidateFilter's threshold is 0.70 (lc_candidate_filter.cc:76); scans of the synthetic
     24 m x 16 m room score ~0.4, so callers on that world pass a lower one.
     hitl_device: the HITL constraint's points are selected and packed on the GPU (hitl.select, under the "path" clock) and
@@ -126,6 +127,14 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
     clouds without their transient returns are what the loop-closure tables, map_output and grid_output are made from.  The
     result reports transient_stats (transient.STATS_FIELDS), transient_s and, with movers, the shares of the walkers' and of the
     other returns that were flagged.  Not with world > 1.  Both are off by default and change nothing then.
+    lc_factor: None (or "world") -- every accepted record becomes the odometry-style factor, frozen in the world frame at the target's
+    current heading, at the scalar weights (10, 10) -- or "relative": a relative-pose factor ("Relative-pose
+    factors"; PoseGraph.add_loop_closures(information=...)), which measures the source in the target's frame at every evaluation
+    and carries its own information: with lc_refine "icp" the Gauss-Newton H of the record's refinement over lc_info_sigma_m^2
+    (metres; 1.0 puts a closure on the footing of the ICP blocks), for a record that kept its lattice pose and without lc_refine
+    diag(10^2, 10^2, 10^2).  The result then also reports lc_factor, lc_info_from_icp (accepted records that took their H),
+    lc_info_sigma_m and lc_info_eig_min / lc_info_eig_max over those records' informations (None without any).  An lc_loss' scale
+    is then in standard deviations.  Works with world > 1 (the solve is replicated), both linear solvers and any backend.
     _lc_corrupt: TEST ONLY -- a callable (src, tgt, rel, good) -> rel that replaces the records' transforms before the consistency
     filter and the constraints (tests/test_consistency_loop_gpu.py displaces accepted records with it).
     With world > 1 (one process per GPU under torch.distributed): the window ICP solve is replicated -- its
@@ -183,6 +192,10 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         raise ValueError("run: lc_min_set %r must be >= 0" % (lc_min_set,))
     if lc_max_violation is not None and not 0 <= int(lc_max_violation) <= 1000:
         raise ValueError("run: lc_max_violation %r: permille, 0..1000" % (lc_max_violation,))
+    if lc_factor not in (None, "world", "relative"):
+        raise ValueError("run: lc_factor %r (None, \"world\" or \"relative\")" % (lc_factor,))
+    if lc_factor == "relative" and not (math.isfinite(float(lc_info_sigma_m)) and float(lc_info_sigma_m) > 0.0):
+        raise ValueError("run: lc_info_sigma_m %r must be finite and > 0" % (lc_info_sigma_m,))
     loss = None
     if lc_loss not in (None, "none"):
         from nautilus_amd.loss import Loss
@@ -369,6 +382,7 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         # (csm_score_threshold = -5.0, config/default_config.lua:84-85); optima on the lattice border are open-ended
         good = inside & (m["score"] > csm_score_threshold)
         truth_rel = np.array([bag.true_relative(s, t) for s, t in zip(src, tgt)])
+        refined_of = None  # with lc_refine: (the records' indices, their refined records)
         if lc_refine:
             # the records that passed the score gate go from their lattice pose to the sub-cell pose of point-to-line ICP against
             # the target SCAN (also where the table was a submap, which has no normals; the scans as ingested, with their normals)
@@ -385,6 +399,7 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
             rel[idx[used]] = hostside.refined_to_transform(refined[used])
             out["lc_refined"], out["refine_s"] = int(used.sum()), time.perf_counter() - t1
             out["lc_refine_flags"] = hostside.refine_flag_counts(refined)
+            refined_of = (idx, refined)
         rms = lambda sel: float(np.sqrt(np.mean(np.sum((rel[sel, :2] - truth_rel[sel, :2]) ** 2, axis=1)))) if sel.any() else None
         if lc_verify:
             from nautilus_amd import freespace
@@ -417,9 +432,28 @@ def run(n_scans=320, window=10, seed=20201114, drift_t=0.02, drift_th_deg=0.3, v
         out["lc_accepted"] = int(good.sum())
         out["lc_rel_err_m"] = rms(good)
         lc = (src[good], tgt[good], rel[good])
+        if lc_factor == "relative":
+            # every record's information and heading (cos, sin): the refinement's H and (c, s) where a record carries a refined
+            # pose, the closures' weights and libm's cos / sin of the lattice heading where not
+            with posegraph.clocked("marshal"):
+                info, took = hostside.relpose_information(None, n=len(src), weights=(10.0, 10.0))
+                cs = np.array([(math.cos(t), math.sin(t)) for t in rel[:, 2]], dtype=np.float64).reshape(-1, 2)
+                if refined_of is not None:
+                    info[refined_of[0]], took[refined_of[0]] = hostside.relpose_information(
+                        refined_of[1], sigma_m=float(lc_info_sigma_m), weights=(10.0, 10.0))
+                    mine = refined_of[0][took[refined_of[0]]]
+                    cs[mine] = np.stack([refined_of[1]["c"], refined_of[1]["s"]], axis=1)[took[refined_of[0]]]
+                lc += ({"information": info[good], "rel_cs": cs[good]},)
+            eig = np.array([np.linalg.eigvalsh(np.array([[L[0], L[1], L[2]], [L[1], L[3], L[4]], [L[2], L[4], L[5]]]))
+                            for L in info[good & took]]).reshape(-1, 3)
+            out["lc_factor"], out["lc_info_from_icp"], out["lc_info_sigma_m"] = "relative", int((good & took).sum()), float(lc_info_sigma_m)
+            out["lc_info_eig_min"] = float(eig.min()) if eig.size else None
+            out["lc_info_eig_max"] = float(eig.max()) if eig.size else None
+        elif lc_factor == "world":
+            out["lc_factor"] = "world"
         t0 = time.perf_counter()
         with posegraph.clocked("marshal"):
-            pg.add_loop_closures(*lc, loss=loss)
+            pg.add_loop_closures(*lc[:3], loss=loss, **(lc[3] if len(lc) > 3 else {}))
         poses, _ = pg.solve(iterations=2 * iterations, verbose=verbose, linear_solver=linear_solver)
         out["t_lc_solve_s"] = time.perf_counter() - t0
         pcg_phase("lc")
@@ -568,6 +602,11 @@ if __name__ == "__main__":
     ap.add_argument("--lc-loss-scale", type=float, default=1.0, metavar="A",
                     help="with --lc-loss: the loss' scale in units of the weighted residual (at the closures' weight 10, 1.0 is "
                          "0.1 m or 0.1 rad, two cells of the matcher's lattice)")
+    ap.add_argument("--lc-factor", choices=["world", "relative"], default="world",
+                    help="the loop-closure factor: frozen in the world frame at scalar weights, or relative-pose factors that measure "
+                         "the source in the target's frame and carry each match's information (with --lc-refine icp: the refinement's)")
+    ap.add_argument("--lc-info-sigma", type=float, default=1.0, metavar="M",
+                    help="with --lc-factor relative and --lc-refine icp: the range noise the refinement's H is divided by, squared [m]")
     ap.add_argument("--map-output", metavar="PATH", default=None,
                     help="vectorise the final poses' map on the GPU and write it there, one 'x1,y1,x2,y2' line per wall segment")
     ap.add_argument("--grid-output", metavar="STEM", default=None,
@@ -613,7 +652,8 @@ if __name__ == "__main__":
               grid_output=a.grid_output, lc_verify=a.lc_verify, lc_max_violation=a.lc_max_violation, lc_top_k=a.lc_top_k,
               lc_consistency=a.lc_consistency, lc_min_set=a.lc_min_set, lc_sequence=seq_w, lc_sequence_step=seq_step,
               lc_loss=None if a.lc_loss == "none" else a.lc_loss, lc_loss_scale=a.lc_loss_scale, movers=a.movers,
-              drop_transients=a.drop_transients, lc_refine=a.lc_refine)
+              drop_transients=a.drop_transients, lc_refine=a.lc_refine, lc_factor=None if a.lc_factor == "world" else a.lc_factor,
+              lc_info_sigma_m=a.lc_info_sigma)
     res["world_size"] = world
     if rank == 0 and "transient_stats" in res:
         s = res["transient_stats"]

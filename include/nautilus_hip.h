@@ -471,6 +471,54 @@ int nhip_resid_odometry_robust_normal_eq_dev(const float *d_t_odom, const float 
                                              double rotation_weight, const nhip_loss_spec_t *loss, const double *d_poses,
                                              int32_t n_poses, double *d_out, double *d_weights, void *stream);
 
+/* ------------------------------------------------------------------ K23: relative-pose factors
+ * A factor that measures one pose IN THE FRAME OF ANOTHER, with the measurement's own information (DESIGN.md section 3,
+ * "Relative-pose factors"; kernel nhip_relpose.hip).  Factor f couples a = d_pose_i[f] (a loop closure's target scan) and
+ * b = d_pose_j[f] (its source): d_z[4f ..] = (z_x, z_y, c_z, s_z), pose b in a's frame with the heading as cosine and sine --
+ * a refined record's (tx, ty, c, s); d_info[6f ..] = L00 L01 L02 L11 L12 L22, the information over (x, y, theta) --
+ * nhip_refined_t.info's layout.  All in double, every product and sum rounded on its own, sums in the order written:
+ *   d   = R(theta_a)^T (t_b - t_a):  d_x = c_a D_x + s_a D_y,  d_y = (-s_a) D_x + c_a D_y
+ *   e   = (d_x - z_x, d_y - z_y, atan2(s_e, c_e)),  c_r = c_a c_b + s_a s_b,  s_r = c_a s_b - s_a c_b,
+ *         c_e = c_r c_z + s_r s_z,  s_e = s_r c_z - c_r s_z
+ *   E   = d e / d [a | b]: (-c_a, -s_a, d_y, c_a, s_a, 0), (s_a, -c_a, -d_x, -s_a, c_a, 0), (0, 0, -1, 0, 0, 1)
+ *   W   upper triangular with W^T W = Lambda, from the square-root-free Cholesky of K22's solve: D0 = L00, l10 = L01 / D0,
+ *       l20 = L02 / D0, D1 = L11 - l10 L01, u = L12 - l20 L01, l21 = u / D1, D2 = (L22 - l20 L02) - l21 u, q_k = sqrt(D_k):
+ *       W00 = q0, W01 = q0 l10, W02 = q0 l20, W11 = q1, W12 = q1 l21, W22 = q2
+ *   r_k = sum_{m >= k} W_km e_m,  J_kp = sum_{m >= k} W_km E_mp  (ascending m, every term formed)
+ * nhip_resid_relpose_dev writes r (3 per factor) and, unless NULL, J_i and J_j (3 x 3 row-major each: the halves of J),
+ * d_parts (8 per factor: c_a, s_a, c_b, s_b, e_x, e_y, e_theta, 0) and d_flags (one int32 per factor).  A flagged factor is
+ * all zeros:  NHIP_RELPOSE_BAD_INFO an entry of Lambda is not finite or a pivot D_k is not > 0;  NHIP_RELPOSE_BAD_MEASUREMENT
+ * an entry of z is not finite;  NHIP_RELPOSE_SAME_POSE pose_i == pose_j (a row of the block-sparse system couples two
+ * different blocks).  A pose id outside [0, n_poses) is never dereferenced: zeros, and nhip_dev_status() reports it (kind 16).
+ *
+ * nhip_resid_relpose_normal_eq_dev writes the factors' 28-double rows under a loss (NULL: NONE), exactly as
+ * nhip_resid_odometry_robust_normal_eq_dev forms them from its r and J: s = r0 r0 + r1 r1 + r2 r2 -- here a squared
+ * Mahalanobis distance, so the loss' scale is in standard deviations --, w = sqrt(rho'(s)), r~ = w r, J~ = w J, the upper
+ * triangle of J~^T J~, J~^T r~, and rho(s) in slot 27; d_weights, unless NULL, {s, rho, rho', w} per factor; d_flags, unless
+ * NULL, the flags.  One kernel, nothing allocated; n_factors == 0 launches nothing.  The same input gives the same bits.
+ * NHIP_ERR_ARG before anything is launched, with or without a device: a bad loss spec, a negative size, a null pointer other
+ * than those named optional above.
+ *
+ * nhip_relpose_information (pure host) makes the information of n refined records: Lambda = H (1 / sigma_m^2) -- one rounded
+ * reciprocal of one rounded product, six products -- for a record that carries a refined pose (no flag but
+ * NHIP_REFINE_NOT_CONVERGED); diag(wt wt, wt wt, wr wr) for any other, which kept its lattice pose.  from_icp[k], unless NULL,
+ * is 1 for the former.  refined may be NULL: every record gets the diagonal.  A negative n, a null info, a sigma_m that is not
+ * finite or is <= 0, a wt or wr that is not finite: NHIP_ERR_ARG.  (Declared behind nhip_refined_t, below.) */
+/* CAUCHY under these rows: rho = b log1p_pinned(s / b), log1p for x >= 0 written out in IEEE operations (fdlibm's s_log1p.c, error
+ * below 1 ulp), so that the device, this library's host compilation and nautilus_amd/loss.py's numpy form return the same doubles;
+ * nhip_resid_odometry_robust_normal_eq_dev keeps the device library's log1p.  nhip_loss_log1p_pinned (pure host) evaluates it
+ * on n doubles. */
+int nhip_loss_log1p_pinned(const double *x, int64_t n, double *out);
+#define NHIP_RELPOSE_BAD_INFO 1
+#define NHIP_RELPOSE_BAD_MEASUREMENT 2
+#define NHIP_RELPOSE_SAME_POSE 4
+int nhip_resid_relpose_dev(const double *d_z, const double *d_info, const int32_t *d_pose_i, const int32_t *d_pose_j,
+                           int32_t n_factors, const double *d_poses, int32_t n_poses, double *d_residuals, double *d_jac_i,
+                           double *d_jac_j, double *d_parts, int32_t *d_flags, void *stream);
+int nhip_resid_relpose_normal_eq_dev(const double *d_z, const double *d_info, const int32_t *d_pose_i, const int32_t *d_pose_j,
+                                     int32_t n_factors, const nhip_loss_spec_t *loss, const double *d_poses, int32_t n_poses,
+                                     double *d_out, double *d_weights, int32_t *d_flags, void *stream);
+
 /* ------------------------------------------------------------------ K11: the pose graph's linear system on the device
  * The Gauss-Newton system of a pose graph as a block-sparse matrix of 3 x 3 blocks in fp64 (DESIGN.md section 3,
  * "Block-sparse system").  n_blocks unknown blocks of 3; the sources are 28-double rows (every *_normal_eq_dev call writes
@@ -1329,6 +1377,9 @@ int nhip_refine_icp(const float *xy, const float *normals, const int32_t *offset
                     nhip_refined_t *out, double *trace);
 /* Pure host: (tx, ty, theta = atan2(s, c)) of a refined record. */
 int nhip_refined_to_transform(const nhip_refined_t *r, double *tx, double *ty, double *theta);
+/* Pure host: the information of relative-pose factors made from refined records (K23, above). */
+int nhip_relpose_information(const nhip_refined_t *refined, int32_t n, double sigma_m, double wt, double wr, double *info,
+                             uint8_t *from_icp);
 
 /* ------------------------------------------------------------------ handle API (host pointers) */
 typedef struct nhip_scans nhip_scans_t;
@@ -1528,6 +1579,11 @@ int nhip_resid_odometry(const float *t_odom, const float *r_odom, const int32_t 
                         const int32_t *pose_j, int32_t n_factors, double translation_weight,
                         double rotation_weight, const double *poses, int32_t n_poses,
                         double *residuals, double *jac_i, double *jac_j);
+/* nhip_resid_relpose_dev on host arrays (poses: n_poses x 3 doubles): pose ids are checked on the host (NHIP_ERR_ARG);
+ * jac_i, jac_j, parts and flags may be NULL. */
+int nhip_resid_relpose(const double *z, const double *info, const int32_t *pose_i, const int32_t *pose_j, int32_t n_factors,
+                       const double *poses, int32_t n_poses, double *residuals, double *jac_i, double *jac_j, double *parts,
+                       int32_t *flags);
 int nhip_resid_point_to_line(const float *segments, const float *points, const int32_t *point_block,
                              int64_t n_points, const int32_t *block_pose, const int32_t *block_line,
                              int32_t n_blocks, const double *poses, int32_t n_poses,

@@ -29,6 +29,7 @@ NHIP_RANGESIG_WORKSPACE_MAX = 64 << 20
 NHIP_RANGESIG_UNKNOWN_STOPS = 1
 NHIP_CONSISTENCY_STATE_BYTES = 8448
 NHIP_LOSS_NONE, NHIP_LOSS_HUBER, NHIP_LOSS_SOFT_L1, NHIP_LOSS_CAUCHY = 0, 1, 2, 3
+NHIP_RELPOSE_BAD_INFO, NHIP_RELPOSE_BAD_MEASUREMENT, NHIP_RELPOSE_SAME_POSE = 1, 2, 4
 
 
 class NhipError(RuntimeError):
@@ -224,6 +225,11 @@ PROTOTYPES = {
     "nhip_resid_odometry_normal_eq_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f64, _f64, _vp, _i32, _vp, _vp]),
     "nhip_resid_odometry_robust_normal_eq_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f64, _f64, _P(LossSpec), _vp, _i32, _vp, _vp,
                                                            _vp]),
+    "nhip_resid_relpose_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nhip_resid_relpose_normal_eq_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _P(LossSpec), _vp, _i32, _vp, _vp, _vp, _vp]),
+    "nhip_resid_relpose": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "nhip_loss_log1p_pinned": (C.c_int, [_vp, _i64, _vp]),
+    "nhip_relpose_information": (C.c_int, [_vp, _i32, _f64, _f64, _f64, _vp, _vp]),
     "nhip_bsr_assemble_dev": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "nhip_bsr_pcg_workspace_bytes": (_i64, [_i32, _i32]),
     "nhip_bsr_pcg_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _f64, _f64, _i32, _i32, _vp, _vp, _i64,

@@ -593,6 +593,17 @@ int launch_resid_odometry_robust_normal_eq(const float *d_t_odom, const float *d
                                            double scale, const double *d_poses, int32_t n_poses, double *d_out,
                                            double *d_weights, hipStream_t s);
 
+// relative-pose factors (nhip_relpose.hip, K23): r, J_i, J_j and -- unless null -- the 8 parts and the flags per factor; and
+// their rows under a loss.  The arguments have passed relpose_args_check (nhip_layout.hip), which needs no HIP
+int relpose_args_check(const void *z, const void *info, const void *pose_i, const void *pose_j, int32_t n_factors,
+                       const void *poses, int32_t n_poses, const void *out, const char *who);
+int launch_resid_relpose(const double *d_z, const double *d_info, const int32_t *d_pose_i, const int32_t *d_pose_j,
+                         int32_t n_factors, const double *d_poses, int32_t n_poses, double *d_residuals, double *d_jac_i,
+                         double *d_jac_j, double *d_parts, int32_t *d_flags, hipStream_t s);
+int launch_resid_relpose_normal_eq(const double *d_z, const double *d_info, const int32_t *d_pose_i, const int32_t *d_pose_j,
+                                   int32_t n_factors, int32_t kind, double scale, const double *d_poses, int32_t n_poses,
+                                   double *d_out, double *d_weights, int32_t *d_flags, hipStream_t s);
+
 // the block-sparse linear system of the pose graph (nhip_linsolve.hip, K11): assembly from 28-double rows, and the
 // block-Jacobi preconditioned CG; the arguments have passed the checks of nhip_host_linsolve.hip
 struct PcgStats {  // what the PCG kernels keep in the workspace's first bytes; the host reads it between batches and at the end

@@ -180,6 +180,32 @@ int nhip_resid_odometry_robust_normal_eq_dev(const float *d_t_odom, const float 
                                                 static_cast<hipStream_t>(stream));
 }
 
+int nhip_resid_relpose_dev(const double *d_z, const double *d_info, const int32_t *d_pose_i, const int32_t *d_pose_j,
+                           int32_t n_factors, const double *d_poses, int32_t n_poses, double *d_residuals, double *d_jac_i,
+                           double *d_jac_j, double *d_parts, int32_t *d_flags, void *stream) {
+  // (the sizes and the pointers are an argument error with or without a device)
+  int rc = relpose_args_check(d_z, d_info, d_pose_i, d_pose_j, n_factors, d_poses, n_poses, d_residuals, "resid_relpose_dev");
+  if (rc) return rc;
+  if ((rc = require_device())) return rc;
+  return launch_resid_relpose(d_z, d_info, d_pose_i, d_pose_j, n_factors, d_poses, n_poses, d_residuals, d_jac_i, d_jac_j,
+                              d_parts, d_flags, static_cast<hipStream_t>(stream));
+}
+
+int nhip_resid_relpose_normal_eq_dev(const double *d_z, const double *d_info, const int32_t *d_pose_i, const int32_t *d_pose_j,
+                                     int32_t n_factors, const nhip_loss_spec_t *loss, const double *d_poses, int32_t n_poses,
+                                     double *d_out, double *d_weights, int32_t *d_flags, void *stream) {
+  // (the spec, the sizes and the pointers are an argument error with or without a device)
+  const nhip_loss_spec_t none = {NHIP_LOSS_NONE, 0, 1.0};
+  if (!loss) loss = &none;
+  int rc = loss_spec_check(loss, "resid_relpose_normal_eq_dev");
+  if (rc) return rc;
+  if ((rc = relpose_args_check(d_z, d_info, d_pose_i, d_pose_j, n_factors, d_poses, n_poses, d_out, "resid_relpose_normal_eq_dev")))
+    return rc;
+  if ((rc = require_device())) return rc;
+  return launch_resid_relpose_normal_eq(d_z, d_info, d_pose_i, d_pose_j, n_factors, loss->kind, loss->scale, d_poses, n_poses,
+                                        d_out, d_weights, d_flags, static_cast<hipStream_t>(stream));
+}
+
 // ---------------------------------------------------------------- HITL point selection
 // the accepted ranges of include/nautilus_hip.h
 static int hitl_spec_check(const nhip_hitl_spec_t *s, const char *who) {
@@ -526,6 +552,34 @@ int nhip_resid_odometry(const float *t_odom, const float *r_odom, const int32_t 
   st.fetch(residuals, res, 3 * N);
   st.fetch(jac_i, ji, 9 * N);
   st.fetch(jac_j, jj, 9 * N);
+  return st.finish();
+}
+
+int nhip_resid_relpose(const double *z, const double *info, const int32_t *pose_i, const int32_t *pose_j, int32_t n,
+                       const double *poses, int32_t n_poses, double *residuals, double *jac_i, double *jac_j, double *parts,
+                       int32_t *flags) {
+  int rc = relpose_args_check(z, info, pose_i, pose_j, n, poses, n_poses, residuals, "resid_relpose");
+  if (rc) return rc;
+  for (int32_t f = 0; f < n; f++)
+    NHIP_REQUIRE(pose_i[f] >= 0 && pose_i[f] < n_poses && pose_j[f] >= 0 && pose_j[f] < n_poses,
+                 "resid_relpose: factor %d pose index out of range", f);
+  if ((rc = require_device())) return rc;
+  if (n == 0) return NHIP_OK;
+  const size_t N = (size_t)n;
+  Staged st;
+  const double *dz = st.in(z, 4 * N), *dl = st.in(info, 6 * N);
+  const int32_t *di = st.in(pose_i, N), *dj = st.in(pose_j, N);
+  const double *dp = st.in(poses, 3 * (size_t)n_poses);
+  double *res = st.out<double>(3 * N), *ji = st.out<double>(9 * N), *jj = st.out<double>(9 * N), *pt = st.out<double>(8 * N);
+  int32_t *fl = st.out<int32_t>(N);
+  if (st.ok())
+    st.launched(launch_resid_relpose(dz, dl, di, dj, n, dp, n_poses, res, jac_i ? ji : nullptr, jac_j ? jj : nullptr,
+                                     parts ? pt : nullptr, flags ? fl : nullptr, nullptr));
+  st.fetch(residuals, res, 3 * N);
+  st.fetch(jac_i, ji, 9 * N);
+  st.fetch(jac_j, jj, 9 * N);
+  st.fetch(parts, pt, 8 * N);
+  st.fetch(flags, fl, N);
   return st.finish();
 }
 

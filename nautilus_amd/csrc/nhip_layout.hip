@@ -6,6 +6,7 @@
 
 #include "nhip_common.h"
 #include "nhip_csm_shared.h"  // (the score gate's floor)
+#include "nhip_loss_shared.h"  // (log1p_pinned: its host compilation, for nhip_loss_log1p_pinned)
 
 namespace nhip {
 
@@ -163,11 +164,45 @@ int loss_spec_check(const nhip_loss_spec_t *loss, const char *who) {
   return NHIP_OK;
 }
 
+// ---------------------------------------------------------------- relative-pose factors: their arguments (host)
+int relpose_args_check(const void *z, const void *info, const void *pose_i, const void *pose_j, int32_t n_factors,
+                       const void *poses, int32_t n_poses, const void *out, const char *who) {
+  NHIP_REQUIRE(n_factors >= 0 && n_poses >= 0, "%s: negative size (n_factors %d, n_poses %d)", who, n_factors, n_poses);
+  NHIP_REQUIRE(z && info && pose_i && pose_j && poses && out, "%s: null pointer", who);
+  return NHIP_OK;
+}
+
 }  // namespace nhip
 
 using namespace nhip;
 
 extern "C" {
+
+int nhip_loss_log1p_pinned(const double *x, int64_t n, double *out) {
+  NHIP_REQUIRE(n >= 0 && (n == 0 || (x && out)), "loss_log1p_pinned: bad arguments");
+  for (int64_t i = 0; i < n; i++) out[i] = log1p_pinned(x[i]);
+  return NHIP_OK;
+}
+
+int nhip_relpose_information(const nhip_refined_t *refined, int32_t n, double sigma_m, double wt, double wr, double *info,
+                             uint8_t *from_icp) {
+  NHIP_REQUIRE(n >= 0, "relpose_information: negative size %d", n);
+  NHIP_REQUIRE(std::isfinite(sigma_m) && sigma_m > 0.0, "relpose_information: sigma_m %g must be finite and > 0", sigma_m);
+  NHIP_REQUIRE(std::isfinite(wt) && std::isfinite(wr), "relpose_information: weights (%g, %g) must be finite", wt, wr);
+  NHIP_REQUIRE(n == 0 || info, "relpose_information: null info");
+  const double inv = 1.0 / (sigma_m * sigma_m), tt = wt * wt, rr = wr * wr;
+  for (int32_t k = 0; k < n; k++) {
+    double *L = info + 6 * (size_t)k;
+    const bool icp = refined && (refined[k].flags & ~NHIP_REFINE_NOT_CONVERGED) == 0u;
+    if (icp) {
+      for (int q = 0; q < 6; q++) L[q] = refined[k].info[q] * inv;
+    } else {
+      L[0] = tt, L[1] = 0.0, L[2] = 0.0, L[3] = tt, L[4] = 0.0, L[5] = rr;
+    }
+    if (from_icp) from_icp[k] = icp ? 1 : 0;
+  }
+  return NHIP_OK;
+}
 
 int nhip_grid_layout(const nhip_grid_spec_t *spec, nhip_grid_layout_t *out) {
   GridLayout L;

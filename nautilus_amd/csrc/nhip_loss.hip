@@ -25,41 +25,12 @@
 // The staged form ships: at 100,000 factors it takes 0.67-0.70 of the direct form's time, at 1,000 the two are equal within
 // their spread (tools/loss_bench.py).  A process with NHIP_TUNABLES=1 picks either with
 // NHIP_LOSS_STORE=direct|staged.
-#include "nhip_common.h"
+#include "nhip_loss_shared.h"  // loss_value, and the row's shape: shared with nhip_relpose.hip
 
 namespace nhip {
 namespace {
 
-constexpr int LT = 256;        // lanes per workgroup
-constexpr int ROW = 28;        // doubles per row
-constexpr int ROW_PITCH = 29;  // ... and per row in LDS
-
-struct LossValue {
-  double rho, rho1;
-};
-
-// kind and a are wave-uniform: one branch for the whole wave
-__device__ __forceinline__ LossValue loss_value(int32_t kind, double a, double s) {
-  const double b = a * a;
-  switch (kind) {
-    case NHIP_LOSS_HUBER: {
-      if (s <= b) return {s, 1.0};
-      const double q = sqrt(s);
-      return {(2.0 * a) * q - b, a / q};
-    }
-    case NHIP_LOSS_SOFT_L1: {
-      const double x = s / b;
-      const double q = sqrt(1.0 + x);
-      return {(2.0 * s) / (q + 1.0), 1.0 / q};
-    }
-    case NHIP_LOSS_CAUCHY: {
-      const double x = s / b;
-      return {x < 0x1p-54 ? s : b * log1p(x), 1.0 / (1.0 + x)};
-    }
-    default:
-      return {s, 1.0};
-  }
-}
+constexpr int LT = LOSS_LT, ROW = LOSS_ROW, ROW_PITCH = LOSS_ROW_PITCH;
 
 // the factor's row into o[0 .. 27] (o: registers, or the lane's row in LDS) and its four weights; false: a pose index is
 // outside [0, n_poses) -- reported, and the caller writes zeros

@@ -1271,3 +1271,106 @@ def refined_to_transform(refined):
     r = np.asarray(refined, dtype=REFINED_DTYPE).reshape(-1)
     theta = np.array([math.atan2(s, c) for s, c in zip(r["s"], r["c"])], dtype=np.float64)  # (libm's, as the C helper's)
     return np.stack([r["tx"], r["ty"], theta], axis=1)
+
+
+# ---- relative-pose factors ("Relative-pose factors"; the device form is nhip_relpose.hip, K23) ----
+RELPOSE_BAD_INFO, RELPOSE_BAD_MEASUREMENT, RELPOSE_SAME_POSE = 1, 2, 4
+
+
+def relpose_information(refined, n=None, sigma_m=1.0, weights=(10.0, 10.0)):
+    """nhip_relpose_information in Python, bit for bit: ((n, 6) float64 information L00 L01 L02 L11 L12 L22, (n,) bool mask of
+    the records that took their H).  A record that carries a refined pose (refine_keeps_pose) gets H (1 / sigma_m^2) -- one
+    rounded reciprocal of one rounded product, six products; any other, and every record when `refined` is None (then n
+    counts them), gets diag(w_t w_t, w_t w_t, w_r w_r) of `weights`."""
+    sigma_m, wt, wr = float(sigma_m), float(weights[0]), float(weights[1])
+    if not (math.isfinite(sigma_m) and sigma_m > 0.0):
+        raise ValueError("relpose_information: sigma_m %r must be finite and > 0" % (sigma_m,))
+    if not (math.isfinite(wt) and math.isfinite(wr)):
+        raise ValueError("relpose_information: weights %r must be finite" % (weights,))
+    if refined is None:
+        n = int(n or 0)
+        took = np.zeros(n, dtype=bool)
+        H = np.zeros((n, 6))
+    else:
+        refined = np.asarray(refined, dtype=REFINED_DTYPE).reshape(-1)
+        took = refine_keeps_pose(refined)
+        H = np.array(refined["info"], dtype=np.float64).reshape(-1, 6)
+    inv = 1.0 / (sigma_m * sigma_m)
+    diag = np.array([wt * wt, 0.0, 0.0, wt * wt, 0.0, wr * wr])
+    with np.errstate(all="ignore"):
+        info = np.where(took[:, None], H * inv, diag[None, :])
+    return np.ascontiguousarray(info), took
+
+
+def relpose_rows(z, info, pose_i, pose_j, poses, loss=None, trig=None):
+    """The relative-pose factors in numpy, in the kernel's operation order ("Relative-pose factors"): z (F, 4)
+    (z_x, z_y, c_z, s_z), info (F, 6), pose_i = the target's pose a, pose_j = the source's pose b, poses (n, 3); loss: None or a
+    loss.Loss.  Returns (r (F, 3), J_i (F, 3, 3), J_j (F, 3, 3), rows (F, 28), weights (F, 4), flags (F,) int32): the whitened
+    residual and its Jacobian halves without the loss; the rows and {s, rho, rho', sqrt(rho')} under it.  A flagged factor and one
+    with a pose id outside [0, n) are zeros.  trig: None -- cos, sin and atan2 are libm's -- or the (F,) arrays
+    (c_a, s_a, c_b, s_b, e_theta) of a device run (nhip_resid_relpose_dev's parts): everything else is recomputed from them."""
+    z = np.asarray(z, dtype=np.float64).reshape(-1, 4)
+    F = len(z)
+    L = np.asarray(info, dtype=np.float64).reshape(F, 6)
+    ia, ib = np.asarray(pose_i, dtype=np.int64).reshape(F), np.asarray(pose_j, dtype=np.int64).reshape(F)
+    P = np.asarray(poses, dtype=np.float64).reshape(-1, 3)
+    n = len(P)
+    with np.errstate(all="ignore"):
+        L00, L01, L02, L11, L12, L22 = (L[:, k] for k in range(6))
+        D0 = L00
+        l10, l20 = L01 / D0, L02 / D0
+        D1 = L11 - l10 * L01
+        u = L12 - l20 * L01
+        l21 = u / D1
+        D2 = (L22 - l20 * L02) - l21 * u
+        flags = np.zeros(F, dtype=np.int32)
+        flags[~(np.isfinite(L).all(axis=1) & (D0 > 0.0) & (D1 > 0.0) & (D2 > 0.0))] |= RELPOSE_BAD_INFO
+        flags[~np.isfinite(z).all(axis=1)] |= RELPOSE_BAD_MEASUREMENT
+        flags[ia == ib] |= RELPOSE_SAME_POSE
+        in_range = (ia >= 0) & (ia < n) & (ib >= 0) & (ib < n)
+        ok = in_range & (flags == 0)
+        pa, pb = P[np.where(ok, ia, 0)] if n else np.zeros((F, 3)), P[np.where(ok, ib, 0)] if n else np.zeros((F, 3))
+        if trig is None:
+            ca = np.array([math.cos(t) if math.isfinite(t) else math.nan for t in pa[:, 2]], dtype=np.float64)
+            sa = np.array([math.sin(t) if math.isfinite(t) else math.nan for t in pa[:, 2]], dtype=np.float64)
+            cb = np.array([math.cos(t) if math.isfinite(t) else math.nan for t in pb[:, 2]], dtype=np.float64)
+            sb = np.array([math.sin(t) if math.isfinite(t) else math.nan for t in pb[:, 2]], dtype=np.float64)
+        else:
+            ca, sa, cb, sb = (np.asarray(t, dtype=np.float64).reshape(F) for t in trig[:4])
+        Dx, Dy = pb[:, 0] - pa[:, 0], pb[:, 1] - pa[:, 1]
+        dx, dy = ca * Dx + sa * Dy, (-sa) * Dx + ca * Dy
+        cr, sr = ca * cb + sa * sb, ca * sb - sa * cb
+        ce, se = cr * z[:, 2] + sr * z[:, 3], sr * z[:, 2] - cr * z[:, 3]
+        if trig is None:
+            eth = np.array([math.atan2(s_, c_) for s_, c_ in zip(se, ce)], dtype=np.float64)
+        else:
+            eth = np.asarray(trig[4], dtype=np.float64).reshape(F)
+        e = np.stack([dx - z[:, 0], dy - z[:, 1], eth], axis=1)
+        zero, one = np.zeros(F), np.ones(F)
+        E = np.stack([np.stack([-ca, -sa, dy, ca, sa, zero], axis=1), np.stack([sa, -ca, -dx, -sa, ca, zero], axis=1),
+                      np.stack([zero, zero, -one, zero, zero, one], axis=1)], axis=1)  # (F, 3, 6)
+        q0, q1, q2 = np.sqrt(D0), np.sqrt(D1), np.sqrt(D2)
+        W00, W01, W02, W11, W12, W22 = q0, q0 * l10, q0 * l20, q1, q1 * l21, q2
+        r = np.stack([W00 * e[:, 0] + W01 * e[:, 1] + W02 * e[:, 2], W11 * e[:, 1] + W12 * e[:, 2], W22 * e[:, 2]], axis=1)
+        J = np.stack([W00[:, None] * E[:, 0] + W01[:, None] * E[:, 1] + W02[:, None] * E[:, 2],
+                      W11[:, None] * E[:, 1] + W12[:, None] * E[:, 2], W22[:, None] * E[:, 2]], axis=1)  # (F, 3, 6)
+        r[~ok], J[~ok] = 0.0, 0.0
+        s = r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1] + r[:, 2] * r[:, 2]
+        if loss is None:
+            rho, rho1 = s.copy(), np.ones(F)
+        else:
+            rho, rho1 = loss.pinned().evaluate(np.where(ok, s, 0.0))  # (cauchy: log1p in IEEE operations, as the kernel's)
+        w = np.sqrt(rho1)
+        rt, Jt = w[:, None] * r, w[:, None, None] * J
+        rows = np.zeros((F, 28))
+        k = 0
+        for p in range(6):
+            for q in range(p, 6):
+                rows[:, k] = Jt[:, 0, p] * Jt[:, 0, q] + Jt[:, 1, p] * Jt[:, 1, q] + Jt[:, 2, p] * Jt[:, 2, q]
+                k += 1
+        for p in range(6):
+            rows[:, 21 + p] = Jt[:, 0, p] * rt[:, 0] + Jt[:, 1, p] * rt[:, 1] + Jt[:, 2, p] * rt[:, 2]
+        rows[:, 27] = rho
+        weights = np.stack([s, rho, rho1, w], axis=1)
+        rows[~ok], weights[~ok] = 0.0, 0.0
+    return r, np.ascontiguousarray(J[:, :, :3]), np.ascontiguousarray(J[:, :, 3:]), rows, weights, flags

@@ -27,18 +27,24 @@ KINDS = {"none": _lib.NHIP_LOSS_NONE, "huber": _lib.NHIP_LOSS_HUBER, "soft_l1": 
 
 
 class Loss:
-    """Loss(kind, scale): kind "none" | "huber" | "soft_l1" | "cauchy"; scale a > 0 and finite (unused by "none")."""
+    """Loss(kind, scale): kind "none" | "huber" | "soft_l1" | "cauchy"; scale a > 0 and finite (unused by "none").
+    pinned_log1p: cauchy's logarithm is log1p_pinned (below) instead of numpy's -- what the relative-pose factors take, whose
+    kernel does the same ("Relative-pose factors"); .pinned() returns such a copy."""
 
-    def __init__(self, kind, scale=1.0):
+    def __init__(self, kind, scale=1.0, pinned_log1p=False):
         if kind not in KINDS:
             raise ValueError("Loss: kind %r (one of %s)" % (kind, ", ".join(repr(k) for k in KINDS)))
         scale = float(scale)
         if kind != "none" and not (math.isfinite(scale) and scale > 0.0):
             raise ValueError("Loss: scale %r must be finite and > 0" % (scale,))
-        self.kind, self.scale = kind, scale
+        self.kind, self.scale, self.pinned_log1p = kind, scale, bool(pinned_log1p)
 
     def __repr__(self):
-        return "Loss(%r, %r)" % (self.kind, self.scale)
+        return "Loss(%r, %r%s)" % (self.kind, self.scale, ", pinned_log1p=True" if self.pinned_log1p else "")
+
+    def pinned(self):
+        """This loss with cauchy's logarithm pinned (itself if it is already)."""
+        return self if self.pinned_log1p else Loss(self.kind, self.scale, pinned_log1p=True)
 
     def spec(self):
         """The nhip_loss_spec_t of this loss."""
@@ -59,7 +65,7 @@ class Loss:
                 return (2.0 * s) / (q + 1.0), 1.0 / q
             if self.kind == "cauchy":
                 x = s / b
-                return np.where(x < 2.0 ** -54, s, b * np.log1p(x)), 1.0 / (1.0 + x)
+                return np.where(x < 2.0 ** -54, s, b * (log1p_pinned(x) if self.pinned_log1p else np.log1p(x))), 1.0 / (1.0 + x)
         return s.copy(), np.ones_like(s)
 
     def weights(self, r):
@@ -75,3 +81,46 @@ class Loss:
         wt = self.weights(r)
         w = wt[:, 3]
         return w[:, None] * r, w[:, None, None] * J, wt[:, 1]
+
+
+_LN2_HI, _LN2_LO = 6.93147180369123816490e-01, 1.90821492927058770002e-10
+_LP = (6.666666666666735130e-01, 3.999999999940941908e-01, 2.857142874366239149e-01, 2.222219843214978396e-01,
+       1.818357216161805012e-01, 1.531383769920937332e-01, 1.479819860511658591e-01)
+
+
+def log1p_pinned(x):
+    """log1p(x) for x >= 0 written out in IEEE operations: fdlibm's s_log1p.c, its branches for x >= 0, every sum, product and
+    quotient rounded on its own -- the doubles nhip_loss_shared.h's log1p_pinned returns on the device, bit for bit, where numpy's
+    and the device library's log1p differ from each other in the last bit on a few values in a hundred.  Error below 1 ulp.
+    NaN, inf and anything not >= 0 give x + x."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    shape = x.shape
+    x = x.reshape(-1)
+    with np.errstate(all="ignore"):
+        hx = x.view(np.int64) >> 32
+        special = ~(x >= 0.0) | (hx >= 0x7ff00000)
+        tiny, small, direct, big = hx < 0x3c900000, hx < 0x3e200000, hx < 0x3FDA827A, hx >= 0x43400000
+        u = np.where(big, x, 1.0 + x)
+        ub = u.view(np.int64)
+        hu = ub >> 32
+        k = (hu >> 20) - 1023
+        c = np.where(big, 0.0, np.where(k > 0, 1.0 - (u - x), x - (u - 1.0)) / u)
+        hu = hu & 0x000fffff
+        low = hu < 0x6a09e
+        un = ((np.where(low, hu | 0x3ff00000, hu | 0x3fe00000) << 32) | (ub & 0xffffffff)).view(np.float64)
+        k = np.where(low, k, k + 1)
+        hu = np.where(low, hu, (0x00100000 - hu) >> 2)
+        f = np.where(direct, x, un - 1.0)
+        k, hu, c = np.where(direct, 0, k), np.where(direct, 1, hu), np.where(direct, 0.0, c)
+        hfsq, kd = 0.5 * f * f, k.astype(np.float64)
+        R0 = hfsq * (1.0 - 0.66666666666666666 * f)
+        near = np.where(f == 0.0, np.where(k == 0, 0.0, kd * _LN2_HI + (c + kd * _LN2_LO)),
+                        np.where(k == 0, f - R0, kd * _LN2_HI - ((R0 - (kd * _LN2_LO + c)) - f)))
+        s = f / (2.0 + f)
+        z = s * s
+        R = z * (_LP[0] + z * (_LP[1] + z * (_LP[2] + z * (_LP[3] + z * (_LP[4] + z * (_LP[5] + z * _LP[6]))))))
+        far = np.where(k == 0, f - (hfsq - s * (hfsq + R)), kd * _LN2_HI - ((hfsq - (s * (hfsq + R) + (kd * _LN2_LO + c))) - f))
+        out = np.where(hu == 0, near, far)
+        out = np.where(small, np.where(tiny, x, x - x * x * 0.5), out)
+        out = np.where(special, x + x, out)
+    return out.reshape(shape)

@@ -233,6 +233,37 @@ class HipBackend:
                                                          C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)))
         return d_out
 
+    def relative_pose(self, z, info, pose_i, pose_j, poses):
+        """RelativePoseFactors' arrays at `poses` (n, 3): the whitened residuals (F, 3) and Jacobians (F, 3, 3) x 2
+        (nhip_resid_relpose; DESIGN.md section 3, "Relative-pose factors")."""
+        n = len(pose_i)
+        r, ji, jj = np.empty((n, 3)), np.empty((n, 3, 3)), np.empty((n, 3, 3))
+        P = np.ascontiguousarray(poses, dtype=np.float64)
+        check(self.lib.nhip_resid_relpose(_lib.ptr(z), _lib.ptr(info), _lib.ptr(pose_i), _lib.ptr(pose_j), n, _lib.ptr(P), len(P),
+                                          _lib.ptr(r), _lib.ptr(ji), _lib.ptr(jj), None, None))
+        return r, ji, jj
+
+    def relative_pose_normal_eq_dev(self, factors, d_poses, d_weights=None, loss=None):
+        """The rows of RelativePoseFactors at the (n, 3) float64 device tensor d_poses: (F, 28) float64 on the device over
+        [pose_i | pose_j] (nhip_resid_relpose_normal_eq_dev), under the factors' loss (or `loss` in its place; None: none), and
+        {s, rho, rho', sqrt(rho')} per factor into the (F, 4) float64 device tensor d_weights if one is given.  The factors'
+        arrays go up once."""
+        torch, fac = self.torch, factors
+        loss = loss if loss is not None else getattr(fac, "loss", None)
+        d_out = torch.empty((fac.n, 28), dtype=torch.float64, device=self.dev)
+        if fac.n == 0:
+            return d_out
+        if getattr(fac, "_dev", None) is None or fac._dev[0] != self.dev:
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+            fac._dev = (self.dev, t(fac.z), t(fac.info), t(fac.pose_i), t(fac.pose_j))
+        _, d_z, d_l, d_i, d_j = fac._dev
+        spec = None if loss is None else loss.spec()
+        check(self.lib.nhip_resid_relpose_normal_eq_dev(
+            d_z.data_ptr(), d_l.data_ptr(), d_i.data_ptr(), d_j.data_ptr(), fac.n, None if spec is None else C.byref(spec),
+            d_poses.data_ptr(), d_poses.shape[0], d_out.data_ptr(), None if d_weights is None else d_weights.data_ptr(), None,
+            C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)))
+        return d_out
+
     def device_system(self, structure, fixed=()):
         """The device arrays of a linsolve.BlockStructure -- values, gradient, x, the PCG workspace -- and its two calls
         (linsolve.DeviceSystem: nhip_bsr_assemble_dev, nhip_bsr_pcg_dev)."""
@@ -534,6 +565,63 @@ class OdometryFactors:
         return backend.odometry(self.pose_i, self.pose_j, self.t_odom, self.r_odom, self.tw, self.rw, poses)
 
 
+    def normal_eq_dev(self, backend, d_poses, d_weights=None, loss=None):
+        """The factors' (F, 28) rows on the device (HipBackend.odometry_normal_eq_dev)."""
+        return backend.odometry_normal_eq_dev(self, d_poses, d_weights=d_weights, loss=loss)
+
+
+class RelativePoseFactors:
+    """Batched relative-pose factors ("Relative-pose factors"): factor f measures pose_j[f] (a closure's
+    source) in the frame of pose_i[f] (its target) as z[f] = (z_x, z_y, c_z, s_z), with the information info[f] =
+    (L00 L01 L02 L11 L12 L22) over (x, y, theta).  The residual is whitened by the information's Cholesky factor, so its
+    squared norm is a squared Mahalanobis distance.  loss: as OdometryFactors'; evaluate() returns the plain r and J.  A factor
+    whose information is not positive definite or whose measurement is not finite contributes zeros (the kernel's flags;
+    hostside.relpose_rows returns them)."""
+
+    def __init__(self, pose_i, pose_j, z, info, loss=None):
+        self.loss = None if loss is None else loss.pinned()  # (cauchy's log1p as the kernel takes it: loss.log1p_pinned)
+        self.n = len(pose_i)
+        self.pose_i = np.ascontiguousarray(pose_i, dtype=np.int32).reshape(self.n)
+        self.pose_j = np.ascontiguousarray(pose_j, dtype=np.int32).reshape(self.n)
+        self.z = np.ascontiguousarray(np.reshape(z, (-1, 4)), dtype=np.float64)
+        self.info = np.ascontiguousarray(np.reshape(info, (-1, 6)), dtype=np.float64)
+        if len(self.z) != self.n or len(self.info) != self.n:
+            raise ValueError("RelativePoseFactors: %d factors, %d measurements, %d informations" % (self.n, len(self.z), len(self.info)))
+        if np.any(self.pose_i == self.pose_j):
+            raise ValueError("RelativePoseFactors: a factor couples two different poses (pose_i == pose_j at %d)"
+                             % int(np.nonzero(self.pose_i == self.pose_j)[0][0]))
+
+    def evaluate(self, backend, poses):
+        if self.n == 0:
+            return np.zeros((0, 3)), np.zeros((0, 3, 3)), np.zeros((0, 3, 3))
+        if hasattr(backend, "relative_pose"):
+            return backend.relative_pose(self.z, self.info, self.pose_i, self.pose_j, poses)
+        from . import hostside  # (a backend without the method: the numpy form)
+        return hostside.relpose_rows(self.z, self.info, self.pose_i, self.pose_j, poses)[:3]
+
+    def normal_eq_dev(self, backend, d_poses, d_weights=None, loss=None):
+        """The factors' (F, 28) rows on the device (HipBackend.relative_pose_normal_eq_dev)."""
+        return backend.relative_pose_normal_eq_dev(self, d_poses, d_weights=d_weights, loss=loss)
+
+
+def relative_pose_factors(pairs_src, pairs_tgt, rel, information, weights=(10.0, 10.0), loss=None, rel_cs=None):
+    """One relative-pose factor per loop closure: rel[k] = (tx, ty, theta) is where scan src sits in scan tgt's frame, rel_cs[k]
+    -- if given -- its heading as (cos, sin) (a refined record's c, s; otherwise libm's of rel[k, 2]); information (F, 6), an
+    all-zero row of which is filled with diag(w_t^2, w_t^2, w_r^2) of `weights`."""
+    rel = np.asarray(rel, dtype=np.float64).reshape(-1, 3)
+    info = np.array(information, dtype=np.float64).reshape(-1, 6)
+    if len(info) != len(rel):
+        raise ValueError("relative_pose_factors: %d records, %d informations" % (len(rel), len(info)))
+    wt, wr = float(weights[0]), float(weights[1])
+    info[~info.any(axis=1)] = (wt * wt, 0.0, 0.0, wt * wt, 0.0, wr * wr)
+    if rel_cs is None:
+        cs = np.array([(math.cos(t), math.sin(t)) for t in rel[:, 2]], dtype=np.float64).reshape(-1, 2)
+    else:
+        cs = np.asarray(rel_cs, dtype=np.float64).reshape(-1, 2)
+    z = np.concatenate([rel[:, :2], cs], axis=1)
+    return RelativePoseFactors(np.asarray(pairs_tgt), np.asarray(pairs_src), z, info, loss=loss)
+
+
 def odometry_factors_from_poses(odom, **kw):
     """Consecutive-pose factors in the functor's convention: world-frame translation delta and heading
     delta of the odometry track (what GetSolvedOdomFactors produces from poses, solver.cc:406-427)."""
@@ -661,12 +749,20 @@ class PoseGraph:
         # odometry factors always come from `odom`; the estimate may start elsewhere (previous window pass)
         self.poses = np.array(odom if initial is None else initial, dtype=np.float64)
 
-    def add_loop_closures(self, pairs_src, pairs_tgt, rel, weights=(10.0, 10.0), loss=None):
+    def add_loop_closures(self, pairs_src, pairs_tgt, rel, weights=(10.0, 10.0), loss=None, information=None, rel_cs=None):
         """One odometry-style factor per record (loop_closure_factors), weighted `weights`.  loss: None -- every record
         enters at full weight -- or a loss.Loss: each solve reweights every record by sqrt(rho'(s)) of its own weighted
         squared residual s at the poses it evaluates, and the cost becomes Ceres' robust cost (DESIGN.md section 3,
-        "Robust loss"); closure_weights() reports the weights."""
-        self.lc = loop_closure_factors(self.poses, pairs_src, pairs_tgt, rel, loss=loss, tw=weights[0], rw=weights[1])
+        "Robust loss"); closure_weights() reports the weights.
+        information: None -- the world-frame factor above -- or an (F, 6) array, L00 L01 L02 L11 L12 L22 over (x, y, theta) per
+        record: the records become relative-pose factors ("Relative-pose factors"), which measure the source
+        in the target's frame at every evaluation and weigh it by that information; an all-zero row takes
+        diag(w_t^2, w_t^2, w_r^2) of `weights`.  rel_cs: with an information, the records' headings as (cos, sin) where the
+        caller has them (refined records); otherwise cos and sin of rel[:, 2].  The loss' scale is then in standard deviations."""
+        if information is None:
+            self.lc = loop_closure_factors(self.poses, pairs_src, pairs_tgt, rel, loss=loss, tw=weights[0], rw=weights[1])
+        else:
+            self.lc = relative_pose_factors(pairs_src, pairs_tgt, rel, information, weights=weights, loss=loss, rel_cs=rel_cs)
 
     def closure_weights(self, poses=None):
         """(F, 4) float64 {s, rho, rho', sqrt(rho')} of the loop-closure factors at `poses` (default: the current estimate).
@@ -681,7 +777,7 @@ class PoseGraph:
         if hasattr(be, "odometry_normal_eq_dev"):
             with clocked("path"):
                 d_w = be.torch.empty((self.lc.n, 4), dtype=be.torch.float64, device=be.dev)
-                be.odometry_normal_eq_dev(self.lc, be.torch.from_numpy(poses).to(be.dev), d_weights=d_w, loss=loss)
+                self.lc.normal_eq_dev(be, be.torch.from_numpy(poses).to(be.dev), d_weights=d_w, loss=loss)
                 out = d_w.cpu().numpy()
                 check(be.lib.nhip_dev_status(C.c_void_p(be.torch.cuda.current_stream(be.dev).cuda_stream), None))
             return out
@@ -902,7 +998,7 @@ class PoseGraph:
             d_poses = torch.from_numpy(np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)).to(be.dev)
             d_lines = torch.from_numpy(np.ascontiguousarray(lines, dtype=np.float64).reshape(-1, 3)).to(be.dev)
             parts = [self.icp.normal_equations_dev(self.kind)]
-            parts += [be.odometry_normal_eq_dev(fac, d_poses) for fac in (self.odo, self.lc) if fac is not None]
+            parts += [fac.normal_eq_dev(be, d_poses) for fac in (self.odo, self.lc) if fac is not None]
             parts += [be.point_to_line_normal_eq_dev(con, d_poses, d_lines, c) for c, con in enumerate(self.hitl)]
             rows = torch.cat(parts)
             with clocked("path_linear"):
@@ -951,7 +1047,8 @@ def solve_growing_window(xy, normals, offsets, odom, window_min=1, window_max=10
     lidar_constraint_amount_min to _max the problem is rebuilt -- odometry factors, HITL residuals
     (AddHITLResiduals) plus fresh correspondences for all (i, j) blocks of the window, searched at the current
     estimate -- and solved.  features: as PoseGraph's (FEATURE mode); linear_solver: as PoseGraph.solve's; lc_loss: the loss.Loss
-    add_loop_closures gets in every pass (None: none).  Returns (PoseGraph of the last pass, poses)."""
+    add_loop_closures gets in every pass (None: none); loop_closures: (src, tgt, rel) or (src, tgt, rel, kw), kw the further keywords
+    of add_loop_closures (information=, rel_cs=, weights=).  Returns (PoseGraph of the last pass, poses)."""
     poses = np.array(odom if initial is None else initial, dtype=np.float64)
     backend = backend if backend is not None else HipBackend(device)
     if features is None and hasattr(backend, "reserve_icp"):  # (feature clouds: a few points per scan, nothing to reserve)
@@ -964,7 +1061,7 @@ def solve_growing_window(xy, normals, offsets, odom, window_min=1, window_max=10
         for con in hitl:
             pg.add_hitl(con)
         if loop_closures is not None:
-            pg.add_loop_closures(*loop_closures, loss=lc_loss)
+            pg.add_loop_closures(*loop_closures[:3], loss=lc_loss, **(loop_closures[3] if len(loop_closures) > 3 else {}))
         poses, hist = pg.solve(iterations=iterations, verbose=verbose, linear_solver=linear_solver)
         if verbose:
             print("window %d: cost %.6g -> %.6g" % (w, hist[0], hist[-1]))
