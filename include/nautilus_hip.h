@@ -1612,6 +1612,15 @@ int nhip_allgather_matches(void *comm, const nhip_match_t *d_local, int32_t n_lo
  * the pass, i.e. whose windows hold only empty cells; out[2], out[3] = the same two for the single poses of 16-bit grids
  * read from the 16-bit image.  out[1] == out[0] and out[3] == out[2] under NHIP_BNB_ZERO_CHUNKS=0 (synchronises; resets). */
 int nhip_bnb_stats_chunks(uint64_t out[4]);
+/* ... and, for the same reason here: the SEEDS of the kernel that takes a pair's bounds (every wave's highest-bound block,
+ * evaluated exactly before anything is pruned), since the last call.  out[0..2] = shader-clock sums of the seed passes'
+ * wave time by part: window origins, sub-block bounds, exact sums (in the split form nhip_bnb_stats_levels' out[5..7] add
+ * the candidates' kernel's to these); out[3] = seed passes; out[4] = those that began while the pair's best sum was still 0
+ * (no score gate, no other wave's seed landed yet); out[5] = those of out[4] that left their sub-block bounds out -- all of
+ * them unless NHIP_BNB_SEED_BOUNDS=1 or a search without sub-block bounds; out[6] = seed blocks whose sub-block bounds were
+ * taken and of which a sub-block that holds a pose had bound 0 -- what a pass without bounds evaluates in vain; out[7]
+ * unused (synchronises; resets). */
+int nhip_bnb_stats_seeds(uint64_t out[8]);
 
 #ifdef __cplusplus
 }

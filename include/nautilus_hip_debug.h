@@ -29,7 +29,9 @@ int nhip_host_phases(double out[8]);
  * bit 1: the kernels that keep a list of level-2 runs take their strip bounds from it (clear: NHIP_BNB_L2_RUNS=0),
  * bit 2: the candidates' kernels take two live sub-blocks side by side in one pass (clear: NHIP_BNB_PAIR_SUBS=0),
  * bit 3: their exact sums leave out the chunks of the cell list whose windows hold only empty cells (clear:
- * NHIP_BNB_ZERO_CHUNKS=0; what that saves is counted by nhip_bnb_stats_chunks, declared at the end of nautilus_hip.h);
+ * NHIP_BNB_ZERO_CHUNKS=0; what that saves is counted by nhip_bnb_stats_chunks, declared at the end of nautilus_hip.h),
+ * bit 4: a seed takes its block's sub-block bounds even while the pair's best sum is 0 (set: NHIP_BNB_SEED_BOUNDS=1; clear,
+ * the default: such a seed evaluates its block without them; nhip_bnb_stats_seeds, also at the end of nautilus_hip.h);
  * out[7] n_pairs. */
 int nhip_csm_last_launch(int32_t out[8]);
 /* What the calling thread's last nhip_csm_get_transformation did: {the coarse optimum's score, the form the fine level ran in

@@ -207,6 +207,7 @@ PROTOTYPES = {
     "nhip_bnb_timeline_candidates": (C.c_int, [_vp, _i32]),
     "nhip_bnb_stats_levels": (C.c_int, [_P(C.c_uint64)]),
     "nhip_bnb_stats_chunks": (C.c_int, [_P(C.c_uint64)]),
+    "nhip_bnb_stats_seeds": (C.c_int, [_P(C.c_uint64)]),
     "nhip_csm_scores_dev": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _P(GridSpec), _i32, _i32, _vp, _vp, _i32, _i32,
                                       _P(Search), _vp, _vp]),
     "nhip_resid_lidar_dev": (C.c_int, [C.c_int, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _i32, _vp,

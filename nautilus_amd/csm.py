@@ -284,6 +284,14 @@ def bnb_stats_chunks():
     return {"chunk_visits_full": v[0], "chunk_visits": v[1], "pose_chunk_visits_full": v[2], "pose_chunk_visits": v[3]}
 
 
+def bnb_stats_seeds():
+    """The seed passes' wave clocks by part and their counts, since the last call (nhip_bnb_stats_seeds)."""
+    v = (C.c_uint64 * 8)()
+    check(_lib.load().nhip_bnb_stats_seeds(v))
+    return {"clk_seed_origins": v[0], "clk_seed_sub_bounds": v[1], "clk_seed_exact": v[2], "seed_passes": v[3],
+            "seed_passes_best0": v[4], "seed_passes_without_bounds": v[5], "seed_blocks_zero_sub": v[6]}
+
+
 def score_volume(scans, grids, src, slot, theta0, search, origin=(0, 0)):
     out = np.zeros((search.n_theta, search.nx, search.ny), dtype=np.int32)
     check(_lib.load().nhip_csm_scores(scans._h, grids._h, int(src), int(slot), float(theta0),
@@ -328,6 +336,7 @@ def last_launch():
     return {"form": form.get(out[0], "?"), "form_id": out[0], "pairs_per_round": out[1], "rounds_of_state": out[2],
             "rounds": out[3], "short_scans": bool(out[4]), "hand_over_kernel": bool(out[5]), "instrumented": bool(out[6] & 1),
             "l2_runs": bool(out[6] & 2), "pair_subs": bool(out[6] & 4), "zero_chunks": bool(out[6] & 8),
+            "seed_bounds": bool(out[6] & 16),
             "n_pairs": out[7]}
 
 

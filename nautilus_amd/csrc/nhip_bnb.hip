@@ -336,6 +336,9 @@ __device__ __forceinline__ void strip_sub_blocks(const BnbParams &P, __amdgpu_bu
 struct PhaseClocks {
   long long org, strip, eval;
   uint32_t run_passes, cell_passes_field, cell_passes_full;
+  // the seed passes among them (`done` set): all, those that began at a best sum of 0, those of them that left their strip
+  // bounds out, and the seed blocks whose bounds were taken and held a 0 for a sub-block with a pose
+  uint32_t seed_passes, seed_best0, seed_unbounded, seed_zero_sub;
 };
 
 // The instrumented build's flush into stats[] (indices: include/nautilus_hip_debug.h): work counts n[0..3] as
@@ -374,6 +377,16 @@ __device__ __forceinline__ void flush_stats(unsigned long long *stats, const uin
   }
 }
 
+// ... and the seeds' own slots behind the chunk visits (nhip_bnb_stats_seeds): a wave's clocks by part as they stood when
+// its seed pass was through, and the seed counts of `clk`
+__device__ __forceinline__ void flush_seeds(unsigned long long *stats, const long long (&part)[3], const PhaseClocks &clk) {
+  unsigned long long *at = stats + BNB_STATS_HEAD + (size_t)BNB_STATS_PAIRS + BNB_STATS_CHUNKS;
+  const unsigned long long v[7] = {(unsigned long long)part[0], (unsigned long long)part[1], (unsigned long long)part[2],
+                                   clk.seed_passes, clk.seed_best0, clk.seed_unbounded, clk.seed_zero_sub};
+  for (int i = 0; i < 7; i++)
+    if (v[i]) atomicAdd(&at[i], v[i]);
+}
+
 // ---- one rotation of one pair: its candidate blocks (masks m0 | m1 over block index b = NB * Y + X, bounds u0 / u1
 // lane-wise) through sub-block bounds and exact sums, origins held in registers.  `done`: the workgroup's bound row
 // of this rotation, where finished blocks are zeroed (seeds), or null.  PAIR: the sub-blocks of the strip's blocks that do
@@ -392,6 +405,17 @@ __device__ __forceinline__ void rotation_pass(const BnbParams &P, const PairCtx 
   long long t_mark = 0;
   float cf, sf;
   rotation_k(P, C.pair, k, &cf, &sf);
+  // A seed pass (`done` set: one block, the wave's highest bound) that begins while the pair's best sum is still 0 -- no
+  // score gate, no other wave's seed landed yet -- leaves the strip bounds out.  Against a sum of 0 they prune nothing: every
+  // sub-block with a pose and a bound that is not 0 is alive, an interior block has four and goes whole.  All they could tell
+  // is that a sub-block's windows hold only empty cells, which the highest-bound block of a rotation rarely has, and such
+  // a sub-block's poses sum to 0 and yield keys that never beat the floor key.  With every bound at 0xffffffff, as without
+  // level 2, process_candidate_c takes every sub-block that holds a pose (sub_valid: an edge block with at most two still
+  // never goes whole): a superset of the poses the bounds admit, each with its exact sum, and keys are maxima -- records
+  // and sums are the same.  The sum is read once, here (wave-uniform; one LDS round trip per pass, awaited where it is read).
+  // P.seed_bounds (NHIP_BNB_SEED_BOUNDS=1): the bounds are taken whatever the sum.  profiles/r19_seeds.txt
+  const bool seed_best0 = done != nullptr && best_sum<GLOBAL>(best) == 0u;
+  const bool unbounded = seed_best0 && P.seed_bounds == 0;
   if (BNB_STATS(P)) t_mark = clock64();
   int32_t nrc = RUNS_NONE;
   const int32_t nch = cache_origins<RUNS>(P, C.pts, C.n_pts, cf, sf, C.cx, C.cy, lane, org, true, runs, RUNS && P.l2_runs != 0, &nrc, span);
@@ -403,6 +427,11 @@ __device__ __forceinline__ void rotation_pass(const BnbParams &P, const PairCtx 
     clk.run_passes += nrc > 0 ? 1u : 0u;
     clk.cell_passes_field += nrc == RUNS_FIELD ? 1u : 0u;
     clk.cell_passes_full += nrc == RUNS_FULL ? 1u : 0u;
+  }
+  if (BNB_STATS(P) && done) {
+    clk.seed_passes++;
+    clk.seed_best0 += seed_best0 ? 1u : 0u;
+    clk.seed_unbounded += unbounded && P.levels >= 2 ? 1u : 0u;
   }
   // (stored image + skip map: every offset an evaluation can form lies inside; see nhip_layout.hip make_layout)
   // (8-bit grids: the image, on which the exact sums run; 16-bit grids: the tiled copy of the image, for pose_sum16)
@@ -425,13 +454,19 @@ __device__ __forceinline__ void rotation_pass(const BnbParams &P, const PairCtx 
     }
     uint32_t sb[12];
     uint32_t bcopy = GLOBAL ? best_sum<true>(best) : 0u;  // (one look per strip at a best in global memory)
-    if (P.levels >= 2) {
+    if (P.levels >= 2 && !unbounded) {
       if (BNB_STATS(P)) t_mark = clock64();
       if (RUNS && nrc > 0) strip_bounds_c<RunList<RUN_CHUNKS>, RUNS>(P, p4, runs + lane, nrc, Y, X0, len, CB == 1 ? 1u : 257u, sb, note + lane);
       else strip_bounds_c<CellList>(P, p4, org, nch, Y, X0, len, CB == 1 ? 1u : 257u, sb);
       if (BNB_STATS(P)) clk.strip += clock64() - t_mark;
       n_work[1] += (uint32_t)len;
+      if (BNB_STATS(P) && done) {  // (a seed's strip is its one block)
+        const int32_t vx = block_extent(P.nx, X0), vy = block_extent(P.ny, Y);
+        clk.seed_zero_sub += ((sub_valid(vy, vx, 0, 0) && sb[0] == 0u) || (sub_valid(vy, vx, 0, 1) && sb[1] == 0u) ||
+                              (sub_valid(vy, vx, 1, 0) && sb[2] == 0u) || (sub_valid(vy, vx, 1, 1) && sb[3] == 0u)) ? 1u : 0u;
+      }
     } else {
+      if (P.levels >= 2) n_work[1] += (uint32_t)len;  // (a seed block without its bounds still counts as a candidate refined)
 #pragma unroll
       for (int q = 0; q < 12; q++) sb[q] = 0xffffffffu;
     }
@@ -642,6 +677,7 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : BNB_THREADS, SPLIT ? SPL
     uint32_t *org = s_org + wave * ORG_WAVE + lane;
     // (NHIP_BNB_STATS=1: shader-clock sums -- wave time in phase 3 by part, and the workgroup's wall time)
     PhaseClocks clk = {0, 0, 0, 0u, 0u, 0u};
+    long long clk_seed[3] = {0, 0, 0};  // (the wave's clocks by part when its seed was through: instrumented build)
     long long t_busy = 0, t_wall = 0;
     const long long t_phase1 = BNB_STATS(P) ? clock64() : 0;
     if (BNB_TIMELINE(P) && threadIdx.x == 0 && pair < BNB_STATS_PAIRS) BNB_TIMELINE(P)[4 * pair + 1] = wall_clock64();
@@ -715,6 +751,9 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : BNB_THREADS, SPLIT ? SPL
         if (BNB_STATS(P)) {
           t_busy = clock64();
           t_wall = wall_clock64();
+          clk_seed[0] = clk.org;
+          clk_seed[1] = clk.strip;
+          clk_seed[2] = clk.eval;
         }
         // best first: the rotations in descending order of their highest bound (rank by counting: n_theta^2 compares)
         for (int32_t kk = threadIdx.x; kk < P.n_theta; kk += THREADS) {
@@ -767,6 +806,7 @@ __global__ __launch_bounds__(SPLIT ? 64 * SPLIT_WAVES : BNB_THREADS, SPLIT ? SPL
       atomicAdd(&BNB_STATS(P)[4], (unsigned long long)(now - t_busy));       // wave time in phase 3 (until out of work)
       atomicAdd(&BNB_STATS(P)[11], (unsigned long long)(wall_clock64() - t_wall));  // the same in 100 MHz ticks
       flush_stats(BNB_STATS(P), nullptr, pair, &clk);  // (the counts: through s_cnt, below)
+      flush_seeds(BNB_STATS(P), clk_seed, clk);
       atomicMax(s_slow, (unsigned long long)(now - t_busy));  // slowest wave
       if (wave == 0) {
         atomicAdd(&BNB_STATS(P)[9], (unsigned long long)(t_busy - t_phase1));  // seeds (wave 0's view)

@@ -105,6 +105,7 @@ BnbPlan bnb_plan(const GridLayout &L, const nhip_search_t *search, int32_t n_pai
   p.l2_runs = !is(tunable("NHIP_BNB_L2_RUNS"), '0');       // (0: strip bounds per stored cell everywhere -- the A/B, tests)
   p.pair_subs = !is(tunable("NHIP_BNB_PAIR_SUBS"), '0');   // (0: one pass of exact sums per sub-block -- the A/B, tests)
   p.zero_chunks = !is(tunable("NHIP_BNB_ZERO_CHUNKS"), '0');  // (0: the exact sums visit every chunk of the cell list -- the A/B, tests)
+  p.seed_bounds = is(tunable("NHIP_BNB_SEED_BOUNDS"), '1');  // (1: the seeds take their sub-block bounds while the best sum is 0 too -- the A/B, tests)
   p.general_all = is(tunable("NHIP_BNB_QUEUE"), '1');      // (the general path for every scan)
   static_assert(NHIP_SHORT_SCAN_POINTS == 64 * OCL, "the header's promise is the by-rotation form's limit");
   p.short_scans = (search->flags & NHIP_SEARCH_SHORT_SCANS) != 0 && !p.general_all && (uint32_t)(L.S + 2 * L.pad) < ORG_LIMIT;
@@ -213,7 +214,7 @@ void bnb_last_launch(int32_t out[8]) {
   const BnbPlan &p = t_last_plan;
   const int32_t info[8] = {p.form, (int32_t)p.batch, (int32_t)p.slots, (int32_t)p.rounds, p.short_scans, p.second,
                            (int32_t)p.instrumented | ((int32_t)p.l2_runs << 1) | ((int32_t)p.pair_subs << 2) |
-                               ((int32_t)p.zero_chunks << 3), p.n_pairs};
+                               ((int32_t)p.zero_chunks << 3) | ((int32_t)p.seed_bounds << 4), p.n_pairs};
   memcpy(out, info, sizeof(info));
 }
 
@@ -245,6 +246,7 @@ static void fill_bnb_params(BnbParams &P, const MatchJob &job, const BnbPlan &pl
   P.l2_runs = plan.l2_runs;
   P.pair_subs = plan.pair_subs;
   P.zero_chunks = plan.zero_chunks;
+  P.seed_bounds = plan.seed_bounds;
   P.general_all = plan.general_all;
   P.short_scans = plan.short_scans;
   P.heavy_min = plan.heavy_min;
@@ -259,8 +261,8 @@ static int instr_buffers(const BnbPlan &plan, BnbParams &P, hipStream_t s) {
   std::lock_guard<std::mutex> lock(g_instr_mu);
   if (plan.stats) {
     if (!g_bnb_stats) {
-      NHIP_TRY_HIP(hipMalloc(reinterpret_cast<void **>(&g_bnb_stats), 8 * (BNB_STATS_HEAD + (size_t)BNB_STATS_PAIRS + BNB_STATS_CHUNKS)));
-      NHIP_TRY_HIP(hipMemset(g_bnb_stats, 0, 8 * (BNB_STATS_HEAD + (size_t)BNB_STATS_PAIRS + BNB_STATS_CHUNKS)));
+      NHIP_TRY_HIP(hipMalloc(reinterpret_cast<void **>(&g_bnb_stats), 8 * (BNB_STATS_HEAD + (size_t)BNB_STATS_PAIRS + BNB_STATS_CHUNKS + BNB_STATS_SEEDS)));
+      NHIP_TRY_HIP(hipMemset(g_bnb_stats, 0, 8 * (BNB_STATS_HEAD + (size_t)BNB_STATS_PAIRS + BNB_STATS_CHUNKS + BNB_STATS_SEEDS)));
     }
     P.stats = g_bnb_stats;
   }
@@ -419,6 +421,15 @@ int bnb_stats_chunks_read(unsigned long long out[4]) {
   unsigned long long *at = g_bnb_stats + BNB_STATS_HEAD + (size_t)BNB_STATS_PAIRS;
   NHIP_TRY_HIP(hipMemcpy(out, at, 8 * BNB_STATS_CHUNKS, hipMemcpyDeviceToHost));
   NHIP_TRY_HIP(hipMemset(at, 0, 8 * BNB_STATS_CHUNKS));
+  return NHIP_OK;
+}
+
+int bnb_stats_seeds_read(unsigned long long out[8]) {
+  for (int i = 0; i < BNB_STATS_SEEDS; i++) out[i] = 0;
+  if (!g_bnb_stats) return NHIP_OK;
+  unsigned long long *at = g_bnb_stats + BNB_STATS_HEAD + (size_t)BNB_STATS_PAIRS + BNB_STATS_CHUNKS;
+  NHIP_TRY_HIP(hipMemcpy(out, at, 8 * BNB_STATS_SEEDS, hipMemcpyDeviceToHost));
+  NHIP_TRY_HIP(hipMemset(at, 0, 8 * BNB_STATS_SEEDS));
   return NHIP_OK;
 }
 

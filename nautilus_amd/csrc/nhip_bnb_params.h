@@ -64,6 +64,7 @@ constexpr size_t lds_bytes(size_t first, int32_t n_theta, bool split) {
 constexpr int BNB_STATS_PAIRS = 1 << 20;           // per-pair counters kept by NHIP_BNB_STATS=1
 constexpr int BNB_STATS_HEAD = 24;    // totals: 4 counts, shader-clock sums of the by-rotation kernel, the strip paths (see nhip_bnb_stats_levels)
 constexpr int BNB_STATS_CHUNKS = 4;   // behind the per-pair counts: chunk visits of the exact sums (see nhip_bnb_stats_chunks)
+constexpr int BNB_STATS_SEEDS = 8;    // behind those: the seeds' clocks by part and their counts (see nhip_bnb_stats_seeds)
 
 // One rotation of a pair with many candidates, handed to the second kernel: (pair, rotation) and the mask of its
 // 121 candidate blocks.
@@ -128,6 +129,7 @@ struct BnbParams {
   int32_t l2_runs;  // strip bounds from the list of level-2 runs where a kernel keeps one (0: NHIP_BNB_L2_RUNS=0, per cell everywhere)
   int32_t pair_subs;  // two live sub-blocks side by side on a strip's sub-block row share one pass (0: NHIP_BNB_PAIR_SUBS=0, one pass each)
   int32_t zero_chunks;  // exact sums leave out the cell-list chunks whose windows hold only empty cells (0: NHIP_BNB_ZERO_CHUNKS=0, every chunk)
+  int32_t seed_bounds;  // a seed pass takes its block's sub-block bounds even while the pair's best sum is 0 (1: NHIP_BNB_SEED_BOUNDS=1; 0: it does not)
 };
 
 // The kernel launches of one batch in each build: launchers_product() (nhip_bnb.hip), launchers_instr()

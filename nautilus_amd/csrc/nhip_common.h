@@ -238,6 +238,7 @@ struct BnbPlan {
   bool l2_runs;      // strip bounds over runs of level-2 entries in the kernels that keep that list (NHIP_BNB_L2_RUNS=0: per cell)
   bool pair_subs;    // two live side-by-side sub-blocks of a strip in one pass of exact sums (NHIP_BNB_PAIR_SUBS=0: one pass each)
   bool zero_chunks;  // exact sums skip the cell-list chunks whose level-2 bytes are all zero (NHIP_BNB_ZERO_CHUNKS=0: every chunk)
+  bool seed_bounds;  // seed passes take their sub-block bounds whatever the pair's best sum (NHIP_BNB_SEED_BOUNDS=1; default: only once it is not 0)
   bool sized_split;  // the size rule (bnb_workspace_bytes) gives this list room for the split form
   uint32_t rot_cap, heavy_min, keep_ranks, split_min, split_max;  // split_max 0: by the round's length
   int64_t batch, slots, slot_bytes, rounds;  // pairs per round (0: fused), rounds' state the workspace holds, bytes of one
@@ -281,6 +282,7 @@ void bnb_last_launch(int32_t out[8]);
 bool bnb_fits(const GridLayout &L, const nhip_search_t *search);
 int bnb_stats_read(unsigned long long out[24]);
 int bnb_stats_chunks_read(unsigned long long out[4]);
+int bnb_stats_seeds_read(unsigned long long out[8]);
 int bnb_timeline_read(unsigned long long *out, int32_t n);
 int bnb_timeline_cand_read(unsigned long long *out, int32_t n);
 int bnb_stats_per_pair(unsigned long long *out, int32_t n);

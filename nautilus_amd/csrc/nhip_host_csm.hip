@@ -639,4 +639,13 @@ int nhip_bnb_stats_chunks(uint64_t out[4]) {
   return NHIP_OK;
 }
 
+int nhip_bnb_stats_seeds(uint64_t out[8]) {
+  NHIP_REQUIRE(out != nullptr, "bnb_stats_seeds: null out");
+  unsigned long long v[8];
+  int rc = bnb_stats_seeds_read(v);
+  if (rc) return rc;
+  for (int i = 0; i < 8; i++) out[i] = v[i];
+  return NHIP_OK;
+}
+
 }  // extern "C"
