@@ -7,15 +7,12 @@
 // which the reference runs from scratch for every (i, j) block and every window size
 // (solver.cc:321-356): three tree descents per matched point.
 //
-// Per block one workgroup: the target cloud is staged in LDS (8 B per point) IN THE ORDER OF ITS BUCKETS: a uniform
-// grid with cells a shade wider than the outlier threshold, counting sort on 1024 buckets in LDS; the four cells
-// (4g .. 4g + 3, cy) share a hashed group of four consecutive buckets, so a query's three cells of a row are one or
-// two runs of consecutive points.  Every lane owns a contiguous range of source
-// points, transforms them into the target frame with the float affine inverse(T_target) * T_source
-// (Eigen Affine2f semantics, individually rounded products) and visits the 3 x 3 cells around
-// each: a target that passes sqrt(d2) < outlier_threshold lies in one of them, and so does the
-// global nearest neighbour whenever any target passes, so the kept rows equal an exhaustive
-// scan's (exact nearest neighbour, ties to the lowest index, kept if within the threshold).
+// Per block one workgroup: the target cloud is staged in LDS (8 B per point) in the order of its buckets; every lane owns
+// a contiguous range of source points, transforms them into the target frame with the float affine
+// inverse(T_target) * T_source (Eigen Affine2f semantics, individually rounded products) and visits the 3 x 3 cells
+// around each, so the kept rows equal an exhaustive scan's (exact nearest neighbour, ties to the lowest index, kept if
+// within the threshold).  The search itself -- cells, buckets, the walk, the tie rule, and why they find the exhaustive
+// scan's answer -- is nhip_corr_shared.h, which the match refinement (nhip_refine.hip) uses too.
 // Target clouds larger than the LDS stage, or coordinates so large that float cell indices are
 // no longer exact, take the exhaustive scan (LDS broadcast reads).  Kept rows are written in
 // source order (block-wide exclusive scan of the per-lane counts) as the 8-float rows K4 consumes.
@@ -25,13 +22,14 @@
 // work) -- not the point reads (0.02 ms), not the index indirection (points in bucket order: -3 %), not the per-run
 // setup (runs of three cells instead of nine single cells: -1.5 %); one loop per lane over all nine cells, which would
 // iterate max-over-lanes of the totals, was measured slower (0.68 ms: its cell-advance test runs every iteration).
-#include "nhip_common.h"
+#include "nhip_corr_shared.h"
 
 namespace nhip {
 
 namespace {
 
-constexpr int CT = 256;
+using namespace corr;
+
 constexpr int TGT_CHUNK = 2048;  // target points staged per pass (16 KB)
 constexpr int MAX_PER_LANE = 8;  // source points a lane owns per pass (2048 per pass)
 
@@ -56,10 +54,6 @@ __device__ __forceinline__ Aff2f inverse_f(const Aff2f &A) {
   return R;
 }
 
-__device__ __forceinline__ float dot2(float a, float b, float c, float d) {
-  return __fadd_rn(__fmul_rn(a, b), __fmul_rn(c, d));
-}
-
 __device__ __forceinline__ Aff2f mul_f(const Aff2f &A, const Aff2f &B) {
   Aff2f C;
   C.m00 = dot2(A.m00, B.m00, A.m01, B.m10);
@@ -69,40 +63,6 @@ __device__ __forceinline__ Aff2f mul_f(const Aff2f &A, const Aff2f &B) {
   C.tx = __fadd_rn(dot2(A.m00, B.tx, A.m01, B.ty), A.tx);
   C.ty = __fadd_rn(dot2(A.m10, B.tx, A.m11, B.ty), A.ty);
   return C;
-}
-
-#ifndef NHIP_CORR_NB
-#define NHIP_CORR_NB 1024
-#endif
-constexpr int NB = NHIP_CORR_NB;  // hash buckets of the target grid
-
-// Buckets come in groups of four: the cells (4g .. 4g + 3, cy) of a row occupy four CONSECUTIVE buckets (the group is
-// hashed, the cell's place in it is cx & 3), so the three cells cx - 1 .. cx + 1 a query visits in a row are one run of
-// consecutive buckets -- or two, when they straddle a group -- instead of three separate ones: 4.5 bucket ranges per
-// point instead of 9, each with its hash, its two dependent LDS reads and its short loop (the walk is bound by that
-// per-range overhead: tools/corr_phase_probe.py).  Cells that share a bucket only add candidates the distance test drops.
-__device__ __forceinline__ uint32_t group_hash(int32_t gx, int32_t cy) {
-  return ((((uint32_t)gx * 73856093u) ^ ((uint32_t)cy * 19349663u)) & (uint32_t)(NB / 4 - 1)) << 2;
-}
-__device__ __forceinline__ uint32_t cell_hash(int32_t cx, int32_t cy) {
-  return group_hash(cx >> 2, cy) | ((uint32_t)cx & 3u);
-}
-
-// block-wide inclusive scan of one int per thread: wave scans by shuffles, wave totals through LDS
-// (s_scan: at least CT / 64 ints), two barriers
-__device__ __forceinline__ int32_t block_scan_incl(int32_t v, int32_t *s_scan, int tid) {
-  const int lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int32_t u = __shfl_up(v, off, 64);
-    if (lane >= off) v += u;
-  }
-  __syncthreads();  // s_scan may still be read by the previous user
-  if (lane == 63) s_scan[wv] = v;
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < CT / 64; w++) v += (w < wv) ? s_scan[w] : 0;
-  return v;
 }
 
 // GATE: the normal gate of Solver::GetPointToNormalMatching / FindClosestPointWithSimilarNormal
@@ -136,83 +96,11 @@ __global__ __launch_bounds__(CT) void corr_search_kernel(
   float4 *out = corr + 2 * (size_t)cap_offsets[b];
   int32_t written = 0;  // rows already emitted by earlier source passes (uniform)
 
-  // Cells 0.1 % wider than the threshold: two points closer than thr are less than 0.999 cells apart per axis.  A
-  // float cell coordinate fx = g * inv_cell carries a relative error of ~1.2e-7 (inv_cell and the product are each
-  // rounded), so the computed coordinates of such a pair differ by less than 0.999 + 2.4e-7 |fx|: below 1 -- the
-  // pair lands in the same or in adjacent cells and the 3 x 3 visit finds it -- as long as |fx| < 4166.
-  // Larger coordinates (beyond 4096 cells = 1 km at the 0.25 m threshold) take the exhaustive scan.
-  const float inv_cell = __fdiv_rn(1.0f, __fmul_rn(thr, 1.001f));
-  constexpr float CELL_LIMIT = 4096.0f;
-  bool hashed = nt <= TGT_CHUNK && thr > 0.f && inv_cell < 3.0e38f;
-  if (hashed) {
-    // stage + bucket the whole target cloud once
-    int big = 0;
-    for (int32_t i = tid; i < NB; i += CT) s_start[i] = 0u;
-    __syncthreads();
-    // (all of a thread's target points -- up to TGT_CHUNK / CT = 8 -- are requested before the first is used)
-    constexpr int TPL = TGT_CHUNK / CT;
-    {
-      float2 tg[TPL];
-#pragma unroll
-      for (int k = 0; k < TPL; k++) {
-        const int32_t i = tid + k * CT;
-        if (i < nt) tg[k] = xy[tb + i];
-      }
-#pragma unroll
-      for (int k = 0; k < TPL; k++) {
-        const int32_t i = tid + k * CT;
-        if (i >= nt) continue;
-        const float fx = __fmul_rn(tg[k].x, inv_cell), fy = __fmul_rn(tg[k].y, inv_cell);
-        if (!(fabsf(fx) < CELL_LIMIT) || !(fabsf(fy) < CELL_LIMIT)) big = 1;
-        else atomicAdd(&s_start[cell_hash((int32_t)floorf(fx), (int32_t)floorf(fy))], 1u);
-      }
-    }
-    hashed = !__syncthreads_or(big);
-  }
-  if (hashed) {
-    // exclusive scan of the NB bucket counts (8 per thread), then scatter
-    uint32_t c[NB / CT], tot = 0;
-#pragma unroll
-    for (int k = 0; k < NB / CT; k++) {
-      c[k] = s_start[tid * (NB / CT) + k];
-      tot += c[k];
-    }
-    uint32_t run = (uint32_t)block_scan_incl((int32_t)tot, s_scan, tid) - tot;
-#pragma unroll
-    for (int k = 0; k < NB / CT; k++) {
-      s_start[tid * (NB / CT) + k] = run;
-      s_cur[tid * (NB / CT) + k] = run;
-      run += c[k];
-    }
-    if (tid == CT - 1) s_start[NB] = run;
-    __syncthreads();
-    // The points themselves go to LDS IN BUCKET ORDER (s_tgt[slot], s_tgn[slot]; s_sorted[slot] = the point's index):
-    // the walk then reads a bucket's points at consecutive addresses, with no index to fetch and follow first.  (Read
-    // again from global memory -- the L2 has them -- rather than held in registers across the scan: 16 more registers
-    // would cost the kernel its fifth wave per SIMD.)
-    constexpr int TPL = TGT_CHUNK / CT;
-    float2 tg[TPL], tn[GATE ? TPL : 1];
-#pragma unroll
-    for (int k = 0; k < TPL; k++) {
-      const int32_t i = tid + k * CT;
-      if (i < nt) {
-        tg[k] = xy[tb + i];
-        if (GATE) tn[GATE ? k : 0] = normals[tb + i];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < TPL; k++) {
-      const int32_t i = tid + k * CT;
-      if (i >= nt) continue;
-      const float2 g = tg[k];
-      const uint32_t h = cell_hash((int32_t)floorf(__fmul_rn(g.x, inv_cell)), (int32_t)floorf(__fmul_rn(g.y, inv_cell)));
-      const uint32_t slot = atomicAdd(&s_cur[h], 1u);
-      s_tgt[slot] = g;
-      if (GATE) s_tgn[slot] = tn[GATE ? k : 0];
-      s_sorted[slot] = (uint16_t)i;
-    }
-    __syncthreads();
-  }
+  const Staged S{s_tgt, s_tgn, s_sorted, s_start, s_cur, s_scan};
+  const float inv_cell = inv_cell_of(thr);
+  // stage + bucket the whole target cloud once; a point outside the cell limit, or not finite, sends the block to the scan
+  const bool hashed = nt <= TGT_CHUNK && thr > 0.f && inv_cell < 3.0e38f &&
+                      stage_buckets<TGT_CHUNK / CT, GATE>(S, xy + tb, normals + tb, nt, inv_cell, tid, [](float2) { return true; });
 
   for (int32_t s0 = 0; s0 < ns; s0 += CT * MAX_PER_LANE) {
     const int32_t n_pass = min(ns - s0, CT * MAX_PER_LANE);
@@ -243,39 +131,17 @@ __global__ __launch_bounds__(CT) void corr_search_kernel(
       }
     }
     const bool scan_all = !hashed || __syncthreads_or(hashed ? big : 0);
+    // the normal gate of round k on the target at LDS position i (no gate: every candidate passes)
+    auto gate = [&](int k, uint32_t i, float d2) {
+      return !GATE || (float_norm_root(d2) < thr && fabsf(dot2(s_tgn[i].x, snx[GATE ? k : 0], s_tgn[i].y, sny[GATE ? k : 0])) > min_cos);
+    };
     if (!scan_all) {
 #pragma unroll
       for (int k = 0; k < MAX_PER_LANE; k++) {
         if (SRC_INDEX(k) >= hi) continue;
         const float fx = __fmul_rn(qx[k], inv_cell), fy = __fmul_rn(qy[k], inv_cell);
         if (!(fabsf(fx) < CELL_LIMIT) || !(fabsf(fy) < CELL_LIMIT)) continue;  // NaN / inf: no match
-        const int32_t icx = (int32_t)floorf(fx), icy = (int32_t)floorf(fy);
-        const int32_t lo = icx - 1, hi2 = icx + 1;
-        const bool two = (lo >> 2) != (hi2 >> 2);  // the three cells straddle a group of four
-        for (int32_t oy = -1; oy <= 1; oy++)
-          for (int32_t r = 0; r < 2; r++) {
-            if (r == 1 && !two) break;
-            // first run: from cell lo to cell hi2 or the end of lo's group; second run: the cells of hi2's group
-            const uint32_t b0 = r == 0 ? cell_hash(lo, icy + oy) : group_hash(hi2 >> 2, icy + oy);
-            const uint32_t b1 = r == 0 ? (two ? (b0 | 3u) : b0 + 2u) : b0 + ((uint32_t)hi2 & 3u);
-            const uint32_t e = s_start[b1 + 1];
-            for (uint32_t i = s_start[b0]; i < e; i++) {
-              const float2 g = s_tgt[i];  // (bucket order: consecutive addresses)
-              const float dx = __fsub_rn(g.x, qx[k]), dy = __fsub_rn(g.y, qy[k]);
-              const float d2 = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
-              bool ok = true;
-              if (GATE) {
-                const float2 gn = s_tgn[i];
-                ok = float_norm_root(d2) < thr && fabsf(dot2(gn.x, snx[k], gn.y, sny[k])) > min_cos;
-              }
-              // the order of visits is arbitrary: (d2, index) lexicographic = "lowest index wins ties".  bi[k] holds the
-              // SLOT of the best so far; the indices are fetched only on an exact tie of the squared distances
-              bool better = ok && d2 < best[k];
-              if (ok && d2 == best[k] && bi[k] >= 0) better = s_sorted[i] < s_sorted[bi[k]];
-              best[k] = better ? d2 : best[k];
-              bi[k] = better ? (int32_t)i : bi[k];
-            }
-          }
+        walk_3x3(S, qx[k], qy[k], inv_cell, best[k], bi[k], [&](uint32_t i, float d2) { return gate(k, i, d2); });  // bi[k]: a SLOT
         if (bi[k] >= 0) bi[k] = (int32_t)s_sorted[bi[k]];  // slot -> index of the target point
       }
     } else {
@@ -294,18 +160,9 @@ __global__ __launch_bounds__(CT) void corr_search_kernel(
           // (a hashed block holds its cloud in bucket order: position i is point s_sorted[i], and ties go by index)
           const int32_t idx = hashed ? (int32_t)s_sorted[i] : t0 + i;
 #pragma unroll
-          for (int k = 0; k < MAX_PER_LANE; k++) {
-            const float dx = __fsub_rn(g.x, qx[k]), dy = __fsub_rn(g.y, qy[k]);
-            const float d2 = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
-            bool ok = true;
-            if (GATE) {
-              const float2 gn = s_tgn[i];
-              ok = float_norm_root(d2) < thr && fabsf(dot2(gn.x, snx[GATE ? k : 0], gn.y, sny[GATE ? k : 0])) > min_cos;
-            }
-            const bool better = ok && (d2 < best[k] || (d2 == best[k] && (uint32_t)idx < (uint32_t)bi[k]));  // the lowest index wins ties
-            best[k] = better ? d2 : best[k];
-            bi[k] = better ? idx : bi[k];
-          }
+          for (int k = 0; k < MAX_PER_LANE; k++)
+            consider(g, qx[k], qy[k], idx, best[k], bi[k], [&](float d2) { return gate(k, i, d2); }, true,
+                     [](int32_t c, int32_t at) { return (uint32_t)c < (uint32_t)at; });  // (bi[k]: an INDEX here; over -1 any wins)
         }
       }
     }

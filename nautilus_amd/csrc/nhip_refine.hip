@@ -3,7 +3,7 @@
 // The rule is DESIGN.md section 3, "Match refinement"; tests/refine_reference.py restates it point by point and this kernel
 // equals it bit for bit.  One workgroup of 256 threads per pair, resident for all of the pair's iterations:
 //   * the target scan's points and normals are staged in LDS once, in the order of their buckets (the counting sort on
-//     hashed cell groups as in nhip_corr.hip, cells a shade wider than thr[0]): 2048 points, 44 KB, three workgroups per CU;
+//     hashed cell groups of nhip_corr_shared.h, cells a shade wider than thr[0]): 2048 points, 44 KB, three workgroups per CU;
 //   * a lane owns the source points i = lane (mod 256), at most 8 per pass of 2048, in registers across the iterations
 //     when the scan is one pass long; longer scans read their points again per pass, the lane sums carry on;
 //   * an evaluation at a pose: float transform, exact nearest target (ties to the lowest index), the acceptance test of the
@@ -14,53 +14,21 @@
 //     uniform, nothing is atomically accumulated, no trigonometry, exp or log runs here.
 // Target points that are not finite or lie at 1e6 m or beyond are never staged; the same source points are never queried.
 // A target whose cell coordinates leave the exact float range (4096 cells), or a pose that takes a query there, is
-// searched exhaustively over the staged points: same nearest neighbour.
-#include "nhip_common.h"
+// searched exhaustively over the staged points: same nearest neighbour.  The search is nhip_corr_shared.h's, shared with the
+// correspondence search (nhip_corr.hip): this unit adds which points take part (point_ok) and what is summed over the matches.
+#include "nhip_corr_shared.h"
 
 namespace nhip {
 
 namespace {
 
-// ---- the search helpers: K5's, restated (nhip_corr.hip keeps its own: its unit is pinned as it stands) ----
-constexpr int CT = 256;
-constexpr int NB = 1024;  // hash buckets of the target grid
-
-__device__ __forceinline__ float dot2(float a, float b, float c, float d) {
-  return __fadd_rn(__fmul_rn(a, b), __fmul_rn(c, d));
-}
-
-// Buckets come in groups of four: the cells (4g .. 4g + 3, cy) of a row occupy four consecutive buckets (the group is hashed,
-// the cell's place in it is cx & 3), so the three cells a query visits in a row are one run of consecutive buckets, or two.
-__device__ __forceinline__ uint32_t group_hash(int32_t gx, int32_t cy) {
-  return ((((uint32_t)gx * 73856093u) ^ ((uint32_t)cy * 19349663u)) & (uint32_t)(NB / 4 - 1)) << 2;
-}
-__device__ __forceinline__ uint32_t cell_hash(int32_t cx, int32_t cy) {
-  return group_hash(cx >> 2, cy) | ((uint32_t)cx & 3u);
-}
-
-// block-wide inclusive scan of one int per thread: wave scans by shuffles, wave totals through LDS (s_scan: at least
-// CT / 64 ints), two barriers
-__device__ __forceinline__ int32_t block_scan_incl(int32_t v, int32_t *s_scan, int tid) {
-  const int lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int32_t u = __shfl_up(v, off, 64);
-    if (lane >= off) v += u;
-  }
-  __syncthreads();  // s_scan may still be read by the previous user
-  if (lane == 63) s_scan[wv] = v;
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < CT / 64; w++) v += (w < wv) ? s_scan[w] : 0;
-  return v;
-}
+using namespace corr;
 
 constexpr int TGT_MAX = NHIP_REFINE_TARGET_MAX;
 constexpr int PER_LANE = 8;            // source points a lane owns per pass
 constexpr int PASS = CT * PER_LANE;    // 2048
 constexpr int NSUM = 10;               // H00 H01 H02 H11 H12 H22 g0 g1 g2 cost
 constexpr float COORD_LIMIT = 1.0e6f;  // a point at or beyond it (or not finite) never matches
-constexpr float CELL_LIMIT = 4096.0f;  // float cell indices are exact below it (nhip_corr.hip)
 
 __device__ __forceinline__ bool point_ok(const float2 p) { return fabsf(p.x) < COORD_LIMIT && fabsf(p.y) < COORD_LIMIT; }
 
@@ -74,6 +42,7 @@ struct RefineLds {
   double red[CT / 64][NSUM];   // wave sums
   int32_t red_n[CT / 64];
   double trace[NHIP_REFINE_TRACE_DOUBLES];
+  __device__ __forceinline__ Staged staged() { return {tgt, tgn, sorted, start, cur, scan}; }
 };
 
 struct Sums {
@@ -86,6 +55,7 @@ __device__ __forceinline__ Sums evaluate(RefineLds &L, const float2 *__restrict_
                                          float (&py)[PER_LANE], double c, double s, double tx, double ty, float thr,
                                          float inv_cell, bool hashed, int32_t n_staged, int tid) {
   const float cf = (float)c, sf = (float)s, txf = (float)tx, tyf = (float)ty;
+  const Staged T = L.staged();
   double acc[NSUM];
 #pragma unroll
   for (int j = 0; j < NSUM; j++) acc[j] = 0.0;
@@ -117,40 +87,12 @@ __device__ __forceinline__ Sums evaluate(RefineLds &L, const float2 *__restrict_
 #pragma unroll
       for (int k = 0; k < PER_LANE; k++) {
         if (!(px[k] == px[k])) continue;  // (no point, or one that never matches)
-        const float fx = __fmul_rn(qx[k], inv_cell), fy = __fmul_rn(qy[k], inv_cell);
-        const int32_t icx = (int32_t)floorf(fx), icy = (int32_t)floorf(fy);
-        const int32_t lo = icx - 1, hi2 = icx + 1;
-        const bool two = (lo >> 2) != (hi2 >> 2);  // the three cells straddle a group of four
-        for (int32_t oy = -1; oy <= 1; oy++)
-          for (int32_t r = 0; r < 2; r++) {
-            if (r == 1 && !two) break;
-            const uint32_t b0 = r == 0 ? cell_hash(lo, icy + oy) : group_hash(hi2 >> 2, icy + oy);
-            const uint32_t b1 = r == 0 ? (two ? (b0 | 3u) : b0 + 2u) : b0 + ((uint32_t)hi2 & 3u);
-            const uint32_t e = L.start[b1 + 1];
-            for (uint32_t i = L.start[b0]; i < e; i++) {
-              const float2 g = L.tgt[i];
-              const float dx = __fsub_rn(g.x, qx[k]), dy = __fsub_rn(g.y, qy[k]);
-              const float d2 = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
-              bool better = d2 < best[k];
-              if (d2 == best[k] && bs[k] >= 0) better = L.sorted[i] < L.sorted[bs[k]];
-              best[k] = better ? d2 : best[k];
-              bs[k] = better ? (int32_t)i : bs[k];
-            }
-          }
+        walk_3x3(T, qx[k], qy[k], inv_cell, best[k], bs[k], [](uint32_t, float) { return true; });
       }
     } else {
-      for (int32_t i = 0; i < n_staged; i++) {
-        const float2 g = L.tgt[i];  // same address in every lane: LDS broadcast
-        const uint32_t idx = L.sorted[i];
+      for (int32_t i = 0; i < n_staged; i++) {  // (the same slot in every lane: LDS broadcast)
 #pragma unroll
-        for (int k = 0; k < PER_LANE; k++) {
-          const float dx = __fsub_rn(g.x, qx[k]), dy = __fsub_rn(g.y, qy[k]);
-          const float d2 = __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
-          bool better = d2 < best[k];
-          if (d2 == best[k] && bs[k] >= 0) better = idx < (uint32_t)L.sorted[bs[k]];
-          best[k] = better ? d2 : best[k];
-          bs[k] = better ? i : bs[k];
-        }
+        for (int k = 0; k < PER_LANE; k++) consider_slot(T, i, qx[k], qy[k], best[k], bs[k], [](float) { return true; });
       }
     }
     // a lane adds its points in ascending order
@@ -234,59 +176,13 @@ __global__ __launch_bounds__(CT) void refine_icp_kernel(const RefineParams P) {
   }
 
   // ---- the target, once: counted, scanned, scattered in bucket order ----
-  const float inv_cell = __fdiv_rn(1.0f, __fmul_rn(sp.thr[0], 1.001f));
+  // (points that fail point_ok are left out; a valid one beyond the cell limit leaves the cloud in plain order, NaN for the
+  // left-out ones, and every search exhaustive)
+  const float inv_cell = inv_cell_of(sp.thr[0]);
   constexpr int TPL = TGT_MAX / CT;
-  int big = 0;
-  for (int32_t i = tid; i < NB; i += CT) L.start[i] = 0u;
-  __syncthreads();
-  {
-    float2 tg[TPL];
-#pragma unroll
-    for (int k = 0; k < TPL; k++) {
-      const int32_t i = tid + k * CT;
-      tg[k] = make_float2(NAN, NAN);
-      if (i < nt) tg[k] = P.xy[tb + i];
-    }
-#pragma unroll
-    for (int k = 0; k < TPL; k++) {
-      if (!point_ok(tg[k])) continue;
-      const float fx = __fmul_rn(tg[k].x, inv_cell), fy = __fmul_rn(tg[k].y, inv_cell);
-      if (!(fabsf(fx) < CELL_LIMIT) || !(fabsf(fy) < CELL_LIMIT)) big = 1;
-      else atomicAdd(&L.start[cell_hash((int32_t)floorf(fx), (int32_t)floorf(fy))], 1u);
-    }
-  }
-  const bool hashed = !__syncthreads_or(big);
-  int32_t n_staged = nt;
-  if (hashed) {
-    uint32_t cnt[NB / CT], tot = 0;
-#pragma unroll
-    for (int k = 0; k < NB / CT; k++) {
-      cnt[k] = L.start[tid * (NB / CT) + k];
-      tot += cnt[k];
-    }
-    uint32_t run = (uint32_t)block_scan_incl((int32_t)tot, L.scan, tid) - tot;
-#pragma unroll
-    for (int k = 0; k < NB / CT; k++) {
-      L.start[tid * (NB / CT) + k] = run;
-      L.cur[tid * (NB / CT) + k] = run;
-      run += cnt[k];
-    }
-    if (tid == CT - 1) L.start[NB] = run;
-    __syncthreads();
-    n_staged = (int32_t)L.start[NB];
-#pragma unroll
-    for (int k = 0; k < TPL; k++) {
-      const int32_t i = tid + k * CT;
-      if (i >= nt) continue;
-      const float2 g = P.xy[tb + i];
-      if (!point_ok(g)) continue;
-      const uint32_t h = cell_hash((int32_t)floorf(__fmul_rn(g.x, inv_cell)), (int32_t)floorf(__fmul_rn(g.y, inv_cell)));
-      const uint32_t slot = atomicAdd(&L.cur[h], 1u);
-      L.tgt[slot] = g;
-      L.tgn[slot] = P.normals[tb + i];
-      L.sorted[slot] = (uint16_t)i;
-    }
-  } else {
+  const bool hashed = stage_buckets<TPL, true>(L.staged(), P.xy + tb, P.normals + tb, nt, inv_cell, tid, [](float2 p) { return point_ok(p); });
+  const int32_t n_staged = hashed ? (int32_t)L.start[NB] : nt;
+  if (!hashed) {
 #pragma unroll
     for (int k = 0; k < TPL; k++) {
       const int32_t i = tid + k * CT;
@@ -296,8 +192,8 @@ __global__ __launch_bounds__(CT) void refine_icp_kernel(const RefineParams P) {
       L.tgn[i] = P.normals[tb + i];
       L.sorted[i] = (uint16_t)i;
     }
+    __syncthreads();
   }
-  __syncthreads();
 
   // ---- the source's first pass: in registers for every iteration when it is the only one ----
   const float2 *src = P.xy + sb;

@@ -40,11 +40,11 @@ import numpy as np
 from oracle import oracle as O
 
 F = np.float32
-LANES = 256                  # nhip_corr.hip: CT, threads of a workgroup
+LANES = 256                  # nhip_corr_shared.h (CT, NB, CELL_LIMIT) and nhip_corr.hip: CT, threads of a workgroup
 ROUNDS = 8                   # MAX_PER_LANE: source points a lane owns per pass
 PASS = LANES * ROUNDS        # source points per pass
 STAGE = 2048                 # TGT_CHUNK: target points staged in LDS, the most a hashed block holds (uint16_t s_sorted)
-BUCKETS = 1024               # NB (NHIP_CORR_NB): hash buckets, in groups of four
+BUCKETS = 1024               # NB: hash buckets, in groups of four
 CELL_LIMIT = 4096.0          # CELL_LIMIT: cell coordinates from here on take the exhaustive scan
 SCAN_STEP = 1024             # blocks per step of corr_scan_kernel
 WAVE = 64

@@ -31,10 +31,12 @@ def _rows_of(case, b):
 
 def test_the_kernel_constants_are_the_ones_the_inputs_were_cut_for():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, "nautilus_amd", "csrc", "nhip_corr.hip")) as f:
-        src = f.read()
+    src = ""
+    for unit in ("nhip_corr_shared.h", "nhip_corr.hip"):  # the search K5 shares with the refinement, and K5's own unit
+        with open(os.path.join(root, "nautilus_amd", "csrc", unit)) as f:
+            src += f.read()
     for line in ("constexpr int CT = %d;" % S.LANES, "constexpr int TGT_CHUNK = %d;" % S.STAGE,
-                 "constexpr int MAX_PER_LANE = %d;" % S.ROUNDS, "#define NHIP_CORR_NB %d" % S.BUCKETS,
+                 "constexpr int MAX_PER_LANE = %d;" % S.ROUNDS, "constexpr int NB = %d;" % S.BUCKETS,
                  "constexpr float CELL_LIMIT = %.1ff;" % S.CELL_LIMIT, "base += %d)" % S.SCAN_STEP, "__fmul_rn(thr, 1.001f)",
                  "* 73856093u) ^ ((uint32_t)cy * 19349663u)"):
         assert line in src, line

@@ -91,6 +91,60 @@ def test_host_form_equals_the_restatement(name):
     assert same_bytes(got, want) and same_bytes(got_trace, want_trace)
 
 
+def _first_evaluation(cs, p):
+    """Pair p of a case as K22's first evaluation searches it: (queries, NaN where the source point takes no part; the target
+    points that are staged; thr[0]), or None where the kernel ends before it searches (start pose, target length)."""
+    s, t = int(cs.pair_src[p]), int(cs.pair_tgt[p])
+    src, tgt = cs.xy[cs.offsets[s]:cs.offsets[s + 1]], cs.xy[cs.offsets[t]:cs.offsets[t + 1]]
+    if not np.isfinite(cs.pose0[p]).all() or len(tgt) > R.TARGET_MAX:
+        return None
+    c, s_, tx, ty = (np.float32(v) for v in cs.pose0[p])
+    with np.errstate(all="ignore"):
+        q = np.stack([(c * src[:, 0] + (-s_) * src[:, 1]) + tx, (s_ * src[:, 0] + c * src[:, 1]) + ty], axis=1)
+        q[~(np.abs(src) < np.float32(1.0e6)).all(axis=1)] = np.nan
+        staged = tgt[(np.abs(tgt) < np.float32(1.0e6)).all(axis=1)]
+    assert q.dtype == np.float32
+    return q, staged, cs.fields().thr[0]
+
+
+def test_the_cases_reach_the_seams_of_the_shared_walk():
+    """K22 runs nhip_corr_shared.h's walk with its own staging rule and no gate.  By the path conditions tests/corr_seams.py
+    restates, at thr[0] and over the first evaluation of every case: the queries that WALK visit one run (icx & 3 in 1, 2) and
+    two runs (0, 3) with icx and icy on both sides of zero at every residue; the list holds hashed targets, a target that is
+    searched exhaustively for a point of its own (far_target) and one for a query (far_pose).  A precondition: an edit of the
+    cases that stops reaching a seam fails here, not silently on the device."""
+    from tests import corr_seams as S
+    walked, path = [], {}
+    for cs in R.cases():
+        for p in range(len(cs.pair_src)):
+            ev = _first_evaluation(cs, p)
+            if ev is None:
+                continue
+            q, staged, thr = ev
+            is_hashed = S.hashed(staged, thr)
+            scans = S.scan_everything_passes(q, staged, thr)
+            path.setdefault(cs.name, []).append((is_hashed, scans))
+            for k, scan_all in enumerate(scans):
+                if not scan_all:
+                    part = q[k * S.PASS:(k + 1) * S.PASS]
+                    walked.append(S.cells(part[~np.isnan(part).any(axis=1)], thr))
+            if is_hashed and len(staged):
+                tc = S.cells(staged, thr)
+                assert np.all(S.bucket(tc[:, 0], tc[:, 1]) < S.BUCKETS)
+    cells = np.concatenate(walked)
+    icx, icy, two = cells[:, 0], cells[:, 1], S.two_runs(cells[:, 0])
+    assert set(icx[two] & 3) == {0, 3} and set(icx[~two] & 3) == {1, 2}
+    for r in range(4):
+        at = (icx & 3) == r
+        assert (icx[at] < 0).any() and (icx[at] >= 0).any() and (icy[at] < 0).any() and (icy[at] >= 0).any(), r
+    assert path["far_target"] == [(False, [True])] and path["far_pose"] == [(True, [True])]
+    assert path["src4100"] == [(True, [False] * 3)] and path["tgt2048"] == [(True, [False])] and all(h for h, _ in path["pairs300"])
+    assert "tgt2049" not in path and "skipped" not in path
+    print("refine cases: %d walked queries, %d two-run, cells x %d..%d y %d..%d; hashed pairs %d, exhaustive by target %d, by query %d" % (
+        len(cells), two.sum(), icx.min(), icx.max(), icy.min(), icy.max(), sum(h for v in path.values() for h, _ in v),
+        sum(not h for v in path.values() for h, _ in v), sum(h and any(s) for v in path.values() for h, s in v)))
+
+
 def test_threshold_edge_keeps_the_distance_below_alone():
     """Of the three lone points at 0.25 m minus one float, 0.25 m and 0.25 m plus one float, the first evaluation (identity
     pose: q = p exactly) keeps the first alone."""

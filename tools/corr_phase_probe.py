@@ -1,5 +1,6 @@
-"""Where corr_search_kernel's time goes: the product build and builds with parts of the bucket walk compiled out
-(-DNHIP_CORR_EXPERIMENT=1: no walk; =2: the walk without its point reads; results WRONG), one subprocess each (GPU box)."""
+"""corr_search_kernel's time on bench.bench_icp's workload (9,945 blocks of 1081-point scans): the product library and every
+build/variants/libcorr_*.so present (other builds of the same library, selected through NHIP_LIB), one subprocess each (GPU
+box).  `one` is a single leg: it prints corr_search_ms and normal_eq_ms of the library NHIP_LIB names."""
 import glob, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if len(sys.argv) > 1 and sys.argv[1] == "one":
